@@ -4,6 +4,11 @@
     python bench.py --gpus 8              # spawns 8 ranks itself (re-exec under torch.distributed.run, 127.0.0.1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W        # what the driver does
+    python bench.py --full                # the same headline, then every extra measurement below (minutes)
+    python bench.py --dump-outputs DIR    # + what the last timed step returned, as DIR/<name>.npy (see dump_outputs)
+
+A plain run sets up, warms up, times the K steps, dumps the outputs if asked and prints the line: `value` / `ms_per_step`
+and the workload fields.  Every block described below from `roofline` on is taken with --full only (null otherwise).
 
 A "step" = one LoFTR.forward (HIP path through the C ABI) over one batch of 8 synthetic 640x480 pairs that are
 already resident in HBM, including the match-count read-back the reference's contract has
@@ -73,11 +78,57 @@ def parse_args(argv=None):
                          "reported as `bf16_mode`); fp32: the parity mode (exact indices)")
     ap.add_argument("--coarse-sim", default=None, choices=["fp32", "bf16", "fp16"], help="override LoFTR config['coarse_sim']")
     ap.add_argument("--frac", type=float, default=0.45, help="corresponding fraction of the frame (match count knob)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also take every extra measurement of the line: roofline, h2d_inclusive, parity_mode / bf16_mode / "
+                         "fp16_mode, fine_idle, secondary_workloads, cpu_baseline + parity (a plain run reports them as null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-pairs", type=int, default=1)
     ap.add_argument("--selftest-launch", action="store_true",
                     help="CPU-only check of the multi-rank launch / timing / gather protocol (gloo, no model)")
     return ap.parse_args(argv)
+
+
+DUMP_INPUT_KEYS = ("image0", "image1", "color0", "color1", "mask0", "mask1")
+DUMP_WHOLE_MAX = 16 << 20     # bytes: a larger output is stored as a fixed, seeded sample of DUMP_SAMPLE entries
+DUMP_SAMPLE = 1 << 20
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, data, rows, prefix=""):
+    """--dump-outputs: what a caller of the timed path received in the last timed step, as <out_dir>/<prefix><name>.npy --
+    every tensor LoFTR.forward put into `data` (floating outputs as float32, integer / bool ones as float64: exact) and the
+    packed [pair, x0, y0, x1, y1, conf] rows of the step (`matches_packed`).  data['conf_matrix'] is materialised on demand
+    (737 MB at the benchmark's size): it is stored as `conf_matrix_sample` at the flat indices `conf_matrix_sample_index`,
+    drawn once from a fixed seed.  Called right after the timed steps, before anything else runs on the model."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    outs = {}
+    for k, v in data.items():
+        if k in DUMP_INPUT_KEYS:
+            continue
+        if not torch.is_tensor(v) and callable(getattr(v, "get", None)):   # LazyConfMatrix
+            v = v.get()
+        if torch.is_tensor(v):
+            outs[k] = v
+    outs["matches_packed"] = rows
+    total = 0
+    for k, v in outs.items():
+        v = v.detach()
+        v = v.float() if (v.is_floating_point() and v.dtype != torch.float64) else v.double()
+        if v.numel() * v.element_size() > DUMP_WHOLE_MAX:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, v.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            arrays = {k + "_sample": v.reshape(-1)[idx.to(v.device)], k + "_sample_index": idx.double()}
+        else:
+            arrays = {k: v}
+        for name, a in arrays.items():
+            a = a.cpu().numpy()
+            total += a.nbytes
+            np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs wrote {total} bytes, more than {DUMP_MAX_BYTES}"
+    return total
 
 
 def _free_port():
@@ -229,7 +280,7 @@ def main():
     # pinned host memory asynchronously behind the step that produced them; sync_all() below waits for the last copy.  The pinned slots
     # (capacity = every coarse cell of every pair a match) are allocated HERE, outside the timed region: hipHostMalloc is not part of a step
     host_cap = nb * (H // 8) * (W // 8)
-    host_ring = None if dry else torch.empty(args.steps, host_cap, 6, dtype=torch.float32).pin_memory()
+    host_ring = None if dry else torch.empty(args.steps, host_cap, 6, dtype=torch.float32, pin_memory=True)
     sync_all()
     t0 = time.perf_counter()
     rows = []
@@ -252,11 +303,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     d_last = d
-    solo = rank == 0 and world == 1 and not dry  # the extra measurements below only run in single-GPU jobs
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_last, rows[-1], "" if rank == 0 else f"rank{rank}_")
+    # the extra measurements below run with --full only (a plain run reports them as null), all but the roofline in single-GPU jobs only
+    full = args.full and rank == 0 and not dry
+    solo = full and world == 1
 
     # ---- live roofline of the dominant kernel (instrumented steps outside the timed region) --------
     roof = None
-    if rank == 0 and not dry:
+    if full:
         graph_was, model.use_graph = model.use_graph, False  # events need eager launches
         # ... and one stream: the timed configuration runs the coarse transformer as pair chains on parallel streams (loftr.py: tf_chains),
         # where the event pairs of concurrent launches overlap; the per-kernel table below is taken with ONE chain (12 token launches per
@@ -700,7 +755,7 @@ def main():
         out = {
             "metric": "image-pairs/sec at 640x480", "value": round(pairs / dt, 2), "unit": "pairs/s",
             "n_gpus": world, "n_ranks_seen": n_ranks_seen, "rank_devices": rank_devices, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * dt / args.steps, 3), "higher_is_better": True, "scaling": "weak",
+            "ms_per_step": round(1e3 * dt / args.steps, 3), "higher_is_better": True, "scaling": "weak", "full": bool(args.full),
             "vs_baseline": None, "dtype": getattr(model, "precision", args.precision), "data": "synthetic",
             # what the module really ran as: a tripped fp16 range guard switches it to bf16 for good (gim_amd/loftr/loftr.py::_range_guard)
             "engine_precision": getattr(model, "precision", args.precision), "fp16_overflowed": bool(getattr(model, "fp16_overflowed", False)),

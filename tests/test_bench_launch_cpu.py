@@ -55,3 +55,30 @@ def test_bench_main_single_rank_dry():
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert out["n_gpus"] == 1 and out["n_ranks_seen"] == 1 and out["config"]["matches_per_pair"] == 3.0
+
+
+def test_bench_dump_outputs_dry(tmp_path):
+    """--dump-outputs: the last timed step's outputs as DIR/<name>.npy in float32 / float64, identical from run to run with the
+    same arguments; --steps is the number of timed steps; a plain run leaves the --full blocks null.  Two gloo ranks: rank 1's
+    files carry a `rank1_` prefix."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env["GIM_BENCH_DRY_MODEL"] = "1"
+    outs = []
+    for run, extra in enumerate(([], [], ["--gpus", "2"])):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "2",
+                            "--dump-outputs", str(d)] + extra, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["full"] is False
+        assert out["roofline"] is None and out["cpu_baseline"] is None and out["parity"] is None and out["h2d_inclusive"] is None
+        outs.append({f.name: np.load(f) for f in sorted(d.glob("*.npy"))})
+    assert {"mkpts0_f.npy", "mkpts1_f.npy", "mconf.npy", "m_bids.npy", "matches_packed.npy"} <= set(outs[0])
+    assert "image0.npy" not in outs[0] and "color0.npy" not in outs[0]   # inputs are not outputs
+    assert set(outs[0]) == set(outs[1])
+    for name, a in outs[0].items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        assert np.array_equal(a, outs[1][name]), name
+    assert outs[0]["matches_packed.npy"].shape == (3 * 2, 6)   # 3 matches per pair of the stand-in model, batch 2
+    assert set(outs[2]) == set(outs[0]) | {"rank1_" + n for n in outs[0]}

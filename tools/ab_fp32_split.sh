@@ -2,7 +2,7 @@
 # fp32 mode of the benchmark workload with and without the split-operand products (gim_conv_args.split16): step time + parity block vs the CPU oracle
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 for f in 0 1; do
-  GIM_FLAGS=fp32_split=$f GIM_BENCH_SKIP_DENSE=1 GIM_BENCH_SKIP_LIGHTGLUE=1 GIM_BENCH_SKIP_PARITY_MODE=1 timeout 900 python bench.py --precision fp32 --steps 5 --warmup 2 2>/dev/null | python -c "
+  GIM_FLAGS=fp32_split=$f GIM_BENCH_SKIP_DENSE=1 GIM_BENCH_SKIP_LIGHTGLUE=1 GIM_BENCH_SKIP_PARITY_MODE=1 timeout 900 python bench.py --full --precision fp32 --steps 5 --warmup 2 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 p=d['parity']

@@ -3,7 +3,7 @@
 #   gpurun --timeout T -- 'bash tools/gpu_check.sh <tag> <step> [<step> ...]'
 # steps (run in the order given; every step logs to gpurun_out/<tag>_<step>.log and prints a short tail):
 #   tests[=EXPR]   pytest -m gpu (-k EXPR)                 smoke          __graft_entry__.smoke()
-#   bench[=ARGS]   python bench.py ARGS  (full line)       quick[=ARGS]   bench.py without secondary workloads / alt modes / CPU leg
+#   bench[=ARGS]   python bench.py --full ARGS (full line) quick[=ARGS]   bench.py without secondary workloads / alt modes / CPU leg
 #   prof           rocprofv3 --kernel-trace --stats of the headline command  -> <tag>_kernel_stats.txt      gaps   idle time between the kernels of a replayed forward (tools/prof_gaps.sh)
 #   pmc            MFMA-pipe occupancy per kernel family (tools/pmc_forward.sh)   traffic   HBM bytes (tools/pmc_traffic.sh)
 #   ab=V1;V2;...   same-box A/B of the step time over variants (tools/ab_forward.py: ENV=value[,ENV=value] or lib=alt / lib=new)
@@ -21,8 +21,8 @@ for step in "$@"; do
            else timeout 2400 python -m pytest tests -m gpu -q -x --timeout=900 -p no:cacheprovider > $log 2>&1; fi
            echo "[$name $arg] rc=$?"; tail -6 $log | cut -c1-400 ;;
     smoke) timeout 900 python __graft_entry__.py smoke > $log 2>&1; echo "[smoke] rc=$?"; tail -2 $log | cut -c1-500 ;;
-    bench) timeout 1800 python bench.py $arg > ${o}_${n}_bench.json 2> $log; echo "[bench $arg] rc=$?"; cut -c1-700 ${o}_${n}_bench.json; tail -3 $log | cut -c1-300 ;;
-    quick) GIM_BENCH_SKIP_DENSE=1 GIM_BENCH_SKIP_LIGHTGLUE=1 GIM_BENCH_SKIP_PARITY_MODE=1 timeout 900 python bench.py --no-cpu-baseline $arg > ${o}_${n}_quick.json 2> $log
+    bench) timeout 1800 python bench.py --full $arg > ${o}_${n}_bench.json 2> $log; echo "[bench $arg] rc=$?"; cut -c1-700 ${o}_${n}_bench.json; tail -3 $log | cut -c1-300 ;;
+    quick) GIM_BENCH_SKIP_DENSE=1 GIM_BENCH_SKIP_LIGHTGLUE=1 GIM_BENCH_SKIP_PARITY_MODE=1 timeout 900 python bench.py --full --no-cpu-baseline $arg > ${o}_${n}_quick.json 2> $log
            echo "[quick $arg] rc=$?"; python - ${o}_${n}_quick.json <<'PY'
 import json, sys
 try:
