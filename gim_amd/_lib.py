@@ -70,7 +70,7 @@ class LgAssignArgs(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 113   # gim_version() of the include/gim_hip.h revision the structures and prototypes here mirror
+ABI_VERSION = 114   # gim_version() of the include/gim_hip.h revision the structures and prototypes here mirror
 
 # name -> (restype, argtypes); every symbol declared in include/gim_hip.h
 PROTOTYPES = {

@@ -320,12 +320,17 @@ struct Epilogue {
         if constexpr (G::ES == 4) {
             if (wscale != 1.f) {   // wave-uniform
                 const float inv = 1.f / wscale;   // a power of two: exact
+                // split range guard (version 114): an operand beyond the fp16 range split into hi = +-inf, lo = -+inf, so every accumulator of
+                // its row (or column) holds inf - inf or inf * 0 = NaN.  Checked here, before the residual and the activation (a ReLU scrubs
+                // the NaN); the bias is already in the accumulators but finite.
+                float sum = 0.f;   // NaN propagates through the sum (one register, no lane mask per value)
 #pragma unroll
                 for (int i = 0; i < TN; ++i)
 #pragma unroll
                     for (int j = 0; j < TM; ++j)
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[i][j][r] *= inv;
+                        for (int r = 0; r < 16; ++r) { acc[i][j][r] *= inv; sum += 0.f * acc[i][j][r]; }
+                if (__builtin_expect(sum != sum, 0) && a.health != nullptr) atomicOr(a.health, 8);
             }
         }
         char* wl = stage + wave * WAVE_BYTES;  // this wave's transposition tile [32 px][RB]
@@ -525,10 +530,10 @@ igemm_persistent_kernel(const gim_conv_args a, const int mtiles, const int ntile
         };
         if constexpr (SKIP && G::TN > 1) {
             // the wave's last channel fragment holds only padding channels (wave-uniform)
-            if (n0 + epi.wn * G::WTN + (G::TN - 1) * 32 >= a.N) kloop(IntC<G::TN - 1>(), IntC<BF16 ? 0 : 1>());   // (fp32 operands reach this tile as split launches only)
+            if (n0 + epi.wn * G::WTN + (G::TN - 1) * 32 >= a.N) kloop(IntC<G::TN - 1>(), IntC<BF16 ? 0 : 1>());   // (fp32 operands reach this tile as split launches only: dispatch_persistent checks a.split16 on both branches)
             else kloop(IntC<G::TN>(), IntC<BF16 ? 0 : 1>());
         } else if constexpr (!BF16) {
-            if constexpr (BM == 256 && BN == 256) kloop(IntC<G::TN>(), IntC<1>());   // (only split launches are sent to this tile: dispatch_persistent)
+            if constexpr (BM == 256 && BN == 256) kloop(IntC<G::TN>(), IntC<1>());   // (only split launches are sent to this tile: dispatch_persistent checks a.split16 on both branches)
             else if (a.split16) kloop(IntC<G::TN>(), IntC<1>());   // (a second copy of the loop, selected per launch)
             else kloop(IntC<G::TN>(), IntC<0>());
         } else {
@@ -822,8 +827,9 @@ int dispatch_persistent(const gim_conv_args& a, hipStream_t s) {
         const long long M = (long long)a.B * a.Ho * a.Wo;
         const long long T = ((M + 255) / 256) * (a.npad / 128);
         // 256 x 256 tile, 8 waves, 64 x 128 wave tile: twice the MFMAs per wave and slab against nearly the same
-        // staging / addressing overhead -- for the MFMA-bound layers (no residual, bf16 out, N % 256 == 0)
-        if (a.npad % 256 == 0 && out_is16(a) && !a.res &&
+        // staging / addressing overhead -- for the MFMA-bound layers (no residual, bf16 out, N % 256 == 0).  fp32 operands only as split
+        // launches: this tile has no exact-product loop (split16 = 0 goes to the 128 x 128 tile, which picks the loop per launch)
+        if (a.npad % 256 == 0 && out_is16(a) && !a.res && (BF16 || a.split16) &&
             (a.use_lds_dma == 3 || (nkt >= BIG_MIN_NKT && big_tile_count(((M + 255) / 256) * (a.npad / 256), nkt))))   // 3: the tests' way onto this tile
         {
             // N <= 224 (the FPN's 196-channel layers): the second column half's last fragment is pure padding

@@ -53,6 +53,18 @@ from ..packing import (PackedStem, cstore, is_half, pack_bneck, pack_bneck_ds, p
                        pack_stem7x7, pack_token_mlp, pack_token_emit, split_channels, torch_dtype)
 
 _DT = {"bf16": GIM_BF16, "fp16": GIM_F16, "fp32": GIM_F32}
+# gim_conv_args.split16: the weight operand is scaled by 2^12 before its hi / lo split (conv_igemm.hip), and hi = rn16 of it must stay finite
+SPLIT16_WSCALE, SPLIT16_LIMIT = 4096.0, 65504.0
+
+
+def split16_weight_overflow(packs):
+    """names of the fp32 weight packs (pack_conv results among `packs`' values) whose largest |w| * 4096 reaches 65504: their split products
+    would overflow IEEE fp16 whatever the activations (a BatchNorm-folded filter of a channel with running_var ~ 0: gamma / sqrt(eps) ~ 316 gamma)"""
+    named = [(k, v.w) for k, v in packs.items() if hasattr(v, "w") and torch.is_tensor(v.w) and v.w.dtype == torch.float32 and v.w.numel()]
+    if not named:
+        return []
+    peak = torch.stack([w.abs().max() for _, w in named]).cpu()   # one read-back for all packs
+    return [k for (k, _), m in zip(named, peak.tolist()) if m * SPLIT16_WSCALE >= SPLIT16_LIMIT]
 
 
 # --------------------------------------------------------------------------------------------------
@@ -202,6 +214,9 @@ class LoFTR(nn.Module):
         self.stem_kernel = flag("stem_kernel", True, config)
         # set once the fp16 mode's range guard tripped and the module fell back to bf16 (see forward)
         self.fp16_overflowed = False
+        # set once the fp32 mode's split products left the IEEE-fp16 range (packed weights or bit 8 of the health word) and the module
+        # turned fp32_split off (see _prepack, _range_guard)
+        self.split_overflowed = False
         self.backbone = _ResNetFPN_8_2(config["resnetfpn"])
         self.loftr_coarse = _LocalFeatureTransformer(config["coarse"])
         self.loftr_fine = _LocalFeatureTransformer(config["fine"])
@@ -415,6 +430,17 @@ class LoFTR(nn.Module):
                 self.fp16_overflowed = True
                 self.set_precision("bf16", coarse_sim="fp32" if self.coarse_sim == "fp32" else None)   # a caller's fp32 similarity survives the fallback
                 return self._prepack(device)
+        if self.precision == "fp32" and self.fp32_split:
+            # split range guard, weight side: |w| * 4096 must round to a finite fp16 hi half (gim_conv_args.split16)
+            bad = split16_weight_overflow(P)
+            if bad:
+                import warnings
+                warnings.warn(f"gim_amd LoFTR: folded weights of {bad[:4]}{' ...' if len(bad) > 4 else ''} reach 65504 / 4096 = 16 and would overflow "
+                              "the fp32 mode's IEEE-fp16 split products; falling back to exact fp32 products (fp32_split = False) for this module")
+                self.split_overflowed = True
+                self.fp32_split = False   # same packs: the exact-product launches read the same fp32 weights
+                self._graphs.clear()
+                self._seen.clear()
         self._packed, self._packed_key = P, key
         return P
 
@@ -507,7 +533,7 @@ class LoFTR(nn.Module):
         if K == 1:
             x3, _, x3_out = self._layer(P, 3, 6, x2, o3)
             if x3_out is None:
-                x3_out = ops.conv2d(x3, P["l3o"], lds_dma=self.use_lds_dma)
+                x3_out = ops.conv2d(x3, P["l3o"], lds_dma=self.use_lds_dma, health=self._health)
             return x1, x2, x3_out
         n = B // K
         main = torch.cuda.current_stream()
@@ -521,7 +547,7 @@ class LoFTR(nn.Module):
             sl = slice(g * n, (g + 1) * n)
             x3, _, xo = self._layer(P, 3, 6, x2[sl], o3[sl] if o3 is not None else None, out_last=(None, x3_out[sl]))
             if xo is None:
-                xo = ops.conv2d(x3, P["l3o"], lds_dma=self.use_lds_dma)
+                xo = ops.conv2d(x3, P["l3o"], lds_dma=self.use_lds_dma, health=self._health)
             if xo.data_ptr() != x3_out[sl].data_ptr():
                 ops.copy_segments([(xo.contiguous(), x3_out[sl])])
             keep.append((x3, xo))
@@ -548,7 +574,7 @@ class LoFTR(nn.Module):
         if isinstance(P["stem"], PackedStem):
             x = ops.stem7x7(x, P["stem"], out_dtype=torch_dtype(dt))
         else:
-            x = ops.conv2d(x, P["stem"], ACT_RELU, out_dtype=torch_dtype(dt), lds_dma=dma)   # image dtype may be fp16 in bf16 mode
+            x = ops.conv2d(x, P["stem"], ACT_RELU, out_dtype=torch_dtype(dt), lds_dma=dma, health=self._health)   # image dtype may be fp16 in bf16 mode
         x1, o, _ = self._layer(P, 1, 3, x, None, out_last=(out[0], None) if out else None)
         x2, o, _ = self._layer(P, 2, 4, x1, o, out_last=(out[1], out[2]) if out else None)
         return x1, x2, o
@@ -566,7 +592,7 @@ class LoFTR(nn.Module):
             last = bi == nblk - 1
             outs = out_last if last else None
             if o is None:
-                o = ops.conv2d(x, P[p + "c1"], ACT_RELU, lds_dma=dma)
+                o = ops.conv2d(x, P[p + "c1"], ACT_RELU, lds_dma=dma, health=self._health)
             if fuse and self.bneck_ds and (p + "fused_ds") in P and x.shape[3] == 64 and x.is_contiguous():
                 x, o = ops.bneck64_ds(o, x, P[p + "fused_ds"], out=outs, health=self._health)   # ... and the downsample branch: no identity tensor at all
                 continue
@@ -575,14 +601,14 @@ class LoFTR(nn.Module):
                     and rows_ds % 256 == 0 and rows_ds * 512 * 2 < (1 << 32) - 16):   # 32-bit byte offsets into [rows, 512] (its own REQUIRE): oversize batches take the unfused launches
                 # layer 2's first block: conv2, then ONE kernel for conv3 + the stride-2 downsample branch (extra K) + relu + the next conv1:
                 # no downsample launch, no identity tensor (gim_bneck_tail128_ds)
-                o = ops.conv2d(o, P[p + "c2"], ACT_RELU, lds_dma=dma)
+                o = ops.conv2d(o, P[p + "c2"], ACT_RELU, lds_dma=dma, health=self._health)
                 x, o = ops.bneck_tail_ds(o, x, P[p + "tail_ds"], out=outs, health=self._health)
                 continue
-            idn = ops.conv2d(x, P[p + "ds"], ACT_NONE, lds_dma=dma) if (p + "ds") in P else x
+            idn = ops.conv2d(x, P[p + "ds"], ACT_NONE, lds_dma=dma, health=self._health) if (p + "ds") in P else x
             if fuse:   # conv2 -> conv3 + identity -> the next conv1 (of this layer, or layer2's first), one kernel
                 x, o = ops.bneck64(o, idn, P[p + "fused"], True, out=outs, health=self._health)
                 continue
-            o = ops.conv2d(o, P[p + "c2"], ACT_RELU, lds_dma=dma)
+            o = ops.conv2d(o, P[p + "c2"], ACT_RELU, lds_dma=dma, health=self._health)
             rows = o.shape[0] * o.shape[1] * o.shape[2]
             # the tail kernel walks 256-row tiles with 32-bit byte offsets into the [rows, 4 P] tensors (its own REQUIREs)
             if self.bneck_tail and (p + "tail") in P and rows % 256 == 0 and rows * 4 * o.shape[3] * 2 < (1 << 32) - 16:
@@ -603,10 +629,10 @@ class LoFTR(nn.Module):
         dma = self.use_lds_dma
         # lateral 1x1 conv + F.interpolate(scale_factor=2, bilinear, align_corners=True) of the coarser level + add (resnet.py:
         # 321-327): the upsample-add runs in the conv's epilogue when the launch takes it, else as a second pass over the output
-        x2_out = ops.conv2d(x2, P["l2o"], lds_dma=dma, ups=x3_out)
-        x2_out = ops.conv2d(ops.conv2d(x2_out, P["l2o2a"], ACT_LEAKY, lds_dma=dma), P["l2o2b"], lds_dma=dma)
-        x1_out = ops.conv2d(x1, P["l1o"], lds_dma=dma, ups=x2_out)
-        x1_out = ops.conv2d(ops.conv2d(x1_out, P["l1o2a"], ACT_LEAKY, lds_dma=dma), P["l1o2b"], lds_dma=dma)
+        x2_out = ops.conv2d(x2, P["l2o"], lds_dma=dma, ups=x3_out, health=self._health)
+        x2_out = ops.conv2d(ops.conv2d(x2_out, P["l2o2a"], ACT_LEAKY, lds_dma=dma, health=self._health), P["l2o2b"], lds_dma=dma, health=self._health)
+        x1_out = ops.conv2d(x1, P["l1o"], lds_dma=dma, ups=x2_out, health=self._health)
+        x1_out = ops.conv2d(ops.conv2d(x1_out, P["l1o2a"], ACT_LEAKY, lds_dma=dma, health=self._health), P["l1o2b"], lds_dma=dma, health=self._health)
         return x1_out
 
     class _TfBuffers:
@@ -648,14 +674,14 @@ class LoFTR(nn.Module):
         x_t, s_t = T.CAT[xs, :C], T.CAT[ss, :C]
         # q/k/v projections with elu(.)+1 (attentions.py:31-32) fused into the epilogue of the q and k columns
         if xs == ss:
-            ops.linear(x_t, P[p + "qkv"], T.QKV[xs], ACT_ELU1, dma, act_cols=2 * C)
+            ops.linear(x_t, P[p + "qkv"], T.QKV[xs], ACT_ELU1, dma, act_cols=2 * C, health=self._health)
         else:
             if not have_q:
-                ops.linear(x_t, P[p + "q_proj"], T.QKV[xs, :C], ACT_ELU1, dma)
+                ops.linear(x_t, P[p + "q_proj"], T.QKV[xs, :C], ACT_ELU1, dma, health=self._health)
             if with_q_of_source:
-                ops.linear(s_t, P[p + "qkv"], T.QKV[ss], ACT_ELU1, dma, act_cols=2 * C)
+                ops.linear(s_t, P[p + "qkv"], T.QKV[ss], ACT_ELU1, dma, act_cols=2 * C, health=self._health)
             else:
-                ops.linear(s_t, P[p + "kv"], T.QKV[ss, C:], ACT_ELU1, dma, act_cols=C)
+                ops.linear(s_t, P[p + "kv"], T.QKV[ss, C:], ACT_ELU1, dma, act_cols=C, health=self._health)
         qm = T.MASK[xs] if T.MASK is not None else None  # x_mask / source_mask (transformer.py:50, attentions.py:35-39)
         km = T.MASK[ss] if T.MASK is not None else None
         fused = self.token_fused and (p + "tok") in P
@@ -671,11 +697,11 @@ class LoFTR(nn.Module):
             wts, lnp, eps = P[p + "tok"]
             ops.token_mlp(T.MSG[xs], T.CAT[xs, :C], T.X32[xs], wts, lnp, eps)   # x += norm2(mlp(cat[x, norm1(merge(msg))]))
             return
-        ops.linear(T.MSG[xs], P[p + "merge"], T.MRG[xs], ACT_NONE, dma)
+        ops.linear(T.MSG[xs], P[p + "merge"], T.MRG[xs], ACT_NONE, dma, health=self._health)
         g1, b1, e1 = P[p + "norm1"]
         ops.layernorm_residual(T.MRG[xs], g1, b1, None, None, T.CAT[xs, C:], e1)
-        ops.linear(T.CAT[xs], P[p + "mlp0"], T.HID[xs], ACT_RELU, dma)
-        ops.linear(T.HID[xs], P[p + "mlp2"], T.MLP[xs], ACT_NONE, dma)
+        ops.linear(T.CAT[xs], P[p + "mlp0"], T.HID[xs], ACT_RELU, dma, health=self._health)
+        ops.linear(T.HID[xs], P[p + "mlp2"], T.MLP[xs], ACT_NONE, dma, health=self._health)
         g2, b2, e2 = P[p + "norm2"]
         ops.layernorm_residual(T.MLP[xs], g2, b2, T.X32[xs], T.X32[xs], T.CAT[xs, :C], e2)  # x + message
 
@@ -938,7 +964,8 @@ class LoFTR(nn.Module):
         if count is None:
             count = torch.zeros(2 + bs, dtype=torch.int32, device=dev)
         # the fp16 range guard of the kernels in front of it is that word too, handed to every launch that stores a residual stream
-        self._health = count[1:2] if self.precision == "fp16" else None
+        # (fp32 mode with split products: every split launch ORs bit 8 into it when an operand left the fp16 range of its hi / lo halves)
+        self._health = count[1:2] if (self.precision == "fp16" or (self.precision == "fp32" and ops.FP32_SPLIT)) else None
         tdt = torch_dtype(dt)
         P = self._prepack(dev)
         cfg = self.config
@@ -1034,6 +1061,9 @@ class LoFTR(nn.Module):
 
     @torch.no_grad()
     def forward(self, data):
+        c0 = data.get("color0")
+        if self.precision == "fp32" and self.fp32_split and torch.is_tensor(c0) and c0.is_cuda:
+            self._prepack(c0.device)   # first: the packed weights' range check may turn fp32_split off
         if self.precision == "fp32" and self.fp32_split and not ops.FP32_SPLIT:
             ops.FP32_SPLIT = True   # (module state of gim_amd.ops, read at every fp32 conv / linear launch)
             try:
@@ -1139,10 +1169,17 @@ class LoFTR(nn.Module):
             self._count_pin.copy_(cr.count[:2])  # the one host sync the reference also has
             M, health = int(self._count_pin[0]), int(self._count_pin[1])
         if health:
-            if health & 6:
+            if health & 14:
                 cr.count[1:2].zero_()   # sticky bits: acknowledged
             if self._range_guard(health):
-                return self.forward(data)   # the module is in bf16 now: same inputs, once more
+                # the module is in bf16 now, or its fp32 mode multiplies exactly: same inputs, once more (the split switch of gim_amd.ops
+                # is module state that this forward's caller set: off for the re-run, restored after it)
+                split = ops.FP32_SPLIT
+                ops.FP32_SPLIT = False
+                try:
+                    return self.forward(data)
+                finally:
+                    ops.FP32_SPLIT = split
         self._generation += 1
         if not dev_count and M > 0:
             fine = self._fine_level(f0, f1, cr.b_ids[:M], cr.i_ids[:M], cr.j_ids[:M], cr.mkpts1_c[:M], scale1, "scale0" in data,
@@ -1183,13 +1220,22 @@ class LoFTR(nn.Module):
         other modes the inputs or weights themselves were not finite: warn only.  The reference computes in fp32 and has no such
         case (networks/loftr/utils/coarse_matching.py:174-195 would return no match for a NaN row, silently)."""
         import warnings
-        what = " and ".join(w for b, w in ((4, "a residual-stream value beyond 65504"), (1, "non-finite coarse similarities"),
-                                           (2, "non-finite fine-level outputs")) if health & b)
+        what = " and ".join(w for b, w in ((4, "a residual-stream value beyond 65504"), (8, "a split-product operand beyond 65504"),
+                                           (1, "non-finite coarse similarities"), (2, "non-finite fine-level outputs")) if health & b)
         if self.precision == "fp16":
             warnings.warn(f"gim_amd LoFTR: {what} in the fp16 mode (an activation left the IEEE-fp16 range); "
                           "falling back to precision='bf16' for this module and re-running the batch")
             self.fp16_overflowed = True
             self.set_precision("bf16", coarse_sim="fp32" if self.coarse_sim == "fp32" else None)   # a caller's fp32 similarity survives the fallback
+            return True
+        if self.precision == "fp32" and self.fp32_split and health & 8:
+            # bit 8 (gim_conv_args.split16): an activation or weight of a coarse-stage GEMM did not fit the IEEE-fp16 hi / lo split; the reference
+            # computes in plain fp32, so do the exact products
+            warnings.warn(f"gim_amd LoFTR: {what} in the fp32 mode: split products left the IEEE-fp16 range; "
+                          "falling back to exact fp32 products (fp32_split = False) for this module and re-running the batch")
+            self.split_overflowed = True
+            self.fp32_split = False
+            self._invalidate()
             return True
         warnings.warn(f"gim_amd LoFTR: {what} in the {self.precision} mode: the inputs or the weights are not finite")
         return False

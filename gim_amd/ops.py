@@ -185,8 +185,9 @@ def conv_rows(x, pk, geom, y, act=ACT_NONE, res=None, res_mod=0, lds_dma=True, a
     a.dtype, a.out_dtype = pk.dtype, gim_dtype(y)
     a.res_dtype = gim_dtype(res) if res is not None else GIM_F32
     a.use_lds_dma = (3 if FORCE_BIG_TILE else 1) if lds_dma else 0
-    a.health = _health(health).value if (health is not None and res is not None) else None
     a.split16 = 1 if (FP32_SPLIT and pk.dtype == GIM_F32 and lds_dma) else 0
+    # residual launches: the fp16 range guard (ORs 4); split launches: an operand beyond the fp16 range of the hi / lo split (ORs 8)
+    a.health = _health(health).value if (health is not None and (res is not None or a.split16)) else None
     assert y.shape[0] >= B * Ho * Wo and y.shape[1] >= pk.n_store
     if ups is not None:
         a.ups, a.ups_h, a.ups_w, a.ups_ld = ups.data_ptr(), ups.shape[1], ups.shape[2], ups.shape[3]
@@ -230,7 +231,7 @@ def conv2d(x, pk, act=ACT_NONE, res=None, out_dtype=None, lds_dma=True, ups=None
         return y
     if ups is not None:
         assert ups.shape == (B, Ho // 2, Wo // 2, pk.n_store) and res is None and ups.is_contiguous()
-        if not conv_rows(x.view(-1, cs), pk, geom, y.view(-1, pk.n_store), act, r, 0, lds_dma, ups=ups):
+        if not conv_rows(x.view(-1, cs), pk, geom, y.view(-1, pk.n_store), act, r, 0, lds_dma, ups=ups, health=health):
             upsample2x_add(ups, y)
         return y
     conv_rows(x.view(-1, cs), pk, geom, y.view(-1, pk.n_store), act, r, 0, lds_dma, health=health)
@@ -284,11 +285,11 @@ def conv3x3_halo(x, pk, y, act=ACT_NONE):
     PROFILE.append((e0, e1, 2.0 * B * H * W * pk.cout * pk.cin * 9, f"{pk.cin}->{pk.cout} k3s1 M={B * H * W} halo"))
 
 
-def linear(x, pk, y, act=ACT_NONE, lds_dma=True, act_cols=0):
+def linear(x, pk, y, act=ACT_NONE, lds_dma=True, act_cols=0, health=None):
     """x: row view [rows, >=K] (row stride may exceed K), y: row view [rows, >=N].  y = act(x @ W^T);
-    act_cols > 0 restricts the activation to output columns < act_cols."""
+    act_cols > 0 restricts the activation to output columns < act_cols.  health: see conv_rows (split launches only here)."""
     rows = x.shape[0]
-    conv_rows(x, pk, (1, 1, rows, 1, rows), y, act, None, 0, lds_dma, act_cols)
+    conv_rows(x, pk, (1, 1, rows, 1, rows), y, act, None, 0, lds_dma, act_cols, health=health)
 
 
 # ---- elementwise ------------------------------------------------------------------------------------

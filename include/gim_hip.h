@@ -40,7 +40,9 @@ enum { GIM_OK = 0, GIM_ERR_INVALID = -1, GIM_ERR_LAUNCH = -2, GIM_ERR_UNSUPPORTE
  * the old behaviour;
  * new entries gim_linear_attention_finalize, gim_linear_attention_ws_bytes_chunks.
  * 112 (round 6): gim_coarse_args.precand_per_row appended (zero it for the old behaviour); the library reads no environment variable.
- * 113 (round 6): gim_conv_args.split16 appended (zero it for the old behaviour). */
+ * 113 (round 6): gim_conv_args.split16 appended (zero it for the old behaviour).
+ * 114: health bit 8 -- a split16 launch handed a `health` word reports an operand that left the IEEE-fp16 range (gim_conv_args.split16);
+ * fp32-operand launches with split16 = 0 and a 16-bit output take exact fp32 products (version 113 sent some of them to the split loop). */
 int gim_version(void);
 /* fp16 range guard.  `health` (NULL: no check): a device word into which the fp16 flavour of the kernels that store un-normalised
  * residual streams (gim_bneck64_fused*, gim_bneck_tail*, gim_conv2d_bn_act with a residual operand) OR 4 when a converted value exceeds
@@ -121,11 +123,19 @@ typedef struct gim_conv_args {
                            over y.  Output rows = (image, Y < 2 ups_h, X < 2 ups_w); needs (2 ups_w) % 32 == 0 and a launch the 256 x 256 tile takes
                            (1x1 conv, bf16, no residual, npad % 256 == 0, >= 4 K slabs, >= 512 tiles): gim_conv_ups_supported() */
     int ups_h, ups_w, ups_ld;
-    int32_t* health;    /* fp16 range guard (see the top of this file) or NULL: checked where a residual operand is added (fp16 flavour) */
+    int32_t* health;    /* or NULL.  fp16 range guard (see the top of this file): checked where a residual operand is added (fp16 flavour).  Split launches
+                           (split16 = 1, version 114): bit 8 when an operand left the fp16 range (see split16) */
     int split16;        /* fp32 operands only (ABI 113).  0: products on v_mfma_f32_32x32x2_f32 (exact fp32 products).  1: every fp32 operand value is
                            split in registers into an IEEE-fp16 pair hi + lo and x w is evaluated as hi hi + hi lo + lo hi on v_mfma_f32_32x32x16_f16
                            with fp32 accumulation (weights scaled by 2^12 for the split, accumulators scaled back): 2^-22 relative per product at
-                           3/8 of the matrix-pipe time; needs |x| < 65504 and |w| < 16 (a value beyond becomes inf, the output NaN) */
+                           3/8 of the matrix-pipe time.  Range: |x| < 65520 and |w| < 65520 / 4096 = 15.996 (hi = rn16 of the value must be finite).
+                           Beyond it hi and lo become +-inf and every accumulator of that pixel row (or channel column) NaN -- which a ReLU
+                           epilogue turns into 0 -- so the launch ORs 8 into `health` (version 114; checked once per tile in the epilogue,
+                           before residual and activation).  Accuracy floor: hi + lo carries an activation to about 2^-22 of its value only while
+                           lo is a normal fp16 (|x| >= 2^-3); below, lo is subnormal and the error is up to 2^-25 absolute (the weights, scaled by
+                           2^12 first, keep 2^-37).  A layer whose activations ALL lie near 1e-5 is good to ~1e-3 of its output scale, near 1e-7
+                           to ~4e-2: a documented limit of the mode (tests/test_gpu_split16_range.py pins the bands).  Any value may be
+                           given with split16 = 0 (exact fp32 products). */
     int pad_;
 } gim_conv_args;
 int gim_conv_ups_supported(const gim_conv_args* a);   /* 1 if gim_conv2d_bn_act would take a->ups (set or not) for this launch */
@@ -188,7 +198,8 @@ int gim_layernorm_residual(const void* x, const float* gamma, const float* beta,
  * overflow survived the ReLUs in between; bit 1 (sticky, never cleared here) = gim_fine_fused_dev saw a non-finite fine-level
  * output on this buffer: a host that replays a captured graph on the same buffer learns it with the NEXT call's count read-back;
  * bit 2 (sticky) = the fp16 range guard: a kernel that stores an un-normalised residual stream converted a value beyond 65504
- * that was handed this word as its `health` argument.  The reference has no such word (fp32 has the range);
+ * that was handed this word as its `health` argument; bit 8 (sticky, version 114) = the split range guard: a gim_conv2d_bn_act launch with
+ * split16 = 1 that was handed this word met an fp32 operand beyond the fp16 range of its hi / lo split (gim_conv_args.split16).  The reference has no such word (fp32 has the range);
  * gim_amd/loftr/loftr.py reads it with the match count (coarse_matching.py:193's sync) and re-runs the batch in bf16.
  * scale0/scale1: NULL or fp32 [N,2] per-pair (w,h) scales (coarse_matching.py:237-245). */
 typedef struct gim_coarse_args {

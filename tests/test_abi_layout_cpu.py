@@ -54,3 +54,13 @@ def test_ctypes_mirror_matches_the_header(tmp_path, struct, mirror):
     assert out[0] == ctypes.sizeof(cls), (struct, out[0], ctypes.sizeof(cls))
     for n, off in zip(c_names, out[1:]):
         assert getattr(cls, n).offset == off, (struct, n, off, getattr(cls, n).offset)
+
+
+def test_abi_version_114():
+    """version 114: health bit 8 of the split launches (gim_conv_args.split16).  The library, the ctypes mirror and the header's revision list
+    agree on it: a caller bound to 113 would not know that the word it hands a split launch can come back with bit 8."""
+    from gim_amd import _lib
+    assert _lib.ABI_VERSION == 114 and _lib.lib.gim_version() == 114
+    src = open(HEADER).read()
+    assert re.findall(r"^ \* (\d{3})\b", src, re.M)[-1] == "114"
+    assert "ORs 8 into `health`" in re.search(r"int split16;(.*?)\*/", src, re.S).group(1)

@@ -207,3 +207,60 @@ def test_healthy_checkpoint_never_trips_the_guard():
         d3, msgs = _fwd(m3, c0, c1)
         assert not msgs, msgs
     assert m3.precision == "fp16" and not m3.fp16_overflowed and d3["b_ids"].numel() > 200
+
+
+# ---- the fp32 mode's split products (gim_conv_args.split16, LoFTR.fp32_split): range guard and fallback to exact fp32 products ----------------
+def _fp32_pair(sd, shape, fp32_split=True):
+    model, _ = S.synthetic_model("fp32", fp32_split=fp32_split)
+    model.load_state_dict({k: v.clone() for k, v in sd.items()})
+    return model.to("cuda:0")
+
+
+@pytest.mark.parametrize("shape", [(2, 192, 256), (1, 200, 264)], ids=["pairs-192x256", "odd-200x264"])
+@pytest.mark.parametrize("where", ["stream", "running_var"])
+def test_fp32_split_overflow_falls_back_to_exact_products(where, shape):
+    """`stream`: layer1.1's bn3 shift raised by 1e5 -- the residual stream goes beyond 65504 while every weight stays in range: the next
+    convolution's split launch sees an activation whose fp16 hi half is inf (bit 8 of the health word, read back with the match count).
+    `running_var`: three channels of layer2.0.bn2 with running_var = 0 -- the folded filter is ~316 x gamma x w, beyond 65504 / 4096 (caught when
+    the weights are packed, before the first launch).  Either way the module warns, turns fp32_split off and returns, for that very batch,
+    what a module built with fp32_split=False returns: exact fp32 products, the reference's arithmetic."""
+    n, H, W = shape
+    _, sd = S.synthetic_model("fp32")
+    sd = {k: v.clone() for k, v in sd.items()}
+    if where == "stream":
+        sd["backbone.encode.layer1.1.bn3.bias"] = sd["backbone.encode.layer1.1.bn3.bias"] + 1e5
+    else:
+        sd["backbone.encode.layer2.0.bn2.running_var"][:3] = 0.0
+    model = _fp32_pair(sd, shape)
+    assert model.fp32_split
+    c0, c1 = S.textured_pairs(n, H, W, seed=5)
+    d, msgs = _fwd(model, c0, c1)
+    assert any("exact fp32 products" in m for m in msgs), msgs
+    if where == "stream":
+        assert any("split-product operand beyond 65504" in m for m in msgs), msgs
+    assert not model.fp32_split and model.split_overflowed and model.precision == "fp32"
+    ref_model = _fp32_pair(sd, shape, fp32_split=False)
+    d2, msgs2 = _fwd(ref_model, c0, c1)
+    assert not msgs2, msgs2
+    for k in ("b_ids", "i_ids", "j_ids", "mconf", "mkpts1_f"):
+        assert torch.equal(d[k], d2[k]), k
+    # the next batches stay on exact products, eager and graphed, without another warning
+    for _ in range(2):
+        d3, msgs3 = _fwd(model, c0, c1)
+        assert not msgs3, msgs3
+    assert torch.equal(d3["mkpts1_f"], d2["mkpts1_f"]) and not model.fp32_split
+
+
+def test_fp32_split_healthy_checkpoint_never_trips_the_guard():
+    """the calibrated synthetic checkpoint in fp32 mode with split products: eager, capture and replays, no warning, fp32_split stays on,
+    and the split launches were handed the health word (bit 8 stayed clear)"""
+    from gim_amd import ops
+    model, _ = S.synthetic_model("fp32")
+    model = model.to("cuda:0")
+    assert model.fp32_split and not ops.FP32_SPLIT
+    c0, c1 = S.textured_pairs(2, 192, 256, seed=3)
+    for _ in range(4):   # eager, capture, replays
+        d, msgs = _fwd(model, c0, c1)
+        assert not msgs, msgs
+    assert model.fp32_split and not model.split_overflowed and d["b_ids"].numel() > 200
+    assert not ops.FP32_SPLIT   # the module's forward restores the switch
