@@ -166,6 +166,10 @@ PROTOTYPES = {
     "gim_dense_to_pixels": (c_int, [c_void_p] * 3 + [c_int] + [c_float] * 4 + [c_void_p]),
     "gim_weighted_sample_ws_bytes": (c_int64, [c_int]),
     "gim_weighted_sample": (c_int, [c_void_p] * 3 + [c_int, c_int, ctypes.c_uint32, c_void_p]),
+    # gim_semseg path (additive: the ABI revision stays 114)
+    "gim_ppm_pool": (c_int, [c_void_p] * 2 + [c_int] * 6 + [c_void_p]),
+    "gim_ppm_upsample_concat": (c_int, [c_void_p] * 2 + [c_int] * 7 + [c_void_p]),
+    "gim_seg_head_argmax": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
 }
 
 

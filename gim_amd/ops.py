@@ -218,8 +218,9 @@ def conv2d(x, pk, act=ACT_NONE, res=None, out_dtype=None, lds_dma=True, ups=None
     in the conv's epilogue when the launch supports it, otherwise as a second pass (gim_upsample2x_add)."""
     B, H, W, cs = x.shape
     assert cs == pk.cin_pad, (cs, pk)
-    Ho = (H + 2 * pk.pad - pk.kh) // pk.stride + 1
-    Wo = (W + 2 * pk.pad - pk.kw) // pk.stride + 1
+    d = getattr(pk, "dil", 1)       # dilated taps (packing.pack_conv(dilation=)): effective extent (k - 1) d + 1
+    Ho = (H + 2 * pk.pad - (pk.kh - 1) * d - 1) // pk.stride + 1
+    Wo = (W + 2 * pk.pad - (pk.kw - 1) * d - 1) // pk.stride + 1
     y = torch.empty(B, Ho, Wo, pk.n_store, dtype=out_dtype or x.dtype, device=x.device)
     r = res.view(-1, res.shape[-1]) if res is not None else None
     geom = (B, H, W, Ho, Wo)
@@ -1092,3 +1093,49 @@ def dense_to_pixels(matches, hw0, hw1):
     check(lib.gim_dense_to_pixels(_p(m), _p(k0), _p(k1), n, float(hw0[1]), float(hw0[0]), float(hw1[1]), float(hw1[0]), _stream()),
           "gim_dense_to_pixels")
     return k0, k1
+
+
+# ---- gim_semseg ------------------------------------------------------------------------------------------------
+PPM_SCALES = (1, 2, 3, 6)
+PPM_BINS = 50            # 1 + 4 + 9 + 36 pooled vectors per image, bins of scale s from offset PPM_OFFSETS[s]
+PPM_OFFSETS = {1: 0, 2: 1, 3: 5, 6: 14}
+
+
+def ppm_pool(x, C=None):
+    """x [B,H,W,ld] NHWC (ld >= C channels, e.g. the conv_last concat buffer) -> new fp32 [B,50,C]: adaptive average pooling to the
+    scales 1, 2, 3, 6 (bin order of PPM_OFFSETS, row-major per scale) in one launch (gim_ppm_pool)"""
+    _req_cuda(x)
+    B, H, W, ld = x.shape
+    C = ld if C is None else C
+    assert x.stride(2) == ld and x.stride(-1) == 1 and x.stride(0) == H * W * ld
+    out = torch.empty(B, PPM_BINS, C, dtype=torch.float32, device=x.device)
+    check(lib.gim_ppm_pool(_p(x), _p(out), B, H, W, C, ld, gim_dtype(x), _stream()), "gim_ppm_pool")
+    return out
+
+
+def ppm_upsample_concat(br, y, c_off):
+    """br fp32 [B,50,Cb] (the four branches after 1x1 conv + BN + ReLU) -> bilinear (align_corners=False) to y's h x w, written into
+    channels c_off + i Cb .. of y [B,h,w,ld] (gim_ppm_upsample_concat), in place"""
+    _req_cuda(br, y)
+    B, h, w, ld = y.shape
+    assert br.dtype == torch.float32 and br.is_contiguous() and br.shape[:2] == (B, PPM_BINS) and y.is_contiguous()
+    Cb = br.shape[2]
+    assert c_off + 4 * Cb <= ld
+    check(lib.gim_ppm_upsample_concat(_p(br), _p(y), B, h, w, Cb, ld, c_off, gim_dtype(y), _stream()), "gim_ppm_upsample_concat")
+
+
+def seg_head_argmax(logits, C, size, prob=False, flag=None):
+    """logits fp32 [B,h,w,ld] (C classes) -> uint8 class map [B,H,W] of the bilinear (align_corners=False) upsampling to size = (H, W)
+    and, prob=True, the fp32 maximum softmax probability [B,H,W] (gim_seg_head_argmax; the full-resolution logits are never stored).
+    flag: int32 device word ORed with 1 when a logit is not finite.  Returns cls or (cls, prob)."""
+    _req_cuda(logits, flag)
+    B, h, w, ld = logits.shape
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and C <= ld
+    H, W = int(size[0]), int(size[1])
+    cls = torch.empty(B, H, W, dtype=torch.uint8, device=logits.device)
+    pr = torch.empty(B, H, W, dtype=torch.float32, device=logits.device) if prob else None
+    if flag is not None:
+        assert flag.dtype == torch.int32 and flag.numel() >= 1
+    with _Timed("seg_head_argmax", 10.0 * B * H * W * C):   # 4 taps (7 flops) + the exponential / compare per class and pixel
+        check(lib.gim_seg_head_argmax(_p(logits), _p(cls), _p(pr), _p(flag), B, h, w, C, ld, H, W, _stream()), "gim_seg_head_argmax")
+    return (cls, pr) if prob else cls

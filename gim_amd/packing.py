@@ -49,7 +49,7 @@ def _round_up(x, m):
 
 class PackedConv:
     """One conv / linear layer in kernel layout."""
-    __slots__ = ("w", "bias", "ktab", "kh", "kw", "stride", "pad", "cin", "cin_pad", "cout", "n_store",
+    __slots__ = ("w", "bias", "ktab", "kh", "kw", "stride", "pad", "dil", "cin", "cin_pad", "cout", "n_store",
                  "npad", "kpad", "dtype", "halo")
 
     def __repr__(self):
@@ -149,8 +149,11 @@ def npad_for(cout):
     return npad
 
 
-def pack_conv(weight, bn, dtype, device, stride=1, pad=0, cin_pad=None, bias=None):
-    """weight [Cout, Cin, kh, kw] (or [out, in] for a Linear).  Returns PackedConv on `device`."""
+def pack_conv(weight, bn, dtype, device, stride=1, pad=0, cin_pad=None, bias=None, dilation=1):
+    """weight [Cout, Cin, kh, kw] (or [out, in] for a Linear).  Returns PackedConv on `device`.
+    dilation d > 1 (the segmenter's dilated ResNet, mit_semseg models.py:236-250): the K-group table stores the tap offsets dy * d,
+    dx * d -- the implicit GEMM reads them like any other tap, so no kernel changes -- and no halo pack is built (the halo kernel
+    hard-codes the 3 x 3 / pad-1 taps).  Callers pass pad = d for a same-size output."""
     if weight.dim() == 2:
         weight = weight[:, :, None, None]
     w, b = fold_bn(weight, bn)
@@ -177,7 +180,8 @@ def pack_conv(weight, bn, dtype, device, stride=1, pad=0, cin_pad=None, bias=Non
     gidx = torch.arange(ngrp, dtype=torch.int64) * g
     tap = gidx // cin_pad
     c = gidx % cin_pad
-    dy, dx = tap // kw, tap % kw
+    assert dilation >= 1 and (max(kh, kw) - 1) * dilation <= 254, "tap offsets are 8-bit fields, 255 is the K-padding sentinel"
+    dy, dx = tap // kw * dilation, tap % kw * dilation
     ent = c | (dx << 16) | (dy << 24)
     ent = torch.where(tap < kh * kw, ent, torch.full_like(ent, 0xFF000000))
     ent = torch.where(ent >= 2 ** 31, ent - 2 ** 32, ent).to(torch.int32)
@@ -191,12 +195,12 @@ def pack_conv(weight, bn, dtype, device, stride=1, pad=0, cin_pad=None, bias=Non
     else:
         p.bias = None
     p.ktab = ent.to(device)
-    p.kh, p.kw, p.stride, p.pad = kh, kw, stride, pad
+    p.kh, p.kw, p.stride, p.pad, p.dil = kh, kw, stride, pad, dilation
     p.cin, p.cin_pad, p.cout = cin, cin_pad, cout
     p.n_store = cstore(cout, dtype)
     p.npad, p.kpad, p.dtype = npad, kpad, dtype
     p.halo = None
-    if is_half(dtype) and kh == 3 and kw == 3 and stride == 1 and pad == 1:
+    if is_half(dtype) and kh == 3 and kw == 3 and stride == 1 and pad == 1 and dilation == 1:
         wh, tab, nslab = pack_halo(wp, cin_pad, device, torch_dtype(dtype))
         bh = p.bias
         if bh is not None and wh.shape[0] > npad:      # the halo kernel's N tile is 128 wide: its bias reads cover wh.shape[0] entries

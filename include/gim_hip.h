@@ -605,6 +605,26 @@ int gim_dense_to_pixels(const float* matches, float* kpts0, float* kpts1, int n,
 int64_t gim_weighted_sample_ws_bytes(int n);
 int gim_weighted_sample(const float* w, int64_t* out, void* ws, int n, int k, uint32_t seed, gim_stream_t stream);
 
+/* ======================================================================================================
+ * gim_semseg path: the CSAIL ADE20K-150 segmenter of gim's SfM / video paths (networks/mit_semseg, ResnetDilated + PPMDeepsup).
+ * Its convolutions (dilated 3x3s included: the K-group table stores dy*d, dx*d) run on gim_conv2d_bn_act; these three are the rest.
+ * ====================================================================================================== */
+
+/* nn.AdaptiveAvgPool2d(s) of conv5 for s = 1, 2, 3, 6 in one launch -- models.py:446-451, 472-477.  x [B,H,W] rows of ldx (C channels,
+ * `dtype`); out fp32 [B][50][C]: bins of s = 1, 2, 3, 6 from offsets 0, 1, 5, 14, row-major.  Bin i of s spans [floor(i H / s),
+ * ceil((i + 1) H / s)) (bins overlap when H < s).  C % 4 == 0. */
+int gim_ppm_pool(const void* x, float* out, int B, int H, int W, int C, int ldx, int dtype, gim_stream_t stream);
+/* F.interpolate(bilinear, align_corners=False) of the four branch outputs (after 1x1 conv + BN + ReLU) from s x s to h x w, written into
+ * channels c_off + i * Cb .. of y (rows [B*h*w][ldy], `dtype`): the concat buffer of conv_last, no torch.cat -- models.py:471-478.
+ * br fp32 [B][50][Cb] in gim_ppm_pool's bin order. */
+int gim_ppm_upsample_concat(const float* br, void* y, int B, int h, int w, int Cb, int ldy, int c_off, int dtype, gim_stream_t stream);
+/* Inference tail of PPMDeepsup.forward + segment()'s torch.max -- models.py:482-486, hloc/utils/__init__.py:42-49: logits fp32 rows
+ * [B*h*w][ld] (C <= 256 classes) upsampled bilinearly (align_corners=False) to H x W per output pixel, arg-max over the classes (the
+ * lowest index wins a tie) -> cls uint8 [B][H][W]; prob (NULL: not written) fp32 [B][H][W] = the maximum softmax probability.  The
+ * full-resolution C-channel tensor is never written.  flag (NULL: no check): a device word ORed with 1 when a logit is not finite. */
+int gim_seg_head_argmax(const float* logits, uint8_t* cls, float* prob, int* flag, int B, int h, int w, int C, int ld, int H, int W,
+                        gim_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
