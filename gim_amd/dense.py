@@ -1,0 +1,282 @@
+"""What the two dense matchers (gim_dkm, gim_roma) are made of: the ConvRefiner cascade and the GP of the reference's
+`networks/dkm/models/dkm.py` / `networks/roma/roma.py` (RoMa's are DKM's with other sizes), and the shared part of their
+`RegressionMatcher` surface -- `match`, the head and tail of `match_batch`, `sample` and the caller-side adapter.
+
+Each engine keeps its encoder, its coarse stage and its `_decode` / `match_batch` body (gim_amd/dkm/dkm.py, gim_amd/roma/roma.py).
+"""
+import math
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import ops
+from ._lib import GIM_F32, GimHipError
+from .packing import PRECISION_DTYPE, cstore, is_half, pack_conv, torch_dtype
+from .switches import flag, tri_flag
+
+HIDDEN_BLOCKS = 8
+
+
+def refiner_dims(refiner_table, scale):
+    """(input channels, hidden channels) of the scale's ConvRefiner; refiner_table[scale] = (feature channels, displacement
+    embedding channels, local-correlation radius or None)"""
+    c, e, r = refiner_table[scale]
+    in_dim = 2 * c + e + ((2 * r + 1) ** 2 if r else 0)
+    return in_dim, {"2": 128 + 16, "1": 24}.get(scale, in_dim)
+
+
+# ---------------------------------------------------------------------------------------- parameter containers
+class GP(nn.Module):
+    def __init__(self, dim):
+        super().__init__()
+        self.pos_conv = nn.Conv2d(2, dim, 1)
+
+
+def _block(ci, co, bn_momentum):
+    return nn.Sequential(nn.Conv2d(ci, co, 5, 1, 2, groups=ci), nn.BatchNorm2d(co, momentum=bn_momentum), nn.ReLU(inplace=True),
+                         nn.Conv2d(co, co, 1))
+
+
+class ConvRefiner(nn.Module):
+    def __init__(self, in_dim, hid, emb_dim, bn_momentum=0.1):
+        super().__init__()
+        self.block1 = _block(in_dim, hid, bn_momentum)
+        self.hidden_blocks = nn.Sequential(*[_block(hid, hid, bn_momentum) for _ in range(HIDDEN_BLOCKS)])
+        self.out_conv = nn.Conv2d(hid, 3, 1)
+        self.disp_emb = nn.Conv2d(2, emb_dim, 1)
+
+
+def _bn_after_bias(bn, bias):
+    """eval BatchNorm applied to conv(x) + bias == BatchNorm with mean - bias applied to conv(x)"""
+    return (bn.weight, bn.bias, bn.running_mean - bias, bn.running_var, bn.eps)
+
+
+# ---------------------------------------------------------------------------------------- ConvRefiner
+def pack_refiner(P, s, ref, in_dim, hid, dt, device):
+    """ConvRefiner `ref` of scale s -> P[cr{s}.{i}.dw / .pw / .pwf], P[cr{s}.out / .emb / .cin_store]"""
+    blocks = [ref.block1] + list(ref.hidden_blocks)
+    for i, blk in enumerate(blocks):
+        conv, bn, _, pw = blk
+        ci = in_dim if i == 0 else hid
+        cpad = cstore(hid, dt)
+        sc = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
+        W = torch.zeros(25, cpad)
+        W[:, :hid] = conv.weight.detach().float().reshape(hid, 25).t().cpu()
+        scale, shift = torch.zeros(cpad), torch.zeros(cpad)
+        scale[:hid] = sc.cpu()
+        shift[:hid] = (bn.bias.detach().float() + (conv.bias.detach().float() - bn.running_mean.detach().float()) * sc).cpu()
+        P[f"cr{s}.{i}.dw"] = (W.to(device), scale.to(device), shift.to(device), ci, hid)
+        P[f"cr{s}.{i}.pw"] = pack_conv(pw.weight, None, dt, device, cin_pad=cpad, bias=pw.bias)
+        if dt != GIM_F32 and cpad in (24, 32, 144) and ci == hid:   # refiner blocks that fit one launch (gim_dwconv5x5_pw): dw 5x5 + BN + ReLU + 1x1
+            npc, kp = (160, 144) if cpad == 144 else (32, 32)
+            wf, bf = torch.zeros(npc, kp), torch.zeros(npc)
+            wf[:hid, :hid] = pw.weight.detach().float().reshape(hid, hid).cpu()
+            bf[:hid] = pw.bias.detach().float().cpu()
+            P[f"cr{s}.{i}.pwf"] = (wf.to(device).to(torch_dtype(dt)).contiguous(), bf.to(device))
+    P[f"cr{s}.out"] = pack_conv(ref.out_conv.weight, None, dt, device, cin_pad=cstore(hid, dt), bias=ref.out_conv.bias)
+    P[f"cr{s}.emb"] = (ref.disp_emb.weight.detach().float().reshape(-1, 2).contiguous().to(device),
+                       ref.disp_emb.bias.detach().float().contiguous().to(device))
+    P[f"cr{s}.cin_store"] = cstore(in_dim, dt)
+
+
+def refine(P, s, dt, x, y, flow, cert, ins, full_hw, dims, fused, emb_scale=None, roma_layout=False):
+    """ConvRefiner.forward + the flow / certainty update of Decoder.forward (dkm.py:75-123, 498-514; roma.py:529-580, 318-331).
+    dims = (c, e, r) of the engine's refiner table; fused: wide-enough blocks as one launch (gim_dwconv5x5_pw);
+    emb_scale: RoMa's disp_emb(40/32 * scale_factor * (flow - coords)), roma.py:545-547; roma_layout: its (dx, dy, certainty) order."""
+    tdt = torch_dtype(dt)
+    b, h, w, _ = x.shape
+    c, e, r = dims
+    cs = P[f"cr{s}.cin_store"]
+    dev = x.device
+    g = 8 if is_half(dt) else 4
+    ew, eb = P[f"cr{s}.emb"]
+    if emb_scale is not None:
+        ew = ew * emb_scale
+    if c % g == 0:
+        D = torch.zeros(b, h, w, cs, dtype=tdt, device=dev)
+        rows = D.view(b * h * w, cs)
+        D[..., :c].copy_(x[..., :c])
+        ops.grid_sample(y, flow, rows[:, c:2 * c])
+        ops.dkm_disp_emb(flow, ew, eb, rows[:, 2 * c:])
+        if r:
+            ops.local_corr(x, y, flow, r, rows[:, 2 * c + e:])
+    else:  # scale 1: 3 image / 9 projected channels (stored with padding) -> assemble the 12- / 24-channel input with copies
+        xh = torch.empty(b * h * w, x.shape[3], dtype=tdt, device=dev)
+        ops.grid_sample(y, flow, xh)
+        emb = torch.empty(b * h * w, cstore(e, dt), dtype=tdt, device=dev)
+        ops.dkm_disp_emb(flow, ew, eb, emb)
+        D = torch.zeros(b, h, w, cs, dtype=tdt, device=dev)
+        D[..., :c].copy_(x[..., :c])
+        D[..., c:2 * c].copy_(xh.view(b, h, w, -1)[..., :c])
+        D[..., 2 * c:2 * c + e].copy_(emb.view(b, h, w, -1)[..., :e])
+    d = D
+    for i in range(1 + HIDDEN_BLOCKS):
+        W_, sc, sh, ci, co = P[f"cr{s}.{i}.dw"]
+        pwf = P.get(f"cr{s}.{i}.pwf") if fused else None
+        if pwf is not None and d.shape[3] == W_.shape[1] and d.is_contiguous():
+            d = ops.dwconv5x5_pw(d, W_, sc, sh, *pwf)   # the whole block in one launch: the depthwise output never leaves the CU
+            continue
+        d = ops.dwconv5x5_bn_relu(d, W_, sc, sh, ci, co)
+        d = ops.conv2d(d, P[f"cr{s}.{i}.pw"])
+    out = torch.empty(b * h * w, P[f"cr{s}.out"].n_store, dtype=torch.float32, device=dev)
+    ops.linear(d.view(b * h * w, d.shape[3]), P[f"cr{s}.out"], out)
+    ops.dkm_flow_update(flow, cert, out, ins / (4.0 * full_hw[1]), ins / (4.0 * full_hw[0]), roma_layout=roma_layout)
+
+
+# ---------------------------------------------------------------------------------------- GP
+def gp_features(pos_conv, h, w, dim):
+    """f = cos(8 pi pos_conv(coords)) of GP.get_pos_enc (dkm.py:314-331, roma.py:94-108): constant per (h, w); built on the host
+    with the reference's fp32 ops as rows [h*w, dim] (the engines cache it on the device)."""
+    ys = torch.linspace(-1 + 1 / h, 1 - 1 / h, h)
+    xs = torch.linspace(-1 + 1 / w, 1 - 1 / w, w)
+    gy, gx = torch.meshgrid(ys, xs, indexing="ij")
+    coords = torch.stack((gx, gy))[None]
+    f = torch.cos(8 * math.pi * F.conv2d(coords, pos_conv.weight.detach().float().cpu(), pos_conv.bias.detach().float().cpu()))
+    return f[0].permute(1, 2, 0).reshape(h * w, dim).contiguous()
+
+
+def gp_posterior(a32, nb, h, w, f, out, exact):
+    """GP.forward, no_cov (dkm.py:340-370, roma.py:110-136) for all nb = 2 * pairs directions (image d is matched against image
+    (d + nb/2) % nb).  a32: fp32 rows [nb*hw (+64 slack), 512] of the projected features; f: gp_features rows [hw, dim] on the
+    device; writes mu into `out` (row view [nb*hw, dim]).  exact (fp32 `out` only): every step in fp64 (gim_gp_posterior_f64);
+    otherwise the fp32 kernel matrix on the MFMA + fp64 Cholesky."""
+    dev = a32.device
+    n = h * w
+    half = nb // 2
+    dim = f.shape[1]
+    if exact and out.dtype == torch.float32:
+        X = a32[:nb * n].view(nb, n, 512)
+        ops.gp_posterior_f64(X, X.roll(-half, 0).contiguous(), f, out, 0.2, 1e-6, 0.1)   # support of direction b: image (b + half) % nb
+        return
+    nrm = ops.row_norms(a32[:nb * n], 512)
+    ld = (n + 63) // 64 * 64
+    npad = (n + 31) // 32 * 32
+    Kyy = torch.zeros(nb, n, ld, dtype=torch.float32, device=dev)
+    Kxy = torch.zeros(nb, n, max(ld, npad), dtype=torch.float32, device=dev)
+    for b in range(nb):
+        o = (b + half) % nb                              # support of direction b = the other image of its pair
+        ops.matmul_nt(a32[o * n:(o + 1) * n], a32[o * n:], n, Kyy[b])
+        ops.matmul_nt(a32[b * n:(b + 1) * n], a32[o * n:], n, Kxy[b])
+    ny = nrm.view(nb, n).roll(-half, 0).contiguous().view(-1)
+    ops.cos_kernel_finish(Kyy.view(nb * n, ld), ny, ny, nb, n, n, 0.2, 1e-6, 0.1)        # K_yy + sigma_noise I
+    ops.cos_kernel_finish(Kxy.view(nb * n, Kxy.shape[2]), nrm, ny, nb, n, n, 0.2, 1e-6, 0.0)
+    Xt = ops.gp_solve(Kyy, f[None].expand(nb, n, dim).contiguous(), npad)
+    for b in range(nb):
+        ops.matmul_nt(Kxy[b][:, :npad], Xt[b], dim, out[b * n:(b + 1) * n])      # mu = K_xy (K_yy + sigma I)^-1 f
+
+
+# ---------------------------------------------------------------------------------------- the matcher surface
+class DenseMatcher(nn.Module):
+    """What `RegressionMatcher` of gim_dkm and gim_roma have in common.  A subclass sets `engine`, `max_batch`, `kde_half`, creates
+    `self.precision` and its parameter tree, and provides `_prepack(device)` (-> `self._packed = (P, dt, device)`) and `match_batch`."""
+    engine = None       # name in messages
+    max_batch = None    # pairs per match_batch call
+    kde_half = False    # sample(): the KDE on fp16-rounded coordinates (roma.py:1018-1023)
+
+    def __init__(self, h, w, sample_mode, upsample_preds, symmetric, name):
+        super().__init__()
+        self.w_resized, self.h_resized = w, h
+        self.sample_mode = sample_mode
+        self.upsample_preds = upsample_preds
+        self.symmetric = symmetric
+        self.name = name
+        self.sample_thresh = 0.05
+        # GP posterior entirely in fp64 (kernel entries, Cholesky, products; csrc/gp_solve.hip: gim_gp_posterior_f64).  None = in
+        # the fp32 parity mode only: the system's condition number (~2e4) turns fp32 rounding of the kernel ENTRIES into ~1e-4 of mu,
+        # the one term of the engine's deviation that is not the reference's own (tests/test_gpu_gp_pins.py)
+        self.gp_exact = tri_flag("gp_exact")
+        # 16-bit modes: the 144- and 24-channel ConvRefiner blocks (scales 2 and 1, both passes) as ONE launch each (gim_dwconv5x5_pw, round 5)
+        self.refiner_fused = flag("refiner_fused", True)
+        self._packed = None
+
+    def _gp_is_exact(self):
+        return (self.precision == "fp32") if self.gp_exact is None else self.gp_exact
+
+    def _images(self, dt, im1, im2, hs, ws):
+        """[B,3,H,W] x 2 -> NHWC [2B, hs, ws, cpad]: queries first, then supports (extract_backbone_features, dkm.py:572-581,
+        roma.py:668-678)"""
+        B = im1.shape[0]
+        x = torch.empty(2 * B, hs, ws, cstore(3, dt), dtype=torch_dtype(dt), device=im1.device)
+        ops.resize_image(im1, x, 0)
+        ops.resize_image(im2, x, B)
+        return x
+
+    @torch.no_grad()
+    def match(self, im1, im2, *args, batched=False):
+        """RegressionMatcher.match (dkm.py:654-752, roma.py:816-917), tensor inputs as gim calls it (`demo.py:433`,
+        `lightning.py:135`): [1,3,H,W] x 2 -> (warp [Hs, 2Ws, 4], certainty [Hs, 2Ws])."""
+        if batched or not self.symmetric:
+            raise NotImplementedError(f"gim runs {self.engine} symmetric and non-batched (lightning.py:30-37); use match_batch for several pairs")
+        if im1.dim() != 4 or im1.shape[0] != 1:
+            raise GimHipError(f"match() takes [1,3,H,W] images, got {tuple(im1.shape)}")
+        warp, certainty = self.match_batch(im1, im2)
+        return warp[0], certainty[0]
+
+    def _enter(self, im1, im2):
+        """head of match_batch: argument checks, packing on demand -> (P, dt, im1, im2 as contiguous fp32)"""
+        if not self.symmetric:
+            raise NotImplementedError("only symmetric matching is built")
+        if not im1.is_cuda:
+            raise GimHipError(f"gim_amd {self.engine} needs device (cuda/HIP) tensors: there is no CPU fallback")
+        if im1.dim() != 4 or im1.shape[1] != 3 or im1.shape != im2.shape or not 1 <= im1.shape[0] <= self.max_batch:
+            raise GimHipError(f"match takes two [B,3,H,W] batches of equal shape with B <= {self.max_batch}, "
+                              f"got {tuple(im1.shape)} / {tuple(im2.shape)}")
+        if self._packed is None or self._packed[2] != im1.device or self._packed[1] != PRECISION_DTYPE[self.precision]:
+            self._prepack(im1.device)
+        P, dt, _ = self._packed
+        return P, dt, im1.contiguous().float(), im2.contiguous().float()
+
+    def _finish(self, im1, im2, flow, cert, low, hs, ws):
+        """tail of match_batch (dkm.py:686-752, roma.py:880-917): flow / cert / low [2B,hs,ws,*] of both directions ->
+        (warp [B,hs,2ws,4], certainty [B,hs,2ws])"""
+        B, dev = im1.shape[0], im1.device
+        warp = torch.empty(B, hs, 2 * ws, 4, dtype=torch.float32, device=dev)
+        certainty = torch.empty(B, hs, 2 * ws, dtype=torch.float32, device=dev)
+        for b in range(B):
+            ops.dkm_match_post((flow[b], flow[b + B]), (cert[b], cert[b + B]), (low[b], low[b + B]),
+                               ops.dkm_black_mask(im1[b:b + 1], (hs, ws)), ops.dkm_black_mask(im2[b:b + 1], (hs, ws)), warp[b], certainty[b])
+        return warp, certainty
+
+    @torch.no_grad()
+    def sample(self, dense_matches, dense_certainty, num=10000):
+        """RegressionMatcher.sample (dkm.py:583-620, roma.py:680-714).  The two multinomial draws are `gim_weighted_sample` (seeded
+        from torch's generator), the balanced-sampling density is the HIP KDE kernel; samples come back as an unordered set."""
+        return balanced_sample(dense_matches, dense_certainty, num, self.sample_mode, self.sample_thresh, kde_half=self.kde_half)
+
+
+@torch.no_grad()
+def balanced_sample(dense_matches, dense_certainty, num, sample_mode, sample_thresh, kde_half):
+    """`sample()` of both dense matchers (dkm.py:583-620, roma.py:680-714): certainty above the threshold counts as 1, draw
+    4 * num matches without replacement, re-draw num of them with weights 1 / (1 + KDE density)."""
+    if "threshold" not in sample_mode or "balanced" not in sample_mode:
+        raise NotImplementedError("gim uses sample_mode='threshold_balanced' (DKMv3.py:5, roma.py:645)")
+    cert_ = dense_certainty.reshape(-1).contiguous()
+    matches = dense_matches.reshape(-1, 4)
+    cert = torch.where(cert_ > sample_thresh, torch.ones_like(cert_), cert_)   # dense_certainty[> thresh] = 1
+    n_pos = int((cert > 0).sum())
+    if n_pos == 0:
+        cert, n_pos = cert + 1e-8, cert.numel()
+    seeds = torch.randint(0, 2 ** 31 - 1, (2,)).tolist()      # torch's (CPU) generator: torch.manual_seed makes sample() reproducible
+    # the kernel returns an unordered set (atomic compaction); sorting makes sample() reproducible from the seed
+    good = ops.weighted_sample(cert, min(4 * num, cert.numel(), n_pos), seeds[0]).sort().values
+    gm, gc = matches[good].contiguous(), cert_[good]
+    density = ops.kde(gm, 0.1, half=kde_half)
+    p = torch.where(density < 10, torch.full_like(density, 1e-7), 1 / (density + 1))
+    bal = ops.weighted_sample(p.contiguous(), min(num, len(gc)), seeds[1]).sort().values
+    return gm[bal], gc[bal]
+
+
+@torch.no_grad()
+def gim_dkm_inference(model, data, num=5000):
+    """`Trainer.gim_dkm_inference` (trainer/lightning.py:134-156; the same adapter serves gim_roma, lightning.py:125): match + sample +
+    pixel coordinates + `mconf > 0` filter, written into `data` (hw0_i, hw1_i, mkpts0_f, mkpts1_f, m_bids, mconf).  data: color0 /
+    color1 [1,3,H,W], imsize0 / imsize1 [1,2] = (height, width) of the un-padded images."""
+    dense_matches, dense_certainty = model.match(data["color0"], data["color1"])
+    sparse_matches, mconf = model.sample(dense_matches, dense_certainty, num)
+    h0, w0 = (float(v) for v in data["imsize0"][0])
+    h1, w1 = (float(v) for v in data["imsize1"][0])
+    kpts0, kpts1 = ops.dense_to_pixels(sparse_matches, (h0, w0), (h1, w1))
+    mask = mconf > 0
+    data.update({"hw0_i": data["color0"].shape[2:], "hw1_i": data["color1"].shape[2:], "mkpts0_f": kpts0[mask], "mkpts1_f": kpts1[mask],
+                 "m_bids": torch.where(mconf[None])[0], "mconf": mconf[mask]})

@@ -18,44 +18,29 @@ projections and the GP's kernel / posterior products on the implicit-GEMM kernel
 host with the reference's own fp32 ops.  `sample()` draws with torch's generator like the reference (the RNG contract
 is "same distribution"); the KDE is a HIP kernel.  No CPU / eager fallback.
 """
-import math
-import os
-
 import torch
-
-from ..precision import resolve as resolve_precision
-from ..switches import flag, tri_flag
 import torch.nn as nn
-import torch.nn.functional as F
 
 from .. import ops
-from .._lib import ACT_NONE, ACT_RELU, GIM_BF16, GIM_F16, GIM_F32, GimHipError
-from ..packing import cstore, pack_conv, torch_dtype
+from .._lib import ACT_RELU, GIM_F32, GimHipError
+from ..dense import (GP, ConvRefiner, DenseMatcher, _bn_after_bias, balanced_sample, gim_dkm_inference,  # noqa: F401  (re-exported)
+                     gp_features, gp_posterior, pack_refiner, refine, refiner_dims)
+from ..packing import PRECISION_DTYPE, bn_params as _bn, cstore, pack_conv, torch_dtype
+from ..precision import resolve as resolve_precision
+from ..resnet50 import LAYERS, add_layers, bottleneck, pack_bottlenecks
+from ..switches import flag
 
 REFINER = {"16": (512, 128, 7), "8": (512, 64, 3), "4": (256, 32, 2), "2": (64, 16, None), "1": (3, 6, None)}
-GP_DIM, DFN_DIM, FEAT_DIM, HIDDEN_BLOCKS = 256, 384, 256, 8
+GP_DIM, DFN_DIM, FEAT_DIM = 256, 384, 256
 
 
-def _refiner_dims(scale):
-    c, e, r = REFINER[scale]
-    in_dim = 2 * c + e + ((2 * r + 1) ** 2 if r else 0)
-    return in_dim, {"2": 128 + 16, "1": 24}.get(scale, in_dim)
+def _stride_schedule(li, bi):
+    """torchvision resnet50: layers 2..4 halve the resolution in their first block; no dilation"""
+    first = 2 if li > 1 and bi == 0 else 1
+    return first, 1, first
 
 
 # ---------------------------------------------------------------------------------------- parameter containers
-class _Bottleneck(nn.Module):
-    def __init__(self, inpl, planes, stride, downsample):
-        super().__init__()
-        self.conv1 = nn.Conv2d(inpl, planes, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
-        self.conv2 = nn.Conv2d(planes, planes, 3, stride, 1, bias=False)
-        self.bn2 = nn.BatchNorm2d(planes)
-        self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
-        self.bn3 = nn.BatchNorm2d(planes * 4)
-        self.downsample = downsample
-        self.stride = stride
-
-
 class _ResNet50(nn.Module):
     """torchvision resnet50 parameter layout without fc (encoders.py:30-41)"""
 
@@ -63,16 +48,7 @@ class _ResNet50(nn.Module):
         super().__init__()
         self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
-        inpl = 64
-        for li, (planes, nblk, stride) in enumerate(((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2)), start=1):
-            blocks = []
-            for bi in range(nblk):
-                ds = None
-                if bi == 0:
-                    ds = nn.Sequential(nn.Conv2d(inpl, planes * 4, 1, stride, bias=False), nn.BatchNorm2d(planes * 4))
-                blocks.append(_Bottleneck(inpl, planes, stride if bi == 0 else 1, ds))
-                inpl = planes * 4
-            setattr(self, f"layer{li}", nn.Sequential(*blocks))
+        add_layers(self, 64, _stride_schedule)
 
 
 class _Encoder(nn.Module):
@@ -109,68 +85,28 @@ class _DFN(nn.Module):
         self.terminal_module = nn.ModuleDict({k: nn.Conv2d(DFN_DIM, 3, 1) for k in ks})
 
 
-class _GP(nn.Module):
-    def __init__(self):
-        super().__init__()
-        self.pos_conv = nn.Conv2d(2, GP_DIM, 1)
-
-
-def _block(ci, co):
-    return nn.Sequential(nn.Conv2d(ci, co, 5, 1, 2, groups=ci), nn.BatchNorm2d(co), nn.ReLU(inplace=True), nn.Conv2d(co, co, 1))
-
-
-class _ConvRefiner(nn.Module):
-    def __init__(self, scale):
-        super().__init__()
-        in_dim, hid = _refiner_dims(scale)
-        self.block1 = _block(in_dim, hid)
-        self.hidden_blocks = nn.Sequential(*[_block(hid, hid) for _ in range(HIDDEN_BLOCKS)])
-        self.out_conv = nn.Conv2d(hid, 3, 1)
-        self.disp_emb = nn.Conv2d(2, REFINER[scale][1], 1)
-
-
 class _Decoder(nn.Module):
     def __init__(self):
         super().__init__()
         self.embedding_decoder = _DFN()
-        self.gps = nn.ModuleDict({"32": _GP(), "16": _GP()})
+        self.gps = nn.ModuleDict({"32": GP(GP_DIM), "16": GP(GP_DIM)})
         self.proj = nn.ModuleDict({"16": nn.Conv2d(1024, 512, 1), "32": nn.Conv2d(2048, 512, 1)})
-        self.conv_refiner = nn.ModuleDict({s: _ConvRefiner(s) for s in REFINER})
+        self.conv_refiner = nn.ModuleDict({s: ConvRefiner(*refiner_dims(REFINER, s), REFINER[s][1]) for s in REFINER})
 
 
-def _bn(m):
-    return (m.weight, m.bias, m.running_mean, m.running_var, m.eps)
+class RegressionMatcher(DenseMatcher):
+    engine, max_batch, kde_half = "DKM", 8, False
 
-
-def _bn_after_bias(bn, bias):
-    """eval BatchNorm applied to conv(x) + bias == BatchNorm with mean - bias applied to conv(x)"""
-    return (bn.weight, bn.bias, bn.running_mean - bias, bn.running_var, bn.eps)
-
-
-class RegressionMatcher(nn.Module):
     def __init__(self, h=384, w=512, sample_mode="threshold_balanced", upsample_preds=True, symmetric=True, name=None,
                  use_soft_mutual_nearest_neighbours=False, precision=None, **kwargs):
-        super().__init__()
+        super().__init__(h, w, sample_mode, upsample_preds, symmetric, name)
         self.encoder = _Encoder()
         self.decoder = _Decoder()
-        self.w_resized, self.h_resized = w, h
-        self.sample_mode = sample_mode
-        self.upsample_preds = upsample_preds
-        self.symmetric = symmetric
-        self.name = name
-        self.sample_thresh = 0.05
         self.upsample_res = (1152, 1536)
         self.use_soft_mutual_nearest_neighbours = use_soft_mutual_nearest_neighbours
         self.precision = resolve_precision(precision, "gim_dkm")
-        # GP posterior entirely in fp64 (kernel entries, Cholesky, products; csrc/gp_solve.hip: gim_gp_posterior_f64).  None = in
-        # the fp32 parity mode only: the system's condition number (~2e4) turns fp32 rounding of the kernel ENTRIES into ~1e-4 of mu,
-        # the one term of the engine's deviation that is not the reference's own (tests/test_gpu_gp_pins.py)
-        self.gp_exact = tri_flag("gp_exact")
-        self._packed = None
         self._gp_f = {}
         self.overlap_gp = flag("dkm_overlap", True)   # GP on a side stream beside the high-res encoder
-        # 16-bit modes: the 144- and 24-channel ConvRefiner blocks (scales 2 and 1, both passes) as ONE launch each (gim_dwconv5x5_pw, round 5)
-        self.refiner_fused = flag("refiner_fused", True)
 
     def load_state_dict(self, state_dict, *a, **k):
         self._packed = None
@@ -184,18 +120,11 @@ class RegressionMatcher(nn.Module):
 
     # ---- one-time packing -------------------------------------------------------------------------------------
     def _prepack(self, device):
-        dt = {"bf16": GIM_BF16, "fp16": GIM_F16, "fp32": GIM_F32}[self.precision]
+        dt = PRECISION_DTYPE[self.precision]
         P = {}
         net = self.encoder.net
         P["stem"] = pack_conv(net.conv1.weight, _bn(net.bn1), dt, device, stride=2, pad=3, cin_pad=cstore(3, dt))
-        for li in (1, 2, 3, 4):
-            for bi, blk in enumerate(getattr(net, f"layer{li}")):
-                p = f"l{li}.{bi}."
-                P[p + "c1"] = pack_conv(blk.conv1.weight, _bn(blk.bn1), dt, device)
-                P[p + "c2"] = pack_conv(blk.conv2.weight, _bn(blk.bn2), dt, device, stride=blk.stride, pad=1)
-                P[p + "c3"] = pack_conv(blk.conv3.weight, _bn(blk.bn3), dt, device)
-                if blk.downsample is not None:
-                    P[p + "ds"] = pack_conv(blk.downsample[0].weight, _bn(blk.downsample[1]), dt, device, stride=blk.stride)
+        pack_bottlenecks(P, net, LAYERS, dt, device, _stride_schedule)
         dec = self.decoder
         for s in ("32", "16"):
             P["proj" + s] = pack_conv(dec.proj[s].weight, None, dt, device, bias=dec.proj[s].bias)
@@ -210,31 +139,7 @@ class RegressionMatcher(nn.Module):
             P["cab" + s + ".c2"] = pack_conv(e.cab[s].conv2.weight, None, GIM_F32, device, bias=e.cab[s].conv2.bias)
             P["term" + s] = pack_conv(e.terminal_module[s].weight, None, dt, device, bias=e.terminal_module[s].bias)
         for s, ref in dec.conv_refiner.items():
-            in_dim, hid = _refiner_dims(s)
-            cin_store = cstore(in_dim, dt)
-            blocks = [ref.block1] + list(ref.hidden_blocks)
-            for i, blk in enumerate(blocks):
-                conv, bn, _, pw = blk
-                ci = in_dim if i == 0 else hid
-                cpad = cstore(hid, dt)
-                sc = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
-                W = torch.zeros(25, cpad)
-                W[:, :hid] = conv.weight.detach().float().reshape(hid, 25).t().cpu()
-                scale, shift = torch.zeros(cpad), torch.zeros(cpad)
-                scale[:hid] = sc.cpu()
-                shift[:hid] = (bn.bias.detach().float() + (conv.bias.detach().float() - bn.running_mean.detach().float()) * sc).cpu()
-                P[f"cr{s}.{i}.dw"] = (W.to(device), scale.to(device), shift.to(device), ci, hid)
-                P[f"cr{s}.{i}.pw"] = pack_conv(pw.weight, None, dt, device, cin_pad=cpad, bias=pw.bias)
-                if dt != GIM_F32 and cpad in (24, 32, 144) and ci == hid:   # refiner blocks that fit one launch (gim_dwconv5x5_pw): dw 5x5 + BN + ReLU + 1x1
-                    npc, kp = (160, 144) if cpad == 144 else (32, 32)
-                    wf, bf = torch.zeros(npc, kp), torch.zeros(npc)
-                    wf[:hid, :hid] = pw.weight.detach().float().reshape(hid, hid).cpu()
-                    bf[:hid] = pw.bias.detach().float().cpu()
-                    P[f"cr{s}.{i}.pwf"] = (wf.to(device).to(torch_dtype(dt)).contiguous(), bf.to(device))
-            P[f"cr{s}.out"] = pack_conv(ref.out_conv.weight, None, dt, device, cin_pad=cstore(hid, dt), bias=ref.out_conv.bias)
-            P[f"cr{s}.emb"] = (ref.disp_emb.weight.detach().float().reshape(-1, 2).contiguous().to(device),
-                               ref.disp_emb.bias.detach().float().contiguous().to(device))
-            P[f"cr{s}.cin_store"] = cin_store
+            pack_refiner(P, s, ref, *refiner_dims(REFINER, s), dt, device)
         self._packed = (P, dt, device)
 
     def _gp_features(self, s, h, w, device):
@@ -242,13 +147,7 @@ class RegressionMatcher(nn.Module):
         host with the reference's fp32 ops, cached on the device as rows [h*w, 256]."""
         key = (s, h, w, str(device))
         if key not in self._gp_f:
-            ys = torch.linspace(-1 + 1 / h, 1 - 1 / h, h)
-            xs = torch.linspace(-1 + 1 / w, 1 - 1 / w, w)
-            gy, gx = torch.meshgrid(ys, xs, indexing="ij")
-            coords = torch.stack((gx, gy))[None]
-            pc = self.decoder.gps[s].pos_conv
-            f = torch.cos(8 * math.pi * F.conv2d(coords, pc.weight.detach().float().cpu(), pc.bias.detach().float().cpu()))
-            self._gp_f[key] = f[0].permute(1, 2, 0).reshape(h * w, GP_DIM).contiguous().to(device)
+            self._gp_f[key] = gp_features(self.decoder.gps[s].pos_conv, h, w, GP_DIM).to(device)
         return self._gp_f[key]
 
     # ---- stages ---------------------------------------------------------------------------------------------------
@@ -258,13 +157,9 @@ class RegressionMatcher(nn.Module):
         x = ops.conv2d(x, P["stem"], ACT_RELU)
         feats[2] = x
         x = ops.maxpool3x3s2(x)
-        for li, nblk in ((1, 3), (2, 4), (3, 6), (4, 3)):
+        for li, (_, nblk) in enumerate(LAYERS, start=1):
             for bi in range(nblk):
-                p = f"l{li}.{bi}."
-                o = ops.conv2d(x, P[p + "c1"], ACT_RELU)
-                o = ops.conv2d(o, P[p + "c2"], ACT_RELU)
-                idn = ops.conv2d(x, P[p + "ds"], ACT_NONE) if (p + "ds") in P else x
-                x = ops.conv2d(o, P[p + "c3"], ACT_RELU, res=idn)
+                x = bottleneck(x, P, f"l{li}.{bi}.")
             feats[2 ** (li + 1)] = x
         return feats
 
@@ -274,72 +169,11 @@ class RegressionMatcher(nn.Module):
         return ops.conv2d(r, P[nm + ".c3"], ACT_RELU, res=x)       # relu(x + conv3(r))
 
     def _gp(self, P, s, a32, nb, h, w, tdt, out):
-        """GP.forward, no_cov (dkm.py:340-370) for all nb = 2 * pairs directions (image d is matched against image
-        (d + nb/2) % nb).  a32: fp32 rows [nb*hw (+64 slack), 512] of the projected features; writes mu into `out`
-        (row view [nb*hw, 256], dtype tdt)."""
-        dev = a32.device
-        n = h * w
-        half = nb // 2
-        exact = (self.precision == "fp32") if self.gp_exact is None else self.gp_exact
-        if exact and out.dtype == torch.float32:
-            X = a32[:nb * n].view(nb, n, 512)
-            ops.gp_posterior_f64(X, X.roll(-half, 0).contiguous(), self._gp_features(s, h, w, dev), out, 0.2, 1e-6, 0.1)   # support of direction b: image (b + half) % nb
-            return
-        nrm = ops.row_norms(a32[:nb * n], 512)
-        ld = (n + 63) // 64 * 64
-        npad = (n + 31) // 32 * 32
-        Kyy = torch.zeros(nb, n, ld, dtype=torch.float32, device=dev)
-        Kxy = torch.zeros(nb, n, max(ld, npad), dtype=torch.float32, device=dev)
-        for b in range(nb):
-            o = (b + half) % nb                              # support of direction b = the other image of its pair
-            ops.matmul_nt(a32[o * n:(o + 1) * n], a32[o * n:], n, Kyy[b])
-            ops.matmul_nt(a32[b * n:(b + 1) * n], a32[o * n:], n, Kxy[b])
-        ny = nrm.view(nb, n).roll(-half, 0).contiguous().view(-1)
-        ops.cos_kernel_finish(Kyy.view(nb * n, ld), ny, ny, nb, n, n, 0.2, 1e-6, 0.1)        # K_yy + sigma_noise I
-        ops.cos_kernel_finish(Kxy.view(nb * n, Kxy.shape[2]), nrm, ny, nb, n, n, 0.2, 1e-6, 0.0)
-        f = self._gp_features(s, h, w, dev)
-        Xt = ops.gp_solve(Kyy, f[None].expand(nb, n, GP_DIM).contiguous(), npad)
-        for b in range(nb):
-            ops.matmul_nt(Kxy[b][:, :npad], Xt[b], GP_DIM, out[b * n:(b + 1) * n])      # mu = K_xy (K_yy + sigma I)^-1 f
+        """GP.forward of scale s (dense.gp_posterior): a32 fp32 rows [nb*hw (+64 slack), 512] -> mu into `out` (row view [nb*hw, 256], dtype tdt)"""
+        gp_posterior(a32, nb, h, w, self._gp_features(s, h, w, a32.device), out, self._gp_is_exact())
 
     def _refine(self, P, s, dt, x, y, flow, cert, ins, full_hw):
-        """ConvRefiner.forward + the flow / certainty update of Decoder.forward (dkm.py:75-123, 498-514)."""
-        tdt = torch_dtype(dt)
-        b, h, w, _ = x.shape
-        c, e, r = REFINER[s]
-        in_dim, hid = _refiner_dims(s)
-        cs = P[f"cr{s}.cin_store"]
-        dev = x.device
-        g = 8 if dt in (GIM_BF16, GIM_F16) else 4
-        if c % g == 0:
-            D = torch.zeros(b, h, w, cs, dtype=tdt, device=dev)
-            rows = D.view(b * h * w, cs)
-            D[..., :c].copy_(x[..., :c])
-            ops.grid_sample(y, flow, rows[:, c:2 * c])
-            ops.dkm_disp_emb(flow, *P[f"cr{s}.emb"], rows[:, 2 * c:])
-            if r:
-                ops.local_corr(x, y, flow, r, rows[:, 2 * c + e:])
-        else:  # scale 1: 3 image channels (stored with padding) -> assemble the 12-channel input with a copy
-            xh = torch.empty(b * h * w, x.shape[3], dtype=tdt, device=dev)
-            ops.grid_sample(y, flow, xh)
-            emb = torch.empty(b * h * w, cstore(e, dt), dtype=tdt, device=dev)
-            ops.dkm_disp_emb(flow, *P[f"cr{s}.emb"], emb)
-            D = torch.zeros(b, h, w, cs, dtype=tdt, device=dev)
-            D[..., :c].copy_(x[..., :c])
-            D[..., c:2 * c].copy_(xh.view(b, h, w, -1)[..., :c])
-            D[..., 2 * c:2 * c + e].copy_(emb.view(b, h, w, -1)[..., :e])
-        d = D
-        for i in range(1 + HIDDEN_BLOCKS):
-            W_, sc, sh, ci, co = P[f"cr{s}.{i}.dw"]
-            pwf = P.get(f"cr{s}.{i}.pwf") if self.refiner_fused else None
-            if pwf is not None and d.shape[3] == W_.shape[1] and d.is_contiguous():
-                d = ops.dwconv5x5_pw(d, W_, sc, sh, *pwf)   # the whole block in one launch: the depthwise output never leaves the CU
-                continue
-            d = ops.dwconv5x5_bn_relu(d, W_, sc, sh, ci, co)
-            d = ops.conv2d(d, P[f"cr{s}.{i}.pw"])
-        out = torch.empty(b * h * w, P[f"cr{s}.out"].n_store, dtype=torch.float32, device=dev)
-        ops.linear(d.view(b * h * w, d.shape[3]), P[f"cr{s}.out"], out)
-        ops.dkm_flow_update(flow, cert, out, ins / (4.0 * full_hw[1]), ins / (4.0 * full_hw[0]))
+        refine(P, s, dt, x, y, flow, cert, ins, full_hw, REFINER[s], self.refiner_fused)
 
     def _gp_stage(self, P, dt, f1, s):
         """proj + GP + DFN feature input of scale s: everything of that scale that does not depend on the coarser
@@ -412,49 +246,18 @@ class RegressionMatcher(nn.Module):
                 cert = ops.resize_bilinear(cert, sizes[ins // 2])
         return out
 
-    def _images(self, dt, im1, im2, hs, ws):
-        """[B,3,H,W] x 2 -> NHWC [2B, hs, ws, cpad]: queries first, then supports (extract_backbone_features, dkm.py:572-581)"""
-        B = im1.shape[0]
-        x = torch.empty(2 * B, hs, ws, cstore(3, dt), dtype=torch_dtype(dt), device=im1.device)
-        ops.resize_image(im1, x, 0)
-        ops.resize_image(im2, x, B)
-        return x
-
     def _side_stream(self, dev):
         if getattr(self, "_side", None) is None or self._side.device != dev:
             self._side = torch.cuda.Stream(device=dev)
         return self._side
 
     @torch.no_grad()
-    def match(self, im1_path, im2_path, *args, batched=False):
-        """RegressionMatcher.match (dkm.py:654-752), tensor inputs as gim calls it (`demo.py:433`, `lightning.py:135`):
-        [1,3,H,W] x 2 -> (warp [Hs, 2Ws, 4], certainty [Hs, 2Ws])."""
-        if batched or not self.symmetric:
-            raise NotImplementedError("gim runs DKM symmetric and non-batched (lightning.py:30-37); use match_batch for several pairs")
-        if im1_path.dim() != 4 or im1_path.shape[0] != 1:
-            raise GimHipError(f"match() takes [1,3,H,W] images, got {tuple(im1_path.shape)}")
-        warp, certainty = self.match_batch(im1_path, im2_path)
-        return warp[0], certainty[0]
-
-    @torch.no_grad()
     def match_batch(self, ims1, ims2):
         """B independent pairs in one pass ([B,3,H,W] x 2 -> warp [B,Hs,2Ws,4], certainty [B,Hs,2Ws]); result b equals
         `match(ims1[b:b+1], ims2[b:b+1])`.  (The reference's own batched mode cannot upsample and masks with pair 0's
         black pixels, dkm.py:662,723-724; batching here is the engine's, as SURVEY 8d prescribes for the batch-4 config.)"""
-        if not self.symmetric:
-            raise NotImplementedError("only symmetric matching is built")
-        im1, im2 = ims1, ims2
-        if not im1.is_cuda:
-            raise GimHipError("gim_amd DKM needs device (cuda/HIP) tensors: there is no CPU fallback")
-        if im1.dim() != 4 or im1.shape[1] != 3 or im1.shape != im2.shape or not 1 <= im1.shape[0] <= 8:
-            raise GimHipError(f"match takes two [B,3,H,W] batches of equal shape with B <= 8, got {tuple(im1.shape)} / {tuple(im2.shape)}")
+        P, dt, im1, im2 = self._enter(ims1, ims2)
         dev = im1.device
-        B = im1.shape[0]
-        want = {"bf16": GIM_BF16, "fp16": GIM_F16, "fp32": GIM_F32}[self.precision]
-        if self._packed is None or self._packed[2] != dev or self._packed[1] != want:
-            self._prepack(dev)
-        P, dt, _ = self._packed
-        im1, im2 = im1.contiguous().float(), im2.contiguous().float()
         hs, ws = self.h_resized, self.w_resized
         if hs % 32 or ws % 32:
             raise GimHipError(f"h_resized / w_resized must be multiples of 32, got {(hs, ws)}")
@@ -483,41 +286,9 @@ class RegressionMatcher(nn.Module):
         if self.upsample_preds:
             cor = self._decode(P, dt, pyr_hi, upsample=True, dense_flow=cor[1][0], dense_certainty=cor[1][1])
         flow, cert = cor[1]
-        warp = torch.empty(B, hs, 2 * ws, 4, dtype=torch.float32, device=dev)
-        certainty = torch.empty(B, hs, 2 * ws, dtype=torch.float32, device=dev)
-        for b in range(B):
-            ops.dkm_match_post((flow[b], flow[b + B]), (cert[b], cert[b + B]), (low[b], low[b + B]),
-                               ops.dkm_black_mask(im1[b:b + 1], (hs, ws)), ops.dkm_black_mask(im2[b:b + 1], (hs, ws)), warp[b], certainty[b])
+        warp, certainty = self._finish(im1, im2, flow, cert, low, hs, ws)
         self._debug = {"corresps": cor}
         return warp, certainty
-
-    @torch.no_grad()
-    def sample(self, dense_matches, dense_certainty, num=10000):
-        """RegressionMatcher.sample (dkm.py:583-620).  The two multinomial draws are `gim_weighted_sample` (seeded from
-        torch's generator), the balanced-sampling density is the HIP KDE kernel; samples come back as an unordered set."""
-        return balanced_sample(dense_matches, dense_certainty, num, self.sample_mode, self.sample_thresh, kde_half=False)
-
-
-@torch.no_grad()
-def balanced_sample(dense_matches, dense_certainty, num, sample_mode, sample_thresh, kde_half):
-    """`sample()` of both dense matchers (dkm.py:583-620, roma.py:680-714): certainty above the threshold counts as 1, draw
-    4 * num matches without replacement, re-draw num of them with weights 1 / (1 + KDE density)."""
-    if "threshold" not in sample_mode or "balanced" not in sample_mode:
-        raise NotImplementedError("gim uses sample_mode='threshold_balanced' (DKMv3.py:5, roma.py:645)")
-    cert_ = dense_certainty.reshape(-1).contiguous()
-    matches = dense_matches.reshape(-1, 4)
-    cert = torch.where(cert_ > sample_thresh, torch.ones_like(cert_), cert_)   # dense_certainty[> thresh] = 1
-    n_pos = int((cert > 0).sum())
-    if n_pos == 0:
-        cert, n_pos = cert + 1e-8, cert.numel()
-    seeds = torch.randint(0, 2 ** 31 - 1, (2,)).tolist()      # torch's (CPU) generator: torch.manual_seed makes sample() reproducible
-    # the kernel returns an unordered set (atomic compaction); sorting makes sample() reproducible from the seed
-    good = ops.weighted_sample(cert, min(4 * num, cert.numel(), n_pos), seeds[0]).sort().values
-    gm, gc = matches[good].contiguous(), cert_[good]
-    density = ops.kde(gm, 0.1, half=kde_half)
-    p = torch.where(density < 10, torch.full_like(density, 1e-7), 1 / (density + 1))
-    bal = ops.weighted_sample(p.contiguous(), min(num, len(gc)), seeds[1]).sort().values
-    return gm[bal], gc[bal]
 
 
 def DKMv3(weights, h, w, symmetric=True, sample_mode="threshold_balanced", **kwargs):
@@ -525,18 +296,3 @@ def DKMv3(weights, h, w, symmetric=True, sample_mode="threshold_balanced", **kwa
     the caller's job, `demo.py:364-376`)."""
     kwargs.pop("device", None)
     return RegressionMatcher(h=h, w=w, name="DKMv3", sample_mode=sample_mode, symmetric=symmetric, **kwargs)
-
-
-@torch.no_grad()
-def gim_dkm_inference(model, data, num=5000):
-    """`Trainer.gim_dkm_inference` (trainer/lightning.py:134-156): match + sample + pixel coordinates + `mconf > 0` filter,
-    written into `data` (hw0_i, hw1_i, mkpts0_f, mkpts1_f, m_bids, mconf).  data: color0 / color1 [1,3,H,W], imsize0 /
-    imsize1 [1,2] = (height, width) of the un-padded images."""
-    dense_matches, dense_certainty = model.match(data["color0"], data["color1"])
-    sparse_matches, mconf = model.sample(dense_matches, dense_certainty, num)
-    h0, w0 = (float(v) for v in data["imsize0"][0])
-    h1, w1 = (float(v) for v in data["imsize1"][0])
-    kpts0, kpts1 = ops.dense_to_pixels(sparse_matches, (h0, w0), (h1, w1))
-    mask = mconf > 0
-    data.update({"hw0_i": data["color0"].shape[2:], "hw1_i": data["color1"].shape[2:], "mkpts0_f": kpts0[mask], "mkpts1_f": kpts1[mask],
-                 "m_bids": torch.where(mconf[None])[0], "mconf": mconf[mask]})

@@ -23,8 +23,8 @@ from ..precision import resolve as resolve_precision
 import torch.nn as nn
 
 from .. import ops
-from .._lib import ACT_RELU, GIM_BF16, GIM_F16, GIM_F32, GimHipError
-from ..packing import pack_conv, torch_dtype
+from .._lib import ACT_RELU, GimHipError
+from ..packing import PRECISION_DTYPE, pack_conv, torch_dtype
 
 
 class SuperPoint(nn.Module):
@@ -66,7 +66,7 @@ class SuperPoint(nn.Module):
 
     # ---- one-time weight packing ------------------------------------------------------------------------
     def _prepack(self, device):
-        dt = {"bf16": GIM_BF16, "fp16": GIM_F16, "fp32": GIM_F32}[self.precision]
+        dt = PRECISION_DTYPE[self.precision]
         pk = {}
 
         def conv(name, w, b, cin_pad=None):
@@ -93,7 +93,7 @@ class SuperPoint(nn.Module):
         if not image.is_cuda:
             raise GimHipError("gim_amd SuperPoint needs device (cuda/HIP) tensors: there is no CPU fallback")
         dev = image.device
-        if self._packed is None or self._packed[2] != dev or self._packed[1] != ({"bf16": GIM_BF16, "fp16": GIM_F16, "fp32": GIM_F32}[self.precision]):
+        if self._packed is None or self._packed[2] != dev or self._packed[1] != PRECISION_DTYPE[self.precision]:
             self._prepack(dev)
         pk, dt, _ = self._packed
         tdt = torch_dtype(dt)

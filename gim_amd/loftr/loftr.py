@@ -48,11 +48,10 @@ import torch.nn as nn
 
 from .. import ops
 from ..switches import flag
-from .._lib import ACT_ELU1, ACT_LEAKY, ACT_NONE, ACT_RELU, GIM_BF16, GIM_F16, GIM_F32, GimHipError
-from ..packing import (PackedStem, cstore, is_half, pack_bneck, pack_bneck_ds, pack_bneck_tail, pack_conv, pack_conv_split, pack_fine_fused,
+from .._lib import ACT_ELU1, ACT_LEAKY, ACT_NONE, ACT_RELU, GIM_F16, GimHipError
+from ..packing import (PRECISION_DTYPE as _DT, PackedStem, cstore, is_half, pack_bneck, pack_bneck_ds, pack_bneck_tail, pack_conv, pack_conv_split, pack_fine_fused,
                        pack_stem7x7, pack_token_mlp, pack_token_emit, split_channels, torch_dtype)
 
-_DT = {"bf16": GIM_BF16, "fp16": GIM_F16, "fp32": GIM_F32}
 # gim_conv_args.split16: the weight operand is scaled by 2^12 before its hi / lo split (conv_igemm.hip), and hi = rn16 of it must stay finite
 SPLIT16_WSCALE, SPLIT16_LIMIT = 4096.0, 65504.0
 

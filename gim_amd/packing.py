@@ -17,6 +17,7 @@ from . import _lib
 
 KTILE_BYTES = _lib.lib.gim_ktile_bytes()
 NPAD = _lib.lib.gim_npad_granule()
+PRECISION_DTYPE = {"bf16": _lib.GIM_BF16, "fp16": _lib.GIM_F16, "fp32": _lib.GIM_F32}     # an engine's `precision` -> operand kind
 
 
 def torch_dtype(dt):
@@ -55,6 +56,11 @@ class PackedConv:
     def __repr__(self):
         return (f"PackedConv({self.cin}->{self.cout} k{self.kh} s{self.stride} cin_pad={self.cin_pad} "
                 f"n_store={self.n_store} npad={self.npad} kpad={self.kpad} dt={self.dtype})")
+
+
+def bn_params(m):
+    """an eval-mode BatchNorm module as the tuple fold_bn / pack_conv take"""
+    return (m.weight, m.bias, m.running_mean, m.running_var, m.eps)
 
 
 def fold_bn(weight, bn):

@@ -23,31 +23,23 @@ position embedding, the GP's Fourier features) are built once per shape on the h
 No CPU / eager fallback.
 """
 import math
-import os
 
 import torch
-
-from ..precision import resolve as resolve_precision
-from ..switches import flag, tri_flag
 import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from .._lib import ACT_GELU, ACT_NONE, ACT_RELU, GIM_BF16, GIM_F16, GIM_F32, GimHipError
-from ..dkm.dkm import _bn_after_bias, balanced_sample
-from ..packing import cstore, pack_conv, torch_dtype
+from .._lib import ACT_GELU, ACT_NONE, ACT_RELU, GIM_F32, GimHipError
+from ..dense import (GP, ConvRefiner, DenseMatcher, _bn_after_bias, gim_dkm_inference, gp_features, gp_posterior, pack_refiner, refine,
+                     refiner_dims)
+from ..packing import PRECISION_DTYPE, cstore, pack_conv, torch_dtype
+from ..precision import resolve as resolve_precision
 
 VGG_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M"]      # vgg19_bn.features[:40]
 REFINER = {"16": (512, 128, 7), "8": (512, 64, 3), "4": (256, 32, 2), "2": (64, 16, None), "1": (9, 6, None)}
 PROJ = {"16": (1024, 512), "8": (512, 512), "4": (256, 256), "2": (128, 64), "1": (64, 9)}
-GP_DIM, DEC_DIM, DEC_HEADS, DEC_BLOCKS, CLS_RES, HIDDEN_BLOCKS = 512, 1024, 8, 5, 64, 8
+GP_DIM, DEC_DIM, DEC_HEADS, DEC_BLOCKS, CLS_RES = 512, 1024, 8, 5, 64
 VIT_DIM, VIT_DEPTH, VIT_HEADS, VIT_PATCH, VIT_GRID = 1024, 24, 16, 14, 37                      # vit_large, img_size 518
-
-
-def _refiner_dims(scale):
-    c, e, r = REFINER[scale]
-    in_dim = 2 * c + e + ((2 * r + 1) ** 2 if r else 0)
-    return in_dim, {"2": 128 + 16, "1": 24}.get(scale, in_dim)
 
 
 # ---------------------------------------------------------------------------------------- parameter containers
@@ -102,33 +94,13 @@ class _TransformerDecoder(nn.Module):
         self.to_out = nn.Linear(DEC_DIM, CLS_RES ** 2 + 1)
 
 
-class _GP(nn.Module):
-    def __init__(self):
-        super().__init__()
-        self.pos_conv = nn.Conv2d(2, GP_DIM, 1)
-
-
-def _block(ci, co):
-    return nn.Sequential(nn.Conv2d(ci, co, 5, 1, 2, groups=ci), nn.BatchNorm2d(co, momentum=0.01), nn.ReLU(inplace=True), nn.Conv2d(co, co, 1))
-
-
-class _ConvRefiner(nn.Module):
-    def __init__(self, scale):
-        super().__init__()
-        in_dim, hid = _refiner_dims(scale)
-        self.block1 = _block(in_dim, hid)
-        self.hidden_blocks = nn.Sequential(*[_block(hid, hid) for _ in range(HIDDEN_BLOCKS)])
-        self.out_conv = nn.Conv2d(hid, 3, 1)
-        self.disp_emb = nn.Conv2d(2, REFINER[scale][1], 1)
-
-
 class _Decoder(nn.Module):
     def __init__(self):
         super().__init__()
         self.embedding_decoder = _TransformerDecoder()
-        self.gps = nn.ModuleDict({"16": _GP()})
+        self.gps = nn.ModuleDict({"16": GP(GP_DIM)})
         self.proj = nn.ModuleDict({s: nn.Sequential(nn.Conv2d(ci, co, 1, 1), nn.BatchNorm2d(co)) for s, (ci, co) in PROJ.items()})
-        self.conv_refiner = nn.ModuleDict({s: _ConvRefiner(s) for s in REFINER})
+        self.conv_refiner = nn.ModuleDict({s: ConvRefiner(*refiner_dims(REFINER, s), REFINER[s][1], bn_momentum=0.01) for s in REFINER})
 
 
 class _Workspace:
@@ -144,34 +116,23 @@ class _Workspace:
         self.hid = torch.empty(R, 4 * dim, dtype=tdt, device=dev)
 
 
-class RegressionMatcher(nn.Module):
+class RegressionMatcher(DenseMatcher):
+    engine, max_batch, kde_half = "RoMa", 4, True      # the KDE of sample() runs on fp16-rounded coordinates like roma.py:1018-1023
+
     def __init__(self, h=448, w=448, sample_mode="threshold_balanced", upsample_preds=True, symmetric=True, name=None,
                  attenuate_cert=True, precision=None, dinov2_weights=None):
-        super().__init__()
+        super().__init__(h, w, sample_mode, upsample_preds, symmetric, name)
         self.attenuate_cert = attenuate_cert
         self.encoder = _Encoder()
         self.decoder = _Decoder()
-        self.name = name
-        self.w_resized, self.h_resized = w, h
-        self.sample_mode = sample_mode
-        self.upsample_preds = upsample_preds
         self.upsample_res = (14 * 16 * 6, 14 * 16 * 6)
-        self.symmetric = symmetric
-        self.sample_thresh = 0.05
         # round 6: IEEE fp16 is gim_roma's default 16-bit mode (gim_amd/precision.py has the argument; bf16 moves the warp by ~3 px at 560 x 560,
         # fp16 stays < 5e-6 of scale from the fp32 mode: tests/test_gpu_roma.py, tests/test_gpu_dense_fullsize.py); `_fp16_checked` = the
         # output check of match_batch below has passed once for the current weights
         self.precision = resolve_precision(precision, "gim_roma", default="fp16")
         self._fp16_default = precision is None and self.precision == "fp16"
         self._fp16_checked = False
-        # GP posterior entirely in fp64 (kernel entries, Cholesky, products; csrc/gp_solve.hip: gim_gp_posterior_f64).  None = in
-        # the fp32 parity mode only: the system's condition number (~2e4) turns fp32 rounding of the kernel ENTRIES into ~1e-4 of mu,
-        # the one term of the engine's deviation that is not the reference's own (tests/test_gpu_gp_pins.py)
-        self.gp_exact = tri_flag("gp_exact")
-        # 16-bit modes: the 144- and 24-channel ConvRefiner blocks (scales 2 and 1, both passes) as ONE launch each (gim_dwconv5x5_pw, round 5)
-        self.refiner_fused = flag("refiner_fused", True)
         self._dino = [None]          # a list, like roma.py:612: the ViT is not a registered sub-module / not in state_dict()
-        self._packed = None
         self._tables = {}
         if dinov2_weights is not None:
             self.load_dinov2(dinov2_weights)
@@ -224,7 +185,7 @@ class RegressionMatcher(nn.Module):
     def _prepack(self, device):
         if self._dino[0] is None:
             raise GimHipError("RoMa needs the DINOv2 ViT-L/14 weights: RoMa(img_size, dinov2_weights=sd) or model.load_dinov2(sd)")
-        dt = {"bf16": GIM_BF16, "fp16": GIM_F16, "fp32": GIM_F32}[self.precision]
+        dt = PRECISION_DTYPE[self.precision]
         P = {}
         layers = self.encoder.cnn.layers
         idx = 0
@@ -256,30 +217,7 @@ class RegressionMatcher(nn.Module):
         for s, seq in dec.proj.items():
             P["proj" + s] = pack_conv(seq[0].weight, _bn_after_bias(seq[1], seq[0].bias), dt, device)
         for s, ref in dec.conv_refiner.items():
-            in_dim, hid = _refiner_dims(s)
-            blocks = [ref.block1] + list(ref.hidden_blocks)
-            for i, blk in enumerate(blocks):
-                conv, bn, _, pw = blk
-                ci = in_dim if i == 0 else hid
-                cpad = cstore(hid, dt)
-                sc = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
-                W = torch.zeros(25, cpad)
-                W[:, :hid] = conv.weight.detach().float().reshape(hid, 25).t().cpu()
-                scale, shift = torch.zeros(cpad), torch.zeros(cpad)
-                scale[:hid] = sc.cpu()
-                shift[:hid] = (bn.bias.detach().float() + (conv.bias.detach().float() - bn.running_mean.detach().float()) * sc).cpu()
-                P[f"cr{s}.{i}.dw"] = (W.to(device), scale.to(device), shift.to(device), ci, hid)
-                P[f"cr{s}.{i}.pw"] = pack_conv(pw.weight, None, dt, device, cin_pad=cpad, bias=pw.bias)
-                if dt != GIM_F32 and cpad in (24, 32, 144) and ci == hid:   # refiner blocks that fit one launch (gim_dwconv5x5_pw): dw 5x5 + BN + ReLU + 1x1
-                    npc, kp = (160, 144) if cpad == 144 else (32, 32)
-                    wf, bf = torch.zeros(npc, kp), torch.zeros(npc)
-                    wf[:hid, :hid] = pw.weight.detach().float().reshape(hid, hid).cpu()
-                    bf[:hid] = pw.bias.detach().float().cpu()
-                    P[f"cr{s}.{i}.pwf"] = (wf.to(device).to(torch_dtype(dt)).contiguous(), bf.to(device))
-            P[f"cr{s}.out"] = pack_conv(ref.out_conv.weight, None, dt, device, cin_pad=cstore(hid, dt), bias=ref.out_conv.bias)
-            P[f"cr{s}.emb"] = (ref.disp_emb.weight.detach().float().reshape(-1, 2).contiguous().to(device),
-                               ref.disp_emb.bias.detach().float().contiguous().to(device))
-            P[f"cr{s}.cin_store"] = cstore(in_dim, dt)
+            pack_refiner(P, s, ref, *refiner_dims(REFINER, s), dt, device)
         self._packed = (P, dt, device)
 
     def _gp_features(self, h, w, device):
@@ -287,13 +225,7 @@ class RegressionMatcher(nn.Module):
         with the reference's fp32 ops, cached on the device as rows [h*w, 512]."""
         key = ("gp", h, w, str(device))
         if key not in self._tables:
-            ys = torch.linspace(-1 + 1 / h, 1 - 1 / h, h)
-            xs = torch.linspace(-1 + 1 / w, 1 - 1 / w, w)
-            gy, gx = torch.meshgrid(ys, xs, indexing="ij")
-            coords = torch.stack((gx, gy))[None]
-            pc = self.decoder.gps["16"].pos_conv
-            f = torch.cos(8 * math.pi * F.conv2d(coords, pc.weight.detach().float().cpu(), pc.bias.detach().float().cpu()))
-            self._tables[key] = f[0].permute(1, 2, 0).reshape(h * w, GP_DIM).contiguous().to(device)
+            self._tables[key] = gp_features(self.decoder.gps["16"].pos_conv, h, w, GP_DIM).to(device)
         return self._tables[key]
 
     def _pos_table(self, hs, ws, device):
@@ -387,32 +319,8 @@ class RegressionMatcher(nn.Module):
         return a32
 
     def _gp(self, a32, nb, h, w, out):
-        """GP.forward, no_cov (roma.py:110-136) for all nb = 2 * pairs directions (image d against image (d + nb/2) % nb).
-        a32: fp32 rows [nb*hw (+64 slack), 512] of the projected features; writes mu into `out` (row view [nb*hw, 512])."""
-        dev = a32.device
-        n = h * w
-        half = nb // 2
-        exact = (self.precision == "fp32") if self.gp_exact is None else self.gp_exact
-        if exact and out.dtype == torch.float32:
-            X = a32[:nb * n].view(nb, n, 512)
-            ops.gp_posterior_f64(X, X.roll(-half, 0).contiguous(), self._gp_features(h, w, dev), out, 0.2, 1e-6, 0.1)   # support of direction b: image (b + half) % nb
-            return
-        nrm = ops.row_norms(a32[:nb * n], 512)
-        ld = (n + 63) // 64 * 64
-        npad = (n + 31) // 32 * 32
-        Kyy = torch.zeros(nb, n, ld, dtype=torch.float32, device=dev)
-        Kxy = torch.zeros(nb, n, max(ld, npad), dtype=torch.float32, device=dev)
-        for b in range(nb):
-            o = (b + half) % nb
-            ops.matmul_nt(a32[o * n:(o + 1) * n], a32[o * n:], n, Kyy[b])
-            ops.matmul_nt(a32[b * n:(b + 1) * n], a32[o * n:], n, Kxy[b])
-        ny = nrm.view(nb, n).roll(-half, 0).contiguous().view(-1)
-        ops.cos_kernel_finish(Kyy.view(nb * n, ld), ny, ny, nb, n, n, 0.2, 1e-6, 0.1)        # K_yy + sigma_noise I
-        ops.cos_kernel_finish(Kxy.view(nb * n, Kxy.shape[2]), nrm, ny, nb, n, n, 0.2, 1e-6, 0.0)
-        f = self._gp_features(h, w, dev)
-        Xt = ops.gp_solve(Kyy, f[None].expand(nb, n, GP_DIM).contiguous(), npad)
-        for b in range(nb):
-            ops.matmul_nt(Kxy[b][:, :npad], Xt[b], GP_DIM, out[b * n:(b + 1) * n])
+        """GP.forward (dense.gp_posterior): a32 fp32 rows [nb*hw (+64 slack), 512] -> mu into `out` (row view [nb*hw, 512])"""
+        gp_posterior(a32, nb, h, w, self._gp_features(h, w, a32.device), out, self._gp_is_exact())
 
     def _coarse(self, P, dt, feat16):
         """scale 16 of Decoder.forward (roma.py:263-296): proj -> GP -> TransformerDecoder -> cls_to_flow_refine
@@ -439,45 +347,8 @@ class RegressionMatcher(nn.Module):
         return a, flow, cert
 
     def _refine(self, P, s, dt, x, y, flow, cert, ins, full_hw, scale_factor):
-        """ConvRefiner.forward + the flow / certainty update of Decoder.forward (roma.py:529-580, 318-331)."""
-        tdt = torch_dtype(dt)
-        b, h, w, _ = x.shape
-        c, e, r = REFINER[s]
-        in_dim, hid = _refiner_dims(s)
-        cs = P[f"cr{s}.cin_store"]
-        dev = x.device
-        g = 8 if dt in (GIM_BF16, GIM_F16) else 4
-        ew, eb = P[f"cr{s}.emb"]
-        ew = ew * (40.0 / 32.0 * scale_factor)            # disp_emb(40/32 * scale_factor * (flow - coords)), roma.py:545-547
-        if c % g == 0:
-            D = torch.zeros(b, h, w, cs, dtype=tdt, device=dev)
-            rows = D.view(b * h * w, cs)
-            D[..., :c].copy_(x[..., :c])
-            ops.grid_sample(y, flow, rows[:, c:2 * c])
-            ops.dkm_disp_emb(flow, ew, eb, rows[:, 2 * c:])
-            if r:
-                ops.local_corr(x, y, flow, r, rows[:, 2 * c + e:])
-        else:  # scale 1: 9 projected channels (stored with padding) -> assemble the 24-channel input with copies
-            xh = torch.empty(b * h * w, x.shape[3], dtype=tdt, device=dev)
-            ops.grid_sample(y, flow, xh)
-            emb = torch.empty(b * h * w, cstore(e, dt), dtype=tdt, device=dev)
-            ops.dkm_disp_emb(flow, ew, eb, emb)
-            D = torch.zeros(b, h, w, cs, dtype=tdt, device=dev)
-            D[..., :c].copy_(x[..., :c])
-            D[..., c:2 * c].copy_(xh.view(b, h, w, -1)[..., :c])
-            D[..., 2 * c:2 * c + e].copy_(emb.view(b, h, w, -1)[..., :e])
-        d = D
-        for i in range(1 + HIDDEN_BLOCKS):
-            W_, sc, sh, ci, co = P[f"cr{s}.{i}.dw"]
-            pwf = P.get(f"cr{s}.{i}.pwf") if self.refiner_fused else None
-            if pwf is not None and d.shape[3] == W_.shape[1] and d.is_contiguous():
-                d = ops.dwconv5x5_pw(d, W_, sc, sh, *pwf)   # the whole block in one launch: the depthwise output never leaves the CU
-                continue
-            d = ops.dwconv5x5_bn_relu(d, W_, sc, sh, ci, co)
-            d = ops.conv2d(d, P[f"cr{s}.{i}.pw"])
-        out = torch.empty(b * h * w, P[f"cr{s}.out"].n_store, dtype=torch.float32, device=dev)
-        ops.linear(d.view(b * h * w, d.shape[3]), P[f"cr{s}.out"], out)
-        ops.dkm_flow_update(flow, cert, out, ins / (4.0 * full_hw[1]), ins / (4.0 * full_hw[0]), roma_layout=True)
+        refine(P, s, dt, x, y, flow, cert, ins, full_hw, REFINER[s], self.refiner_fused, emb_scale=40.0 / 32.0 * scale_factor,
+               roma_layout=True)
 
     def _decode(self, P, dt, f1, upsample=False, flow=None, cert=None, scale_factor=1.0):
         """Decoder.forward on the symmetric pair (f2 = f1 with the two images swapped) -> {scale: (flow, certainty)}"""
@@ -505,43 +376,12 @@ class RegressionMatcher(nn.Module):
                 cert = ops.resize_bilinear(cert, sizes[ins // 2])
         return out
 
-    def _images(self, dt, im1, im2, hs, ws):
-        """[B,3,H,W] x 2 -> NHWC [2B, hs, ws, cpad]: im_A first, then im_B (extract_backbone_features, roma.py:668-678)"""
-        B = im1.shape[0]
-        x = torch.empty(2 * B, hs, ws, cstore(3, dt), dtype=torch_dtype(dt), device=im1.device)
-        ops.resize_image(im1, x, 0)
-        ops.resize_image(im2, x, B)
-        return x
-
-    @torch.no_grad()
-    def match(self, im_A_path, im_B_path, *args, batched=False):
-        """RegressionMatcher.match (roma.py:816-917), tensor inputs as gim calls it (`demo.py:433`, `lightning.py:135`):
-        [1,3,H,W] x 2 -> (warp [Hs, 2Ws, 4], certainty [Hs, 2Ws])."""
-        if batched or not self.symmetric:
-            raise NotImplementedError("gim runs RoMa symmetric and non-batched; use match_batch for several pairs")
-        if im_A_path.dim() != 4 or im_A_path.shape[0] != 1:
-            raise GimHipError(f"match() takes [1,3,H,W] images, got {tuple(im_A_path.shape)}")
-        warp, certainty = self.match_batch(im_A_path, im_B_path)
-        return warp[0], certainty[0]
-
     @torch.no_grad()
     def match_batch(self, ims_A, ims_B):
         """B independent pairs in one pass ([B,3,H,W] x 2 -> warp [B,Hs,2Ws,4], certainty [B,Hs,2Ws]); result b equals
         `match(ims_A[b:b+1], ims_B[b:b+1])` (the engine's batching, like gim_amd.dkm)."""
-        if not self.symmetric:
-            raise NotImplementedError("only symmetric matching is built")
-        im1, im2 = ims_A, ims_B
-        if not im1.is_cuda:
-            raise GimHipError("gim_amd RoMa needs device (cuda/HIP) tensors: there is no CPU fallback")
-        if im1.dim() != 4 or im1.shape[1] != 3 or im1.shape != im2.shape or not 1 <= im1.shape[0] <= 4:
-            raise GimHipError(f"match takes two [B,3,H,W] batches of equal shape with B <= 4, got {tuple(im1.shape)} / {tuple(im2.shape)}")
-        dev = im1.device
-        B = im1.shape[0]
-        want = {"bf16": GIM_BF16, "fp16": GIM_F16, "fp32": GIM_F32}[self.precision]
-        if self._packed is None or self._packed[2] != dev or self._packed[1] != want:
-            self._prepack(dev)
-        P, dt, _ = self._packed
-        im1, im2 = im1.contiguous().float(), im2.contiguous().float()
+        P, dt, im1, im2 = self._enter(ims_A, ims_B)
+        B, dev = im1.shape[0], im1.device
         hs, ws = self.h_resized, self.w_resized
         cor = self._decode(P, dt, self._encode(P, dt, self._images(dt, im1, im2, hs, ws)))
         stages = {"low": cor}
@@ -557,11 +397,7 @@ class RegressionMatcher(nn.Module):
             cor = self._decode(P, dt, pyr_hi, upsample=True, flow=cor[1][0], cert=cor[1][1], scale_factor=sf)
             stages["high"] = cor
         flow, cert = cor[1]
-        warp = torch.empty(B, hs, 2 * ws, 4, dtype=torch.float32, device=dev)
-        certainty = torch.empty(B, hs, 2 * ws, dtype=torch.float32, device=dev)
-        for b in range(B):
-            ops.dkm_match_post((flow[b], flow[b + B]), (cert[b], cert[b + B]), (low[b], low[b + B]),
-                               ops.dkm_black_mask(im1[b:b + 1], (hs, ws)), ops.dkm_black_mask(im2[b:b + 1], (hs, ws)), warp[b], certainty[b])
+        warp, certainty = self._finish(im1, im2, flow, cert, low, hs, ws)
         self._debug = stages
         # fp16 as the DEFAULT mode carries a range check of what it hands out (an explicit precision='fp16' is the caller's decision):
         # every stored activation of this engine sits behind a BatchNorm / LayerNorm, so an overflow needs pathological weights -- it then
@@ -576,11 +412,6 @@ class RegressionMatcher(nn.Module):
                 self.precision, self._packed = "bf16", None
                 return self.match_batch(ims_A, ims_B)
         return warp, certainty
-
-    @torch.no_grad()
-    def sample(self, dense_matches, dense_certainty, num=10000):
-        """RegressionMatcher.sample (roma.py:680-714); the KDE runs on fp16-rounded coordinates like roma.py:1018-1023."""
-        return balanced_sample(dense_matches, dense_certainty, num, self.sample_mode, self.sample_thresh, kde_half=True)
 
 
 def RoMa(img_size, pretrained_backbone=False, **kwargs):
@@ -620,5 +451,4 @@ def random_dinov2_weights(dev, seed=0):
 @torch.no_grad()
 def gim_roma_inference(model, data, num=5000):
     """`Trainer.gim_dkm_inference` (trainer/lightning.py:134-156) -- the same adapter serves gim_roma (lightning.py:125)."""
-    from ..dkm.dkm import gim_dkm_inference
     return gim_dkm_inference(model, data, num)

@@ -24,12 +24,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from .._lib import ACT_NONE, ACT_RELU, GIM_BF16, GIM_F16, GIM_F32, GimHipError
-from ..packing import cstore, pack_conv, torch_dtype
+from .._lib import ACT_NONE, ACT_RELU, GIM_F32, GimHipError
+from ..packing import PRECISION_DTYPE, bn_params as _bn, cstore, pack_conv, torch_dtype
 from ..precision import resolve as resolve_precision
+from ..resnet50 import LAYERS, add_layers, bottleneck, pack_bottlenecks
 
 FC_DIM, NUM_CLASS, PPM_DIM = 2048, 150, 512
-LAYERS = ((64, 3), (128, 4), (256, 6), (512, 3))
 
 
 def dilation_schedule(li, bi):
@@ -47,19 +47,11 @@ def downsample_stride(li):
     return 2 if li == 2 else 1
 
 
+def _schedule(li, bi):
+    return (*dilation_schedule(li, bi), downsample_stride(li))
+
+
 # ---------------------------------------------------------------------------------------- parameter containers
-class Bottleneck(nn.Module):
-    def __init__(self, inpl, planes, stride, dilation, downsample):
-        super().__init__()
-        self.conv1 = nn.Conv2d(inpl, planes, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
-        self.conv2 = nn.Conv2d(planes, planes, 3, stride, dilation, dilation, bias=False)
-        self.bn2 = nn.BatchNorm2d(planes)
-        self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
-        self.bn3 = nn.BatchNorm2d(planes * 4)
-        self.downsample = downsample
-
-
 class ResnetDilated(nn.Module):
     """resnet50 (deep stem, inplanes 128: resnet.py:95-135) with the dilate_scale = 8 schedule, parameter names of models.py:208-233"""
 
@@ -71,17 +63,7 @@ class ResnetDilated(nn.Module):
         self.bn2 = nn.BatchNorm2d(64)
         self.conv3 = nn.Conv2d(64, 128, 3, 1, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(128)
-        inpl = 128
-        for li, (planes, nblk) in enumerate(LAYERS, start=1):
-            blocks = []
-            for bi in range(nblk):
-                ds = None
-                if bi == 0:
-                    ds = nn.Sequential(nn.Conv2d(inpl, planes * 4, 1, downsample_stride(li), bias=False), nn.BatchNorm2d(planes * 4))
-                st, d = dilation_schedule(li, bi)
-                blocks.append(Bottleneck(inpl, planes, st, d, ds))
-                inpl = planes * 4
-            setattr(self, f"layer{li}", nn.Sequential(*blocks))
+        add_layers(self, 128, _schedule)
 
 
 def _cbr(ci, co, k):
@@ -142,13 +124,6 @@ class ModelBuilder:
         return dec
 
 
-def _bn(m):
-    return (m.weight, m.bias, m.running_mean, m.running_var, m.eps)
-
-
-_DT = {"bf16": GIM_BF16, "fp16": GIM_F16, "fp32": GIM_F32}
-
-
 class SegmentationModule(nn.Module):
     """models.py:21-47.  `precision`: 'bf16' (default), 'fp16' or 'fp32' (exact fp32 products), resolved like the other ResNet-50 engines."""
 
@@ -174,22 +149,13 @@ class SegmentationModule(nn.Module):
         key = (str(device), precision)
         if key in self._packs:
             return self._packs[key]
-        dt = _DT[precision]
+        dt = PRECISION_DTYPE[precision]
         enc, dec = self.encoder, self.decoder
         P = {}
         P["c1"] = pack_conv(enc.conv1.weight, _bn(enc.bn1), dt, device, stride=2, pad=1, cin_pad=cstore(3, dt))
         P["c2"] = pack_conv(enc.conv2.weight, _bn(enc.bn2), dt, device, pad=1)
         P["c3"] = pack_conv(enc.conv3.weight, _bn(enc.bn3), dt, device, pad=1)
-        for li, (_, nblk) in enumerate(LAYERS, start=1):
-            for bi in range(nblk):
-                blk = getattr(enc, f"layer{li}")[bi]
-                p = f"l{li}.{bi}."
-                st, d = dilation_schedule(li, bi)
-                P[p + "c1"] = pack_conv(blk.conv1.weight, _bn(blk.bn1), dt, device)
-                P[p + "c2"] = pack_conv(blk.conv2.weight, _bn(blk.bn2), dt, device, stride=st, pad=d, dilation=d)
-                P[p + "c3"] = pack_conv(blk.conv3.weight, _bn(blk.bn3), dt, device)
-                if blk.downsample is not None:
-                    P[p + "ds"] = pack_conv(blk.downsample[0].weight, _bn(blk.downsample[1]), dt, device, stride=downsample_stride(li))
+        pack_bottlenecks(P, enc, LAYERS, dt, device, _schedule)
         # the four branch 1x1s run on the fp32 pooled vectors (50 rows per image: exact fp32 products in every mode)
         for i, s in enumerate(ops.PPM_SCALES):
             P[f"ppm{s}"] = pack_conv(dec.ppm[i][1].weight, _bn(dec.ppm[i][2]), GIM_F32, device)
@@ -214,18 +180,17 @@ class SegmentationModule(nn.Module):
         for li, (_, nblk) in enumerate(LAYERS, start=1):
             for bi in range(nblk):
                 p = f"l{li}.{bi}."
+                if li < 4 or bi < nblk - 1:
+                    x = bottleneck(x, P, p, health)
+                    continue
+                # the last block: conv3 goes straight into channels 0..2047 of conv_last's concat buffer (row stride 4096)
                 o = ops.conv2d(x, P[p + "c1"], ACT_RELU)
                 o = ops.conv2d(o, P[p + "c2"], ACT_RELU)
-                idn = ops.conv2d(x, P[p + "ds"], ACT_NONE) if (p + "ds") in P else x
-                if li == 4 and bi == nblk - 1:
-                    # conv5 goes straight into channels 0..2047 of conv_last's concat buffer (row stride 4096)
-                    b_, h8, w8, cs = o.shape
-                    cat = torch.empty(b_, h8, w8, FC_DIM + 4 * PPM_DIM, dtype=tdt, device=img.device)
-                    rows = b_ * h8 * w8
-                    ops.conv_rows(o.view(-1, cs), P[p + "c3"], (1, 1, rows, 1, rows), cat.view(rows, -1)[:, :FC_DIM], ACT_RELU,
-                                  res=idn.view(rows, -1), health=health)
-                else:
-                    x = ops.conv2d(o, P[p + "c3"], ACT_RELU, res=idn, health=health)
+                b_, h8, w8, cs = o.shape
+                cat = torch.empty(b_, h8, w8, FC_DIM + 4 * PPM_DIM, dtype=tdt, device=img.device)
+                rows = b_ * h8 * w8
+                ops.conv_rows(o.view(-1, cs), P[p + "c3"], (1, 1, rows, 1, rows), cat.view(rows, -1)[:, :FC_DIM], ACT_RELU,
+                              res=x.view(rows, -1), health=health)
         B, h8, w8, _ = cat.shape
         pooled = ops.ppm_pool(cat, FC_DIM)
         br = torch.empty(B, ops.PPM_BINS, PPM_DIM, dtype=torch.float32, device=img.device)
