@@ -170,6 +170,8 @@ PROTOTYPES = {
     "gim_ppm_pool": (c_int, [c_void_p] * 2 + [c_int] * 6 + [c_void_p]),
     "gim_ppm_upsample_concat": (c_int, [c_void_p] * 2 + [c_int] * 7 + [c_void_p]),
     "gim_seg_head_argmax": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
+    # feature bank of gim_loftr (additive: the ABI revision stays 114)
+    "gim_slot_copy": (c_int, [c_void_p] * 4 + [c_int, c_int64, c_int, c_int, c_void_p]),
 }
 
 

@@ -181,6 +181,28 @@ class LazyConfMatrix:
         return torch.Size([a.N, a.L, a.S])
 
 
+class StaleFeaturesError(RuntimeError):
+    """a LoFTRFeatures handle was extracted under another precision mode, split setting or set of weights than the module has now"""
+
+
+class LoFTRFeatures:
+    """Backbone maps of N independent images, resident on the device (`LoFTR.extract`): `coarse` [N, H/8, W/8, 256] and `fine`
+    [N, H/2, W/2, 128] (NHWC) in the dtype the backbone produces in the module's precision mode, the image size `hw_i` = (H, W) and
+    the `tag` (precision, fp32_split, weights generation) of the module state they were computed under.  `LoFTR.match_features`
+    matches any pairs of them; a handle whose tag no longer equals the module's is refused."""
+
+    def __init__(self, coarse, fine, hw_i, tag):
+        assert coarse.shape[0] == fine.shape[0] and coarse.is_contiguous() and fine.is_contiguous()
+        self.coarse, self.fine, self.hw_i, self.tag = coarse, fine, torch.Size(hw_i), tag
+
+    def __len__(self):
+        return self.coarse.shape[0]
+
+    @property
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.coarse, self.fine))
+
+
 def _precision_from(config):
     from ..precision import resolve
     return resolve(config.get("precision"), "loftr", default="fp16")
@@ -267,6 +289,7 @@ class LoFTR(nn.Module):
         self._graphs = collections.OrderedDict()
         self._seen = collections.OrderedDict()
         self._generation = 0
+        self._weights_gen = getattr(self, "_weights_gen", 0)   # moved by _invalidate(): tags the LoFTRFeatures handles (see feature_tag)
         if config.get("weight") is not None:
             self.load_state_dict(torch.load(config["weight"], map_location="cpu"))
 
@@ -285,6 +308,7 @@ class LoFTR(nn.Module):
         counter would send the next forward of a known shape straight into capture with nothing packed)"""
         self._packed = None
         self._health_sync_left = 3
+        self._weights_gen = getattr(self, "_weights_gen", 0) + 1   # part of the tag of every LoFTRFeatures handle (see extract)
         if hasattr(self, "_graphs"):
             self._graphs.clear()
             self._seen.clear()
@@ -955,29 +979,48 @@ class LoFTR(nn.Module):
         """Everything from the NHWC images up to and including coarse matching: a fixed launch sequence with no host sync and
         no data-dependent shape, so it can be captured once per input shape into a HIP graph and replayed.
         xs: [x_all] (both images of all pairs in one [2 bs, H, W, c] tensor: equal image shapes) or [x0, x1] (loftr.py:59-63).
-        Returns a dict of device tensors (graph-owned when captured)."""
+        Returns a dict of device tensors (graph-owned when captured).
+        It is the composition of `_extract_stage` (per image) and `_match_stage` (per pair): `extract` / `match_features` run the two
+        halves apart, on the same kernels."""
         dev = xs[0].device
-        dt = self._dt()
         # [match count, health word, per-pair counts] of this forward's coarse matching.  The health word doubles as the fp16 range
         # guard of the kernels in front of it (registered here, read back with the count): allocated before the first launch
         if count is None:
             count = torch.zeros(2 + bs, dtype=torch.int32, device=dev)
-        # the fp16 range guard of the kernels in front of it is that word too, handed to every launch that stores a residual stream
-        # (fp32 mode with split products: every split launch ORs bit 8 into it when an operand left the fp16 range of its hi / lo halves)
-        self._health = count[1:2] if (self.precision == "fp16" or (self.precision == "fp32" and ops.FP32_SPLIT)) else None
-        tdt = torch_dtype(dt)
+        self._health = self._health_word(count[1:2])
         P = self._prepack(dev)
-        cfg = self.config
         if len(xs) == 1:
             # (round 4: the fine head on a second stream beside the coarse level -- a graph with two branches, the head's persistent
             # workgroups filling the CUs the transformer's 600-tile launches leave idle -- measured SLOWER, 10.96 vs 10.70 ms per step:
             # the two branches fight over L2 and LDS instead of complementing each other; one stream it is)
-            c_all, f_all = self._backbone(P, xs[0], dt)
+            c_all, f_all = self._extract_stage(P, xs[0])
             c0, c1 = c_all[:bs], c_all[bs:]
             f0, f1 = f_all[:bs], f_all[bs:]
         else:  # different input shapes (loftr.py:62-63)
-            c0, f0 = self._backbone(P, xs[0], dt)
-            c1, f1 = self._backbone(P, xs[1], dt)
+            c_all = None
+            c0, f0 = self._extract_stage(P, xs[0])
+            c1, f1 = self._extract_stage(P, xs[1])
+        return self._match_stage(P, c0, c1, f0, f1, c_all, bs, xs[0].shape[1], scale0, scale1, mask0, mask1, count)
+
+    def _health_word(self, word):
+        """the device word the launches of a stage report range trouble into: the fp16 range guard of the kernels that store a residual
+        stream, and (fp32 mode with split products) bit 8 of every split launch whose operand left the fp16 range of its hi / lo halves"""
+        return word if (self.precision == "fp16" or (self.precision == "fp32" and ops.FP32_SPLIT)) else None
+
+    def _extract_stage(self, P, x):
+        """the per-image half: NHWC images [B,H,W,cstore(3)] -> (coarse map [B,H/8,W/8,256], fine map [B,H/2,W/2,128]) in the compute dtype.
+        No image's maps depend on another image of the batch (eval-mode BatchNorm is folded into the weights)."""
+        return self._backbone(P, x, self._dt())
+
+    def _match_stage(self, P, c0, c1, f0, f1, c_all, bs, H0, scale0, scale1, mask0, mask1, count):
+        """the per-pair half: coarse maps c0 / c1 [bs,h,w,256] and fine maps f0 / f1 of the bs pairs -> position encoding, coarse
+        transformer, coarse matching.  c_all: c0 and c1 as ONE [2 bs,h,w,256] tensor when they are its two halves (equal shapes), else
+        None.  H0: height of image 0 (the coarse scale).  count: the [2 + bs] int32 buffer of the coarse matching, zeroed by the caller."""
+        dev = c0.device
+        dt = self._dt()
+        self._health = self._health_word(count[1:2])
+        tdt = torch_dtype(dt)
+        cfg = self.config
         hw0_c, hw1_c = c0.shape[1:3], c1.shape[1:3]
         # 2. coarse transformer on pos-encoded tokens (NHWC rows == 'n (h w) c', loftr.py:74-75)
         C = cfg["coarse"]["d_model"]
@@ -991,11 +1034,11 @@ class LoFTR(nn.Module):
         # (the positional encoding itself runs inside _transformer: in front of the first layer's projections -- the projection-only token
         #  kernel adds it on the fly where it can, gim_posenc_add does it otherwise)
         T.pos = [(c0.reshape(-1, C), self._pos_encoding(C, *hw0_c, dev)), (c1.reshape(-1, C), self._pos_encoding(C, *hw1_c, dev))]
-        T.pos_all = c_all.reshape(-1, C) if len(xs) == 1 else None    # both sides' feature rows as one tensor (same image shapes)
+        T.pos_all = c_all.reshape(-1, C) if c_all is not None else None    # both sides' feature rows as one tensor (same image shapes)
         self._transformer(P, "c", self.loftr_coarse, T, bs, L, bs, S)
         # 3. coarse matching (coarse_matching.py:88-259), fused
         mc = cfg["match_coarse"]
-        scale = xs[0].shape[1] / hw0_c[0]
+        scale = H0 / hw0_c[0]
         if is_half(dt) and self.coarse_sim == self.precision:
             # opt-in: the operand-dtype copy of the final tokens (written by the last LayerNorm for the next GEMM)
             # feeds the similarity -- bf16 MFMA with fp32 accumulation, not index-exact against the fp32 tokens
@@ -1081,9 +1124,6 @@ class LoFTR(nn.Module):
                               "and the module to 'cuda'")
         dev = color0.device
         self._prepack(dev)   # first: packing may still change the mode (fp16 weights out of range -> bf16, see _prepack)
-        dt = self._dt()
-        tdt = torch_dtype(dt)
-        cfg = self.config
         color0 = color0.contiguous().float()
         color1 = color1.contiguous().float()
         scale0, scale1 = data.get("scale0"), data.get("scale1")
@@ -1128,6 +1168,14 @@ class LoFTR(nn.Module):
                 self._seen[key] = self._seen.get(key, 0) + 1
                 while len(self._seen) > 64:
                     self._seen.popitem(last=False)
+        return self._finish(data, st, graphed, scale1, lambda: self.forward(data))
+
+    def _finish(self, data, st, graphed, scale1, rerun):
+        """The tail of a forward behind coarse matching, shared by `forward` and `match_features`: the read-back of the match count, the
+        fine level launched with the device-side count, the health word, the private copies of the match lists and the `data.update`
+        calls in the reference's key order.  `rerun()` is what to do when the range guard changed the module's mode (forward: the same
+        batch once more; match_features: the handles are stale)."""
+        dev = st["c0"].device
         c0, c1, f0, f1, cr = st["c0"], st["c1"], st["f0"], st["f1"], st["cr"]
         if self.debug is not None:
             self.debug.update({k: st[k] for k in ("c0", "c1", "f0", "f1", "feat_c0", "feat_c1")})
@@ -1176,7 +1224,7 @@ class LoFTR(nn.Module):
                 split = ops.FP32_SPLIT
                 ops.FP32_SPLIT = False
                 try:
-                    return self.forward(data)
+                    return rerun()
                 finally:
                     ops.FP32_SPLIT = split
         self._generation += 1
@@ -1211,6 +1259,217 @@ class LoFTR(nn.Module):
         if self.debug is not None:
             self.debug.update({"fine0": fine0, "fine1": fine1})
         data.update({"expec_f": expec_f, "mkpts0_f": data["mkpts0_c"], "mkpts1_f": mkpts1_f})
+
+    # ---- features once, pairs many times ---------------------------------------------------------------
+    def feature_tag(self):
+        """(precision, fp32_split, weights generation): what a LoFTRFeatures handle must have been extracted under to be matched now.
+        The generation moves with load_state_dict, a precision change (the fp16 -> bf16 fallback included), a device move and the
+        fp32 mode's fallback to exact products."""
+        return (self.precision, bool(self.fp32_split), self._weights_gen)
+
+    def _split_scope(self, fn, device):
+        """run fn() under the fp32 mode's split-product switch exactly as forward() does (pack-time weight check first)"""
+        if self.precision == "fp32" and self.fp32_split:
+            self._prepack(device)   # first: the packed weights' range check may turn fp32_split off
+        if self.precision == "fp32" and self.fp32_split and not ops.FP32_SPLIT:
+            ops.FP32_SPLIT = True
+            try:
+                return fn()
+            finally:
+                ops.FP32_SPLIT = False
+        return fn()
+
+    @torch.no_grad()
+    def extract(self, color):
+        """color [N,3,H,W] on the device, N >= 1 independent images -> LoFTRFeatures: the per-image half of forward() (layout kernel +
+        ResNet-FPN backbone), eager launches.  Owns a health word for its launches and reads it back once at the end: on the fp16 range
+        trip the module warns, switches to bf16 (`_range_guard`) and the images are extracted again inside this call; in the fp32 mode
+        the split products fall back to exact ones the same way."""
+        if not (torch.is_tensor(color) and color.dim() == 4 and color.shape[0] >= 1):
+            raise ValueError("LoFTR.extract takes a [N,3,H,W] tensor of N >= 1 images")
+        if not color.is_cuda:
+            raise GimHipError("gim_amd LoFTR runs on the HIP device only (no CPU fallback): move the inputs "
+                              "and the module to 'cuda'")
+        return self._split_scope(lambda: self._extract(color), color.device)
+
+    def _extract(self, color):
+        dev = color.device
+        P = self._prepack(dev)   # first: packing may still change the mode (fp16 weights out of range -> bf16, see _prepack)
+        color = color.contiguous().float()
+        word = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._health = self._health_word(word)
+        guarded = self._health is not None
+        try:
+            coarse, fine = self._extract_stage(P, self._to_nhwc([color], self._img_dt()))
+        finally:
+            self._health = None
+        health = int(word.item()) if guarded else 0   # the one read-back of an extraction
+        if health and self._range_guard(health):
+            # the module is in bf16 now, or its fp32 mode multiplies exactly: same images, once more
+            split = ops.FP32_SPLIT
+            ops.FP32_SPLIT = False
+            try:
+                return self.extract(color)
+            finally:
+                ops.FP32_SPLIT = split
+        return LoFTRFeatures(coarse, fine, color.shape[2:], self.feature_tag())
+
+    def _check_handle(self, feats, name):
+        if not isinstance(feats, LoFTRFeatures):
+            raise TypeError(f"{name} must be a LoFTRFeatures handle (LoFTR.extract)")
+        if feats.tag != self.feature_tag():
+            raise StaleFeaturesError(f"{name} was extracted under (precision, fp32_split, weights generation) = {feats.tag}, the module is at "
+                                     f"{self.feature_tag()} (weights loaded, precision changed or a range fallback since): extract again")
+
+    @torch.no_grad()
+    def match_features(self, feats0, feats1, idx0=None, idx1=None, data=None):
+        """The per-pair half of forward() on extracted features: pair p = (image idx0[p] of feats0, image idx1[p] of feats1); idx0 / idx1
+        are integer sequences or tensors of one length P (default: arange over the handle).  feats0 and feats1 may be one handle.
+        `data` may carry scale0 / scale1 and mask0 / mask1 per pair as forward() takes them; it is updated in place (a new dict when
+        None) with the keys forward() adds, in its order, and returned: bs = P, hw0_i / hw1_i from the handles.
+        Two gather launches per level (one when both sides read one slab) fill contiguous buffers in front of the match part, which is
+        captured per shape into a HIP graph like forward()'s coarse stage: other indices replay the same graph."""
+        self._check_handle(feats0, "feats0")
+        self._check_handle(feats1, "feats1")
+        dev = feats0.coarse.device
+        out = self._split_scope(lambda: self._match_features(feats0, feats1, idx0, idx1, {} if data is None else data), dev)
+        return out
+
+    @staticmethod
+    def _host_index(idx, n):
+        """idx (None: arange(n)) as a list of Python ints when it lives on the host, range-checked; a device tensor is returned as is"""
+        if idx is None:
+            return list(range(n))
+        if torch.is_tensor(idx) and idx.is_cuda:
+            if idx.dim() != 1 or idx.dtype.is_floating_point:
+                raise ValueError("pair indices must be a 1-D integer tensor")
+            return idx
+        idx = [int(v) for v in (idx.tolist() if torch.is_tensor(idx) else idx)]
+        for v in idx:
+            if not 0 <= v < n:
+                raise IndexError(f"pair index {v} outside the handle's [0, {n})")
+        return idx
+
+    def _gather_pairs(self, feats0, feats1, i0, i1, bs, out=None):
+        """slots i0 of feats0 / i1 of feats1 -> contiguous (c0, c1, f0, f1, c_all, f_all); `out`: an earlier result to fill again (a
+        captured graph's static inputs).  Equal shapes: c0 / c1 are the halves of ONE buffer c_all as in forward(); both sides on one
+        slab: one launch per level over the concatenated indices."""
+        same = feats0.coarse.shape[1:] == feats1.coarse.shape[1:]
+        if out is None:
+            new = lambda t, n: torch.empty(n, *t.shape[1:], dtype=t.dtype, device=t.device)   # noqa: E731
+            if same:
+                c_all, f_all = new(feats0.coarse, 2 * bs), new(feats0.fine, 2 * bs)
+                out = (c_all[:bs], c_all[bs:], f_all[:bs], f_all[bs:], c_all, f_all)
+            else:
+                out = (new(feats0.coarse, bs), new(feats1.coarse, bs), new(feats0.fine, bs), new(feats1.fine, bs), None, None)
+        c0, c1, f0, f1, c_all, f_all = out
+        one_slab = same and feats0.coarse.data_ptr() == feats1.coarse.data_ptr() and feats0.fine.data_ptr() == feats1.fine.data_ptr()
+        if one_slab:
+            if isinstance(i0, list) and isinstance(i1, list):
+                ii = i0 + i1
+            else:
+                ii = torch.cat([ops.slot_index(i, len(feats0), c0.device) for i in (i0, i1)])
+            ii = ops.slot_index(ii, len(feats0), c0.device)
+            ops.slot_copy(feats0.coarse, c_all, src_idx=ii)
+            ops.slot_copy(feats0.fine, f_all, src_idx=ii)
+        else:
+            i0, i1 = ops.slot_index(i0, len(feats0), c0.device), ops.slot_index(i1, len(feats1), c0.device)
+            ops.slot_copy(feats0.coarse, c0, src_idx=i0)
+            ops.slot_copy(feats1.coarse, c1, src_idx=i1)
+            ops.slot_copy(feats0.fine, f0, src_idx=i0)
+            ops.slot_copy(feats1.fine, f1, src_idx=i1)
+        return out
+
+    def _match_stage_graphed(self, key, gather, bs, H0, scale0, scale1, mask0, mask1):
+        """HIP-graph replay of `_match_stage` (one graph per shape / precision).  The graph's static inputs are the gathered buffers, as the
+        NHWC image tensor is for `_coarse_stage_graphed`: the gather launches run eagerly in front of the replay."""
+        ent = self._graphs.get(key)
+        if ent is None:
+            bufs = gather(None)
+            dev = bufs[0].device
+            P = self._prepack(dev)   # host-side caches are filled BEFORE capture starts (see _coarse_stage_graphed)
+            C = self.config["coarse"]["d_model"]
+            for c in bufs[:2]:
+                self._pos_encoding(C, c.shape[1], c.shape[2], dev)
+            sin = [bufs,
+                   scale0.clone().float() if scale0 is not None else None,
+                   scale1.clone().float() if scale1 is not None else None,
+                   mask0.clone() if mask0 is not None else None, mask1.clone() if mask1 is not None else None,
+                   torch.zeros(2 + bs, dtype=torch.int32, device=dev)]   # zeroed HERE, outside the capture (its health bit 1 is sticky)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                out = self._match_stage(P, *bufs[:5], bs, H0, *sin[1:])
+            while len(self._graphs) >= self.graph_cache_size:  # LRU eviction frees that graph's pool
+                self._graphs.popitem(last=False)
+            ent = self._graphs[key] = (graph, sin, out)
+        else:
+            self._graphs.move_to_end(key)
+            gather(ent[1][0])
+        graph, sin, out = ent
+        small = []
+        if scale0 is not None:
+            small += [(scale0, sin[1]), (scale1, sin[2])]
+        if mask0 is not None:
+            small += [(mask0, sin[3]), (mask1, sin[4])]
+        ops.copy_segments(small)
+        graph.replay()
+        return out
+
+    def _match_features(self, feats0, feats1, idx0, idx1, data):
+        dev = feats0.coarse.device
+        if feats1.coarse.device != dev:
+            raise ValueError("feats0 and feats1 live on different devices")
+        P = self._prepack(dev)
+        self._check_handle(feats0, "feats0")   # (packing may have changed the mode)
+        self._check_handle(feats1, "feats1")
+        i0, i1 = self._host_index(idx0, len(feats0)), self._host_index(idx1, len(feats1))
+        bs = len(i0) if isinstance(i0, list) else i0.numel()
+        if bs != (len(i1) if isinstance(i1, list) else i1.numel()) or bs < 1:
+            raise ValueError("idx0 and idx1 must name the same number of pairs (>= 1)")
+        scale0, scale1 = data.get("scale0"), data.get("scale1")
+        if scale0 is not None:
+            scale0 = scale0.to(device=dev, dtype=torch.float32).contiguous()
+            scale1 = scale1.to(device=dev, dtype=torch.float32).contiguous()
+            if scale0.shape[0] != bs or scale1.shape[0] != bs:
+                raise ValueError(f"scale0/scale1 must have one row per pair ({bs})")
+        mask0 = mask1 = None
+        if "mask0" in data:  # [P, h/8, w/8] padding masks, '0' = padded (loftr.py:49-50, 77-79)
+            mask0 = data["mask0"].to(device=dev).ne(0).to(torch.uint8).contiguous()
+            mask1 = data["mask1"].to(device=dev).ne(0).to(torch.uint8).contiguous()
+            if tuple(mask0.shape) != (bs, *feats0.coarse.shape[1:3]) or tuple(mask1.shape) != (bs, *feats1.coarse.shape[1:3]):
+                raise ValueError(f"mask0/mask1 must be [P, H/8, W/8]: got {tuple(mask0.shape)}, {tuple(mask1.shape)}")
+        data.update({"bs": bs, "hw0_i": feats0.hw_i, "hw1_i": feats1.hw_i})
+        H0 = feats0.hw_i[0]
+        gather = lambda out: self._gather_pairs(feats0, feats1, i0, i1, bs, out)   # noqa: E731
+        graphed = False
+        if self.use_graph and self.debug is None:
+            key = ("match_features", bs, tuple(feats0.coarse.shape[1:]), tuple(feats1.coarse.shape[1:]), tuple(feats0.hw_i), tuple(feats1.hw_i),
+                   scale0 is not None, mask0 is not None, self.precision, bool(self.fp32_split), self.coarse_sim, str(dev))
+            if key in self._graphs or self._seen.get(key, 0) >= 1:
+                try:
+                    st = self._match_stage_graphed(key, gather, bs, H0, scale0, scale1, mask0, mask1)
+                    graphed = True
+                except RuntimeError as e:   # a failed capture only (see _forward)
+                    if key in self._graphs or "captur" not in str(e).lower():
+                        raise
+                    import warnings
+                    warnings.warn(f"gim_amd: HIP graph capture failed ({e!r}); using eager kernel launches")
+                    self.use_graph = False
+                    self._graphs.clear()
+        if not graphed:
+            bufs = gather(None)
+            st = self._match_stage(P, *bufs[:5], bs, H0, scale0, scale1, mask0, mask1, torch.zeros(2 + bs, dtype=torch.int32, device=dev))
+            if self.use_graph and self.debug is None:
+                self._seen[key] = self._seen.get(key, 0) + 1
+                while len(self._seen) > 64:
+                    self._seen.popitem(last=False)
+
+        def stale():
+            raise StaleFeaturesError("the range guard changed the module's mode while these features were matched: extract them again")
+
+        self._finish(data, st, graphed, scale1, stale)
+        return data
 
     def _range_guard(self, health):
         """A non-finite value reached coarse matching (bit 0) or left the fine level (bit 1).  In the fp16 mode that is the IEEE-fp16

@@ -139,6 +139,48 @@ def copy_segments(pairs):
         check(lib.gim_copy_segments(ctypes.byref(seg), _stream()), "gim_copy_segments")
 
 
+def slot_index(idx, slots, device):
+    """slot indices for `slot_copy`: a host sequence / CPU tensor is range-checked against `slots` HERE and uploaded as int32; a device tensor
+    is handed through as int32 (the kernel skips what is out of range, nothing waits for it).  None stays None (identity)."""
+    if idx is None:
+        return None
+    if torch.is_tensor(idx) and idx.is_cuda:
+        assert idx.dim() == 1 and not idx.dtype.is_floating_point
+        return idx if (idx.dtype == torch.int32 and idx.is_contiguous()) else idx.to(torch.int32).contiguous()
+    host = [int(v) for v in (idx.tolist() if torch.is_tensor(idx) else idx)]
+    bad = [v for v in host if not 0 <= v < slots]
+    if bad:
+        raise IndexError(f"slot index {bad[0]} outside [0, {slots})")
+    return torch.tensor(host, dtype=torch.int32).to(device, non_blocking=True)
+
+
+def slot_copy(src, dst, src_idx=None, dst_idx=None, n=None):
+    """Blocks of src [S, ...] -> blocks of dst [D, ...] in ONE launch (gim_slot_copy): block src_idx[i] of src goes to block dst_idx[i] of
+    dst for i < n.  Both tensors are contiguous with the same bytes per block (a multiple of 16); an index is a host sequence (checked
+    here, then uploaded), a device integer tensor, or None (identity).  n defaults to the length of an index, else to S.  Destination
+    indices must be distinct."""
+    _req_cuda(src, dst)
+    assert src.is_contiguous() and dst.is_contiguous() and src.dim() >= 1 and dst.dim() >= 1
+    S, D = src.shape[0], dst.shape[0]
+    bb = src[0].numel() * src.element_size() if S else dst[0].numel() * dst.element_size()
+    assert D == 0 or dst[0].numel() * dst.element_size() == bb, "slot_copy: source and destination blocks differ in size"
+    if bb % 16:
+        raise ValueError(f"slot_copy: {bb} bytes per block is not a multiple of 16")
+    si, di = slot_index(src_idx, S, src.device), slot_index(dst_idx, D, dst.device)
+    lens = {t.numel() for t in (si, di) if t is not None}
+    if n is None:
+        n = lens.pop() if len(lens) == 1 else (S if not lens else -1)
+    if any(t is not None and t.numel() < n for t in (si, di)) or n < 0:
+        raise ValueError("slot_copy: the index arrays and n disagree")
+    if dst_idx is not None and not (torch.is_tensor(dst_idx) and dst_idx.is_cuda):
+        if len(set(int(v) for v in dst_idx)) != len(dst_idx):
+            raise ValueError("slot_copy: destination indices must be distinct")
+    if (si is None and n > S) or (di is None and n > D):
+        raise IndexError(f"slot_copy: identity over {n} blocks needs that many slots (source {S}, destination {D})")
+    check(lib.gim_slot_copy(_p(src), _p(dst), _p(si), _p(di), int(n), int(bb), int(S), int(D), _stream()), "gim_slot_copy")
+    return dst
+
+
 def pack_matches(m_bids, mkpts0, mkpts1, mconf, pair_ids=None, pid_base=0):
     """rows [pair_id, x0, y0, x1, y1, conf] fp32 [M, 6]; pair_id = pair_ids[m_bids] (device int64 tensor) or pid_base + m_bids"""
     _req_cuda(m_bids, mkpts0, mkpts1, mconf, pair_ids)

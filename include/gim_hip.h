@@ -625,6 +625,21 @@ int gim_ppm_upsample_concat(const float* br, void* y, int B, int h, int w, int C
 int gim_seg_head_argmax(const float* logits, uint8_t* cls, float* prob, int* flag, int B, int h, int w, int C, int ld, int H, int W,
                         gim_stream_t stream);
 
+/* ======================================================================================================
+ * Feature bank (gim_loftr): the backbone maps of an image are extracted once and matched in many pairs (additive: the ABI
+ * revision stays 114).  The reference recomputes them per pair (networks/loftr/loftr.py:59-72).
+ * ====================================================================================================== */
+
+/* Indexed block copy between two slabs of equally sized slots, ONE launch: for i in [0, n) the block_bytes bytes (a positive multiple
+ * of 16; both slabs 16-byte aligned) at src + src_idx[i] * block_bytes go to dst + dst_idx[i] * block_bytes, as 16-byte vector loads
+ * and stores.  src_idx / dst_idx: DEVICE int32 arrays read by the kernel (the host does not wait for them), NULL = identity (i), which
+ * needs n <= that side's slot count.  src_slots / dst_slots: slot counts of the slabs; a block whose source or destination index is
+ * outside [0, slots) is skipped as a whole -- nothing is read or written out of bounds.  Destination indices must be distinct and the
+ * slabs must not overlap.  Serves both directions: scatter of extracted maps into bank slots (src_idx NULL) and gather of a pair batch's
+ * slots into the contiguous [bs, h, w, C] buffers the stages read (dst_idx NULL). */
+int gim_slot_copy(const void* src, void* dst, const int32_t* src_idx, const int32_t* dst_idx, int n, int64_t block_bytes, int src_slots,
+                  int dst_slots, gim_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
