@@ -172,6 +172,9 @@ PROTOTYPES = {
     "gim_seg_head_argmax": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
     # feature bank of gim_loftr (additive: the ABI revision stays 114)
     "gim_slot_copy": (c_int, [c_void_p] * 4 + [c_int, c_int64, c_int, c_int, c_void_p]),
+    # root_sift baseline (additive: the ABI revision stays 114)
+    "gim_nn_match_ws_bytes": (c_int64, [c_int] * 4),
+    "gim_nn_match": (c_int, [c_void_p] * 2 + [c_int] * 4 + [c_float] + [c_void_p] * 5),
 }
 
 

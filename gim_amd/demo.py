@@ -1,4 +1,5 @@
-"""`demo.py --model {gim_dkm, gim_roma, gim_loftr, gim_lightglue}` of the reference, on the HIP engine.
+"""`demo.py --model {gim_dkm, gim_roma, gim_loftr, gim_lightglue}` of the reference, on the HIP engine, plus `root_sift`, the fifth
+entry of its model zoo (test.py:61; trainer/lightning.py:195-241).
 
     python -m gim_amd.demo --model gim_lightglue [--weights weights/gim_lightglue_100h.ckpt] \
            [--image0 assets/demo/a1.png --image1 assets/demo/a2.png] [--precision bf16|fp32] [--resize-max N]
@@ -24,7 +25,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-MODELS = ("gim_dkm", "gim_roma", "gim_loftr", "gim_lightglue")
+MODELS = ("gim_dkm", "gim_roma", "gim_loftr", "gim_lightglue", "root_sift")
 CKPT = {"gim_dkm": "gim_dkm_100h.ckpt", "gim_roma": "gim_roma_100h.ckpt", "gim_loftr": "gim_loftr_50h.ckpt",
         "gim_lightglue": "gim_lightglue_100h.ckpt"}   # demo.py:328-347
 
@@ -126,6 +127,10 @@ def build(model_name, weights=None, precision=None, device="cuda", dinov2_weight
                 elif k.startswith("model."):
                     sd[k.replace("model.", "", 1)] = sd.pop(k)
             model.load_state_dict(sd)
+    elif model_name == "root_sift":      # no weights: OpenCV's SIFT on the host, the fused matcher on the device
+        from .nn_match import RootSiftMatcher, _cv2
+        _cv2()                           # without the detector: the documented error, before anything touches the device
+        return RootSiftMatcher(device=device), None
     else:
         raise ValueError(f"--model must be one of {MODELS}, got {model_name!r}")
     if detector is not None:
@@ -146,6 +151,11 @@ def match_pair(model_name, model, detector, path0, path1, device="cuda", resize_
         h, w = (672, 896) if model_name == "gim_dkm" else (672, 672)   # demo.py:421-424 (named width, height there)
         kpts0, kpts1, b_ids, mconf = dense_demo_inference(model, image0, image1, h, w, num)
     elif model_name == "gim_loftr":
+        model(data)
+        kpts0, kpts1, b_ids, mconf = data["mkpts0_f"], data["mkpts1_f"], data["m_bids"], data["mconf"]
+    elif model_name == "root_sift":      # pixels of the original images (kpts * scale, lightning.py:228-229)
+        data.update(scale0=torch.tensor(scale0, dtype=torch.float32, device=device)[None],
+                    scale1=torch.tensor(scale1, dtype=torch.float32, device=device)[None])
         model(data)
         kpts0, kpts1, b_ids, mconf = data["mkpts0_f"], data["mkpts1_f"], data["m_bids"], data["mconf"]
     else:
@@ -188,9 +198,9 @@ def main(argv=None):
     ap.add_argument("--dinov2-weights", default=None, help="gim_roma: the DINOv2 ViT-L/14 file the reference downloads")
     args = ap.parse_args(argv)
     weights = args.weights
-    if weights is None and os.path.exists(join("weights", CKPT[args.model])):
+    if weights is None and args.model in CKPT and os.path.exists(join("weights", CKPT[args.model])):
         weights = join("weights", CKPT[args.model])
-    if weights is None:
+    if weights is None and args.model in CKPT:
         print(f"gim_amd.demo: no checkpoint ({join('weights', CKPT[args.model])} not found): running on the modules' seeded init")
     model, detector = build(args.model, weights, args.precision, dinov2_weights=args.dinov2_weights)
     out = match_pair(args.model, model, detector, args.image0, args.image1, resize_max=args.resize_max)

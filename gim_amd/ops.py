@@ -1137,6 +1137,35 @@ def dense_to_pixels(matches, hw0, hw1):
     return k0, k1
 
 
+# ---- root_sift baseline ----------------------------------------------------------------------------------------
+def nn_match(desc0, desc1, rootsift=False, ratio=0.8, count=None):
+    """desc0 [n0,D], desc1 [n1,D] fp32 (D % 16 == 0, 16 <= D <= 256) -> (match0 int32 [n0]: index into desc1 or -1, score0 fp32 [n0]:
+    the row maximum of desc0 @ desc1.T): mutual nearest neighbour + Lowe's ratio test (trainer/lightning.py:215-226) in one sweep of
+    gim_nn_match; nothing of size n0 x n1 is allocated.  rootsift: rows -> sqrt(d / sum d) first.  ratio <= 0: no ratio test.
+    count: optional int32 device tensor whose word [0] receives the number of matched rows (no host synchronisation here)."""
+    _req_cuda(desc0, desc1, count)
+    assert desc0.dim() == 2 and desc1.dim() == 2 and desc0.shape[1] == desc1.shape[1]
+    assert desc0.dtype == torch.float32 and desc1.dtype == torch.float32
+    desc0, desc1 = desc0.contiguous(), desc1.contiguous()
+    n0, n1, D = desc0.shape[0], desc1.shape[0], desc0.shape[1]
+    dev = desc0.device
+    if count is None:
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+    assert count.dtype == torch.int32 and count.numel() >= 1
+    if n0 == 0 or n1 == 0:       # the library writes the count only
+        match0 = torch.zeros(n0, dtype=torch.int32, device=dev) - 1
+        score0 = torch.zeros(n0, dtype=torch.float32, device=dev)
+        ws = None
+    else:
+        match0 = torch.empty(n0, dtype=torch.int32, device=dev)
+        score0 = torch.empty(n0, dtype=torch.float32, device=dev)
+        ws = torch.empty(lib.gim_nn_match_ws_bytes(n0, n1, D, int(bool(rootsift))), dtype=torch.uint8, device=dev)
+    with _Timed("nn_match", 2.0 * n0 * n1 * D):
+        check(lib.gim_nn_match(_p(desc0), _p(desc1), n0, n1, D, int(bool(rootsift)), float(ratio), _p(match0), _p(score0), _p(count),
+                               _p(ws), _stream()), "gim_nn_match")
+    return match0, score0
+
+
 # ---- gim_semseg ------------------------------------------------------------------------------------------------
 PPM_SCALES = (1, 2, 3, 6)
 PPM_BINS = 50            # 1 + 4 + 9 + 36 pooled vectors per image, bins of scale s from offset PPM_OFFSETS[s]

@@ -640,6 +640,25 @@ int gim_seg_head_argmax(const float* logits, uint8_t* cls, float* prob, int* fla
 int gim_slot_copy(const void* src, void* dst, const int32_t* src_idx, const int32_t* dst_idx, int n, int64_t block_bytes, int src_slots,
                   int dst_slots, gim_stream_t stream);
 
+/* ======================================================================================================
+ * root_sift baseline: descriptor matching (additive: the ABI revision stays 114 -- no existing structure or prototype changes, a
+ * caller bound to 114 keeps working).
+ * ====================================================================================================== */
+
+/* RootSIFT normalisation, similarity, mutual nearest neighbour and Lowe's ratio test of root_sift_inference --
+ * trainer/lightning.py:215-226, 230 (the same lines again in video_preprocessor.py:379-390) -- without the [n0, n1] similarity
+ * matrix: desc0 [n0][D], desc1 [n1][D] fp32 row-major, 16-byte aligned, D a multiple of 16 in [16, 256] (SIFT 128, SuperPoint 256).
+ * rootsift = 1: rows become sqrt(d / sum d) first (:215; copies in ws, the inputs are not modified).  Products are exact fp32.
+ * match0 int32 [n0] = the index into desc1 or -1; score0 fp32 [n0] = the row maximum of the similarity (`mconf`; 0 for a row without
+ * a comparable value); count = device int32 word, the number of rows with match0 >= 0.  ratio (0.8 at both reference call sites) <= 0
+ * switches the ratio test off (plain mutual nearest neighbour).  A row that ties its maximum in several columns reports the lowest
+ * such column, then tests mutuality (the reference picks a mutual one among them); NaN similarities (zero-sum row under rootsift)
+ * never match; n1 == 1 has no second neighbour, so a positive ratio rejects every row; n0 == 0 or n1 == 0 writes count = 0 only.
+ * ws: gim_nn_match_ws_bytes(n0, n1, D, rootsift) bytes, 16-byte aligned -- O((n0 + n1) D), nothing of size n0 x n1 exists. */
+int64_t gim_nn_match_ws_bytes(int n0, int n1, int D, int rootsift);
+int gim_nn_match(const float* desc0, const float* desc1, int n0, int n1, int D, int rootsift, float ratio, int32_t* match0,
+                 float* score0, int32_t* count, void* ws, gim_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
