@@ -175,6 +175,10 @@ PROTOTYPES = {
     # root_sift baseline (additive: the ABI revision stays 114)
     "gim_nn_match_ws_bytes": (c_int64, [c_int] * 4),
     "gim_nn_match": (c_int, [c_void_p] * 2 + [c_int] * 4 + [c_float] + [c_void_p] * 5),
+    # sparse fine FPN tail of gim_loftr (additive: the ABI revision stays 114)
+    "gim_conv3x3_halo_tiles": (c_int, [ctypes.POINTER(ConvArgs), c_void_p, c_void_p, c_int, c_void_p]),
+    "gim_fine_tile_list_max_flags": (c_int, []),
+    "gim_fine_tile_list": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p, c_void_p, c_int, c_void_p]),
 }
 
 

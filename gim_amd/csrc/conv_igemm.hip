@@ -592,14 +592,18 @@ int launch_persistent(const gim_conv_args& a, hipStream_t stream) {
 // [BN][64] slab per K step of four 16-channel sub-steps; K order is (chunk, tap, channel) for the full chunks and
 // (tap, channel) for the last, narrower one (Cin = 196: three chunks + nine 16-channel sub-steps packed four to a slab), a
 // small per-slab table in LDS tells every sub-step its row shift and its channel offset inside the halo row.
+//
+// LIST: the workgroups walk a device-side list of patches instead of all of them (gim_conv3x3_halo_tiles): `tlist` holds `*tcount`
+// patch indices (image * tiles_y + ty) * tiles_x + tx, read on the device -- the grid stays the resident-slot grid, workgroups whose share
+// of the list is empty return, and patches outside the list are never written.  Same K loop, same arithmetic per patch.
 constexpr int HTH = 8, HTW = 32, HW2 = HTW + 2, HROWS = (HTH + 2) * HW2;  // 340 halo rows
 constexpr int HPIECES = (HROWS + 7) / 8;                                 // 43 LDS-DMA pieces of 8 rows
 constexpr int HA_BYTES = HPIECES * 8 * KTB;                              // 44032 B per halo buffer
 constexpr int HNPA = (HPIECES + 7) / 8;                                  // pieces per wave (6)
 
-template <int TN>  // wave tile: 64 pixels x TN * 32 channels; BN = 2 * TN * 32
-__global__ void __launch_bounds__(512, 2)
-conv3x3_halo_kernel(const gim_conv_args a, const int tiles_x, const int tiles_y, const int ntiles, const int nslab) {
+template <int TN, bool LIST>  // wave tile: 64 pixels x TN * 32 channels; BN = 2 * TN * 32
+__device__ __forceinline__ void conv3x3_halo_body(const gim_conv_args& a, const int tiles_x, const int tiles_y, const int ntiles, const int nslab,
+                                                  const int* __restrict__ tlist, const int* __restrict__ tcount, const int tcap) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int BM = 256, BN = 2 * TN * 32, PB = BN / 64;
     typedef gim::Igemm<BM, BN, 4, 2, true, true> G;
@@ -608,10 +612,25 @@ conv3x3_halo_kernel(const gim_conv_args a, const int tiles_x, const int tiles_y,
     char* const sBb = smem + 2 * HA_BYTES;     // [2][BN * KTB]
     int* const tab = (int*)(sBb + 2 * BN * KTB);
 
+    const int npatch = tiles_x * tiles_y * a.B;
+    int nwalk = npatch;   // patches this launch computes
+    if constexpr (LIST) {
+        const int c = *tcount;
+        nwalk = c < 0 ? 0 : (c < tcap ? c : tcap);
+    }
     unsigned first, step, end;
-    tile_list((unsigned)(tiles_x * tiles_y * a.B * ntiles), first, step, end);
+    tile_list((unsigned)(nwalk * ntiles), first, step, end);   // (LIST: XCD-contiguous chunks of the ascending list -- neighbouring patches share an L2)
     if (first >= end) return;
     for (int i = threadIdx.x; i < nslab * 8; i += 512) tab[i] = a.ktab[i];
+    // walked tile index -> patch index: through the list (clamped: an entry outside the map must not become an address)
+    auto patch_of = [&](const unsigned tile) -> int {
+        const int p = (int)(tile / (unsigned)ntiles);
+        if constexpr (LIST) {
+            const int e = tlist[p];
+            return e < 0 ? 0 : (e < npatch ? e : npatch - 1);
+        }
+        return p;
+    };
 
     const int t = threadIdx.x, lane = t & 63;
     E epi;  // wave, wm, wn, l31, lh, rrow, rslot
@@ -625,8 +644,7 @@ conv3x3_halo_kernel(const gim_conv_args a, const int tiles_x, const int tiles_y,
     // ---- per-thread staging coordinates ---------------------------------------------------------------------------------
     unsigned offA[HNPA];   // byte offset of (pixel, channel group) of this thread's slot in piece i, 0xFFFFFFFF = outside the image
     int gch[HNPA];         // first channel (within the chunk) of that slot
-    auto decode = [&](const unsigned tile) {
-        const int mt = (int)(tile / (unsigned)ntiles);
+    auto decode = [&](const int mt) {
         const int tx = mt % tiles_x, ty = (mt / tiles_x) % tiles_y, b = mt / (tiles_x * tiles_y);
         const int x0 = tx * HTW, y0 = ty * HTH;
 #pragma unroll
@@ -665,7 +683,8 @@ conv3x3_halo_kernel(const gim_conv_args a, const int tiles_x, const int tiles_y,
     unsigned tile = first;
     int n0 = (int)(tile % (unsigned)ntiles) * BN;
     epi.init_acc(a, acc, n0);
-    decode(tile);
+    int mt = patch_of(tile);
+    decode(mt);
     issue_A(0, 0);
     issue_B(n0, 0, 0);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -680,7 +699,7 @@ conv3x3_halo_kernel(const gim_conv_args a, const int tiles_x, const int tiles_y,
         const unsigned tile_n = tile + step;
         const bool has_next = tile_n < end;
         const int n0n = has_next ? (int)(tile_n % (unsigned)ntiles) * BN : n0;
-        const int mt = (int)(tile / (unsigned)ntiles);
+        const int mt_n = has_next ? patch_of(tile_n) : mt;   // (LIST: the list entry is fetched a whole K loop ahead of the halo prefetch that needs it)
         auto kloop = [&](auto live) __attribute__((always_inline)) {
         constexpr int LIVE = decltype(live)::value;
         for (int s = 0; s < nslab; ++s) {
@@ -693,7 +712,7 @@ conv3x3_halo_kernel(const gim_conv_args a, const int tiles_x, const int tiles_y,
             if (flags & 1) {
                 const int cnext = __builtin_amdgcn_readfirstlane(te[6]);  // channel base of the next chunk, -1: the tile's last chunk
                 if (cnext >= 0) issue_A(cnext, ab ^ 1);
-                else if (has_next) { decode(tile_n); issue_A(0, ab ^ 1); }
+                else if (has_next) { decode(mt_n); issue_A(0, ab ^ 1); }
             }
             // ---- MFMAs of this slab ---------------------------------------------------------------------------------------
             const char* sA = sAh + ab * HA_BYTES;
@@ -764,6 +783,7 @@ conv3x3_halo_kernel(const gim_conv_args a, const int tiles_x, const int tiles_y,
         }
         epi.init_acc(a, acc, n0n);
         n0 = n0n;
+        mt = mt_n;
         __syncthreads();  // the transposition tiles live in a halo buffer the next chunk's DMA will overwrite
         tt_e += GIM_TT_NOW() - tt_b; ++tt_n;
     }
@@ -772,15 +792,28 @@ conv3x3_halo_kernel(const gim_conv_args a, const int tiles_x, const int tiles_y,
 }
 
 template <int TN>
-int launch_halo(const gim_conv_args& a, hipStream_t stream) {
+__global__ void __launch_bounds__(512, 2)
+conv3x3_halo_kernel(const gim_conv_args a, const int tiles_x, const int tiles_y, const int ntiles, const int nslab) {
+    conv3x3_halo_body<TN, false>(a, tiles_x, tiles_y, ntiles, nslab, nullptr, nullptr, 0);
+}
+
+template <int TN>
+__global__ void __launch_bounds__(512, 2)
+conv3x3_halo_tiles_kernel(const gim_conv_args a, const int tiles_x, const int tiles_y, const int ntiles, const int nslab,
+                          const int* __restrict__ tlist, const int* __restrict__ tcount, const int tcap) {
+    conv3x3_halo_body<TN, true>(a, tiles_x, tiles_y, ntiles, nslab, tlist, tcount, tcap);
+}
+
+template <int TN, bool LIST = false>
+int launch_halo(const gim_conv_args& a, hipStream_t stream, const int* tlist = nullptr, const int* tcount = nullptr, int tcap = 0) {
     constexpr int BN = 2 * TN * 32;
     const int nslab = a.kpad / 64;
     const int smem = 2 * HA_BYTES + 2 * BN * KTB + nslab * 8 * 4;
     GIM_REQUIRE(smem <= 160 * 1024, "conv3x3 halo: %d slabs do not fit the LDS table", nslab);
-    auto kern = conv3x3_halo_kernel<TN>;
-    static GimPerDevice attr_done;
+    const void* kern = LIST ? (const void*)conv3x3_halo_tiles_kernel<TN> : (const void*)conv3x3_halo_kernel<TN>;
+    static GimPerDevice attr_done;   // (one per instantiation, i.e. per kernel)
     if (attr_done.needed()) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) {
             gim_set_error("hipFuncSetAttribute(160 KiB LDS): %s", hipGetErrorString(e));
             return GIM_ERR_LAUNCH;
@@ -788,11 +821,14 @@ int launch_halo(const gim_conv_args& a, hipStream_t stream) {
         attr_done.done();
     }
     const int tiles_x = (a.W + HTW - 1) / HTW, tiles_y = (a.H + HTH - 1) / HTH, ntiles = a.npad / BN;
-    const int T = tiles_x * tiles_y * a.B * ntiles;
+    const int npatch = tiles_x * tiles_y * a.B;
+    const int T = (LIST ? (tcap < npatch ? tcap : npatch) : npatch) * ntiles;   // LIST: the most the list can hold; the count itself stays on the device
+    if (T <= 0) return GIM_OK;
     constexpr int RESIDENT = 256;  // one workgroup per CU
     const int grid = T < RESIDENT ? T : RESIDENT;   // (see launch_persistent)
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, stream, a, tiles_x, tiles_y, ntiles, nslab);
-    return gim_check_launch("conv3x3_halo_kernel");
+    if constexpr (LIST) hipLaunchKernelGGL(conv3x3_halo_tiles_kernel<TN>, dim3((unsigned)grid), dim3(512), smem, stream, a, tiles_x, tiles_y, ntiles, nslab, tlist, tcount, tcap);
+    else hipLaunchKernelGGL(conv3x3_halo_kernel<TN>, dim3((unsigned)grid), dim3(512), smem, stream, a, tiles_x, tiles_y, ntiles, nslab);
+    return gim_check_launch(LIST ? "conv3x3_halo_tiles_kernel" : "conv3x3_halo_kernel");
 }
 
 // Tile-selection thresholds of dispatch_persistent (round-3 sweep, profiles/r03_knob_sweep.txt): the 256 x 256 / 8-wave tile takes a layer
@@ -901,9 +937,42 @@ static bool ups_supported(const gim_conv_args& a) {
     return a.use_lds_dma == 3 || (nkt >= BIG_MIN_NKT && big_tile_count(((M + 255) / 256) * (a.npad / 256), nkt));
 }
 
+// argument checks every launch of this file shares
+static int conv_check(const gim_conv_args& a) {
+    const int es = a.dtype == GIM_H16 ? 2 : 4;
+    GIM_REQUIRE(a.dtype == GIM_H16 || a.dtype == GIM_F32, "conv: bad dtype %d", a.dtype);
+    GIM_REQUIRE(a.x && a.w && a.y && a.ktab, "conv: NULL x/w/y/ktab");
+    GIM_REQUIRE(a.npad > 0 && a.npad % 64 == 0, "conv: npad=%d must be a multiple of 64", a.npad);
+    GIM_REQUIRE(a.kpad > 0 && (a.kpad * es) % KTB == 0, "conv: kpad=%d is not a multiple of the %d-byte K slab", a.kpad, KTB);
+    GIM_REQUIRE(a.N > 0 && a.N % 4 == 0 && a.N <= a.npad, "conv: N=%d must be a multiple of 4 and <= npad=%d", a.N, a.npad);
+    GIM_REQUIRE(a.x_bytes > 0 && a.x_bytes < (int64_t)0xFFFFFFF0ll, "conv: x_bytes=%lld must be < 4 GiB", (long long)a.x_bytes);
+    GIM_REQUIRE(a.ldx % (16 / es) == 0, "conv: ldx=%d breaks 16-byte alignment", a.ldx);
+    GIM_REQUIRE(a.ldy % 4 == 0 && (!a.res || a.ldres % 4 == 0), "conv: ldy/ldres must be multiples of 4");
+    GIM_REQUIRE(!out_is16(a) || (a.N % 8 == 0 && a.ldy % 8 == 0), "conv: 16-bit output needs N and ldy multiples of 8 (16-byte row stores)");
+    GIM_REQUIRE(!a.res || (a.res_dtype == a.out_dtype && (a.res_dtype != GIM_H16 || a.ldres % 8 == 0)), "conv: residual must have the output dtype (and ldres %% 8 == 0 for 16-bit rows)");
+    GIM_REQUIRE(a.act_cols >= 0 && a.act_cols % 128 == 0, "conv: act_cols=%d must be a multiple of 128", a.act_cols);
+    GIM_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0 && a.Ho > 0 && a.Wo > 0 && a.stride > 0, "conv: bad geometry");
+    GIM_REQUIRE((int64_t)a.B * a.Ho * a.Wo < (int64_t)0x7fffffff, "conv: too many output rows");
+    GIM_REQUIRE(!a.ups || ups_supported(a), "conv: this launch cannot take the fused upsample-add (see gim_conv_ups_supported)");
+    return GIM_OK;
+}
+
+// 3x3 halo kernel: w / ktab / kpad describe the halo packing (gim_amd/packing.py::pack_halo); tiles != NULL: the patch-list walk
+static int halo_launch(const gim_conv_args& a, const int* tiles, const int* n_tiles, int tiles_cap, hipStream_t s) {
+    GIM_REQUIRE(a.dtype == GIM_H16 && a.out_dtype == GIM_H16 && !a.res && a.stride == 1 && a.pad == 1 && a.H == a.Ho && a.W == a.Wo,
+                "conv3x3 halo: 16-bit in / out, stride 1, pad 1, no residual");
+    GIM_REQUIRE(a.npad % 128 == 0 && a.kpad % 64 == 0 && a.res_mod > 0 && a.res_mod <= a.ldx && a.act_cols == 0, "conv3x3 halo: bad packing");
+    if (tiles) {
+        GIM_REQUIRE(n_tiles && tiles_cap >= 0, "conv3x3 halo: a tile list needs its device count and a capacity >= 0");
+        return a.npad % 256 == 0 ? launch_halo<4, true>(a, s, tiles, n_tiles, tiles_cap) : launch_halo<2, true>(a, s, tiles, n_tiles, tiles_cap);
+    }
+    return a.npad % 256 == 0 ? launch_halo<4>(a, s) : launch_halo<2>(a, s);
+}
+
 #if !GIM_HALF_KIND
 extern "C" int gim_conv_ups_supported_f16(const gim_conv_args* ap);
 extern "C" int gim_conv2d_bn_act_f16(const gim_conv_args* ap, gim_stream_t stream);
+extern "C" int gim_conv3x3_halo_tiles_f16(const gim_conv_args* ap, const int* tiles, const int* n_tiles, int tiles_cap, gim_stream_t stream);
 #endif
 extern "C" int GIM_FN(gim_conv_ups_supported)(const gim_conv_args* ap) {
 #if !GIM_HALF_KIND
@@ -928,28 +997,23 @@ extern "C" int GIM_FN(gim_conv2d_bn_act)(const gim_conv_args* ap, gim_stream_t s
     GIM_REQUIRE(a.out_dtype != GIM_BF16 || (a.dtype == GIM_H16 && !a.res && !a.ups && a.use_lds_dma == 1),
                 "conv: fp16 operands with bf16 output: no residual, no upsample operand, LDS-DMA path only");
 #endif
-    const int es = a.dtype == GIM_H16 ? 2 : 4;
-    GIM_REQUIRE(a.dtype == GIM_H16 || a.dtype == GIM_F32, "conv: bad dtype %d", a.dtype);
-    GIM_REQUIRE(a.x && a.w && a.y && a.ktab, "conv: NULL x/w/y/ktab");
-    GIM_REQUIRE(a.npad > 0 && a.npad % 64 == 0, "conv: npad=%d must be a multiple of 64", a.npad);
-    GIM_REQUIRE(a.kpad > 0 && (a.kpad * es) % KTB == 0, "conv: kpad=%d is not a multiple of the %d-byte K slab", a.kpad, KTB);
-    GIM_REQUIRE(a.N > 0 && a.N % 4 == 0 && a.N <= a.npad, "conv: N=%d must be a multiple of 4 and <= npad=%d", a.N, a.npad);
-    GIM_REQUIRE(a.x_bytes > 0 && a.x_bytes < (int64_t)0xFFFFFFF0ll, "conv: x_bytes=%lld must be < 4 GiB", (long long)a.x_bytes);
-    GIM_REQUIRE(a.ldx % (16 / es) == 0, "conv: ldx=%d breaks 16-byte alignment", a.ldx);
-    GIM_REQUIRE(a.ldy % 4 == 0 && (!a.res || a.ldres % 4 == 0), "conv: ldy/ldres must be multiples of 4");
-    GIM_REQUIRE(!out_is16(a) || (a.N % 8 == 0 && a.ldy % 8 == 0), "conv: 16-bit output needs N and ldy multiples of 8 (16-byte row stores)");
-    GIM_REQUIRE(!a.res || (a.res_dtype == a.out_dtype && (a.res_dtype != GIM_H16 || a.ldres % 8 == 0)), "conv: residual must have the output dtype (and ldres %% 8 == 0 for 16-bit rows)");
-    GIM_REQUIRE(a.act_cols >= 0 && a.act_cols % 128 == 0, "conv: act_cols=%d must be a multiple of 128", a.act_cols);
-    GIM_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0 && a.Ho > 0 && a.Wo > 0 && a.stride > 0, "conv: bad geometry");
-    GIM_REQUIRE((int64_t)a.B * a.Ho * a.Wo < (int64_t)0x7fffffff, "conv: too many output rows");
-    GIM_REQUIRE(!a.ups || ups_supported(a), "conv: this launch cannot take the fused upsample-add (see gim_conv_ups_supported)");
+    if (const int rc = conv_check(a)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (a.use_lds_dma == 2) {  // 3x3 halo kernel: w / ktab / kpad describe the halo packing (gim_amd/packing.py::pack_halo)
-        GIM_REQUIRE(a.dtype == GIM_H16 && a.out_dtype == GIM_H16 && !a.res && a.stride == 1 && a.pad == 1 && a.H == a.Ho && a.W == a.Wo,
-                    "conv3x3 halo: 16-bit in / out, stride 1, pad 1, no residual");
-        GIM_REQUIRE(a.npad % 128 == 0 && a.kpad % 64 == 0 && a.res_mod > 0 && a.res_mod <= a.ldx && a.act_cols == 0, "conv3x3 halo: bad packing");
-        return a.npad % 256 == 0 ? launch_halo<4>(a, s) : launch_halo<2>(a, s);
-    }
+    if (a.use_lds_dma == 2) return halo_launch(a, nullptr, nullptr, 0, s);
     if (a.dtype == GIM_H16) return a.use_lds_dma ? dispatch_persistent<true>(a, s) : dispatch_tile<true, false>(a, s);
     return a.use_lds_dma ? dispatch_persistent<false>(a, s) : dispatch_tile<false, false>(a, s);
+}
+
+// gim_conv2d_bn_act's halo launch (use_lds_dma = 2) over a device-side list of 8 x 32 patches: tiles[0 .. min(*n_tiles, tiles_cap)) are
+// patch indices (image * ceil(H / 8) + ty) * ceil(W / 32) + tx; the count is read on the device (no host sync, fixed grid), 0 writes
+// nothing, and pixels of patches outside the list keep whatever y held
+extern "C" int GIM_FN(gim_conv3x3_halo_tiles)(const gim_conv_args* ap, const int* tiles, const int* n_tiles, int tiles_cap, gim_stream_t stream) {
+    GIM_REQUIRE(ap && tiles && n_tiles && tiles_cap >= 0, "gim_conv3x3_halo_tiles: NULL args / tiles / n_tiles or a negative capacity");
+#if !GIM_HALF_KIND
+    if (ap->dtype == GIM_F16) return gim_conv3x3_halo_tiles_f16(ap, tiles, n_tiles, tiles_cap, stream);
+#endif
+    const gim_conv_args& a = *ap;
+    GIM_REQUIRE(a.use_lds_dma == 2 && !a.ups, "gim_conv3x3_halo_tiles: the args must describe a halo launch (use_lds_dma = 2, halo packing)");
+    if (const int rc = conv_check(a)) return rc;
+    return halo_launch(a, tiles, n_tiles, tiles_cap, (hipStream_t)stream);
 }

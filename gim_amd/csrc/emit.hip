@@ -5,6 +5,10 @@
 // (clone, zeros) per forward before -- one launch here.  `gim_pack_matches` is the reporting row
 // [pair_id, x0, y0, x1, y1, conf] of gim_amd/runner.py (was: index + 4-way torch.cat + a pageable host-to-device copy).
 //
+// `gim_fine_tile_list` turns the match lists into the ascending list of 8 x 32 patches of the 1/2-resolution maps that the fine level
+// can read (5 x 5 windows at stride 4 around every coarse match, plus the 3 x 3 receptive field of the FPN's last convolution): the last
+// two FPN layers then run on those patches only (conv_igemm.hip: gim_conv3x3_halo_tiles).
+//
 // Replaces (reference file:line): the tensor construction at networks/loftr/utils/coarse_matching.py:236-259 as far as it
 // only moves data, and the per-pair metric rows of trainer/lightning.py:258-270 (packed form).
 #include "gim_common.h"
@@ -41,7 +45,80 @@ __global__ void __launch_bounds__(256) pack_matches_kernel(const int64_t* __rest
     *(float2*)(o + 4) = make_float2(p1.y, conf[m]);
 }
 
+// One workgroup: zero the patch flags in LDS, mark the patches every match's reach touches, compact the flags in ascending order.
+// The reach of match cell (cy, cx) is [stride * cy - 3, stride * cy + 3] x [stride * cx - 3, stride * cx + 3] clipped to the map: the fine
+// window's +-2 (fine_fused.hip, gather) and one more pixel for the input of the last 3 x 3 convolution.  Rows whose ids lie outside the
+// batch or the coarse map are skipped.
+constexpr int TL_THREADS = 1024, TL_MAX_FLAGS = 32768;
+
+__global__ void __launch_bounds__(TL_THREADS) fine_tile_list_kernel(const int64_t* __restrict__ b_ids, const int64_t* __restrict__ i_ids,
+                                                                  const int64_t* __restrict__ j_ids, const int* __restrict__ count, int cap,
+                                                                  int bs, int w0c, int w1c, int stride, int H, int W,
+                                                                  int* __restrict__ tiles, int* __restrict__ n_tiles, int tiles_cap) {
+    __shared__ unsigned char flags[TL_MAX_FLAGS];
+    __shared__ int part[TL_THREADS];
+    const int t = threadIdx.x;
+    const int tiles_x = (W + 31) / 32, tiles_y = (H + 7) / 8, per_img = tiles_x * tiles_y, nflags = 2 * bs * per_img;
+    for (int i = t; i < nflags; i += TL_THREADS) flags[i] = 0;
+    __syncthreads();
+    int M = count[0];
+    M = M < 0 ? 0 : (M < cap ? M : cap);
+    for (int m = t; m < M; m += TL_THREADS) {
+        const int64_t b = b_ids[m];
+        if (b < 0 || b >= bs) continue;
+#pragma unroll
+        for (int side = 0; side < 2; ++side) {
+            const int64_t cell = side ? j_ids[m] : i_ids[m];
+            const int wc = side ? w1c : w0c;
+            if (cell < 0 || cell >= (int64_t)wc * ((H + stride - 1) / stride)) continue;
+            const int cy = (int)cell / wc, cx = (int)cell - cy * wc;
+            int y0 = cy * stride - 3, y1 = cy * stride + 3, x0 = cx * stride - 3, x1 = cx * stride + 3;
+            y0 = y0 < 0 ? 0 : y0; x0 = x0 < 0 ? 0 : x0;
+            y1 = y1 > H - 1 ? H - 1 : y1; x1 = x1 > W - 1 ? W - 1 : x1;
+            if (y0 > y1 || x0 > x1) continue;
+            const int img = side * bs + (int)b;
+            for (int ty = y0 >> 3; ty <= (y1 >> 3); ++ty)
+                for (int tx = x0 >> 5; tx <= (x1 >> 5); ++tx) flags[(img * tiles_y + ty) * tiles_x + tx] = 1;   // (every writer stores the same byte)
+        }
+    }
+    __syncthreads();
+    // ordered compaction: thread t owns flags [t * per, (t + 1) * per)
+    const int per = (nflags + TL_THREADS - 1) / TL_THREADS;
+    const int lo = t * per < nflags ? t * per : nflags, hi = lo + per < nflags ? lo + per : nflags;
+    int n = 0;
+    for (int i = lo; i < hi; ++i) n += flags[i];
+    part[t] = n;
+    __syncthreads();
+    for (int d = 1; d < TL_THREADS; d <<= 1) {   // inclusive scan
+        const int v = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    int o = part[t] - n;
+    for (int i = lo; i < hi; ++i)
+        if (flags[i]) {
+            if (o < tiles_cap) tiles[o] = i;
+            ++o;
+        }
+    if (t == TL_THREADS - 1) n_tiles[0] = part[t] < tiles_cap ? part[t] : tiles_cap;
+}
+
 }  // namespace
+
+extern "C" int gim_fine_tile_list_max_flags(void) { return TL_MAX_FLAGS; }
+
+extern "C" int gim_fine_tile_list(const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, const int* count, int cap, int bs,
+                                  int w0c, int w1c, int stride, int H, int W, int* tiles, int* n_tiles, int tiles_cap, gim_stream_t stream) {
+    GIM_REQUIRE(b_ids && i_ids && j_ids && count && tiles && n_tiles, "gim_fine_tile_list: NULL pointer");
+    GIM_REQUIRE(cap >= 0 && bs > 0 && w0c > 0 && w1c > 0 && stride > 0 && H > 0 && W > 0, "gim_fine_tile_list: bad geometry");
+    const int64_t nflags = 2ll * bs * ((W + 31) / 32) * ((H + 7) / 8);
+    GIM_REQUIRE(nflags <= TL_MAX_FLAGS, "gim_fine_tile_list: %lld patches exceed the %d flags of the one-workgroup kernel", (long long)nflags, TL_MAX_FLAGS);
+    GIM_REQUIRE(tiles_cap >= nflags, "gim_fine_tile_list: the list holds %d entries, the maps have %lld patches", tiles_cap, (long long)nflags);
+    hipLaunchKernelGGL(fine_tile_list_kernel, dim3(1), dim3(TL_THREADS), 0, (hipStream_t)stream, b_ids, i_ids, j_ids, count, cap, bs, w0c, w1c,
+                       stride, H, W, tiles, n_tiles, tiles_cap);
+    return gim_check_launch("fine_tile_list_kernel");
+}
 
 extern "C" int gim_copy_segments(const gim_copy_segs* sp, gim_stream_t stream) {
     GIM_REQUIRE(sp, "gim_copy_segments: NULL args");

@@ -275,6 +275,9 @@ class LoFTR(nn.Module):
         # the first layer's [k | v] projection as partial KV states too (token kernel, projection only) instead of a GEMM + la_kv launches
         self.kv_init = flag("kv_init", True, config)
         self.pos_fused = flag("pos_fused", True, config)   # ... with the positional encoding added on the fly by that launch (False: gim_posenc_add in front)
+        # 16-bit modes, forward() on equal image shapes: the FPN's last two 3x3 layers (layer1_outconv2, 1/2 resolution) run behind coarse matching, on
+        # the 8 x 32 patches the fine windows of the matches can read and nowhere else (see _fine_tail_sparse; False: the dense maps, as extract() keeps them)
+        self.fine_sparse = flag("fine_sparse", True, config)
         self._packed = None
         self._health = None          # fp16 range guard word of the forward in flight (count[1] of its coarse matching), see _coarse_stage
         self._health_sync_left = 3   # forwards that still wait for the fine kernel to read its health bit at once (fp16 mode)
@@ -504,11 +507,13 @@ class LoFTR(nn.Module):
             off += im.shape[0]
         return out
 
-    def _backbone(self, P, x, dt):
+    def _backbone(self, P, x, dt, fine_tail=True):
         """x: NHWC [B,H,W,cstore(3)] images in the compute dtype.  Returns (x3_out NHWC [B,h8,w8,256], feat_f NHWC [B,h2,w2,128])
-        in the compute dtype.  (resnet.py:230-235, 306-329)"""
+        in the compute dtype.  (resnet.py:230-235, 306-329)  fine_tail = False: the second tensor is the INPUT of the fine head's last
+        two layers instead ([B,h2,w2,196], see _fpn_fine_tail)."""
         x1, x2, x3_out = self._backbone_trunk(P, x, dt)
-        return x3_out, self._fpn_fine(P, x1, x2, x3_out)
+        x1_out = self._fpn_fine(P, x1, x2, x3_out)
+        return x3_out, (self._fpn_fine_tail(P, x1_out) if fine_tail else x1_out)
 
     def _backbone_trunk(self, P, x, dt):
         """stem + layer1-3 + layer3_outconv (resnet.py:306-320): returns (x1, x2, x3_out) -- the coarse features x3_out are complete
@@ -647,16 +652,58 @@ class LoFTR(nn.Module):
         return x, o, x3_out
 
     def _fpn_fine(self, P, x1, x2, x3_out):
-        """the FPN's top-down path to the 1/2-resolution fine features (resnet.py:321-329): six convolutions that nothing of the coarse
-        level (position encoding, transformer, coarse matching) depends on"""
+        """the FPN's top-down path to the 1/2 resolution (resnet.py:321-328): four convolutions that nothing of the coarse level (position
+        encoding, transformer, coarse matching) depends on.  Returns the lateral sum x1_out; `_fpn_fine_tail` makes the fine features of it."""
         dma = self.use_lds_dma
         # lateral 1x1 conv + F.interpolate(scale_factor=2, bilinear, align_corners=True) of the coarser level + add (resnet.py:
         # 321-327): the upsample-add runs in the conv's epilogue when the launch takes it, else as a second pass over the output
         x2_out = ops.conv2d(x2, P["l2o"], lds_dma=dma, ups=x3_out, health=self._health)
         x2_out = ops.conv2d(ops.conv2d(x2_out, P["l2o2a"], ACT_LEAKY, lds_dma=dma, health=self._health), P["l2o2b"], lds_dma=dma, health=self._health)
-        x1_out = ops.conv2d(x1, P["l1o"], lds_dma=dma, ups=x2_out, health=self._health)
-        x1_out = ops.conv2d(ops.conv2d(x1_out, P["l1o2a"], ACT_LEAKY, lds_dma=dma, health=self._health), P["l1o2b"], lds_dma=dma, health=self._health)
-        return x1_out
+        return ops.conv2d(x1, P["l1o"], lds_dma=dma, ups=x2_out, health=self._health)
+
+    def _fine_halo(self, P, h2, w2):
+        """do the fine head's last two layers run on the 3x3 halo kernel at this 1/2-resolution size?  With `fine_sparse` on, every path of the
+        module (forward, extract, debug) sends them there wherever the map is whole 8 x 32 patches, whether the launch then walks a patch list
+        or all patches: one kernel, one K order, so forward() and extract() + match_features() stay bit-identical."""
+        return bool(self.fine_sparse and is_half(self._dt()) and self.use_lds_dma and ops.HALO and P["l1o2a"].halo is not None
+                    and P["l1o2b"].halo is not None and h2 % 8 == 0 and w2 % 32 == 0)
+
+    def _fpn_fine_tail(self, P, x1_out, tiles=None, n_tiles=None):
+        """layer1_outconv2 (resnet.py:329): the two 3x3 layers at 1/2 resolution whose output is the fine map.  tiles / n_tiles
+        (ops.fine_tile_list): only those 8 x 32 patches are computed (see _fine_tail_sparse)."""
+        B, H, W, _ = x1_out.shape
+        if self._fine_halo(P, H, W):
+            # (no health word: these launches add no residual -- ops.conv_rows hands the word to residual / split launches only)
+            mid = torch.empty(B, H, W, P["l1o2a"].n_store, dtype=x1_out.dtype, device=x1_out.device)
+            f = torch.empty(B, H, W, P["l1o2b"].n_store, dtype=x1_out.dtype, device=x1_out.device)
+            ops.conv3x3_halo(x1_out, P["l1o2a"], mid, ACT_LEAKY, tiles=tiles, n_tiles=n_tiles)
+            ops.conv3x3_halo(mid, P["l1o2b"], f, ACT_NONE, tiles=tiles, n_tiles=n_tiles)
+            return f
+        assert tiles is None
+        dma = self.use_lds_dma
+        return ops.conv2d(ops.conv2d(x1_out, P["l1o2a"], ACT_LEAKY, lds_dma=dma, health=self._health), P["l1o2b"], lds_dma=dma, health=self._health)
+
+    def _fine_sparse_ok(self, P, xs):
+        """may this forward compute the fine map under the matched windows only?  (the conditions of _fine_tail_sparse)"""
+        if self.debug is not None or len(xs) != 1:   # debug dumps and the extract() handles hold complete maps
+            return False
+        half = lambda v: (v - 1) // 2 + 1   # noqa: E731
+        B, H, W = xs[0].shape[:3]
+        h2, w2 = half(H), half(W)
+        h8, w8 = half(half(h2)), half(half(w2))
+        # the window stride the gather uses (4 h8 = h2), and no more patches than the one-workgroup list kernel flags
+        return self._fine_halo(P, h2, w2) and h2 == 4 * h8 and w2 == 4 * w8 and B * (h2 // 8) * (w2 // 32) <= ops.FINE_TILE_MAX_FLAGS
+
+    def _fine_tail_sparse(self, P, x1_out, cr, bs):
+        """`_fpn_fine_tail` on the 8 x 32 patches that the fine level can read, behind coarse matching.  The fine map has ONE consumer: the
+        gather of a 5 x 5 window per match and side at rows 4 cy - 2 .. 4 cy + 2 (fine_fused.hip / gim_fine_gather; zeros outside the image).
+        A window pixel of the second layer reads the first layer at +-1 more, so both launches walk one list: the patches that hold a pixel
+        of [4 cy - 3, 4 cy + 3] x [4 cx - 3, 4 cx + 3] for some match (gim_fine_tile_list, from the device-side match count -- no host sync,
+        same captured graph).  Every input of a listed first-layer pixel lies in x1_out, which is dense.  Pixels of other patches are never
+        written and never read: the buffers are NOT cleared (a replayed graph leaves the previous forward's values there)."""
+        _, H, W, _ = x1_out.shape
+        tiles, n_tiles = ops.fine_tile_list(cr.b_ids, cr.i_ids, cr.j_ids, cr.count, bs, cr.args.w0c, cr.args.w1c, 4, H, W)
+        return self._fpn_fine_tail(P, x1_out, tiles, n_tiles)
 
     class _TfBuffers:
         """Row buffers of one LocalFeatureTransformer run over R rows of width C.  The q / k / v rows, the message, the pre-LayerNorm
@@ -993,6 +1040,13 @@ class LoFTR(nn.Module):
             # (round 4: the fine head on a second stream beside the coarse level -- a graph with two branches, the head's persistent
             # workgroups filling the CUs the transformer's 600-tile launches leave idle -- measured SLOWER, 10.96 vs 10.70 ms per step:
             # the two branches fight over L2 and LDS instead of complementing each other; one stream it is)
+            if self._fine_sparse_ok(P, xs):
+                # the fine head stops in front of its last two layers; they run behind coarse matching, under the matched windows only
+                c_all, x1_out = self._extract_stage(P, xs[0], fine_tail=False)
+                st = self._match_stage(P, c_all[:bs], c_all[bs:], None, None, c_all, bs, xs[0].shape[1], scale0, scale1, mask0, mask1, count)
+                f_all = self._fine_tail_sparse(P, x1_out, st["cr"], bs)
+                st["f0"], st["f1"] = f_all[:bs], f_all[bs:]
+                return st
             c_all, f_all = self._extract_stage(P, xs[0])
             c0, c1 = c_all[:bs], c_all[bs:]
             f0, f1 = f_all[:bs], f_all[bs:]
@@ -1007,10 +1061,11 @@ class LoFTR(nn.Module):
         stream, and (fp32 mode with split products) bit 8 of every split launch whose operand left the fp16 range of its hi / lo halves"""
         return word if (self.precision == "fp16" or (self.precision == "fp32" and ops.FP32_SPLIT)) else None
 
-    def _extract_stage(self, P, x):
+    def _extract_stage(self, P, x, fine_tail=True):
         """the per-image half: NHWC images [B,H,W,cstore(3)] -> (coarse map [B,H/8,W/8,256], fine map [B,H/2,W/2,128]) in the compute dtype.
-        No image's maps depend on another image of the batch (eval-mode BatchNorm is folded into the weights)."""
-        return self._backbone(P, x, self._dt())
+        No image's maps depend on another image of the batch (eval-mode BatchNorm is folded into the weights).
+        fine_tail = False (forward's sparse fine tail): the fine head's last two layers are left to the caller, see _backbone."""
+        return self._backbone(P, x, self._dt(), fine_tail)
 
     def _match_stage(self, P, c0, c1, f0, f1, c_all, bs, H0, scale0, scale1, mask0, mask1, count):
         """the per-pair half: coarse maps c0 / c1 [bs,h,w,256] and fine maps f0 / f1 of the bs pairs -> position encoding, coarse
@@ -1055,7 +1110,7 @@ class LoFTR(nn.Module):
 
     def _graph_key(self, color0, color1, scale0, mask0):
         return (tuple(color0.shape), tuple(color1.shape), scale0 is not None, mask0 is not None, self.precision, bool(self.fp32_split),
-                self.coarse_sim, self._img_dt(), self._split(), self._stem_k(), str(color0.device))
+                bool(self.fine_sparse), self.coarse_sim, self._img_dt(), self._split(), self._stem_k(), str(color0.device))
 
     def _coarse_stage_graphed(self, key, color0, color1, scale0, scale1, mask0=None, mask1=None):
         """HIP-graph replay of `_coarse_stage` (one graph per input shape / precision).  ~140 kernel launches collapse into one

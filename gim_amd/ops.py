@@ -292,6 +292,8 @@ def _halo_pays(pk, B, H, W):
     the layers that qualify, -2 % on the 196-channel ones"""
     if H % 8 or W % 32:
         return False
+    if HALO_MIN_TILES <= 0:   # tests: every layer with a halo packing, the padded ones included
+        return True
     npad = pk.halo[0].shape[0]
     bn = 256 if npad % 256 == 0 else 128
     if pk.n_store <= npad - 32:     # incl. the 64-channel layers (SuperPoint / VGG19 / ResNet stems) in the 128-wide tile: half of it would be
@@ -299,9 +301,11 @@ def _halo_pays(pk, B, H, W):
     return B * (H // 8) * (W // 32) * (npad // bn) >= HALO_MIN_TILES
 
 
-def conv3x3_halo(x, pk, y, act=ACT_NONE):
-    """x [B,H,W,cin_pad] bf16 -> y [B,H,W,n_store] bf16 through the halo-tile kernel (3x3, stride 1, pad 1, no residual)"""
-    _req_cuda(x, y)
+def conv3x3_halo(x, pk, y, act=ACT_NONE, tiles=None, n_tiles=None):
+    """x [B,H,W,cin_pad] bf16 -> y [B,H,W,n_store] bf16 through the halo-tile kernel (3x3, stride 1, pad 1, no residual).
+    tiles / n_tiles (int32 device tensors, `fine_tile_list`): only the 8 x 32 patches tiles[:n_tiles[0]] are computed, the count stays on
+    the device; every other pixel of y keeps what it held (gim_conv3x3_halo_tiles)."""
+    _req_cuda(x, y, tiles, n_tiles)
     assert x.is_contiguous() and y.is_contiguous(), "conv3x3_halo addresses pixels as (b*H + y)*W + x rows of width cin_pad"
     B, H, W, cs = x.shape
     w, tab, nslab, bias = pk.halo
@@ -318,14 +322,47 @@ def conv3x3_halo(x, pk, y, act=ACT_NONE):
     a.dtype = a.out_dtype = gim_dtype(x)
     a.res_dtype = GIM_F32
     a.use_lds_dma = 2
+    if tiles is None:
+        launch = lambda: check(lib.gim_conv2d_bn_act(ctypes.byref(a), _stream()), "gim_conv2d_bn_act(halo)")   # noqa: E731
+    else:
+        assert tiles.dtype == n_tiles.dtype == torch.int32 and tiles.is_contiguous() and n_tiles.numel() >= 1
+        assert y.shape[:3] == x.shape[:3]
+        launch = lambda: check(lib.gim_conv3x3_halo_tiles(ctypes.byref(a), _p(tiles), _p(n_tiles), tiles.numel(), _stream()),   # noqa: E731
+                               "gim_conv3x3_halo_tiles")
     if PROFILE is None:
-        check(lib.gim_conv2d_bn_act(ctypes.byref(a), _stream()), "gim_conv2d_bn_act(halo)")
+        launch()
         return
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    check(lib.gim_conv2d_bn_act(ctypes.byref(a), _stream()), "gim_conv2d_bn_act(halo)")
+    launch()
     e1.record()
-    PROFILE.append((e0, e1, 2.0 * B * H * W * pk.cout * pk.cin * 9, f"{pk.cin}->{pk.cout} k3s1 M={B * H * W} halo"))
+    label = f"{pk.cin}->{pk.cout} k3s1 M={B * H * W} halo"
+    if tiles is None:
+        PROFILE.append((e0, e1, 2.0 * B * H * W * pk.cout * pk.cin * 9, label))
+    else:   # the live measurement alone reads the count back: computed patches x per-patch flops
+        PROFILE.append((e0, e1, 2.0 * int(n_tiles[0].item()) * 256 * pk.cout * pk.cin * 9, label + " sparse"))
+
+
+FINE_TILE_MAX_FLAGS = lib.gim_fine_tile_list_max_flags()
+
+
+def fine_tile_list(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W, tiles=None, n_tiles=None):
+    """(tiles int32 [2 bs ceil(H/8) ceil(W/32)], n_tiles int32 [1]): the ascending list of 8 x 32 patches of the 1/2-resolution maps
+    [2 bs, H, W, .] that the fine windows of the first min(count[0], capacity) matches reach through one 3 x 3 convolution
+    (gim_fine_tile_list; one launch, the count is read on the device)"""
+    _req_cuda(b_ids, i_ids, j_ids, count, tiles, n_tiles)
+    assert b_ids.dtype == i_ids.dtype == j_ids.dtype == torch.int64 and count.dtype == torch.int32
+    assert b_ids.is_contiguous() and i_ids.is_contiguous() and j_ids.is_contiguous()
+    cap = min(b_ids.numel(), i_ids.numel(), j_ids.numel())
+    total = 2 * bs * ((H + 7) // 8) * ((W + 31) // 32)
+    if tiles is None:
+        tiles = torch.empty(total, dtype=torch.int32, device=b_ids.device)
+    if n_tiles is None:
+        n_tiles = torch.empty(1, dtype=torch.int32, device=b_ids.device)
+    assert tiles.dtype == n_tiles.dtype == torch.int32 and tiles.is_contiguous()
+    check(lib.gim_fine_tile_list(_p(b_ids), _p(i_ids), _p(j_ids), _p(count), cap, bs, w0c, w1c, stride, H, W, _p(tiles), _p(n_tiles),
+                                 tiles.numel(), _stream()), "gim_fine_tile_list")
+    return tiles, n_tiles
 
 
 def linear(x, pk, y, act=ACT_NONE, lds_dma=True, act_cols=0, health=None):

@@ -9,6 +9,11 @@ names); since round 5 they are plain attributes of the module objects, set
         GIM_FLAGS="fine_fused=0,tf_chains=4"        (separators: , ; +)
     read once at import.
 
+Switches of gim_loftr (`LoFTR.__init__` has each with its comment): stem_fp16, stem_split, stem_kernel, lds_dma, fine_fused, token_fused,
+fine_dev_count, token_emit, bneck_fused, bneck_tail, bneck_ds, bneck_tail_ds, depth_groups, l3_chains, trunk_chains, tf_chains, fp32_split,
+kv_fused, q_local, kv_init, pos_fused, fine_sparse (the FPN's last two layers only under the matched fine windows), graph, graph_cache;
+of gim_amd.ops: conv_halo, conv_halo_min_tiles, force_big_tile, fp32_split_all, ups_fused.
+
 Environment variables the package reads -- all of them, the C library reads none (round 6: the last two getenv() calls left csrc/):
 GIM_PRECISION (default precision mode, gim_amd/precision.py), GIM_FLAGS (this file), GIM_LIB (an alternative libgimhip.so,
 gim_amd/_lib.py), GIM_POSE_BACKEND (host RANSAC backend, gim_amd/pose.py) and the build's GIM_HIPCC_EXTRA / GIM_BUILD_JOBS

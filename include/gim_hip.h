@@ -140,6 +140,12 @@ typedef struct gim_conv_args {
 } gim_conv_args;
 int gim_conv_ups_supported(const gim_conv_args* a);   /* 1 if gim_conv2d_bn_act would take a->ups (set or not) for this launch */
 int gim_conv2d_bn_act(const gim_conv_args* a, gim_stream_t stream);
+/* The 3x3 halo launch of gim_conv2d_bn_act (use_lds_dma = 2: 16-bit, stride 1, pad 1, halo packing) over a device-side list of
+ * 8 x 32-pixel output patches (additive: the ABI revision stays 114).  tiles[0 .. min(*n_tiles, tiles_cap)): int32 patch indices
+ * (image * ceil(H / 8) + ty) * ceil(W / 32) + tx, ascending for L2 locality; *n_tiles is read ON THE DEVICE (no host sync, the grid
+ * does not depend on it; 0 writes nothing).  Listed patches get exactly what the dense launch writes; pixels of every other patch
+ * keep whatever y held.  Entries outside the map are clamped into it. */
+int gim_conv3x3_halo_tiles(const gim_conv_args* a, const int* tiles, const int* n_tiles, int tiles_cap, gim_stream_t stream);
 
 /* y[m,:] += bilinear_upsample_2x(x)[m,:], align_corners=True (resnet.py:321,325: F.interpolate +
  * the `x2_out+x3_out_2x` add).  x: [B,h,w,C] rows (ldx), y: [B,2h,2w,C] rows (ldy), in place. */
@@ -515,6 +521,15 @@ typedef struct gim_copy_segs {
 int gim_copy_segments(const gim_copy_segs* segs, gim_stream_t stream);
 int gim_pack_matches(const int64_t* m_bids, const float* mkpts0, const float* mkpts1, const float* mconf,
                      const int64_t* pair_ids, int64_t pid_base, float* out, int M, gim_stream_t stream);
+/* The patches of the 1/2-resolution fine maps [2 bs, H, W, .] (images of side 0, then of side 1) that the fine level of the first
+ * min(count[0], cap) matches can read, for gim_conv3x3_halo_tiles (additive: the ABI revision stays 114).  A patch is listed when it
+ * holds a pixel of [stride cy - 3, stride cy + 3] x [stride cx - 3, stride cx + 3] clipped to the map, (cy, cx) = the match's coarse cell
+ * (i_ids / w0c on side 0, j_ids / w1c on side 1): the 5 x 5 fine window (fine_preprocess.py:40-47) plus the one-pixel reach of a 3 x 3
+ * convolution.  tiles: ascending int32 patch indices ((side * bs + b) * ceil(H / 8) + ty) * ceil(W / 32) + tx, n_tiles[0] their number;
+ * tiles_cap >= the patch total.  One workgroup, the count is read on the device; at most gim_fine_tile_list_max_flags() patches. */
+int gim_fine_tile_list_max_flags(void);
+int gim_fine_tile_list(const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, const int* count, int cap, int bs,
+                       int w0c, int w1c, int stride, int H, int W, int* tiles, int* n_tiles, int tiles_cap, gim_stream_t stream);
 
 /* ======================================================================================================
  * gim_dkm path (kernels D1-D9).  Convolutions / 1x1 projections / the cosine-kernel and
