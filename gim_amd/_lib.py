@@ -179,6 +179,9 @@ PROTOTYPES = {
     "gim_conv3x3_halo_tiles": (c_int, [ctypes.POINTER(ConvArgs), c_void_p, c_void_p, c_int, c_void_p]),
     "gim_fine_tile_list_max_flags": (c_int, []),
     "gim_fine_tile_list": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p, c_void_p, c_int, c_void_p]),
+    # RANSAC hypothesis scoring of gim_amd/pose.py (additive: the ABI revision stays 114)
+    "gim_ransac_score": (c_int, [c_void_p] * 5 + [c_int, c_int, ctypes.c_double, c_void_p, c_void_p]),
+    "gim_ransac_mask": (c_int, [c_void_p] * 4 + [c_int, ctypes.c_double, c_void_p, c_void_p]),
 }
 
 

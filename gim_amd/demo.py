@@ -182,7 +182,9 @@ def match_pair(model_name, model, detector, path0, path1, device="cuda", resize_
             _, mask = cv2.findFundamentalMat(p0, p1, cv2.USAC_MAGSAC, ransacReprojThreshold=1.0, confidence=0.999999, maxIters=10000)
             out["inliers"] = mask.ravel() > 0 if mask is not None else np.zeros(len(p0), dtype=bool)
         else:
-            _, mask = pose.find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000)
+            # the seven-point candidates are scored on the model's device (pose.DeviceScorer), the solver stays on the host
+            _, mask = pose.find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000,
+                                                device=kpts0.device if kpts0.is_cuda else None)
             out["inliers"] = mask
     return out
 

@@ -1203,6 +1203,70 @@ def nn_match(desc0, desc1, rootsift=False, ratio=0.8, count=None):
     return match0, score0
 
 
+# ---- RANSAC hypothesis scoring (gim_amd/pose.py) -----------------------------------------------------------------
+def _ransac_points(x0, x1, offsets, B):
+    """checks of the point arguments shared by ransac_score / ransac_mask -> (offsets int32 [B + 1] on the device, Ptot)"""
+    for t in (x0, x1):
+        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 2 or not t.is_contiguous():
+            raise _lib.GimHipError(f"ransac points must be contiguous fp64 [P, 2], got {t.dtype} {tuple(t.shape)}")
+    if x0.shape != x1.shape or x0.device != x1.device:
+        raise _lib.GimHipError("ransac points x0 and x1 differ in shape or device")
+    P = x0.shape[0]
+    if offsets is None:
+        return torch.tensor([0, P], dtype=torch.int32, device=x0.device), P
+    if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.shape[0] != B + 1 or not offsets.is_contiguous() or offsets.device != x0.device:
+        raise _lib.GimHipError(f"ransac offsets must be contiguous int32 [B + 1 = {B + 1}] on the points' device")
+    # the kernels trust the offsets, so they are read back once here (B + 1 words; the callers wait for the counts anyway)
+    o = offsets.tolist()
+    if o[0] != 0 or o[-1] != P or any(a > b for a, b in zip(o, o[1:])):
+        raise _lib.GimHipError(f"ransac offsets must rise from 0 to the point count {P}, got {o[:8]}{'...' if len(o) > 8 else ''}")
+    return offsets, P
+
+
+def ransac_score(models, x0, x1, thr2, valid=None, offsets=None):
+    """Inlier counts of candidate models over matched points (gim_ransac_score; fp64, the arithmetic of pose.sampson_error).
+    One pair: models fp64 [K,3,3], x0 / x1 fp64 [P,2], valid bool / uint8 [K] or None -> int32 [K].
+    B pairs: offsets int32 [B+1] (pair b owns the points offsets[b] .. offsets[b+1] of the concatenated x0 / x1), models [B,K,3,3],
+    valid [B,K] -> int32 [B,K].  An invalid or NaN model counts 0."""
+    _req_cuda(models, x0, x1, valid, offsets)
+    single = offsets is None
+    want = 3 if single else 4
+    if models.dtype != torch.float64 or models.dim() != want or models.shape[-2:] != (3, 3) or not models.is_contiguous():
+        raise _lib.GimHipError(f"ransac models must be contiguous fp64 {'[K,3,3]' if single else '[B,K,3,3]'}, got {models.dtype} {tuple(models.shape)}")
+    B, K = (1, models.shape[0]) if single else models.shape[:2]
+    offsets, P = _ransac_points(x0, x1, offsets, B)
+    if models.device != x0.device:
+        raise _lib.GimHipError("ransac models and points are on different devices")
+    if valid is not None:
+        if valid.dtype == torch.bool:
+            valid = valid.view(torch.uint8)
+        if valid.dtype != torch.uint8 or valid.shape != models.shape[:-2] or not valid.is_contiguous() or valid.device != x0.device:
+            raise _lib.GimHipError(f"ransac valid must be contiguous bool / uint8 {tuple(models.shape[:-2])} on the models' device")
+    if P == 0 or B * K == 0:      # nothing to read: every count is 0
+        return torch.zeros(models.shape[:-2], dtype=torch.int32, device=x0.device)
+    counts = torch.empty(models.shape[:-2], dtype=torch.int32, device=x0.device)
+    check(lib.gim_ransac_score(_p(models), _p(valid), _p(x0), _p(x1), _p(offsets), B, K, float(thr2), _p(counts), _stream()),
+          "gim_ransac_score")
+    return counts
+
+
+def ransac_mask(models, x0, x1, thr2, offsets=None):
+    """Inlier mask of one model per pair (gim_ransac_mask): model fp64 [3,3] (one pair) or [B,3,3] with offsets int32 [B+1]
+    -> bool [Ptot], sampson_error(model of the point's pair) <= thr2."""
+    _req_cuda(models, x0, x1, offsets)
+    single = offsets is None
+    if models.dtype != torch.float64 or models.shape != ((3, 3) if single else (models.shape[0], 3, 3)) or not models.is_contiguous():
+        raise _lib.GimHipError(f"ransac_mask models must be contiguous fp64 {'[3,3]' if single else '[B,3,3]'}, got {models.dtype} {tuple(models.shape)}")
+    B = 1 if single else models.shape[0]
+    offsets, P = _ransac_points(x0, x1, offsets, B)
+    if models.device != x0.device:
+        raise _lib.GimHipError("ransac models and points are on different devices")
+    mask = torch.empty(P, dtype=torch.uint8, device=x0.device)
+    if P and B:
+        check(lib.gim_ransac_mask(_p(models), _p(x0), _p(x1), _p(offsets), B, float(thr2), _p(mask), _stream()), "gim_ransac_mask")
+    return mask.view(torch.bool)
+
+
 # ---- gim_semseg ------------------------------------------------------------------------------------------------
 PPM_SCALES = (1, 2, 3, 6)
 PPM_BINS = 50            # 1 + 4 + 9 + 36 pooled vectors per image, bins of scale s from offset PPM_OFFSETS[s]

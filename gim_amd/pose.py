@@ -24,7 +24,11 @@ What is restated (OpenCV 4.x, modules/calib3d/src/five-point.cpp and ptsetreg.cp
 Parity: UNPINNED against cv2 (no OpenCV here to record vectors from; sampling is random in both).  tests/test_pose_cpu.py pins
 the solvers on exact synthetic geometry (every ground-truth E / F is among the candidates to 1e-9, recovered poses within 1e-6
 of the truth on noise-free data, sub-degree on noisy data with 50 % outliers) and compares with cv2 under `importorskip`.
-Batched numpy: 250 samples (2 500 candidate models) are solved and scored per step; a 2 000-match pair takes ~0.2-0.5 s.
+Batched numpy: 250 samples (2 500 candidate models) are solved and scored per step.  Scoring was most of a step, and it can run on
+the GPU (`device=` / `DeviceScorer`, csrc/ransac_score.hip; sampling, the solvers, the iteration bound and recover_pose stay here,
+and the result for a seed is the host's).  Measured on one MI355X box (tools/bench_pose.py, profiles/r12_pose_score.txt; 2 000
+matches, 50 % outliers): one scoring step 53.6 ms on the host against 0.23 ms on the device, estimate_pose 242 ms per pair on the
+host against 53 ms with `device=`.
 """
 import itertools
 import os
@@ -194,15 +198,41 @@ def _count_inliers(Ms, valid, x0, x1, thr2, chunk=128):
     return np.where(valid, out, 0)
 
 
-def _ransac(x0, x1, solver, m, thr, conf, max_iters, rng, s0=None, s1=None, batch=250):
-    """RANSACPointSetRegistrator::run with `solver` on samples of m points; the error is evaluated on (x0, x1), the solver sees
-    (s0, s1) when given (normalised copies of the same points).  -> (model [3,3] or None, mask [P] bool)"""
-    P = x0.shape[0]
-    if P < m:
-        return None, np.zeros(P, dtype=bool)
-    s0 = x0 if s0 is None else s0
-    s1 = x1 if s1 is None else s1
-    thr2 = float(thr) ** 2
+class DeviceScorer:
+    """The scoring half of a RANSAC step on the GPU (csrc/ransac_score.hip through ops.ransac_score / ops.ransac_mask): the points go
+    to the device once, every step uploads its candidate models and reads the counts back, the final mask is one more call.  Same
+    fp64 arithmetic as `sampson_error`, so a RANSAC run scored here walks the trajectory of the host run with the same seed.
+    One pair: x0, x1 [P, 2].  Several pairs in lockstep (`find_essential_mat_batch`): their points concatenated and `offsets` [B + 1];
+    `counts` then takes models [B, K, 3, 3] / valid [B, K] and `mask` one model per pair [B, 3, 3] -> bool [Ptot]."""
+
+    def __init__(self, x0, x1, thr2, device, offsets=None):
+        import torch
+        from . import ops
+        self._torch, self._ops = torch, ops
+        self.device = torch.device(device)
+        self.thr2 = float(thr2)
+        with torch.cuda.device(self.device):
+            self.x0 = torch.from_numpy(np.ascontiguousarray(x0, dtype=np.float64)).to(self.device)
+            self.x1 = torch.from_numpy(np.ascontiguousarray(x1, dtype=np.float64)).to(self.device)
+            self.offsets = None if offsets is None else torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int32)).to(self.device)
+
+    def _up(self, a, dtype):
+        return self._torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(self.device)
+
+    def counts(self, Ms, valid):
+        with self._torch.cuda.device(self.device):
+            c = self._ops.ransac_score(self._up(Ms, np.float64), self.x0, self.x1, self.thr2, valid=self._up(valid, np.uint8), offsets=self.offsets)
+            return c.cpu().numpy().astype(np.int64)
+
+    def mask(self, M):
+        with self._torch.cuda.device(self.device):
+            return self._ops.ransac_mask(self._up(M, np.float64), self.x0, self.x1, self.thr2, offsets=self.offsets).cpu().numpy()
+
+
+def _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch=250):
+    """The sampling / solving / bookkeeping half of RANSACPointSetRegistrator::run as a generator: every step yields its candidate
+    models (Ms [nb * k, 3, 3], valid [nb * k]) and is sent their inlier counts [nb * k]; the generator's return value is the best
+    model [3, 3] or None.  Who counts (the host, a device, one launch for many pairs in lockstep) is the driver's business."""
     lconf = np.log(max(1.0 - conf, 1e-300))
     best_n, best_M = 0, None
     niters, done = int(max_iters), 0
@@ -214,7 +244,7 @@ def _ransac(x0, x1, solver, m, thr, conf, max_iters, rng, s0=None, s1=None, batc
         Ms, valid = solver(s0[idx], s1[idx])
         k = Ms.shape[1]
         Ms = Ms.reshape(-1, 3, 3)
-        per = _count_inliers(Ms, valid.reshape(-1), x0, x1, thr2).reshape(nb, k)
+        per = (yield Ms, valid.reshape(-1)).reshape(nb, k)
         # walk the batch in sample order so that the shrinking iteration bound behaves like the sequential loop
         for s in range(nb):
             j = int(per[s].argmax())
@@ -229,22 +259,97 @@ def _ransac(x0, x1, solver, m, thr, conf, max_iters, rng, s0=None, s1=None, batc
             if done + s + 1 >= niters:
                 break
         done += nb
+    return best_M
+
+
+def _ransac(x0, x1, solver, m, thr, conf, max_iters, rng, s0=None, s1=None, batch=250, scorer=None):
+    """RANSACPointSetRegistrator::run with `solver` on samples of m points; the error is evaluated on (x0, x1), the solver sees
+    (s0, s1) when given (normalised copies of the same points).  `scorer`: None counts inliers and takes the final mask on the host
+    (`_count_inliers`, `sampson_error`); otherwise an object with counts(Ms [K,3,3], valid [K]) -> int64 [K] and
+    mask(M [3,3]) -> bool [P] over the same points and threshold (`DeviceScorer`).  -> (model [3,3] or None, mask [P] bool)"""
+    P = x0.shape[0]
+    if P < m:
+        return None, np.zeros(P, dtype=bool)
+    s0 = x0 if s0 is None else s0
+    s1 = x1 if s1 is None else s1
+    thr2 = float(thr) ** 2
+    steps = _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch)
+    try:
+        Ms, valid = next(steps)
+        while True:
+            counts = _count_inliers(Ms, valid, x0, x1, thr2) if scorer is None else scorer.counts(Ms, valid)
+            Ms, valid = steps.send(counts)
+    except StopIteration as stop:
+        best_M = stop.value
     if best_M is None:
         return None, np.zeros(P, dtype=bool)
-    return best_M, sampson_error(best_M, x0, x1) <= thr2
+    return best_M, (sampson_error(best_M, x0, x1) <= thr2) if scorer is None else scorer.mask(best_M)
 
 
-def find_essential_mat(x0, x1, threshold, prob=0.999, max_iters=1000, seed=0):
-    """cv2.findEssentialMat(x0, x1, eye(3), method=RANSAC, prob, threshold) on normalised points -> (E [3,3] | None, mask [P])"""
+def find_essential_mat(x0, x1, threshold, prob=0.999, max_iters=1000, seed=0, device=None):
+    """cv2.findEssentialMat(x0, x1, eye(3), method=RANSAC, prob, threshold) on normalised points -> (E [3,3] | None, mask [P]).
+    device: score the candidates on that GPU (`DeviceScorer`); same trajectory, model and mask as the host run of the same seed."""
     x0 = np.ascontiguousarray(x0, dtype=np.float64)
     x1 = np.ascontiguousarray(x1, dtype=np.float64)
-    return _ransac(x0, x1, five_point, 5, threshold, prob, max_iters, np.random.default_rng(seed))
+    scorer = DeviceScorer(x0, x1, float(threshold) ** 2, device) if device is not None and x0.shape[0] >= 5 else None
+    return _ransac(x0, x1, five_point, 5, threshold, prob, max_iters, np.random.default_rng(seed), scorer=scorer)
 
 
-def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, seed=0):
+def find_essential_mat_batch(pairs, threshold, prob=0.999, max_iters=1000, seed=0, device=None, scorer=None):
+    """`find_essential_mat(x0, x1, threshold, prob, max_iters, seed)` for every (x0, x1) of `pairs`, run in lockstep: a step solves
+    the samples of every unfinished pair on the host and scores all of them in ONE launch (ragged point sets through offsets); every
+    pair has its own default_rng(seed) and its own shrinking iteration bound, so its result is that of the single call.
+    scorer: an object like DeviceScorer over the concatenated points (counts(models [B,K,3,3], valid [B,K]) -> [B,K],
+    mask(models [B,3,3]) -> bool [Ptot]); default DeviceScorer on `device`; neither: the pairs run one by one on the host.
+    -> [(E [3,3] | None, mask [P_b] bool)] in the order of `pairs`."""
+    pairs = [(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 2), np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 2)) for a, b in pairs]
+    if scorer is None and device is None:
+        return [find_essential_mat(a, b, threshold, prob, max_iters, seed) for a, b in pairs]
+    B = len(pairs)
+    if B == 0:
+        return []
+    offsets = np.concatenate([[0], np.cumsum([a.shape[0] for a, _ in pairs])]).astype(np.int64)
+    if scorer is None:
+        scorer = DeviceScorer(np.concatenate([a for a, _ in pairs]), np.concatenate([b for _, b in pairs]), float(threshold) ** 2, device,
+                              offsets=offsets)
+    best = [None] * B
+    steps, pending = {}, {}
+    for b, (a, c) in enumerate(pairs):
+        if a.shape[0] >= 5:
+            steps[b] = _ransac_steps(a.shape[0], five_point, 5, prob, max_iters, np.random.default_rng(seed), a, c)
+
+    def advance(b, counts):
+        try:
+            pending[b] = next(steps[b]) if counts is None else steps[b].send(counts)
+        except StopIteration as stop:
+            best[b] = stop.value
+            pending.pop(b, None)
+
+    for b in steps:
+        advance(b, None)
+    while pending:
+        K = max(Ms.shape[0] for Ms, _ in pending.values())
+        models, valid = np.zeros((B, K, 3, 3)), np.zeros((B, K), dtype=bool)   # finished pairs and padding: valid = 0
+        for b, (Ms, v) in pending.items():
+            models[b, :Ms.shape[0]], valid[b, :Ms.shape[0]] = Ms, v
+        counts = scorer.counts(models, valid)
+        for b in list(pending):
+            advance(b, counts[b, :pending[b][0].shape[0]])
+    found = [b for b in range(B) if best[b] is not None]
+    masks = np.zeros(offsets[-1], dtype=bool)
+    if found:
+        models = np.zeros((B, 3, 3))
+        for b in found:
+            models[b] = best[b]
+        masks = scorer.mask(models)
+    return [(best[b], masks[offsets[b]:offsets[b + 1]] if best[b] is not None else np.zeros(offsets[b + 1] - offsets[b], dtype=bool))
+            for b in range(B)]
+
+
+def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None):
     """Plain RANSAC over seven-point samples with the Sampson distance in pixels (the demo's geometry filter, demo.py:514-517;
     the reference's USAC_MAGSAC scoring is not restated).  The solver works on Hartley-normalised points, the candidates are
-    mapped back to pixel units for scoring.  -> (F [3,3] | None, mask [P])"""
+    mapped back to pixel units for scoring (on `device` when given, as in find_essential_mat).  -> (F [3,3] | None, mask [P])"""
     p0 = np.ascontiguousarray(p0, dtype=np.float64)
     p1 = np.ascontiguousarray(p1, dtype=np.float64)
     if p0.shape[0] < 7:
@@ -265,7 +370,8 @@ def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, 
         nrm = np.linalg.norm(Fp.reshape(*Fp.shape[:-2], 9), axis=-1)
         return Fp / np.where(nrm > 0, nrm, 1.0)[..., None, None], v
 
-    return _ransac(p0, p1, solver, 7, threshold, prob, max_iters, np.random.default_rng(seed), s0=q0, s1=q1)
+    scorer = DeviceScorer(p0, p1, float(threshold) ** 2, device) if device is not None else None
+    return _ransac(p0, p1, solver, 7, threshold, prob, max_iters, np.random.default_rng(seed), s0=q0, s1=q1, scorer=scorer)
 
 
 def decompose_essential(E):

@@ -123,17 +123,24 @@ def relative_pose_error(T_0to1, R, t, ignore_gt_t_thr=0.0):
     return t_err, np.rad2deg(np.abs(np.arccos(cos))), t_err2
 
 
-def estimate_pose(kpts0, kpts1, K0, K1, thresh=0.5, conf=0.99999):
-    """tools/metrics.py:77-103 (findEssentialMat RANSAC + recoverPose).  Host only.  OpenCV when it imports (the reference's own
-    call), otherwise the numpy restatement of the same two OpenCV routines in gim_amd/pose.py (`GIM_POSE_BACKEND` forces one)."""
+def _normalise(kpts0, kpts1, K0, K1, thresh):
+    """pixels -> normalised image coordinates and the RANSAC threshold in those units (tools/metrics.py:82-86)"""
+    kpts0 = (kpts0 - K0[[0, 1], [2, 2]][None]) / K0[[0, 1], [0, 1]][None]
+    kpts1 = (kpts1 - K1[[0, 1], [2, 2]][None]) / K1[[0, 1], [0, 1]][None]
+    return kpts0, kpts1, thresh / np.mean([K0[0, 0], K1[1, 1], K0[0, 0], K1[1, 1]])
+
+
+def estimate_pose(kpts0, kpts1, K0, K1, thresh=0.5, conf=0.99999, device=None):
+    """tools/metrics.py:77-103 (findEssentialMat RANSAC + recoverPose).  OpenCV when it imports (the reference's own call),
+    otherwise the numpy restatement of the same two OpenCV routines in gim_amd/pose.py (`GIM_POSE_BACKEND` forces one).
+    device: on the numpy backend, score the RANSAC candidates on that GPU (pose.DeviceScorer; same result as the host run);
+    sampling, the five-point solver and recoverPose stay on the host.  OpenCV ignores it."""
     from . import pose
     if len(kpts0) < 5:
         return None
-    kpts0 = (kpts0 - K0[[0, 1], [2, 2]][None]) / K0[[0, 1], [0, 1]][None]
-    kpts1 = (kpts1 - K1[[0, 1], [2, 2]][None]) / K1[[0, 1], [0, 1]][None]
-    ransac_thr = thresh / np.mean([K0[0, 0], K1[1, 1], K0[0, 0], K1[1, 1]])
+    kpts0, kpts1, ransac_thr = _normalise(kpts0, kpts1, K0, K1, thresh)
     if pose.backend() == "numpy":
-        E, mask = pose.find_essential_mat(kpts0, kpts1, ransac_thr, prob=conf)
+        E, mask = pose.find_essential_mat(kpts0, kpts1, ransac_thr, prob=conf, device=device)
         if E is None:
             return None
         n, R, t, _ = pose.recover_pose(E, kpts0, kpts1, 1e9, mask=mask)
@@ -166,25 +173,61 @@ def _np(x):
     return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
 
 
-def evaluate_batch(batch, estimate=None):
+def device_estimator(device, thresh=0.5, conf=0.99999):
+    """`estimate=` hook of evaluate_batch / run_scene: estimate_pose with the RANSAC candidates scored on `device`"""
+    return lambda a, b, k0, k1: estimate_pose(a, b, k0, k1, thresh, conf, device=device)
+
+
+def device_batch_estimator(device, thresh=0.5, conf=0.99999):
+    """`estimate_batch=` hook of evaluate_batch / run_scene: the pairs of a batch through pose.find_essential_mat_batch -- their
+    RANSAC loops advance in lockstep and every step scores all pairs' candidates in one launch on `device`.  Needs one threshold
+    for the batch, so pairs whose intrinsics give another normalised threshold (and every pair when OpenCV is the backend) go through
+    estimate_pose one by one.  pairs: [(kpts0, kpts1, K0, K1)] -> [(R, t, inliers) | None], equal to estimate_pose on each pair."""
+    from . import pose
+
+    def estimate_batch(pairs):
+        out = [None] * len(pairs)
+        if pose.backend() != "numpy":
+            return [estimate_pose(a, b, k0, k1, thresh, conf) for a, b, k0, k1 in pairs]
+        groups = {}
+        for i, (a, b, k0, k1) in enumerate(pairs):
+            if len(a) >= 5:
+                a, b, thr = _normalise(a, b, k0, k1, thresh)
+                groups.setdefault(float(thr), []).append((i, a, b))
+        for thr, members in groups.items():
+            found = pose.find_essential_mat_batch([(a, b) for _, a, b in members], thr, prob=conf, device=device)
+            for (i, a, b), (E, mask) in zip(members, found):
+                if E is not None:
+                    n, R, t, _ = pose.recover_pose(E, a, b, 1e9, mask=mask)
+                    out[i] = (R, t, mask) if n > 0 else None
+        return out
+    return estimate_batch
+
+
+def evaluate_batch(batch, estimate=None, estimate_batch=None):
     """Per-pair dump rows of one matched batch = `Trainer.compute_metrics` (lightning.py:101-122) +
     `compute_symmetrical_epipolar_errors` / `compute_pose_errors` (tools/metrics.py:56-74,107-168).
     `batch` needs mkpts0_f, mkpts1_f, m_bids (the matcher's outputs) and K0, K1, T_0to1, scene_id, pair_names,
     covisible0, covisible1 (the ZEB loaders' fields).  `estimate(kpts0, kpts1, K0, K1)` defaults to the cv2
-    RANSAC of the reference (thresh 0.5, conf 0.99999 -- the values tools/metrics.py:139 hard-codes)."""
+    RANSAC of the reference (thresh 0.5, conf 0.99999 -- the values tools/metrics.py:139 hard-codes).
+    `estimate_batch([(kpts0, kpts1, K0, K1)] of the whole batch) -> [ret]`, when given, replaces the per-pair calls
+    (`device_batch_estimator`)."""
     estimate = estimate or (lambda a, b, k0, k1: estimate_pose(a, b, k0, k1, 0.5, 0.99999))
     m_bids = _np(batch["m_bids"])
     pts0, pts1 = _np(batch["mkpts0_f"]).astype(np.float64), _np(batch["mkpts1_f"]).astype(np.float64)
     K0, K1, T = _np(batch["K0"]).astype(np.float64), _np(batch["K1"]).astype(np.float64), _np(batch["T_0to1"]).astype(np.float64)
     names = list(zip(batch["scene_id"], *batch["pair_names"]))
     rows = []
+    rets = None
+    if estimate_batch is not None:
+        rets = estimate_batch([(pts0[m_bids == b], pts1[m_bids == b], K0[b], K1[b]) for b in range(K0.shape[0])])
     for b in range(K0.shape[0]):
         sel = m_bids == b
         p0, p1 = pts0[sel], pts1[sel]
         t = T[b, :3, 3]
         Tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
         epi = symmetric_epipolar_distance(p0, p1, Tx @ T[b, :3, :3], K0[b], K1[b]) if len(p0) else np.zeros(0)
-        ret = estimate(p0, p1, K0[b], K1[b])
+        ret = estimate(p0, p1, K0[b], K1[b]) if rets is None else rets[b]
         if ret is None:
             R_err = t_err = t_err2 = np.inf
             inl = np.array([]).astype(bool)
@@ -196,7 +239,7 @@ def evaluate_batch(batch, estimate=None):
     return rows
 
 
-def run_scene(matcher, batches, out_path, rank=0, world=1, estimate=None, skip_existing=True):
+def run_scene(matcher, batches, out_path, rank=0, world=1, estimate=None, skip_existing=True, estimate_batch=None):
     """The ZEB test loop of `test.py:188-231` + `trainer/lightning.py:243-275` without Lightning.
     Every rank runs `matcher(batch)` (mutates the batch like LoFTR.forward) over ITS batches -- shard with
     `gim_amd.runner.shard_pairs` or a DistributedSampler -- and scores them on the host; the per-pair rows
@@ -207,7 +250,7 @@ def run_scene(matcher, batches, out_path, rank=0, world=1, estimate=None, skip_e
     rows = []
     for batch in batches:
         matcher(batch)
-        rows.extend(evaluate_batch(batch, estimate))
+        rows.extend(evaluate_batch(batch, estimate, estimate_batch))
     if world > 1:
         import torch.distributed as dist
         gathered = [None] * world

@@ -674,6 +674,27 @@ int64_t gim_nn_match_ws_bytes(int n0, int n1, int D, int rootsift);
 int gim_nn_match(const float* desc0, const float* desc1, int n0, int n1, int D, int rootsift, float ratio, int32_t* match0,
                  float* score0, int32_t* count, void* ws, gim_stream_t stream);
 
+/* ======================================================================================================
+ * RANSAC hypothesis scoring for the pose half of the ZEB loop (additive: the ABI revision stays 114).  Sampling, the minimal
+ * solvers, the iteration bound and recoverPose stay on the host (gim_amd/pose.py); this is the inlier count that was 90 % of its step.
+ * ====================================================================================================== */
+
+/* Inlier counts of K candidate 3x3 models per pair over that pair's points, B pairs in ONE launch.  All pointers are DEVICE memory.
+ * models fp64 [B][K][3][3] row-major; valid uint8 [B][K] or NULL (all valid); x0, x1 fp64 [Ptot][2] (16-byte aligned), the points of
+ * the pairs concatenated; offsets int32 [B + 1], non-decreasing: pair b owns the points offsets[b] .. offsets[b + 1] (the kernel
+ * trusts them -- the caller checks 0 <= offsets[b] <= offsets[b + 1] <= Ptot).  fp64 throughout:
+ *   err = (x1^T M x0)^2 / max(|M x0|_xy^2 + |M^T x1|_xy^2, 1e-300)   with x = (x, y, 1),   inlier when err <= thr2
+ * (pose.sampson_error; EMEstimatorCallback::computeError).  counts int32 [B][K] is FULLY written by the call (no memset by the
+ * caller): 0 for a model with valid == 0, 0 for a model with a NaN entry (its comparison is false), the pair's point count for an
+ * all-zero valid model (0 / 1e-300 = 0, as numpy), 0 for a pair without points.  Only integer sums cross threads: the result does not
+ * depend on the launch shape.  B == 0 or K == 0 returns without touching anything.  B <= 65535. */
+int gim_ransac_score(const double* models, const uint8_t* valid, const double* x0, const double* x1, const int32_t* offsets, int B,
+                     int K, double thr2, int32_t* counts, gim_stream_t stream);
+/* The inlier mask of ONE model per pair with the same arithmetic: models fp64 [B][3][3]; mask uint8 [Ptot], 1 where err <= thr2;
+ * every point of [offsets[0], offsets[B]) is written.  B == 0 returns without touching anything. */
+int gim_ransac_mask(const double* models, const double* x0, const double* x1, const int32_t* offsets, int B, double thr2,
+                    uint8_t* mask, gim_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
