@@ -40,8 +40,10 @@ Coarse similarity (`config['coarse_sim']`; default = the precision mode):
           bench.py reports the flip rate of both settings next to the throughput.
 """
 import collections
+import contextlib
 import math
 import os
+import warnings
 
 import torch
 import torch.nn as nn
@@ -54,6 +56,11 @@ from ..packing import (PRECISION_DTYPE as _DT, PackedStem, cstore, is_half, pack
 
 # gim_conv_args.split16: the weight operand is scaled by 2^12 before its hi / lo split (conv_igemm.hip), and hi = rn16 of it must stay finite
 SPLIT16_WSCALE, SPLIT16_LIMIT = 4096.0, 65504.0
+
+
+def _half(v):
+    """output extent of a stride-2 convolution with pad = k // 2 (k7 p3, k3 p1) over an extent of v"""
+    return (v - 1) // 2 + 1
 
 
 def split16_weight_overflow(packs):
@@ -281,6 +288,7 @@ class LoFTR(nn.Module):
         self._packed = None
         self._health = None          # fp16 range guard word of the forward in flight (count[1] of its coarse matching), see _coarse_stage
         self._health_sync_left = 3   # forwards that still wait for the fine kernel to read its health bit at once (fp16 mode)
+        self._split16 = None         # True inside an entry point of the fp32 mode with fp32_split on (see _launch_scope); None: the launches follow the default of gim_amd.ops
         self._packed_key = None
         self._pe_cache = {}
         self.debug = None  # set to a dict to capture stage outputs (tests): coarse/fine maps, token features
@@ -450,7 +458,6 @@ class LoFTR(nn.Module):
             # range guard, weight side: a BatchNorm-folded weight beyond the IEEE-fp16 range became inf when it was packed
             bad = [k for k, v in P.items() if hasattr(v, "w") and torch.is_tensor(v.w) and not bool(torch.isfinite(v.w).all())]
             if bad:
-                import warnings
                 warnings.warn(f"gim_amd LoFTR: folded weights of {bad[:4]}{' ...' if len(bad) > 4 else ''} exceed the IEEE-fp16 range; "
                               "falling back to precision='bf16' for this module")
                 self.fp16_overflowed = True
@@ -460,7 +467,6 @@ class LoFTR(nn.Module):
             # split range guard, weight side: |w| * 4096 must round to a finite fp16 hi half (gim_conv_args.split16)
             bad = split16_weight_overflow(P)
             if bad:
-                import warnings
                 warnings.warn(f"gim_amd LoFTR: folded weights of {bad[:4]}{' ...' if len(bad) > 4 else ''} reach 65504 / 4096 = 16 and would overflow "
                               "the fp32 mode's IEEE-fp16 split products; falling back to exact fp32 products (fp32_split = False) for this module")
                 self.split_overflowed = True
@@ -489,6 +495,28 @@ class LoFTR(nn.Module):
             pe[3::4] = torch.cos(y_pos * div)
             self._pe_cache[key] = pe.permute(1, 2, 0).reshape(h * w, d_model).contiguous().to(device)
         return self._pe_cache[key]
+
+    # ---- launches ------------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def _launch_scope(self, device):
+        """What forward / extract / match_features run under: the fp32 mode's split products are armed for this module's launches (`_conv`,
+        `_linear`) and for nobody else's.  The weights are packed first: their range check may turn fp32_split off (device None: nothing to
+        pack for, the entry point raises on its inputs).  A scope entered inside another one (the re-run behind `_range_guard`) arms its own
+        value; the outer one is back when it leaves."""
+        if self.precision == "fp32" and self.fp32_split and device is not None:
+            self._prepack(device)
+        outer = self._split16
+        self._split16 = True if (self.precision == "fp32" and self.fp32_split) else None
+        try:
+            yield
+        finally:
+            self._split16 = outer
+
+    def _conv(self, x, pk, act=ACT_NONE, **kw):
+        return ops.conv2d(x, pk, act, lds_dma=self.use_lds_dma, health=self._health, split16=self._split16, **kw)
+
+    def _linear(self, x, pk, y, act=ACT_NONE, **kw):
+        ops.linear(x, pk, y, act, self.use_lds_dma, health=self._health, split16=self._split16, **kw)
 
     # ---- stages -------------------------------------------------------------------------------------
     def _to_nhwc(self, images, dt, out=None):
@@ -527,18 +555,16 @@ class LoFTR(nn.Module):
         B = x.shape[0]
         K = self.l3_chains if (self.debug is None and self.l3_chains > 1 and B % self.l3_chains == 0) else 1
         if K > 1:   # a chain must keep the shapes the fused Bottleneck tails take (256-row tiles at 1/4 and 1/8 resolution), else it would fall back to unfused launches
-            half_ = lambda v: (v - 1) // 2 + 1   # noqa: E731
-            h4, w4 = half_(half_(x.shape[1])), half_(half_(x.shape[2]))
-            if (B // K * h4 * w4) % 256 != 0 or (B // K * half_(h4) * half_(w4)) % 256 != 0:
+            h4, w4 = _half(_half(x.shape[1])), _half(_half(x.shape[2]))
+            if (B // K * h4 * w4) % 256 != 0 or (B // K * _half(h4) * _half(w4)) % 256 != 0:
                 K = 1
         whole = K > 1 and self.trunk_chains   # the chains start at the stem instead of at layer 3
         G = K if whole else (self.depth_groups if (self.debug is None and self.depth_groups > 1 and B % self.depth_groups == 0) else 1)
         o3 = None
         if G > 1:
             n = B // G
-            half = lambda v: (v - 1) // 2 + 1   # noqa: E731
-            H1, W1 = half(x.shape[1]), half(x.shape[2])
-            H2, W2 = half(H1), half(W1)
+            H1, W1 = _half(x.shape[1]), _half(x.shape[2])
+            H2, W2 = _half(H1), _half(W1)
             tdt = torch_dtype(dt)
             x1 = torch.empty(B, H1, W1, P["l1.2.c3"].n_store, dtype=tdt, device=x.device)
             x2 = torch.empty(B, H2, W2, P["l2.3.c3"].n_store, dtype=tdt, device=x.device)
@@ -561,12 +587,12 @@ class LoFTR(nn.Module):
         if K == 1:
             x3, _, x3_out = self._layer(P, 3, 6, x2, o3)
             if x3_out is None:
-                x3_out = ops.conv2d(x3, P["l3o"], lds_dma=self.use_lds_dma, health=self._health)
+                x3_out = self._conv(x3, P["l3o"])
             return x1, x2, x3_out
         n = B // K
         main = torch.cuda.current_stream()
         sides = self._side_streams(x.device, K - 1)
-        x3_out = torch.empty(B, (x2.shape[1] - 1) // 2 + 1, (x2.shape[2] - 1) // 2 + 1, P["l3o"].n_store, dtype=x2.dtype, device=x2.device)
+        x3_out = torch.empty(B, _half(x2.shape[1]), _half(x2.shape[2]), P["l3o"].n_store, dtype=x2.dtype, device=x2.device)
         keep = []   # tensors that cross streams stay referenced until the join (the caching allocator re-uses a freed block per stream)
 
         def chain(g):
@@ -575,7 +601,7 @@ class LoFTR(nn.Module):
             sl = slice(g * n, (g + 1) * n)
             x3, _, xo = self._layer(P, 3, 6, x2[sl], o3[sl] if o3 is not None else None, out_last=(None, x3_out[sl]))
             if xo is None:
-                xo = ops.conv2d(x3, P["l3o"], lds_dma=self.use_lds_dma, health=self._health)
+                xo = self._conv(x3, P["l3o"])
             if xo.data_ptr() != x3_out[sl].data_ptr():
                 ops.copy_segments([(xo.contiguous(), x3_out[sl])])
             keep.append((x3, xo))
@@ -598,11 +624,10 @@ class LoFTR(nn.Module):
     def _trunk12(self, P, x, dt, out=None):
         """stem + layer 1 + layer 2 of a batch (or image group) -> (x1, x2, conv1 output of layer 3's first block or None);
         out = (x1, x2, o3) destinations for the fused kernels' outputs (image-group mode)"""
-        dma = self.use_lds_dma
         if isinstance(P["stem"], PackedStem):
             x = ops.stem7x7(x, P["stem"], out_dtype=torch_dtype(dt))
         else:
-            x = ops.conv2d(x, P["stem"], ACT_RELU, out_dtype=torch_dtype(dt), lds_dma=dma, health=self._health)   # image dtype may be fp16 in bf16 mode
+            x = self._conv(x, P["stem"], ACT_RELU, out_dtype=torch_dtype(dt))   # image dtype may be fp16 in bf16 mode
         x1, o, _ = self._layer(P, 1, 3, x, None, out_last=(out[0], None) if out else None)
         x2, o, _ = self._layer(P, 2, 4, x1, o, out_last=(out[1], out[2]) if out else None)
         return x1, x2, o
@@ -612,7 +637,6 @@ class LoFTR(nn.Module):
         kernel already produced it.  Returns (x', conv1 output of the NEXT layer's first block or None, x3_out or None: the FPN's
         layer3_outconv when layer 3's last fused tail produced it).  out_last = (x', t1') destinations of the last block's fused
         kernel (either may be None)."""
-        dma = self.use_lds_dma
         x3_out = None
         fuse = li == 1 and self.bneck_fused and "l1.0.fused" in P and x.shape[1] % 8 == 0 and x.shape[2] % 32 == 0
         for bi in range(nblk):
@@ -620,23 +644,23 @@ class LoFTR(nn.Module):
             last = bi == nblk - 1
             outs = out_last if last else None
             if o is None:
-                o = ops.conv2d(x, P[p + "c1"], ACT_RELU, lds_dma=dma, health=self._health)
+                o = self._conv(x, P[p + "c1"], ACT_RELU)
             if fuse and self.bneck_ds and (p + "fused_ds") in P and x.shape[3] == 64 and x.is_contiguous():
                 x, o = ops.bneck64_ds(o, x, P[p + "fused_ds"], out=outs, health=self._health)   # ... and the downsample branch: no identity tensor at all
                 continue
-            rows_ds = x.shape[0] * ((x.shape[1] - 1) // 2 + 1) * ((x.shape[2] - 1) // 2 + 1)   # output rows of a stride-2 block
+            rows_ds = x.shape[0] * _half(x.shape[1]) * _half(x.shape[2])   # output rows of a stride-2 block
             if (self.bneck_tail and self.bneck_tail_ds and (p + "tail_ds") in P and x.is_contiguous() and x.shape[3] == 256
                     and rows_ds % 256 == 0 and rows_ds * 512 * 2 < (1 << 32) - 16):   # 32-bit byte offsets into [rows, 512] (its own REQUIRE): oversize batches take the unfused launches
                 # layer 2's first block: conv2, then ONE kernel for conv3 + the stride-2 downsample branch (extra K) + relu + the next conv1:
                 # no downsample launch, no identity tensor (gim_bneck_tail128_ds)
-                o = ops.conv2d(o, P[p + "c2"], ACT_RELU, lds_dma=dma, health=self._health)
+                o = self._conv(o, P[p + "c2"], ACT_RELU)
                 x, o = ops.bneck_tail_ds(o, x, P[p + "tail_ds"], out=outs, health=self._health)
                 continue
-            idn = ops.conv2d(x, P[p + "ds"], ACT_NONE, lds_dma=dma, health=self._health) if (p + "ds") in P else x
+            idn = self._conv(x, P[p + "ds"], ACT_NONE) if (p + "ds") in P else x
             if fuse:   # conv2 -> conv3 + identity -> the next conv1 (of this layer, or layer2's first), one kernel
                 x, o = ops.bneck64(o, idn, P[p + "fused"], True, out=outs, health=self._health)
                 continue
-            o = ops.conv2d(o, P[p + "c2"], ACT_RELU, lds_dma=dma, health=self._health)
+            o = self._conv(o, P[p + "c2"], ACT_RELU)
             rows = o.shape[0] * o.shape[1] * o.shape[2]
             # the tail kernel walks 256-row tiles with 32-bit byte offsets into the [rows, 4 P] tensors (its own REQUIREs)
             if self.bneck_tail and (p + "tail") in P and rows % 256 == 0 and rows * 4 * o.shape[3] * 2 < (1 << 32) - 16:
@@ -647,19 +671,18 @@ class LoFTR(nn.Module):
                 else:
                     x, o = ops.bneck_tail(o, idn.contiguous(), P[p + "tail"], out=outs, health=self._health)   # x' and the next block's conv1 output
                 continue
-            x = ops.conv2d(o, P[p + "c3"], ACT_RELU, res=idn, lds_dma=dma, health=self._health)   # the unfused block stores the stream too
+            x = self._conv(o, P[p + "c3"], ACT_RELU, res=idn)   # the unfused block stores the stream too
             o = None
         return x, o, x3_out
 
     def _fpn_fine(self, P, x1, x2, x3_out):
         """the FPN's top-down path to the 1/2 resolution (resnet.py:321-328): four convolutions that nothing of the coarse level (position
         encoding, transformer, coarse matching) depends on.  Returns the lateral sum x1_out; `_fpn_fine_tail` makes the fine features of it."""
-        dma = self.use_lds_dma
         # lateral 1x1 conv + F.interpolate(scale_factor=2, bilinear, align_corners=True) of the coarser level + add (resnet.py:
         # 321-327): the upsample-add runs in the conv's epilogue when the launch takes it, else as a second pass over the output
-        x2_out = ops.conv2d(x2, P["l2o"], lds_dma=dma, ups=x3_out, health=self._health)
-        x2_out = ops.conv2d(ops.conv2d(x2_out, P["l2o2a"], ACT_LEAKY, lds_dma=dma, health=self._health), P["l2o2b"], lds_dma=dma, health=self._health)
-        return ops.conv2d(x1, P["l1o"], lds_dma=dma, ups=x2_out, health=self._health)
+        x2_out = self._conv(x2, P["l2o"], ups=x3_out)
+        x2_out = self._conv(self._conv(x2_out, P["l2o2a"], ACT_LEAKY), P["l2o2b"])
+        return self._conv(x1, P["l1o"], ups=x2_out)
 
     def _fine_halo(self, P, h2, w2):
         """do the fine head's last two layers run on the 3x3 halo kernel at this 1/2-resolution size?  With `fine_sparse` on, every path of the
@@ -680,17 +703,15 @@ class LoFTR(nn.Module):
             ops.conv3x3_halo(mid, P["l1o2b"], f, ACT_NONE, tiles=tiles, n_tiles=n_tiles)
             return f
         assert tiles is None
-        dma = self.use_lds_dma
-        return ops.conv2d(ops.conv2d(x1_out, P["l1o2a"], ACT_LEAKY, lds_dma=dma, health=self._health), P["l1o2b"], lds_dma=dma, health=self._health)
+        return self._conv(self._conv(x1_out, P["l1o2a"], ACT_LEAKY), P["l1o2b"])
 
     def _fine_sparse_ok(self, P, xs):
         """may this forward compute the fine map under the matched windows only?  (the conditions of _fine_tail_sparse)"""
         if self.debug is not None or len(xs) != 1:   # debug dumps and the extract() handles hold complete maps
             return False
-        half = lambda v: (v - 1) // 2 + 1   # noqa: E731
         B, H, W = xs[0].shape[:3]
-        h2, w2 = half(H), half(W)
-        h8, w8 = half(half(h2)), half(half(w2))
+        h2, w2 = _half(H), _half(W)
+        h8, w8 = _half(_half(h2)), _half(_half(w2))
         # the window stride the gather uses (4 h8 = h2), and no more patches than the one-workgroup list kernel flags
         return self._fine_halo(P, h2, w2) and h2 == 4 * h8 and w2 == 4 * w8 and B * (h2 // 8) * (w2 // 32) <= ops.FINE_TILE_MAX_FLAGS
 
@@ -740,18 +761,17 @@ class LoFTR(nn.Module):
         also projects the source's queries for the second one (`with_q_of_source`: one [q|k|v] GEMM on the source rows instead of a
         [k|v] GEMM now and a q GEMM later -- those rows do not change in between), which then runs with `have_q`."""
         C = T.X32.shape[1]
-        dma = self.use_lds_dma
         x_t, s_t = T.CAT[xs, :C], T.CAT[ss, :C]
         # q/k/v projections with elu(.)+1 (attentions.py:31-32) fused into the epilogue of the q and k columns
         if xs == ss:
-            ops.linear(x_t, P[p + "qkv"], T.QKV[xs], ACT_ELU1, dma, act_cols=2 * C, health=self._health)
+            self._linear(x_t, P[p + "qkv"], T.QKV[xs], ACT_ELU1, act_cols=2 * C)
         else:
             if not have_q:
-                ops.linear(x_t, P[p + "q_proj"], T.QKV[xs, :C], ACT_ELU1, dma, health=self._health)
+                self._linear(x_t, P[p + "q_proj"], T.QKV[xs, :C], ACT_ELU1)
             if with_q_of_source:
-                ops.linear(s_t, P[p + "qkv"], T.QKV[ss], ACT_ELU1, dma, act_cols=2 * C, health=self._health)
+                self._linear(s_t, P[p + "qkv"], T.QKV[ss], ACT_ELU1, act_cols=2 * C)
             else:
-                ops.linear(s_t, P[p + "kv"], T.QKV[ss, C:], ACT_ELU1, dma, act_cols=C, health=self._health)
+                self._linear(s_t, P[p + "kv"], T.QKV[ss, C:], ACT_ELU1, act_cols=C)
         qm = T.MASK[xs] if T.MASK is not None else None  # x_mask / source_mask (transformer.py:50, attentions.py:35-39)
         km = T.MASK[ss] if T.MASK is not None else None
         fused = self.token_fused and (p + "tok") in P
@@ -767,11 +787,11 @@ class LoFTR(nn.Module):
             wts, lnp, eps = P[p + "tok"]
             ops.token_mlp(T.MSG[xs], T.CAT[xs, :C], T.X32[xs], wts, lnp, eps)   # x += norm2(mlp(cat[x, norm1(merge(msg))]))
             return
-        ops.linear(T.MSG[xs], P[p + "merge"], T.MRG[xs], ACT_NONE, dma, health=self._health)
+        self._linear(T.MSG[xs], P[p + "merge"], T.MRG[xs], ACT_NONE)
         g1, b1, e1 = P[p + "norm1"]
         ops.layernorm_residual(T.MRG[xs], g1, b1, None, None, T.CAT[xs, C:], e1)
-        ops.linear(T.CAT[xs], P[p + "mlp0"], T.HID[xs], ACT_RELU, dma, health=self._health)
-        ops.linear(T.HID[xs], P[p + "mlp2"], T.MLP[xs], ACT_NONE, dma, health=self._health)
+        self._linear(T.CAT[xs], P[p + "mlp0"], T.HID[xs], ACT_RELU)
+        self._linear(T.HID[xs], P[p + "mlp2"], T.MLP[xs], ACT_NONE)
         g2, b2, e2 = P[p + "norm2"]
         ops.layernorm_residual(T.MLP[xs], g2, b2, T.X32[xs], T.X32[xs], T.CAT[xs, :C], e2)  # x + message
 
@@ -903,14 +923,14 @@ class LoFTR(nn.Module):
         for (li, sides), blks in groups.items():
             p, r = f"{name}{li}.", rs(sides)
             x_t, q = T.CAT[r, :C], QK[li & 1]
-            blks = sorted(blks)
+            blks = sorted(blks)   # (16-bit packs, no residual: ops.conv_rows drops the health word _linear passes for such launches)
             if blks == [0, 1, 2]:
-                ops.linear(x_t, P[p + "qkv"], q[r], ACT_ELU1, self.use_lds_dma, act_cols=2 * C)
+                self._linear(x_t, P[p + "qkv"], q[r], ACT_ELU1, act_cols=2 * C)
             elif blks == [1, 2]:
-                ops.linear(x_t, P[p + "kv"], q[r, C:], ACT_ELU1, self.use_lds_dma, act_cols=C)
+                self._linear(x_t, P[p + "kv"], q[r, C:], ACT_ELU1, act_cols=C)
             else:
                 assert blks == [0], blks
-                ops.linear(x_t, P[p + "q_proj"], q[r, :C], ACT_ELU1, self.use_lds_dma)
+                self._linear(x_t, P[p + "q_proj"], q[r, :C], ACT_ELU1)
 
         # Fused KV state (token_mlp.hip): the k / v rows of a side have one reader, the state reduction of the call they are the source of.
         # A token tail that would emit them writes its tiles' partial states into that call's workspace instead; the call then only sums them
@@ -1059,7 +1079,8 @@ class LoFTR(nn.Module):
     def _health_word(self, word):
         """the device word the launches of a stage report range trouble into: the fp16 range guard of the kernels that store a residual
         stream, and (fp32 mode with split products) bit 8 of every split launch whose operand left the fp16 range of its hi / lo halves"""
-        return word if (self.precision == "fp16" or (self.precision == "fp32" and ops.FP32_SPLIT)) else None
+        split = ops.FP32_SPLIT if self._split16 is None else self._split16
+        return word if (self.precision == "fp16" or (self.precision == "fp32" and split)) else None
 
     def _extract_stage(self, P, x, fine_tail=True):
         """the per-image half: NHWC images [B,H,W,cstore(3)] -> (coarse map [B,H/8,W/8,256], fine map [B,H/2,W/2,128]) in the compute dtype.
@@ -1112,40 +1133,34 @@ class LoFTR(nn.Module):
         return (tuple(color0.shape), tuple(color1.shape), scale0 is not None, mask0 is not None, self.precision, bool(self.fp32_split),
                 bool(self.fine_sparse), self.coarse_sim, self._img_dt(), self._split(), self._stem_k(), str(color0.device))
 
-    def _coarse_stage_graphed(self, key, color0, color1, scale0, scale1, mask0=None, mask1=None):
-        """HIP-graph replay of `_coarse_stage` (one graph per input shape / precision).  ~140 kernel launches collapse into one
-        graph launch.  The graph's static input is the NHWC image tensor: the two layout kernels that fill it from the caller's
-        NCHW images run eagerly in front of the replay, so the images are never copied as such."""
+    def _stage_graphed(self, key, fill, warm, stage, bs, dev, scale0, scale1, mask0, mask1):
+        """HIP-graph replay of a shape-static stage (one graph per `key`: input shapes / precision): forward's `_coarse_stage` (~140 kernel
+        launches collapse into one graph launch) or match_features' `_match_stage`.  fill(None) builds the graph's static inputs and
+        fill(them) refills them -- the NHWC image tensors from the caller's NCHW images (`_to_nhwc`: the images are never copied as such), or
+        the gathered feature maps (`_gather_pairs`); those launches run eagerly in front of the replay.  warm() fills the host-side caches;
+        stage(static inputs, scale0, scale1, mask0, mask1, count) is what is captured."""
         ent = self._graphs.get(key)
-        dt = self._dt()
-        same = color0.shape[2:] == color1.shape[2:]
-        groups = [[color0, color1]] if same else [[color0], [color1]]
         if ent is None:
             # host-side caches (weight packing does pageable H2D copies, the position table is built on the CPU) must be
             # filled BEFORE capture starts, whatever ran earlier
-            self._prepack(color0.device)
-            C = self.config["coarse"]["d_model"]
-            half = lambda n: (n - 1) // 2 + 1   # noqa: E731  the three stride-2 convs (k7 p3, k3 p1, k3 p1)
-            for c in (color0, color1):
-                self._pos_encoding(C, half(half(half(c.shape[2]))), half(half(half(c.shape[3]))), c.device)
-            sin = [[self._to_nhwc(g, self._img_dt()) for g in groups],
+            warm()
+            sin = [fill(None),
                    scale0.clone().float() if scale0 is not None else None,
                    scale1.clone().float() if scale1 is not None else None,
-                   mask0.clone() if mask0 is not None else None, mask1.clone() if mask1 is not None else None]
-            # the count buffer of the captured coarse matching: zeroed HERE, outside the capture (its health bit 1 is sticky)
-            sin.append(torch.zeros(2 + color0.shape[0], dtype=torch.int32, device=color0.device))
+                   mask0.clone() if mask0 is not None else None, mask1.clone() if mask1 is not None else None,
+                   # the count buffer of the captured coarse matching: zeroed HERE, outside the capture (its health bit 1 is sticky)
+                   torch.zeros(2 + bs, dtype=torch.int32, device=dev)]
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             # thread_local: other threads (e.g. RCCL's watchdog in multi-GPU runs) may issue HIP calls meanwhile
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                out = self._coarse_stage(sin[0], color0.shape[0], *sin[1:])
+                out = stage(*sin)
             while len(self._graphs) >= self.graph_cache_size:  # LRU eviction frees that graph's pool
                 self._graphs.popitem(last=False)
             ent = self._graphs[key] = (graph, sin, out)
         else:
             self._graphs.move_to_end(key)
-            for g, x in zip(groups, ent[1][0]):
-                self._to_nhwc(g, self._img_dt(), out=x)
+            fill(ent[1][0])
         graph, sin, out = ent
         small = []
         if scale0 is not None:
@@ -1156,18 +1171,52 @@ class LoFTR(nn.Module):
         graph.replay()
         return out
 
+    def _run_stage(self, key, graphed, eager):
+        """graphed() or eager() -> (the stage's result, whether a graph replay produced it).  A key is captured the second time it is seen:
+        its first call runs eagerly, doubles as the warm-up and raises whatever the inputs deserve."""
+        counted = self.use_graph and self.debug is None
+        if counted and (key in self._graphs or self._seen.get(key, 0) >= 1):
+            try:
+                return graphed(), True
+            except RuntimeError as e:
+                # only a failed *capture* (HIP graphs unsupported in this environment) lands here: input errors
+                # (ValueError / GimHipError from argument checks) were raised by this key's eager first call
+                if key in self._graphs or "captur" not in str(e).lower():   # '... when stream is capturing', 'StreamCapture...'
+                    raise
+                warnings.warn(f"gim_amd: HIP graph capture failed ({e!r}); using eager kernel launches")
+                self.use_graph = counted = False
+                self._graphs.clear()
+        st = eager()
+        if counted:   # only once the eager call went through (bad inputs raised above)
+            self._seen[key] = self._seen.get(key, 0) + 1
+            while len(self._seen) > 64:
+                self._seen.popitem(last=False)
+        return st, False
+
+    @staticmethod
+    def _pair_inputs(data, dev, exp0, exp1, per="N", rows=None):
+        """data's optional scale0 / scale1 (fp32) and mask0 / mask1 (uint8 0 / 1: '0' = padded, loftr.py:49-50, 77-79) on dev, None where
+        absent.  exp0 / exp1: the [n, H/8, W/8] shapes the masks must have; rows: the row count the scales must have (match_features);
+        per: how the messages name the leading dimension."""
+        scale0, scale1 = data.get("scale0"), data.get("scale1")
+        if scale0 is not None:
+            scale0 = scale0.to(device=dev, dtype=torch.float32).contiguous()
+            scale1 = scale1.to(device=dev, dtype=torch.float32).contiguous()
+            if rows is not None and (scale0.shape[0] != rows or scale1.shape[0] != rows):
+                raise ValueError(f"scale0/scale1 must have one row per pair ({rows})")
+        mask0 = mask1 = None
+        if "mask0" in data:
+            mask0 = data["mask0"].to(device=dev).ne(0).to(torch.uint8).contiguous()
+            mask1 = data["mask1"].to(device=dev).ne(0).to(torch.uint8).contiguous()
+            if tuple(mask0.shape) != tuple(exp0) or tuple(mask1.shape) != tuple(exp1):
+                raise ValueError(f"mask0/mask1 must be [{per}, H/8, W/8]: got {tuple(mask0.shape)}, {tuple(mask1.shape)}")
+        return scale0, scale1, mask0, mask1
+
     @torch.no_grad()
     def forward(self, data):
         c0 = data.get("color0")
-        if self.precision == "fp32" and self.fp32_split and torch.is_tensor(c0) and c0.is_cuda:
-            self._prepack(c0.device)   # first: the packed weights' range check may turn fp32_split off
-        if self.precision == "fp32" and self.fp32_split and not ops.FP32_SPLIT:
-            ops.FP32_SPLIT = True   # (module state of gim_amd.ops, read at every fp32 conv / linear launch)
-            try:
-                return self._forward(data)
-            finally:
-                ops.FP32_SPLIT = False
-        return self._forward(data)
+        with self._launch_scope(c0.device if torch.is_tensor(c0) and c0.is_cuda else None):
+            return self._forward(data)
 
     def _forward(self, data):
         for k in ("image0", "image1", "color0", "color1"):
@@ -1181,48 +1230,29 @@ class LoFTR(nn.Module):
         self._prepack(dev)   # first: packing may still change the mode (fp16 weights out of range -> bf16, see _prepack)
         color0 = color0.contiguous().float()
         color1 = color1.contiguous().float()
-        scale0, scale1 = data.get("scale0"), data.get("scale1")
-        if scale0 is not None:
-            scale0 = scale0.to(device=dev, dtype=torch.float32).contiguous()
-            scale1 = scale1.to(device=dev, dtype=torch.float32).contiguous()
-
-        mask0 = mask1 = None
-        if "mask0" in data:  # [N, h/8, w/8] padding masks, '0' = padded (loftr.py:49-50, 77-79)
-            mask0 = data["mask0"].to(device=dev).ne(0).to(torch.uint8).contiguous()
-            mask1 = data["mask1"].to(device=dev).ne(0).to(torch.uint8).contiguous()
-            exp0 = (color0.shape[0], color0.shape[2] // 8, color0.shape[3] // 8)
-            exp1 = (color1.shape[0], color1.shape[2] // 8, color1.shape[3] // 8)
-            if tuple(mask0.shape) != exp0 or tuple(mask1.shape) != exp1:
-                raise ValueError(f"mask0/mask1 must be [N, H/8, W/8]: got {tuple(mask0.shape)}, {tuple(mask1.shape)}")
-
+        scale0, scale1, mask0, mask1 = self._pair_inputs(data, dev, (color0.shape[0], color0.shape[2] // 8, color0.shape[3] // 8),
+                                                         (color1.shape[0], color1.shape[2] // 8, color1.shape[3] // 8))
         data.update({"bs": data["image0"].size(0),
                      "hw0_i": data["image0"].shape[2:], "hw1_i": data["image1"].shape[2:]})
         bs = data["bs"]
-        graphed = False
-        if self.use_graph and self.debug is None:
-            key = self._graph_key(color0, color1, scale0, mask0)
-            if key in self._graphs or self._seen.get(key, 0) >= 1:
-                try:
-                    st = self._coarse_stage_graphed(key, color0, color1, scale0, scale1, mask0, mask1)
-                    graphed = True
-                except RuntimeError as e:
-                    # only a failed *capture* (HIP graphs unsupported in this environment) lands here: input errors
-                    # (ValueError / GimHipError from argument checks) were raised by this shape's eager first call
-                    if key in self._graphs or "captur" not in str(e).lower():   # '... when stream is capturing', 'StreamCapture...'
-                        raise
-                    import warnings
-                    warnings.warn(f"gim_amd: HIP graph capture failed ({e!r}); using eager kernel launches")
-                    self.use_graph = False
-                    self._graphs.clear()
-        if not graphed:
-            same = color0.shape[2:] == color1.shape[2:]
-            idt = self._img_dt()
-            xs = [self._to_nhwc([color0, color1], idt)] if same else [self._to_nhwc([color0], idt), self._to_nhwc([color1], idt)]
-            st = self._coarse_stage(xs, bs, scale0, scale1, mask0, mask1)
-            if self.use_graph and self.debug is None:   # counted only once the eager call went through (bad inputs raise above)
-                self._seen[key] = self._seen.get(key, 0) + 1
-                while len(self._seen) > 64:
-                    self._seen.popitem(last=False)
+        groups = [[color0, color1]] if color0.shape[2:] == color1.shape[2:] else [[color0], [color1]]
+
+        def to_nhwc(out):
+            if out is None:
+                return [self._to_nhwc(g, self._img_dt()) for g in groups]
+            for g, x in zip(groups, out):
+                self._to_nhwc(g, self._img_dt(), out=x)
+
+        def warm():
+            self._prepack(dev)
+            for c in (color0, color1):   # the coarse maps behind the three stride-2 convs (k7 p3, k3 p1, k3 p1)
+                self._pos_encoding(self.config["coarse"]["d_model"], _half(_half(_half(c.shape[2]))), _half(_half(_half(c.shape[3]))), dev)
+
+        key = self._graph_key(color0, color1, scale0, mask0)
+        st, graphed = self._run_stage(
+            key, lambda: self._stage_graphed(key, to_nhwc, warm, lambda xs, *rest: self._coarse_stage(xs, color0.shape[0], *rest), color0.shape[0], dev,
+                                             scale0, scale1, mask0, mask1),
+            lambda: self._coarse_stage(to_nhwc(None), bs, scale0, scale1, mask0, mask1))
         return self._finish(data, st, graphed, scale1, lambda: self.forward(data))
 
     def _finish(self, data, st, graphed, scale1, rerun):
@@ -1274,14 +1304,9 @@ class LoFTR(nn.Module):
             if health & 14:
                 cr.count[1:2].zero_()   # sticky bits: acknowledged
             if self._range_guard(health):
-                # the module is in bf16 now, or its fp32 mode multiplies exactly: same inputs, once more (the split switch of gim_amd.ops
-                # is module state that this forward's caller set: off for the re-run, restored after it)
-                split = ops.FP32_SPLIT
-                ops.FP32_SPLIT = False
-                try:
-                    return rerun()
-                finally:
-                    ops.FP32_SPLIT = split
+                # the module is in bf16 now, or its fp32 mode multiplies exactly: same inputs, once more (the re-run's own _launch_scope
+                # arms what the module's mode asks for now)
+                return rerun()
         self._generation += 1
         if not dev_count and M > 0:
             fine = self._fine_level(f0, f1, cr.b_ids[:M], cr.i_ids[:M], cr.j_ids[:M], cr.mkpts1_c[:M], scale1, "scale0" in data,
@@ -1322,18 +1347,6 @@ class LoFTR(nn.Module):
         fp32 mode's fallback to exact products."""
         return (self.precision, bool(self.fp32_split), self._weights_gen)
 
-    def _split_scope(self, fn, device):
-        """run fn() under the fp32 mode's split-product switch exactly as forward() does (pack-time weight check first)"""
-        if self.precision == "fp32" and self.fp32_split:
-            self._prepack(device)   # first: the packed weights' range check may turn fp32_split off
-        if self.precision == "fp32" and self.fp32_split and not ops.FP32_SPLIT:
-            ops.FP32_SPLIT = True
-            try:
-                return fn()
-            finally:
-                ops.FP32_SPLIT = False
-        return fn()
-
     @torch.no_grad()
     def extract(self, color):
         """color [N,3,H,W] on the device, N >= 1 independent images -> LoFTRFeatures: the per-image half of forward() (layout kernel +
@@ -1345,7 +1358,8 @@ class LoFTR(nn.Module):
         if not color.is_cuda:
             raise GimHipError("gim_amd LoFTR runs on the HIP device only (no CPU fallback): move the inputs "
                               "and the module to 'cuda'")
-        return self._split_scope(lambda: self._extract(color), color.device)
+        with self._launch_scope(color.device):
+            return self._extract(color)
 
     def _extract(self, color):
         dev = color.device
@@ -1360,13 +1374,7 @@ class LoFTR(nn.Module):
             self._health = None
         health = int(word.item()) if guarded else 0   # the one read-back of an extraction
         if health and self._range_guard(health):
-            # the module is in bf16 now, or its fp32 mode multiplies exactly: same images, once more
-            split = ops.FP32_SPLIT
-            ops.FP32_SPLIT = False
-            try:
-                return self.extract(color)
-            finally:
-                ops.FP32_SPLIT = split
+            return self.extract(color)   # the module is in bf16 now, or its fp32 mode multiplies exactly: same images, once more
         return LoFTRFeatures(coarse, fine, color.shape[2:], self.feature_tag())
 
     def _check_handle(self, feats, name):
@@ -1386,9 +1394,8 @@ class LoFTR(nn.Module):
         captured per shape into a HIP graph like forward()'s coarse stage: other indices replay the same graph."""
         self._check_handle(feats0, "feats0")
         self._check_handle(feats1, "feats1")
-        dev = feats0.coarse.device
-        out = self._split_scope(lambda: self._match_features(feats0, feats1, idx0, idx1, {} if data is None else data), dev)
-        return out
+        with self._launch_scope(feats0.coarse.device):
+            return self._match_features(feats0, feats1, idx0, idx1, {} if data is None else data)
 
     @staticmethod
     def _host_index(idx, n):
@@ -1435,42 +1442,6 @@ class LoFTR(nn.Module):
             ops.slot_copy(feats1.fine, f1, src_idx=i1)
         return out
 
-    def _match_stage_graphed(self, key, gather, bs, H0, scale0, scale1, mask0, mask1):
-        """HIP-graph replay of `_match_stage` (one graph per shape / precision).  The graph's static inputs are the gathered buffers, as the
-        NHWC image tensor is for `_coarse_stage_graphed`: the gather launches run eagerly in front of the replay."""
-        ent = self._graphs.get(key)
-        if ent is None:
-            bufs = gather(None)
-            dev = bufs[0].device
-            P = self._prepack(dev)   # host-side caches are filled BEFORE capture starts (see _coarse_stage_graphed)
-            C = self.config["coarse"]["d_model"]
-            for c in bufs[:2]:
-                self._pos_encoding(C, c.shape[1], c.shape[2], dev)
-            sin = [bufs,
-                   scale0.clone().float() if scale0 is not None else None,
-                   scale1.clone().float() if scale1 is not None else None,
-                   mask0.clone() if mask0 is not None else None, mask1.clone() if mask1 is not None else None,
-                   torch.zeros(2 + bs, dtype=torch.int32, device=dev)]   # zeroed HERE, outside the capture (its health bit 1 is sticky)
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                out = self._match_stage(P, *bufs[:5], bs, H0, *sin[1:])
-            while len(self._graphs) >= self.graph_cache_size:  # LRU eviction frees that graph's pool
-                self._graphs.popitem(last=False)
-            ent = self._graphs[key] = (graph, sin, out)
-        else:
-            self._graphs.move_to_end(key)
-            gather(ent[1][0])
-        graph, sin, out = ent
-        small = []
-        if scale0 is not None:
-            small += [(scale0, sin[1]), (scale1, sin[2])]
-        if mask0 is not None:
-            small += [(mask0, sin[3]), (mask1, sin[4])]
-        ops.copy_segments(small)
-        graph.replay()
-        return out
-
     def _match_features(self, feats0, feats1, idx0, idx1, data):
         dev = feats0.coarse.device
         if feats1.coarse.device != dev:
@@ -1482,43 +1453,21 @@ class LoFTR(nn.Module):
         bs = len(i0) if isinstance(i0, list) else i0.numel()
         if bs != (len(i1) if isinstance(i1, list) else i1.numel()) or bs < 1:
             raise ValueError("idx0 and idx1 must name the same number of pairs (>= 1)")
-        scale0, scale1 = data.get("scale0"), data.get("scale1")
-        if scale0 is not None:
-            scale0 = scale0.to(device=dev, dtype=torch.float32).contiguous()
-            scale1 = scale1.to(device=dev, dtype=torch.float32).contiguous()
-            if scale0.shape[0] != bs or scale1.shape[0] != bs:
-                raise ValueError(f"scale0/scale1 must have one row per pair ({bs})")
-        mask0 = mask1 = None
-        if "mask0" in data:  # [P, h/8, w/8] padding masks, '0' = padded (loftr.py:49-50, 77-79)
-            mask0 = data["mask0"].to(device=dev).ne(0).to(torch.uint8).contiguous()
-            mask1 = data["mask1"].to(device=dev).ne(0).to(torch.uint8).contiguous()
-            if tuple(mask0.shape) != (bs, *feats0.coarse.shape[1:3]) or tuple(mask1.shape) != (bs, *feats1.coarse.shape[1:3]):
-                raise ValueError(f"mask0/mask1 must be [P, H/8, W/8]: got {tuple(mask0.shape)}, {tuple(mask1.shape)}")
+        scale0, scale1, mask0, mask1 = self._pair_inputs(data, dev, (bs, *feats0.coarse.shape[1:3]), (bs, *feats1.coarse.shape[1:3]), per="P", rows=bs)
         data.update({"bs": bs, "hw0_i": feats0.hw_i, "hw1_i": feats1.hw_i})
         H0 = feats0.hw_i[0]
-        gather = lambda out: self._gather_pairs(feats0, feats1, i0, i1, bs, out)   # noqa: E731
-        graphed = False
-        if self.use_graph and self.debug is None:
-            key = ("match_features", bs, tuple(feats0.coarse.shape[1:]), tuple(feats1.coarse.shape[1:]), tuple(feats0.hw_i), tuple(feats1.hw_i),
-                   scale0 is not None, mask0 is not None, self.precision, bool(self.fp32_split), self.coarse_sim, str(dev))
-            if key in self._graphs or self._seen.get(key, 0) >= 1:
-                try:
-                    st = self._match_stage_graphed(key, gather, bs, H0, scale0, scale1, mask0, mask1)
-                    graphed = True
-                except RuntimeError as e:   # a failed capture only (see _forward)
-                    if key in self._graphs or "captur" not in str(e).lower():
-                        raise
-                    import warnings
-                    warnings.warn(f"gim_amd: HIP graph capture failed ({e!r}); using eager kernel launches")
-                    self.use_graph = False
-                    self._graphs.clear()
-        if not graphed:
-            bufs = gather(None)
-            st = self._match_stage(P, *bufs[:5], bs, H0, scale0, scale1, mask0, mask1, torch.zeros(2 + bs, dtype=torch.int32, device=dev))
-            if self.use_graph and self.debug is None:
-                self._seen[key] = self._seen.get(key, 0) + 1
-                while len(self._seen) > 64:
-                    self._seen.popitem(last=False)
+        gather = lambda out=None: self._gather_pairs(feats0, feats1, i0, i1, bs, out)   # noqa: E731
+        stage = lambda bufs, *rest: self._match_stage(P, *bufs[:5], bs, H0, *rest)   # noqa: E731
+
+        def warm():
+            self._prepack(dev)
+            for f in (feats0, feats1):
+                self._pos_encoding(self.config["coarse"]["d_model"], *f.coarse.shape[1:3], dev)
+
+        key = ("match_features", bs, tuple(feats0.coarse.shape[1:]), tuple(feats1.coarse.shape[1:]), tuple(feats0.hw_i), tuple(feats1.hw_i),
+               scale0 is not None, mask0 is not None, self.precision, bool(self.fp32_split), self.coarse_sim, str(dev))
+        st, graphed = self._run_stage(key, lambda: self._stage_graphed(key, gather, warm, stage, bs, dev, scale0, scale1, mask0, mask1),
+                                      lambda: stage(gather(), scale0, scale1, mask0, mask1, torch.zeros(2 + bs, dtype=torch.int32, device=dev)))
 
         def stale():
             raise StaleFeaturesError("the range guard changed the module's mode while these features were matched: extract them again")
@@ -1532,7 +1481,6 @@ class LoFTR(nn.Module):
         this module to bf16 for good -- same kernels, fp32's exponent range -- and tell the caller to run the batch again.  In the
         other modes the inputs or weights themselves were not finite: warn only.  The reference computes in fp32 and has no such
         case (networks/loftr/utils/coarse_matching.py:174-195 would return no match for a NaN row, silently)."""
-        import warnings
         what = " and ".join(w for b, w in ((4, "a residual-stream value beyond 65504"), (8, "a split-product operand beyond 65504"),
                                            (1, "non-finite coarse similarities"), (2, "non-finite fine-level outputs")) if health & b)
         if self.precision == "fp16":

@@ -204,10 +204,10 @@ def nhwc_to_nchw(src, C):
 
 
 # ---- conv / linear --------------------------------------------------------------------------------
-def conv_rows(x, pk, geom, y, act=ACT_NONE, res=None, res_mod=0, lds_dma=True, act_cols=0, ups=None, health=None):
+def conv_rows(x, pk, geom, y, act=ACT_NONE, res=None, res_mod=0, lds_dma=True, act_cols=0, ups=None, health=None, split16=None):
     """Generic launch.  x: 2-D row view [rows_in, ldx]; geom = (B, H, W, Ho, Wo); y: 2-D row view.  ups: half-resolution NHWC
     tensor whose bilinear x2 upsampling is added in the epilogue, or a callable that performs that addition as a separate pass when
-    the launch cannot take it (returns True when it was fused)."""
+    the launch cannot take it (returns True when it was fused).  split16: fp32 operands as split products (None: the module's default, below)."""
     _req_cuda(x, y, res)
     B, H, W, Ho, Wo = geom
     a = _lib.ConvArgs()
@@ -227,7 +227,7 @@ def conv_rows(x, pk, geom, y, act=ACT_NONE, res=None, res_mod=0, lds_dma=True, a
     a.dtype, a.out_dtype = pk.dtype, gim_dtype(y)
     a.res_dtype = gim_dtype(res) if res is not None else GIM_F32
     a.use_lds_dma = (3 if FORCE_BIG_TILE else 1) if lds_dma else 0
-    a.split16 = 1 if (FP32_SPLIT and pk.dtype == GIM_F32 and lds_dma) else 0
+    a.split16 = 1 if ((FP32_SPLIT if split16 is None else split16) and pk.dtype == GIM_F32 and lds_dma) else 0
     # residual launches: the fp16 range guard (ORs 4); split launches: an operand beyond the fp16 range of the hi / lo split (ORs 8)
     a.health = _health(health).value if (health is not None and (res is not None or a.split16)) else None
     assert y.shape[0] >= B * Ho * Wo and y.shape[1] >= pk.n_store
@@ -250,12 +250,12 @@ def conv_rows(x, pk, geom, y, act=ACT_NONE, res=None, res_mod=0, lds_dma=True, a
 
 FORCE_BIG_TILE = flag("force_big_tile", False)   # tests: the 256 x 256 tile on every eligible launch, whatever its size (gim_conv_args.use_lds_dma = 3)
 # fp32 operands multiplied as IEEE-fp16 hi / lo pairs on the 16-bit MFMA (gim_conv_args.split16: three products per 16 K instead of eight fp32 MFMAs, 2^-22 per
-# product); module state read at every launch -- gim_loftr's fp32 mode switches it on around its forward (LoFTR.fp32_split)
+# product): the default of the launches that pass no `split16` -- gim_loftr's fp32 mode passes its own per launch (LoFTR.fp32_split)
 FP32_SPLIT = flag("fp32_split_all", False)
 UPS_FUSED = flag("ups_fused", True)   # FPN: bilinear x2 + add inside the lateral 1x1 conv's epilogue (False: a second pass over the output)
 
 
-def conv2d(x, pk, act=ACT_NONE, res=None, out_dtype=None, lds_dma=True, ups=None, health=None):
+def conv2d(x, pk, act=ACT_NONE, res=None, out_dtype=None, lds_dma=True, ups=None, health=None, split16=None):
     """x [B,H,W,cin_pad] NHWC -> new [B,Ho,Wo,n_store].  ups: [B,Ho/2,Wo/2,n_store] -> y += bilinear_x2(ups) (align_corners=True):
     in the conv's epilogue when the launch supports it, otherwise as a second pass (gim_upsample2x_add)."""
     B, H, W, cs = x.shape
@@ -274,10 +274,10 @@ def conv2d(x, pk, act=ACT_NONE, res=None, out_dtype=None, lds_dma=True, ups=None
         return y
     if ups is not None:
         assert ups.shape == (B, Ho // 2, Wo // 2, pk.n_store) and res is None and ups.is_contiguous()
-        if not conv_rows(x.view(-1, cs), pk, geom, y.view(-1, pk.n_store), act, r, 0, lds_dma, ups=ups, health=health):
+        if not conv_rows(x.view(-1, cs), pk, geom, y.view(-1, pk.n_store), act, r, 0, lds_dma, ups=ups, health=health, split16=split16):
             upsample2x_add(ups, y)
         return y
-    conv_rows(x.view(-1, cs), pk, geom, y.view(-1, pk.n_store), act, r, 0, lds_dma, health=health)
+    conv_rows(x.view(-1, cs), pk, geom, y.view(-1, pk.n_store), act, r, 0, lds_dma, health=health, split16=split16)
     return y
 
 
@@ -365,11 +365,11 @@ def fine_tile_list(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W, tiles
     return tiles, n_tiles
 
 
-def linear(x, pk, y, act=ACT_NONE, lds_dma=True, act_cols=0, health=None):
+def linear(x, pk, y, act=ACT_NONE, lds_dma=True, act_cols=0, health=None, split16=None):
     """x: row view [rows, >=K] (row stride may exceed K), y: row view [rows, >=N].  y = act(x @ W^T);
     act_cols > 0 restricts the activation to output columns < act_cols.  health: see conv_rows (split launches only here)."""
     rows = x.shape[0]
-    conv_rows(x, pk, (1, 1, rows, 1, rows), y, act, None, 0, lds_dma, act_cols, health=health)
+    conv_rows(x, pk, (1, 1, rows, 1, rows), y, act, None, 0, lds_dma, act_cols, health=health, split16=split16)
 
 
 # ---- elementwise ------------------------------------------------------------------------------------

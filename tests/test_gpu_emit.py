@@ -63,7 +63,7 @@ def test_graph_survives_precision_round_trip_and_reload():
         model.set_precision("bf16")
         b = fwd()                                # eager again: nothing is packed, the counters are gone
         assert not model._graphs
-        c = fwd()                                # capture with a cold pack cache inside _coarse_stage_graphed
+        c = fwd()                                # capture with a cold pack cache inside _stage_graphed
         assert len(model._graphs) == 1 and model.use_graph
         model.load_state_dict({k: v.clone() for k, v in sd.items()})
         model._seen[model._graph_key(c0.cuda(), c1.cuda(), None, None)] = 1   # a stale counter, as before the fix: straight into capture

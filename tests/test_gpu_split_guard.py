@@ -264,3 +264,59 @@ def test_fp32_split_healthy_checkpoint_never_trips_the_guard():
         assert not msgs, msgs
     assert model.fp32_split and not model.split_overflowed and d["b_ids"].numel() > 200
     assert not ops.FP32_SPLIT   # the module's forward restores the switch
+
+
+# ---- the split switch travels per launch: no module writes ops.FP32_SPLIT ----------------------------------------------------------------
+OUT_KEYS = ("b_ids", "i_ids", "j_ids", "mconf", "mkpts1_f")
+
+
+def _recorded_fwd(model, c0, c1, monkeypatch):
+    """one forward with every ops.conv_rows launch noted: (the pack is fp32, ops.FP32_SPLIT at the launch, the split16 argument)"""
+    from gim_amd import _lib, ops
+    seen, launch = [], ops.conv_rows
+
+    def recorder(x, pk, *a, **k):
+        seen.append((pk.dtype == _lib.GIM_F32, ops.FP32_SPLIT, k.get("split16")))
+        return launch(x, pk, *a, **k)
+
+    with monkeypatch.context() as mp:
+        mp.setattr(ops, "conv_rows", recorder)
+        d, msgs = _fwd(model, c0, c1)
+    assert ops.conv_rows is launch and not msgs, msgs
+    return d, seen
+
+
+def test_fp32_split_is_a_launch_argument_and_modules_share_no_state(monkeypatch):
+    """fp32 synthetic modules on one 96 x 128 pair (coarse map 12 x 16), eager: the module with fp32_split hands split16=True to each of its
+    fp32 launches while the process-wide default stays off at every launch; the module without hands a true split16 to none; and a
+    fp32_split=False module returns the same bits before and after the split module ran in the same process."""
+    from gim_amd import ops
+    assert not ops.FP32_SPLIT
+    c0, c1 = S.textured_pairs(1, 96, 128, seed=3)
+    exact, _ = S.synthetic_model("fp32", fp32_split=False, graph=False)
+    exact = exact.to("cuda:0")
+    before, msgs = _fwd(exact, c0, c1)
+    assert not msgs and before["b_ids"].numel() > 20
+
+    model, _ = S.synthetic_model("fp32", graph=False)
+    model = model.to("cuda:0")
+    d, seen = _recorded_fwd(model, c0, c1, monkeypatch)
+    fp32_launches = [s for s in seen if s[0]]
+    print(f"split module: {len(seen)} conv_rows launches, {len(fp32_launches)} on fp32 packs")
+    assert len(fp32_launches) > 50 and len(fp32_launches) == len(seen)   # backbone, both transformers: every pack of the fp32 mode is fp32
+    assert all(g is False for _, g, _ in seen)
+    assert all(s16 is True for _, _, s16 in fp32_launches)
+    assert model.fp32_split and model._split16 is None and not ops.FP32_SPLIT
+    d2, msgs = _fwd(model, c0, c1)   # recorder removed
+    assert not msgs
+    for k in OUT_KEYS:
+        assert torch.equal(d[k], d2[k]), k
+
+    e, seen = _recorded_fwd(exact, c0, c1, monkeypatch)
+    assert len(seen) == len(fp32_launches) and all(g is False for _, g, _ in seen)
+    assert not any(s16 for _, _, s16 in seen)
+    after, msgs = _fwd(exact, c0, c1)
+    assert not msgs
+    for k in OUT_KEYS:
+        assert torch.equal(before[k], e[k]) and torch.equal(before[k], after[k]), k
+    assert not torch.equal(before["mconf"], d["mconf"])   # (the two modules do multiply differently: the comparison above is not vacuous)
