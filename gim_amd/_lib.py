@@ -70,7 +70,7 @@ class LgAssignArgs(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 114   # gim_version() of the include/gim_hip.h revision the structures and prototypes here mirror
+ABI_VERSION = 115   # gim_version() of the include/gim_hip.h revision the structures and prototypes here mirror
 
 # name -> (restype, argtypes); every symbol declared in include/gim_hip.h
 PROTOTYPES = {
@@ -83,7 +83,6 @@ PROTOTYPES = {
     "gim_nhwc_to_nchw": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
     "gim_stem7x7_weight_bytes": (c_int64, [c_int]),
     "gim_stem7x7": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
-    "gim_stem7x7_f16": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
     "gim_conv2d_bn_act": (c_int, [ctypes.POINTER(ConvArgs), c_void_p]),
     "gim_conv_ups_supported": (c_int, [ctypes.POINTER(ConvArgs)]),
     "gim_upsample2x_add": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
@@ -100,26 +99,17 @@ PROTOTYPES = {
     "gim_coarse_conf_matrix": (c_int, [ctypes.POINTER(CoarseArgs), c_void_p, c_void_p]),
     "gim_fine_gather": (c_int, [c_void_p] * 7 + [c_int] * 14 + [c_void_p]),
     "gim_fine_match": (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_float, c_int, c_void_p]),
-    "gim_bneck64_fused": (c_int, [c_void_p] * 10 + [c_int] * 4 + [c_void_p, c_void_p]),       # ..., health, stream
-    "gim_bneck64_fused_f16": (c_int, [c_void_p] * 10 + [c_int] * 4 + [c_void_p, c_void_p]),
-    "gim_bneck64_fused_ds": (c_int, [c_void_p] * 11 + [c_int] * 3 + [c_void_p, c_void_p]),
-    "gim_bneck64_fused_ds_f16": (c_int, [c_void_p] * 11 + [c_int] * 3 + [c_void_p, c_void_p]),
-    "gim_bneck_tail128": (c_int, [c_void_p] * 8 + [c_int] * 3 + [c_void_p, c_void_p]),
-    "gim_bneck_tail128_f16": (c_int, [c_void_p] * 8 + [c_int] * 3 + [c_void_p, c_void_p]),
-    "gim_bneck_tail128_ds": (c_int, [c_void_p] * 8 + [c_int] * 7 + [c_void_p, c_void_p]),
-    "gim_bneck_tail128_ds_f16": (c_int, [c_void_p] * 8 + [c_int] * 7 + [c_void_p, c_void_p]),
-    "gim_bneck_tail256": (c_int, [c_void_p] * 8 + [c_int] * 3 + [c_void_p, c_void_p]),
-    "gim_bneck_tail256_f16": (c_int, [c_void_p] * 8 + [c_int] * 3 + [c_void_p, c_void_p]),
+    "gim_bneck64_fused": (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_void_p, c_void_p]),       # ..., dtype, health, stream
+    "gim_bneck64_fused_ds": (c_int, [c_void_p] * 11 + [c_int] * 4 + [c_void_p, c_void_p]),
+    "gim_bneck_tail128": (c_int, [c_void_p] * 8 + [c_int] * 4 + [c_void_p, c_void_p]),
+    "gim_bneck_tail128_ds": (c_int, [c_void_p] * 8 + [c_int] * 8 + [c_void_p, c_void_p]),
+    "gim_bneck_tail256": (c_int, [c_void_p] * 8 + [c_int] * 4 + [c_void_p, c_void_p]),
     "gim_token_mlp_weight_bytes": (c_int64, []),
-    "gim_token_mlp": (c_int, [c_void_p] * 7 + [c_int] * 7 + [c_float, c_void_p]),
-    "gim_token_mlp_f16": (c_int, [c_void_p] * 7 + [c_int] * 7 + [c_float, c_void_p]),
-    "gim_token_mlp_emit": (c_int, [c_void_p] * 7 + [c_int] * 7 + [c_float, c_void_p, c_void_p]),
-    "gim_token_mlp_emit_f16": (c_int, [c_void_p] * 7 + [c_int] * 7 + [c_float, c_void_p, c_void_p]),
+    "gim_token_mlp": (c_int, [c_void_p] * 7 + [c_int] * 7 + [c_float, c_int, c_void_p]),                     # ..., ln_eps, dtype, stream
+    "gim_token_mlp_emit": (c_int, [c_void_p] * 7 + [c_int] * 7 + [c_float, c_int, c_void_p, c_void_p]),      # ..., ln_eps, dtype, emit, stream
     "gim_fine_fused_weight_bytes": (c_int64, []),
-    "gim_fine_fused": (c_int, [c_void_p] * 13 + [c_int] * 11 + [c_float, c_float, c_int, c_void_p]),
-    "gim_fine_fused_f16": (c_int, [c_void_p] * 13 + [c_int] * 11 + [c_float, c_float, c_int, c_void_p]),
-    "gim_fine_fused_dev": (c_int, [c_void_p] * 11 + [c_int, c_void_p] + [c_int] * 10 + [c_float, c_float, c_int, c_void_p]),
-    "gim_fine_fused_dev_f16": (c_int, [c_void_p] * 11 + [c_int, c_void_p] + [c_int] * 10 + [c_float, c_float, c_int, c_void_p]),
+    "gim_fine_fused": (c_int, [c_void_p] * 13 + [c_int] * 11 + [c_float, c_float, c_int, c_int, c_void_p]),  # ..., has_scale0, dtype, stream
+    "gim_fine_fused_dev": (c_int, [c_void_p] * 11 + [c_int, c_void_p] + [c_int] * 10 + [c_float, c_float, c_int, c_int, c_void_p]),
     "gim_copy_segments": (c_int, [ctypes.POINTER(CopySegs), c_void_p]),
     "gim_pack_matches": (c_int, [c_void_p] * 5 + [c_int64, c_void_p, c_int, c_void_p]),
     # gim_lightglue path
@@ -166,20 +156,20 @@ PROTOTYPES = {
     "gim_dense_to_pixels": (c_int, [c_void_p] * 3 + [c_int] + [c_float] * 4 + [c_void_p]),
     "gim_weighted_sample_ws_bytes": (c_int64, [c_int]),
     "gim_weighted_sample": (c_int, [c_void_p] * 3 + [c_int, c_int, ctypes.c_uint32, c_void_p]),
-    # gim_semseg path (additive: the ABI revision stays 114)
+    # gim_semseg path (added within ABI revision 114)
     "gim_ppm_pool": (c_int, [c_void_p] * 2 + [c_int] * 6 + [c_void_p]),
     "gim_ppm_upsample_concat": (c_int, [c_void_p] * 2 + [c_int] * 7 + [c_void_p]),
     "gim_seg_head_argmax": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
-    # feature bank of gim_loftr (additive: the ABI revision stays 114)
+    # feature bank of gim_loftr (added within ABI revision 114)
     "gim_slot_copy": (c_int, [c_void_p] * 4 + [c_int, c_int64, c_int, c_int, c_void_p]),
-    # root_sift baseline (additive: the ABI revision stays 114)
+    # root_sift baseline (added within ABI revision 114)
     "gim_nn_match_ws_bytes": (c_int64, [c_int] * 4),
     "gim_nn_match": (c_int, [c_void_p] * 2 + [c_int] * 4 + [c_float] + [c_void_p] * 5),
-    # sparse fine FPN tail of gim_loftr (additive: the ABI revision stays 114)
+    # sparse fine FPN tail of gim_loftr (added within ABI revision 114)
     "gim_conv3x3_halo_tiles": (c_int, [ctypes.POINTER(ConvArgs), c_void_p, c_void_p, c_int, c_void_p]),
     "gim_fine_tile_list_max_flags": (c_int, []),
     "gim_fine_tile_list": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p, c_void_p, c_int, c_void_p]),
-    # RANSAC hypothesis scoring of gim_amd/pose.py (additive: the ABI revision stays 114)
+    # RANSAC hypothesis scoring of gim_amd/pose.py (added within ABI revision 114)
     "gim_ransac_score": (c_int, [c_void_p] * 5 + [c_int, c_int, ctypes.c_double, c_void_p, c_void_p]),
     "gim_ransac_mask": (c_int, [c_void_p] * 4 + [c_int, ctypes.c_double, c_void_p, c_void_p]),
 }

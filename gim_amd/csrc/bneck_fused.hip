@@ -331,9 +331,11 @@ __global__ void __launch_bounds__(512, 2) bneck64_kernel(const Args a) {
 
 }  // namespace
 
+GIM_TWIN(gim_bneck64_fused_ds)
 extern "C" int GIM_FN(gim_bneck64_fused_ds)(const void* t1, const void* x_in, void* x_out, void* t1_next, const void* w2, const void* w3,
                                     const void* wds, const void* w1n, const float* b2, const float* b3ds, const float* b1n, int B, int H, int W,
-                                    int32_t* health, gim_stream_t stream) {
+                                    int dtype, int32_t* health, gim_stream_t stream) {
+    GIM_ROUTE_H16(dtype, gim_bneck64_fused_ds, t1, x_in, x_out, t1_next, w2, w3, wds, w1n, b2, b3ds, b1n, B, H, W, dtype, health, stream);
     GIM_REQUIRE(t1 && x_in && x_out && t1_next && w2 && w3 && wds && w1n && b2 && b3ds && b1n, "bneck64_fused_ds: NULL pointer");
     GIM_REQUIRE(B > 0 && H > 0 && W > 0 && H % TH == 0 && W % TW == 0, "bneck64_fused_ds: H %% 8 == 0 and W %% 32 == 0 required (got %d x %d)", H, W);
     GIM_REQUIRE((int64_t)B * H * W * C4 * 2 < (int64_t)0xFFFFFFF0ll, "bneck64_fused_ds: tensor too large for 32-bit buffer offsets");
@@ -352,9 +354,11 @@ extern "C" int GIM_FN(gim_bneck64_fused_ds)(const void* t1, const void* x_in, vo
     return gim_check_launch("bneck64_fused_ds");
 }
 
+GIM_TWIN(gim_bneck64_fused)
 extern "C" int GIM_FN(gim_bneck64_fused)(const void* t1, const void* res, void* x_out, void* t1_next, const void* w2, const void* w3,
                                  const void* w1n, const float* b2, const float* b3, const float* b1n, int B, int H, int W,
-                                 int n_next, int32_t* health, gim_stream_t stream) {
+                                 int n_next, int dtype, int32_t* health, gim_stream_t stream) {
+    GIM_ROUTE_H16(dtype, gim_bneck64_fused, t1, res, x_out, t1_next, w2, w3, w1n, b2, b3, b1n, B, H, W, n_next, dtype, health, stream);
     GIM_REQUIRE(t1 && res && x_out && w2 && w3 && b2 && b3, "bneck64_fused: NULL pointer");
     GIM_REQUIRE((t1_next == nullptr) == (w1n == nullptr) && (t1_next == nullptr || b1n), "bneck64_fused: t1_next, w1n and b1n go together");
     GIM_REQUIRE(t1_next ? (n_next == 64 || n_next == 128) : n_next == 0, "bneck64_fused: n_next must be 64 or 128 with t1_next, 0 without (got %d)", n_next);

@@ -380,15 +380,19 @@ int tail_entry(int P, const void* t2, const void* res, void* x_out, void* t1_nex
 
 }  // namespace
 
+GIM_TWIN(gim_bneck_tail128)
 extern "C" int GIM_FN(gim_bneck_tail128)(const void* t2, const void* res, void* x_out, void* t1_next, const void* w3, const void* w1n,
-                                         const float* b3, const float* b1n, int M, int n_next, int act_next, int32_t* health, gim_stream_t stream) {
+                                         const float* b3, const float* b1n, int M, int n_next, int act_next, int dtype, int32_t* health, gim_stream_t stream) {
+    GIM_ROUTE_H16(dtype, gim_bneck_tail128, t2, res, x_out, t1_next, w3, w1n, b3, b1n, M, n_next, act_next, dtype, health, stream);
     GIM_REQUIRE(x_out, "bneck_tail128: NULL x_out");
     return tail_entry(128, t2, res, x_out, t1_next, w3, w1n, b3, b1n, M, n_next, act_next, health, stream);
 }
 
+GIM_TWIN(gim_bneck_tail128_ds)
 extern "C" int GIM_FN(gim_bneck_tail128_ds)(const void* t2, const void* x_in, void* x_out, void* t1_next, const void* w3ds, const void* w1n,
                                             const float* b3ds, const float* b1n, int B, int Ho, int Wo, int Hin, int Win, int n_next, int act_next,
-                                            int32_t* health, gim_stream_t stream) {
+                                            int dtype, int32_t* health, gim_stream_t stream) {
+    GIM_ROUTE_H16(dtype, gim_bneck_tail128_ds, t2, x_in, x_out, t1_next, w3ds, w1n, b3ds, b1n, B, Ho, Wo, Hin, Win, n_next, act_next, dtype, health, stream);
     GIM_REQUIRE(t2 && x_in && x_out && t1_next && w3ds && w1n && b3ds && b1n, "bneck_tail128_ds: NULL pointer");
     GIM_REQUIRE(act_next == GIM_ACT_RELU || act_next == GIM_ACT_NONE, "bneck_tail128_ds: activation of the next conv1 must be relu or none");
     GIM_REQUIRE(B > 0 && Ho > 0 && Wo > 0 && Hin >= 2 * Ho - 1 && Win >= 2 * Wo - 1, "bneck_tail128_ds: the input map must cover the stride-2 samples (%d x %d -> %d x %d)", Hin, Win, Ho, Wo);
@@ -404,7 +408,9 @@ extern "C" int GIM_FN(gim_bneck_tail128_ds)(const void* t2, const void* x_in, vo
     return launch_tail<128, 128, 8, true>(a, (hipStream_t)stream);
 }
 
+GIM_TWIN(gim_bneck_tail256)
 extern "C" int GIM_FN(gim_bneck_tail256)(const void* t2, const void* res, void* x_out, void* t1_next, const void* w3, const void* w1n,
-                                         const float* b3, const float* b1n, int M, int n_next, int act_next, int32_t* health, gim_stream_t stream) {
+                                         const float* b3, const float* b1n, int M, int n_next, int act_next, int dtype, int32_t* health, gim_stream_t stream) {
+    GIM_ROUTE_H16(dtype, gim_bneck_tail256, t2, res, x_out, t1_next, w3, w1n, b3, b1n, M, n_next, act_next, dtype, health, stream);
     return tail_entry(256, t2, res, x_out, t1_next, w3, w1n, b3, b1n, M, n_next, act_next, health, stream);
 }

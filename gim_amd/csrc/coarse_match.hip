@@ -942,13 +942,9 @@ static int cm_prepare(const gim_coarse_args& a, CmWs& w, CmGeom& g) {
     return GIM_OK;
 }
 
-#if !GIM_HALF_KIND
-extern "C" int gim_coarse_match_f16(const gim_coarse_args* ap, gim_stream_t stream);
-#endif
+GIM_TWIN(gim_coarse_match)
 extern "C" int GIM_FN(gim_coarse_match)(const gim_coarse_args* ap, gim_stream_t stream) {
-#if !GIM_HALF_KIND
-    if (ap && ap->feat_dtype == GIM_F16) return gim_coarse_match_f16(ap, stream);   // the fp16 objects of this file
-#endif
+    GIM_TO_F16(ap && ap->feat_dtype == GIM_F16, gim_coarse_match, ap, stream);
     GIM_REQUIRE(ap, "coarse_match: NULL args");
     const gim_coarse_args& a = *ap;
     int rc = validate(a);
@@ -991,13 +987,9 @@ extern "C" int GIM_FN(gim_coarse_match)(const gim_coarse_args* ap, gim_stream_t 
     return gim_check_launch("coarse_match");
 }
 
-#if !GIM_HALF_KIND
-extern "C" int gim_coarse_conf_matrix_f16(const gim_coarse_args* ap, float* conf, gim_stream_t stream);
-#endif
+GIM_TWIN(gim_coarse_conf_matrix)
 extern "C" int GIM_FN(gim_coarse_conf_matrix)(const gim_coarse_args* ap, float* conf, gim_stream_t stream) {
-#if !GIM_HALF_KIND
-    if (ap && ap->feat_dtype == GIM_F16) return gim_coarse_conf_matrix_f16(ap, conf, stream);   // the fp16 objects of this file
-#endif
+    GIM_TO_F16(ap && ap->feat_dtype == GIM_F16, gim_coarse_conf_matrix, ap, conf, stream);
     GIM_REQUIRE(ap && conf, "coarse_conf_matrix: NULL args");
     const gim_coarse_args& a = *ap;
     int rc = validate(a);

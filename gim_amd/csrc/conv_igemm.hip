@@ -969,25 +969,21 @@ static int halo_launch(const gim_conv_args& a, const int* tiles, const int* n_ti
     return a.npad % 256 == 0 ? launch_halo<4>(a, s) : launch_halo<2>(a, s);
 }
 
-#if !GIM_HALF_KIND
-extern "C" int gim_conv_ups_supported_f16(const gim_conv_args* ap);
-extern "C" int gim_conv2d_bn_act_f16(const gim_conv_args* ap, gim_stream_t stream);
-extern "C" int gim_conv3x3_halo_tiles_f16(const gim_conv_args* ap, const int* tiles, const int* n_tiles, int tiles_cap, gim_stream_t stream);
-#endif
+GIM_TWIN(gim_conv_ups_supported)
+GIM_TWIN(gim_conv2d_bn_act)
+GIM_TWIN(gim_conv3x3_halo_tiles)
 extern "C" int GIM_FN(gim_conv_ups_supported)(const gim_conv_args* ap) {
-#if !GIM_HALF_KIND
-    if (ap && ap->dtype == GIM_F16) return gim_conv_ups_supported_f16(ap);
-#endif
+    GIM_TO_F16(ap && ap->dtype == GIM_F16, gim_conv_ups_supported, ap);
     return ap && ups_supported(*ap) ? 1 : 0;
 }
 
 extern "C" int GIM_FN(gim_conv2d_bn_act)(const gim_conv_args* ap, gim_stream_t stream) {
     GIM_REQUIRE(ap, "gim_conv2d_bn_act: NULL args");
-#if !GIM_HALF_KIND
     // the fp16 objects of this file: fp16 operands, or fp32 operands with an fp16 output / residual (the dense matchers' fp32 GP products
     // and kernel matrices feeding 16-bit feature maps: round 5, their IEEE-fp16 flavour)
-    if (ap->dtype == GIM_F16 || (ap->dtype == GIM_F32 && (ap->out_dtype == GIM_F16 || (ap->res && ap->res_dtype == GIM_F16))))
-        return gim_conv2d_bn_act_f16(ap, stream);
+    GIM_TO_F16(ap->dtype == GIM_F16 || (ap->dtype == GIM_F32 && (ap->out_dtype == GIM_F16 || (ap->res && ap->res_dtype == GIM_F16))),
+               gim_conv2d_bn_act, ap, stream);
+#if !GIM_HALF_KIND
     GIM_REQUIRE(ap->out_dtype != GIM_F16 && (!ap->res || ap->res_dtype != GIM_F16), "conv: bf16 operands cannot take an fp16 output / residual");
 #endif
     const gim_conv_args& a = *ap;
@@ -1009,9 +1005,7 @@ extern "C" int GIM_FN(gim_conv2d_bn_act)(const gim_conv_args* ap, gim_stream_t s
 // nothing, and pixels of patches outside the list keep whatever y held
 extern "C" int GIM_FN(gim_conv3x3_halo_tiles)(const gim_conv_args* ap, const int* tiles, const int* n_tiles, int tiles_cap, gim_stream_t stream) {
     GIM_REQUIRE(ap && tiles && n_tiles && tiles_cap >= 0, "gim_conv3x3_halo_tiles: NULL args / tiles / n_tiles or a negative capacity");
-#if !GIM_HALF_KIND
-    if (ap->dtype == GIM_F16) return gim_conv3x3_halo_tiles_f16(ap, tiles, n_tiles, tiles_cap, stream);
-#endif
+    GIM_TO_F16(ap->dtype == GIM_F16, gim_conv3x3_halo_tiles, ap, tiles, n_tiles, tiles_cap, stream);
     const gim_conv_args& a = *ap;
     GIM_REQUIRE(a.use_lds_dma == 2 && !a.ups, "gim_conv3x3_halo_tiles: the args must describe a halo launch (use_lds_dma = 2, halo packing)");
     if (const int rc = conv_check(a)) return rc;

@@ -602,7 +602,9 @@ __global__ void __launch_bounds__(256, 2) fine_fused_kernel(const FineArgs a) {
 
 }  // namespace
 
-extern "C" int64_t GIM_FN(gim_fine_fused_weight_bytes)(void) { return (int64_t)2 * W_LAYER * 16; }
+#if !GIM_HALF_KIND   // the same constant in both flavours: one copy, in the bf16 objects
+extern "C" int64_t gim_fine_fused_weight_bytes(void) { return (int64_t)2 * W_LAYER * 16; }
+#endif
 
 static int fine_fused_launch(const void* feat_f0, const void* feat_f1, const int64_t* b_ids, const int64_t* i_ids,
                               const int64_t* j_ids, const float* mkpts1_c, const float* scale1, const void* weights,
@@ -635,20 +637,26 @@ static int fine_fused_launch(const void* feat_f0, const void* feat_f1, const int
     return gim_check_launch("fine_fused");
 }
 
+GIM_TWIN(gim_fine_fused)
 extern "C" int GIM_FN(gim_fine_fused)(const void* feat_f0, const void* feat_f1, const int64_t* b_ids, const int64_t* i_ids,
                               const int64_t* j_ids, const float* mkpts1_c, const float* scale1, const void* weights,
                               const float* ln_params, float* expec_f, float* mkpts1_f, float* dbg_fine0, float* dbg_fine1,
                               int M, int hf0, int wf0, int hf1, int wf1, int C_, int ldf, int w0c, int w1c, int stride, int W,
-                              float scale, float ln_eps, int has_scale0, gim_stream_t stream) {
+                              float scale, float ln_eps, int has_scale0, int dtype, gim_stream_t stream) {
+    GIM_ROUTE_H16(dtype, gim_fine_fused, feat_f0, feat_f1, b_ids, i_ids, j_ids, mkpts1_c, scale1, weights, ln_params, expec_f, mkpts1_f, dbg_fine0, dbg_fine1,
+                  M, hf0, wf0, hf1, wf1, C_, ldf, w0c, w1c, stride, W, scale, ln_eps, has_scale0, dtype, stream);
     return fine_fused_launch(feat_f0, feat_f1, b_ids, i_ids, j_ids, mkpts1_c, scale1, weights, ln_params, expec_f, mkpts1_f, dbg_fine0, dbg_fine1,
                              M, hf0, wf0, hf1, wf1, C_, ldf, w0c, w1c, stride, W, scale, ln_eps, has_scale0, nullptr, stream);
 }
 
+GIM_TWIN(gim_fine_fused_dev)
 extern "C" int GIM_FN(gim_fine_fused_dev)(const void* feat_f0, const void* feat_f1, const int64_t* b_ids, const int64_t* i_ids,
                                   const int64_t* j_ids, const float* mkpts1_c, const float* scale1, const void* weights,
                                   const float* ln_params, float* expec_f, float* mkpts1_f, int M_cap, const int* count_dev,
                                   int hf0, int wf0, int hf1, int wf1, int C_, int ldf, int w0c, int w1c, int stride, int W,
-                                  float scale, float ln_eps, int has_scale0, gim_stream_t stream) {
+                                  float scale, float ln_eps, int has_scale0, int dtype, gim_stream_t stream) {
+    GIM_ROUTE_H16(dtype, gim_fine_fused_dev, feat_f0, feat_f1, b_ids, i_ids, j_ids, mkpts1_c, scale1, weights, ln_params, expec_f, mkpts1_f, M_cap, count_dev,
+                  hf0, wf0, hf1, wf1, C_, ldf, w0c, w1c, stride, W, scale, ln_eps, has_scale0, dtype, stream);
     GIM_REQUIRE(count_dev, "fine_fused_dev: NULL count");
     return fine_fused_launch(feat_f0, feat_f1, b_ids, i_ids, j_ids, mkpts1_c, scale1, weights, ln_params, expec_f, mkpts1_f, nullptr, nullptr,
                              M_cap, hf0, wf0, hf1, wf1, C_, ldf, w0c, w1c, stride, W, scale, ln_eps, has_scale0, count_dev, stream);

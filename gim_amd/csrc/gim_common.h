@@ -61,18 +61,33 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) { return cvt
 // (tools/precision_emulation.py, profiles/r03_precision_emulation*.txt): fp16 operands cut the match-set flip rate against the
 // fp32 reference from 1.95 % to 0.47 %, because three more significand bits survive every activation store.
 // A source file is compiled ONCE PER FLAVOUR (gim_amd/build.py: -DGIM_HALF_KIND=0 / 1): everything that touches 16-bit values
-// goes through the helpers below, `GIM_H16` is the dtype tag of the flavour and GIM_FN() names the entry points of the
-// fp16 objects (`*_f16`); the bf16 objects carry the public names and forward dtype == GIM_F16 calls.
+// goes through the helpers below and `GIM_H16` is the dtype tag of the flavour.
+// ONE RULE for the entry points: the public name (include/gim_hip.h) takes a dtype tag and the library routes.  The bf16 objects define
+// the public names; the fp16 objects define link-level twins `name_f16` (GIM_FN) that no header declares.  An entry point reads
+//     GIM_TWIN(gim_x)
+//     extern "C" int GIM_FN(gim_x)(<arguments>) {
+//         GIM_TO_F16(dtype == GIM_F16, gim_x, <arguments>);
+// GIM_TWIN declares the twin with the TYPE of the header's prototype, in both flavours: argument types are written in the header and in
+// the definition only, and a definition that drifts from the header does not compile in the fp16 object (conflicting declaration of a
+// C function).  GIM_TO_F16 hands the call to the twin when `cond` holds; in the fp16 object it is empty.
+// GIM_ROUTE_H16 is the form of the entry points that work on one 16-bit kind only (the fused kernels): forward GIM_F16, run GIM_BF16,
+// refuse everything else -- placed FIRST in the body, so that a wrong tag never reaches a pointer check or the HIP runtime.
 #ifndef GIM_HALF_KIND
 #define GIM_HALF_KIND 0
 #endif
+#define GIM_TWIN(name) extern "C" decltype(name) name##_f16;
 #if GIM_HALF_KIND
 #define GIM_H16 GIM_F16
 #define GIM_FN(name) name##_f16
+#define GIM_TO_F16(cond, name, ...) do { } while (0)
 #else
 #define GIM_H16 GIM_BF16
 #define GIM_FN(name) name
+#define GIM_TO_F16(cond, name, ...) do { if (cond) return name##_f16(__VA_ARGS__); } while (0)
 #endif
+#define GIM_ROUTE_H16(dtype, name, ...)                          \
+    GIM_TO_F16((dtype) == GIM_F16, name, __VA_ARGS__);           \
+    GIM_REQUIRE((dtype) == GIM_H16, #name ": dtype tag %d: the 16-bit kinds GIM_BF16 / GIM_F16 only", (int)(dtype))
 typedef _Float16 gim_f16x2_t __attribute__((ext_vector_type(2)));
 typedef _Float16 gim_f16x8_t __attribute__((ext_vector_type(8)));
 typedef __attribute__((ext_vector_type(4))) float gim_f32x4v_t;

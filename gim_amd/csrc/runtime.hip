@@ -21,7 +21,7 @@ int gim_check_launch(const char* what) {
     return GIM_OK;
 }
 
-extern "C" int gim_version(void) { return 114; }   // 110: health word as an argument (no gim_set_range_guard), count[2 + N] layout of gim_coarse_match; 111: gim_token_emit.kv_* (fused KV state), gim_linear_attention_finalize; 112: gim_coarse_args.precand_per_row, the library reads no environment variable; 113: gim_conv_args.split16; 114: health bit 8 (split launches: an operand beyond the fp16 range), fp32 launches with split16 = 0 never take the split loop
+extern "C" int gim_version(void) { return 115; }   // 110: health word as an argument (no gim_set_range_guard), count[2 + N] layout of gim_coarse_match; 111: gim_token_emit.kv_* (fused KV state), gim_linear_attention_finalize; 112: gim_coarse_args.precand_per_row, the library reads no environment variable; 113: gim_conv_args.split16; 114: health bit 8 (split launches: an operand beyond the fp16 range), fp32 launches with split16 = 0 never take the split loop; 115: the fused kernels (gim_bneck64_fused*, gim_bneck_tail*, gim_token_mlp*, gim_fine_fused*) take a dtype tag, no `*_f16` name is declared
 extern "C" const char* gim_last_error(void) { return g_err; }
 extern "C" int gim_ktile_bytes(void) { return 128; }
 extern "C" int gim_npad_granule(void) { return 64; }

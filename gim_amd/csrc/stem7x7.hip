@@ -138,16 +138,14 @@ __global__ void __launch_bounds__(512) stem7x7_kernel(const Args a) {
 
 }  // namespace
 
-extern "C" int64_t GIM_FN(gim_stem7x7_weight_bytes)(int split) { return split ? StemCfg<true>::W_BYTES : StemCfg<false>::W_BYTES; }
-
-#if !GIM_HALF_KIND
-extern "C" int gim_stem7x7_f16(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int split, int dtype, int out_dtype, gim_stream_t stream);
+#if !GIM_HALF_KIND   // the same constant in both flavours: one copy, in the bf16 objects
+extern "C" int64_t gim_stem7x7_weight_bytes(int split) { return split ? StemCfg<true>::W_BYTES : StemCfg<false>::W_BYTES; }
 #endif
+
+GIM_TWIN(gim_stem7x7)
 extern "C" int GIM_FN(gim_stem7x7)(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int split, int dtype,
                                    int out_dtype, gim_stream_t stream) {
-#if !GIM_HALF_KIND
-    if (dtype == GIM_F16) return gim_stem7x7_f16(x, w, bias, y, B, H, W, split, dtype, out_dtype, stream);   // the fp16 objects of this file
-#endif
+    GIM_TO_F16(dtype == GIM_F16, gim_stem7x7, x, w, bias, y, B, H, W, split, dtype, out_dtype, stream);
     GIM_REQUIRE(x && w && bias && y && B > 0 && H > 0 && W > 0, "stem7x7: bad args");
     GIM_REQUIRE(dtype == GIM_H16 && (out_dtype == GIM_BF16 || out_dtype == GIM_F16), "stem7x7: 16-bit operands and output only (dtype %d -> %d)", dtype, out_dtype);
     GIM_REQUIRE((int64_t)B * H * W * 16 < (int64_t)0xFFFFFFF0ll, "stem7x7: image batch too large for 32-bit buffer offsets");

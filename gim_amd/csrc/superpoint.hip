@@ -305,15 +305,10 @@ __global__ void __launch_bounds__(256) sp_sample_desc_kernel(const void* __restr
 
 }  // namespace
 
-#if !GIM_HALF_KIND
-extern "C" int gim_maxpool2x2_f16(const void* x, void* y, int B, int H, int W, int C, int ldx, int ldy, int dtype,
-                              gim_stream_t stream);
-#endif
+GIM_TWIN(gim_maxpool2x2)
 extern "C" int GIM_FN(gim_maxpool2x2)(const void* x, void* y, int B, int H, int W, int C, int ldx, int ldy, int dtype,
                               gim_stream_t stream) {
-#if !GIM_HALF_KIND
-    if (dtype == GIM_F16) return gim_maxpool2x2_f16(x, y, B, H, W, C, ldx, ldy, dtype, stream);   // the fp16 objects of this file
-#endif
+    GIM_TO_F16(dtype == GIM_F16, gim_maxpool2x2, x, y, B, H, W, C, ldx, ldy, dtype, stream);
     const int G = dtype == GIM_H16 ? 8 : 4;
     GIM_REQUIRE(x && y && B > 0 && H > 1 && W > 1 && C > 0 && C % G == 0, "maxpool2x2: bad args (C=%d)", C);
     GIM_REQUIRE(ldx % G == 0 && ldy % G == 0, "maxpool2x2: row strides must keep 16-byte groups aligned");
@@ -324,15 +319,10 @@ extern "C" int GIM_FN(gim_maxpool2x2)(const void* x, void* y, int B, int H, int 
     return gim_check_launch("maxpool2x2");
 }
 
-#if !GIM_HALF_KIND
-extern "C" int gim_sp_scores_f16(const void* logits, float* scores, int B, int h, int w, int ld, int dtype,
-                             gim_stream_t stream);
-#endif
+GIM_TWIN(gim_sp_scores)
 extern "C" int GIM_FN(gim_sp_scores)(const void* logits, float* scores, int B, int h, int w, int ld, int dtype,
                              gim_stream_t stream) {
-#if !GIM_HALF_KIND
-    if (dtype == GIM_F16) return gim_sp_scores_f16(logits, scores, B, h, w, ld, dtype, stream);   // the fp16 objects of this file
-#endif
+    GIM_TO_F16(dtype == GIM_F16, gim_sp_scores, logits, scores, B, h, w, ld, dtype, stream);
     GIM_REQUIRE(logits && scores && B > 0 && h > 0 && w > 0 && ld >= 65, "sp_scores: bad args");
     const int cells = B * h * w;
     hipStream_t s = (hipStream_t)stream;
@@ -392,17 +382,11 @@ extern "C" int gim_sp_topk(const float* nms_scores, void* ws, float* kpts, float
 }
 #endif
 
-#if !GIM_HALF_KIND
-extern "C" int gim_sp_sample_desc_f16(const void* dense, const float* kpts, float* out_f32, void* out_t, int B, int K,
-                                  int h, int w, int C, int ld, int ld_f32, int ld_t, int cell, int dtype,
-                                  gim_stream_t stream);
-#endif
+GIM_TWIN(gim_sp_sample_desc)
 extern "C" int GIM_FN(gim_sp_sample_desc)(const void* dense, const float* kpts, float* out_f32, void* out_t, int B, int K,
                                   int h, int w, int C, int ld, int ld_f32, int ld_t, int cell, int dtype,
                                   gim_stream_t stream) {
-#if !GIM_HALF_KIND
-    if (dtype == GIM_F16) return gim_sp_sample_desc_f16(dense, kpts, out_f32, out_t, B, K, h, w, C, ld, ld_f32, ld_t, cell, dtype, stream);   // the fp16 objects of this file
-#endif
+    GIM_TO_F16(dtype == GIM_F16, gim_sp_sample_desc, dense, kpts, out_f32, out_t, B, K, h, w, C, ld, ld_f32, ld_t, cell, dtype, stream);
     GIM_REQUIRE(dense && kpts && (out_f32 || out_t) && B > 0 && K > 0 && h > 1 && w > 1, "sp_sample_desc: bad args");
     GIM_REQUIRE(C == 256 && ld % 4 == 0 && ld_f32 % 4 == 0 && ld_t % 4 == 0, "sp_sample_desc: C must be 256, strides % 4");
     hipStream_t s = (hipStream_t)stream;

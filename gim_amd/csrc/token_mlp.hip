@@ -655,7 +655,9 @@ __global__ void __launch_bounds__(256, 2) token_mlp_kernel(const Args a) {
 
 }  // namespace
 
-extern "C" int64_t GIM_FN(gim_token_mlp_weight_bytes)(void) { return (int64_t)4 * UNITS_PER_WAVE * UNIT_U4 * 16; }
+#if !GIM_HALF_KIND   // the same constant in both flavours: one copy, in the bf16 objects
+extern "C" int64_t gim_token_mlp_weight_bytes(void) { return (int64_t)4 * UNITS_PER_WAVE * UNIT_U4 * 16; }
+#endif
 
 static int token_mlp_launch(const void* msg, void* xb, float* x32, const void* weights, const float* ln_params, const float* kv,
                             const uint8_t* q_mask, int R, int C_, int L, int S, int ldm, int ldxb, int ldx32, float ln_eps,
@@ -729,14 +731,18 @@ extern "C" int GIM_FN(gim_token_mlp_timing)(unsigned long long* host, int n_wg) 
 }
 #endif
 
+GIM_TWIN(gim_token_mlp)
 extern "C" int GIM_FN(gim_token_mlp)(const void* msg, void* xb, float* x32, const void* weights, const float* ln_params, const float* kv,
                              const uint8_t* q_mask, int R, int C_, int L, int S, int ldm, int ldxb, int ldx32, float ln_eps,
-                             gim_stream_t stream) {
+                             int dtype, gim_stream_t stream) {
+    GIM_ROUTE_H16(dtype, gim_token_mlp, msg, xb, x32, weights, ln_params, kv, q_mask, R, C_, L, S, ldm, ldxb, ldx32, ln_eps, dtype, stream);
     return token_mlp_launch(msg, xb, x32, weights, ln_params, kv, q_mask, R, C_, L, S, ldm, ldxb, ldx32, ln_eps, nullptr, stream);
 }
 
+GIM_TWIN(gim_token_mlp_emit)
 extern "C" int GIM_FN(gim_token_mlp_emit)(const void* msg, void* xb, float* x32, const void* weights, const float* ln_params, const float* kv,
                                   const uint8_t* q_mask, int R, int C_, int L, int S, int ldm, int ldxb, int ldx32, float ln_eps,
-                                  const gim_token_emit* emit, gim_stream_t stream) {
+                                  int dtype, const gim_token_emit* emit, gim_stream_t stream) {
+    GIM_ROUTE_H16(dtype, gim_token_mlp_emit, msg, xb, x32, weights, ln_params, kv, q_mask, R, C_, L, S, ldm, ldxb, ldx32, ln_eps, dtype, emit, stream);
     return token_mlp_launch(msg, xb, x32, weights, ln_params, kv, q_mask, R, C_, L, S, ldm, ldxb, ldx32, ln_eps, emit, stream);
 }

@@ -15,8 +15,9 @@ _DT = {torch.float32: GIM_F32, torch.bfloat16: GIM_BF16, torch.float16: GIM_F16}
 HALF = (torch.bfloat16, torch.float16)   # the two 16-bit operand kinds: same kernels in two flavours (csrc/gim_common.h)
 
 
-# When set to a list, every gim_conv2d_bn_act launch is bracketed by HIP events recorded on the launch
-# stream and (start, end, algorithmic_flops, label) is appended -- bench.py's live roofline measurement.
+# bench.py's live roofline measurement.  When set to a list, every launch of that group is bracketed by HIP events recorded on the launch
+# stream and (start, end, algorithmic_flops, label) is appended (_Timed): PROFILE -- the gim_conv2d_bn_act / gim_conv3x3_halo_tiles
+# launches, label = the layer's shape; PROFILE_FUSED -- the fused kernels, label = the kernel family.
 PROFILE = None
 PROFILE_FUSED = None
 
@@ -26,22 +27,25 @@ def _stream():
 
 
 class _Timed:
-    """bench.py's live measurement of the fused kernels: HIP events on the launch stream around one C-ABI call, appended to
-    PROFILE_FUSED as (start, end, algorithmic_flops, kernel family) when that list is set."""
+    """bench.py's live measurement: HIP events on the launch stream around one C-ABI call, appended as (start, end, algorithmic_flops,
+    label) to PROFILE_FUSED -- or, `conv=True`, to PROFILE -- when that list is set.  `label` / `flops` may be callables: evaluated behind
+    the launch, in measuring runs only (a label nobody else builds, a count that lives on the device)."""
 
-    def __init__(self, family, flops):
-        self.family, self.flops = family, flops
+    def __init__(self, label, flops, conv=False):
+        self.label, self.flops, self.conv = label, flops, conv
 
     def __enter__(self):
-        if PROFILE_FUSED is not None:
+        self.sink = PROFILE if self.conv else PROFILE_FUSED
+        if self.sink is not None:
             self.e0, self.e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             self.e0.record()
         return self
 
     def __exit__(self, *exc):
-        if PROFILE_FUSED is not None:
+        if self.sink is not None:
             self.e1.record()
-            PROFILE_FUSED.append((self.e0, self.e1, self.flops, self.family))
+            flops, label = (v() if callable(v) else v for v in (self.flops, self.label))
+            self.sink.append((self.e0, self.e1, flops, label))
         return False
 
 
@@ -236,15 +240,9 @@ def conv_rows(x, pk, geom, y, act=ACT_NONE, res=None, res_mod=0, lds_dma=True, a
         if not (UPS_FUSED and ups.dtype in HALF and ups.dtype == y.dtype and lib.gim_conv_ups_supported(ctypes.byref(a))):
             a.ups = None
     fused_ups = ups is not None and a.ups is not None
-    if PROFILE is None:
+    with _Timed(lambda: f"{pk.cin}->{pk.cout} k{pk.kh}s{pk.stride} M={B * Ho * Wo}" + (" +ups" if fused_ups else ""),
+                lambda: 2.0 * B * Ho * Wo * pk.cout * pk.cin * pk.kh * pk.kw, conv=True):  # algorithmic flops: real channels, no padding
         check(lib.gim_conv2d_bn_act(ctypes.byref(a), _stream()), "gim_conv2d_bn_act")
-        return fused_ups
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    check(lib.gim_conv2d_bn_act(ctypes.byref(a), _stream()), "gim_conv2d_bn_act")
-    e1.record()
-    flops = 2.0 * B * Ho * Wo * pk.cout * pk.cin * pk.kh * pk.kw  # algorithmic: real channels, no padding
-    PROFILE.append((e0, e1, flops, f"{pk.cin}->{pk.cout} k{pk.kh}s{pk.stride} M={B * Ho * Wo}" + (" +ups" if fused_ups else "")))
     return fused_ups
 
 
@@ -322,25 +320,16 @@ def conv3x3_halo(x, pk, y, act=ACT_NONE, tiles=None, n_tiles=None):
     a.dtype = a.out_dtype = gim_dtype(x)
     a.res_dtype = GIM_F32
     a.use_lds_dma = 2
-    if tiles is None:
-        launch = lambda: check(lib.gim_conv2d_bn_act(ctypes.byref(a), _stream()), "gim_conv2d_bn_act(halo)")   # noqa: E731
-    else:
+    if tiles is not None:
         assert tiles.dtype == n_tiles.dtype == torch.int32 and tiles.is_contiguous() and n_tiles.numel() >= 1
         assert y.shape[:3] == x.shape[:3]
-        launch = lambda: check(lib.gim_conv3x3_halo_tiles(ctypes.byref(a), _p(tiles), _p(n_tiles), tiles.numel(), _stream()),   # noqa: E731
-                               "gim_conv3x3_halo_tiles")
-    if PROFILE is None:
-        launch()
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    launch()
-    e1.record()
-    label = f"{pk.cin}->{pk.cout} k3s1 M={B * H * W} halo"
-    if tiles is None:
-        PROFILE.append((e0, e1, 2.0 * B * H * W * pk.cout * pk.cin * 9, label))
-    else:   # the live measurement alone reads the count back: computed patches x per-patch flops
-        PROFILE.append((e0, e1, 2.0 * int(n_tiles[0].item()) * 256 * pk.cout * pk.cin * 9, label + " sparse"))
+    # sparse: the live measurement alone reads the count back -- computed patches x per-patch flops
+    with _Timed(lambda: f"{pk.cin}->{pk.cout} k3s1 M={B * H * W} halo" + ("" if tiles is None else " sparse"),
+                lambda: 2.0 * (B * H * W if tiles is None else int(n_tiles[0].item()) * 256) * pk.cout * pk.cin * 9, conv=True):
+        if tiles is None:
+            check(lib.gim_conv2d_bn_act(ctypes.byref(a), _stream()), "gim_conv2d_bn_act(halo)")
+        else:
+            check(lib.gim_conv3x3_halo_tiles(ctypes.byref(a), _p(tiles), _p(n_tiles), tiles.numel(), _stream()), "gim_conv3x3_halo_tiles")
 
 
 FINE_TILE_MAX_FLAGS = lib.gim_fine_tile_list_max_flags()
@@ -542,15 +531,14 @@ def bneck64(t1, res, pk, want_next, out=None, health=None):
     _req_cuda(t1, res)
     assert t1.dtype in HALF and res.dtype == t1.dtype and t1.is_contiguous() and res.is_contiguous()
     assert pk[0].dtype == t1.dtype, "bneck64: weights packed for the other 16-bit kind"
-    fn = lib.gim_bneck64_fused_f16 if t1.dtype == torch.float16 else lib.gim_bneck64_fused
     B, H, W, _ = t1.shape
     w2, w3, w1n, b2, b3, b1n = pk
     n1 = w1n.shape[0] if (want_next and w1n is not None) else 0
     assert not want_next or n1 in (64, 128)
     xo, t1n = _outs(out, ((B, H, W, 256), (B, H, W, n1) if n1 else None), t1)
     with _Timed("bneck64_fused", 2.0 * B * H * W * (576 * 64 + 64 * 256 + 256 * n1)):
-        check(fn(_p(t1), _p(res), _p(xo), _p(t1n), _p(w2), _p(w3), _p(w1n if n1 else None), _p(b2), _p(b3),
-                                    _p(b1n if n1 else None), B, H, W, n1, _health(health), _stream()), "gim_bneck64_fused")
+        check(lib.gim_bneck64_fused(_p(t1), _p(res), _p(xo), _p(t1n), _p(w2), _p(w3), _p(w1n if n1 else None), _p(b2), _p(b3),
+                                    _p(b1n if n1 else None), B, H, W, n1, gim_dtype(t1), _health(health), _stream()), "gim_bneck64_fused")
     return xo, t1n
 
 
@@ -561,12 +549,11 @@ def bneck64_ds(t1, x_in, pk, out=None, health=None):
     assert t1.dtype in HALF and x_in.dtype == t1.dtype and t1.is_contiguous() and x_in.is_contiguous() and x_in.shape == t1.shape
     w2, w3, wds, w1n, b2, b3ds, b1n = pk
     assert w2.dtype == t1.dtype and w1n.shape[0] == 64
-    fn = lib.gim_bneck64_fused_ds_f16 if t1.dtype == torch.float16 else lib.gim_bneck64_fused_ds
     B, H, W, _ = t1.shape
     xo, t1n = _outs(out, ((B, H, W, 256), (B, H, W, 64)), t1)
     with _Timed("bneck64_fused", 2.0 * B * H * W * (576 * 64 + 64 * 256 + 64 * 256 + 256 * 64)):
-        check(fn(_p(t1), _p(x_in), _p(xo), _p(t1n), _p(w2), _p(w3), _p(wds), _p(w1n), _p(b2), _p(b3ds), _p(b1n), B, H, W, _health(health), _stream()),
-              "gim_bneck64_fused_ds")
+        check(lib.gim_bneck64_fused_ds(_p(t1), _p(x_in), _p(xo), _p(t1n), _p(w2), _p(w3), _p(wds), _p(w1n), _p(b2), _p(b3ds), _p(b1n), B, H, W,
+                                       gim_dtype(t1), _health(health), _stream()), "gim_bneck64_fused_ds")
     return xo, t1n
 
 
@@ -583,9 +570,10 @@ def bneck_tail(t2, res, pk, act_next=ACT_RELU, store_x=True, out=None, health=No
     assert pl in (128, 256) and w3.shape == (4 * pl, pl) and res.shape == (B, H, W, 4 * pl) and M % 256 == 0
     assert store_x or pl == 256
     xo, t1n = _outs(out, ((B, H, W, 4 * pl) if store_x else None, (B, H, W, n1)), t2)
-    name = "gim_bneck_tail%d%s" % (pl, "_f16" if t2.dtype == torch.float16 else "")
+    fn = lib.gim_bneck_tail128 if pl == 128 else lib.gim_bneck_tail256
     with _Timed("bneck_tail", 2.0 * M * (pl * 4 * pl + 4 * pl * n1)):
-        check(getattr(lib, name)(_p(t2), _p(res), _p(xo), _p(t1n), _p(w3), _p(w1n), _p(b3), _p(b1n), M, n1, act_next, _health(health), _stream()), name)
+        check(fn(_p(t2), _p(res), _p(xo), _p(t1n), _p(w3), _p(w1n), _p(b3), _p(b1n), M, n1, act_next, gim_dtype(t2), _health(health), _stream()),
+              "gim_bneck_tail%d" % pl)
     return xo, t1n
 
 
@@ -603,10 +591,9 @@ def bneck_tail_ds(t2, x_in, pk, act_next=ACT_RELU, out=None, health=None):
     assert pl == 128 and cd == 256 and w3.shape == (512, 384) and w1n.shape == (16, 128, 32) and x_in.shape[0] == B
     assert (Hin - 1) // 2 + 1 == Ho and (Win - 1) // 2 + 1 == Wo and (B * Ho * Wo) % 256 == 0
     xo, t1n = _outs(out, ((B, Ho, Wo, 512), (B, Ho, Wo, n1)), t2)
-    fn = lib.gim_bneck_tail128_ds_f16 if t2.dtype == torch.float16 else lib.gim_bneck_tail128_ds
     with _Timed("bneck_tail", 2.0 * B * Ho * Wo * ((pl + cd) * 4 * pl + 4 * pl * n1)):
-        check(fn(_p(t2), _p(x_in), _p(xo), _p(t1n), _p(w3), _p(w1n), _p(b3), _p(b1n), B, Ho, Wo, Hin, Win, n1, act_next, _health(health),
-                 _stream()), "gim_bneck_tail128_ds")
+        check(lib.gim_bneck_tail128_ds(_p(t2), _p(x_in), _p(xo), _p(t1n), _p(w3), _p(w1n), _p(b3), _p(b1n), B, Ho, Wo, Hin, Win, n1, act_next,
+                                       gim_dtype(t2), _health(health), _stream()), "gim_bneck_tail128_ds")
     return xo, t1n
 
 
@@ -625,7 +612,6 @@ def token_mlp(msg, xb, x32, weights, ln_params, eps, kv=None, L=0, S=0, q_mask=N
         msg = xb
     _req_cuda(msg, xb, x32, weights, ln_params, kv, q_mask, q_weights)
     assert msg.dtype in HALF and xb.dtype == msg.dtype and weights.dtype == msg.dtype and x32.dtype == torch.float32
-    f16 = msg.dtype == torch.float16
     assert msg.stride(1) == 1 and xb.stride(1) == 1 and x32.stride(1) == 1 and msg.shape[0] == xb.shape[0] == x32.shape[0]
     R = msg.shape[0]
     flops = 2.0 * R * (256 * 256 + 512 * 512 + 512 * 256 + (32 * 256 if kv is not None else 0))
@@ -643,13 +629,12 @@ def token_mlp(msg, xb, x32, weights, ln_params, eps, kv=None, L=0, S=0, q_mask=N
         flops += _fill_emit_blocks(em, blocks, R, msg.dtype)
     with _Timed("token_mlp", flops):
         if em is None:
-            fn = lib.gim_token_mlp_f16 if f16 else lib.gim_token_mlp
-            check(fn(_p(msg), _p(xb), _p(x32), _p(weights), _p(ln_params), _p(kv), _p(q_mask), R, 256, L, S,
-                     msg.stride(0), xb.stride(0), x32.stride(0), eps, _stream()), "gim_token_mlp")
+            check(lib.gim_token_mlp(_p(msg), _p(xb), _p(x32), _p(weights), _p(ln_params), _p(kv), _p(q_mask), R, 256, L, S,
+                                    msg.stride(0), xb.stride(0), x32.stride(0), eps, gim_dtype(msg), _stream()), "gim_token_mlp")
         else:
-            fn = lib.gim_token_mlp_emit_f16 if f16 else lib.gim_token_mlp_emit
-            check(fn(_p(msg), _p(xb), _p(x32), _p(weights), _p(ln_params), _p(kv), _p(q_mask), R, 256, L, S,
-                     msg.stride(0), xb.stride(0), x32.stride(0), eps, ctypes.byref(em), _stream()), "gim_token_mlp_emit")
+            check(lib.gim_token_mlp_emit(_p(msg), _p(xb), _p(x32), _p(weights), _p(ln_params), _p(kv), _p(q_mask), R, 256, L, S,
+                                         msg.stride(0), xb.stride(0), x32.stride(0), eps, gim_dtype(msg), ctypes.byref(em), _stream()),
+                  "gim_token_mlp_emit")
 
 
 def linear_attention_state(k, v, nb_kv, S, H, ws=None, kv_mask=None):
@@ -688,10 +673,9 @@ def token_project(xb, emit, pos=None):
         assert x32.dtype == torch.float32 and x32.shape[0] == R and x32.stride(1) == 1 and x32.shape[1] >= 256
         em.pe_feat, em.pe, em.pe_ld, em.pe_hw = feat.data_ptr(), pe.data_ptr(), feat.stride(0), pe.shape[0]
     _fill_emit_blocks(em, blocks, R, xb.dtype)
-    fn = lib.gim_token_mlp_emit_f16 if xb.dtype == torch.float16 else lib.gim_token_mlp_emit
     with _Timed("token_mlp", 2.0 * sum(max(0, min(b[3], R) - b[2]) for b in blocks) * 256 * 256):
-        check(fn(None, _p(xb), _p(x32), None, None, None, None, R, 256, 0, 0, 0, xb.stride(0), x32.stride(0) if x32 is not None else 0, 0.0,
-                 ctypes.byref(em), _stream()), "gim_token_mlp_emit")
+        check(lib.gim_token_mlp_emit(None, _p(xb), _p(x32), None, None, None, None, R, 256, 0, 0, 0, xb.stride(0),
+                                     x32.stride(0) if x32 is not None else 0, 0.0, gim_dtype(xb), ctypes.byref(em), _stream()), "gim_token_mlp_emit")
 
 
 def _fill_emit_blocks(em, blocks, R, dtype):
@@ -741,35 +725,26 @@ def fine_fused(feat_f0, feat_f1, b_ids, i_ids, j_ids, mkpts1_c, scale1, weights,
     `count` (device int32 tensor): M is the CAPACITY of the match lists and the kernel processes the first min(M, count[0]) matches --
     the launch does not wait for the host to learn the count (gim_fine_fused_dev); rows beyond it are left unwritten."""
     _req_cuda(feat_f0, feat_f1, b_ids, mkpts1_c, weights, ln_params, count)
-    if count is not None:
-        assert not debug and count.dtype == torch.int32 and feat_f0.dtype in HALF and weights.dtype == feat_f0.dtype
-        assert feat_f0.is_contiguous() and feat_f1.is_contiguous() and b_ids.numel() >= M
-        fnd = lib.gim_fine_fused_dev_f16 if feat_f0.dtype == torch.float16 else lib.gim_fine_fused_dev
-        _, hf0, wf0, C = feat_f0.shape
-        _, hf1, wf1, _ = feat_f1.shape
-        expec = torch.empty(M, 3, dtype=torch.float32, device=feat_f0.device)
-        mk1 = torch.empty(M, 2, dtype=torch.float32, device=feat_f0.device)
-        with _Timed("fine_fused", 0.0) as tm:   # the caller fills in the flops once it knows the count (patch_last_fused_flops)
-            check(fnd(_p(feat_f0), _p(feat_f1), _p(b_ids), _p(i_ids), _p(j_ids), _p(mkpts1_c), _p(scale1), _p(weights), _p(ln_params),
-                      _p(expec), _p(mk1), M, _p(count), hf0, wf0, hf1, wf1, C, C, w0c, w1c, stride, W, scale, ln_eps,
-                      1 if has_scale0 else 0, _stream()), "gim_fine_fused_dev")
-        return expec, mk1, None, None
-    _req_cuda(feat_f0, feat_f1, b_ids, mkpts1_c, weights, ln_params)
     assert feat_f0.dtype in HALF and feat_f1.dtype == feat_f0.dtype and weights.dtype == feat_f0.dtype
     assert feat_f0.is_contiguous() and feat_f1.is_contiguous()
-    fn = lib.gim_fine_fused_f16 if feat_f0.dtype == torch.float16 else lib.gim_fine_fused
     _, hf0, wf0, C = feat_f0.shape
     _, hf1, wf1, _ = feat_f1.shape
     dev = feat_f0.device
     expec = torch.empty(M, 3, dtype=torch.float32, device=dev)
     mk1 = torch.empty(M, 2, dtype=torch.float32, device=dev)
+    geom = (hf0, wf0, hf1, wf1, C, C, w0c, w1c, stride, W, scale, ln_eps, 1 if has_scale0 else 0, gim_dtype(feat_f0), _stream())
+    if count is not None:
+        assert not debug and count.dtype == torch.int32 and b_ids.numel() >= M
+        with _Timed("fine_fused", 0.0):   # the caller fills in the flops once it knows the count (patch_last_fused_flops)
+            check(lib.gim_fine_fused_dev(_p(feat_f0), _p(feat_f1), _p(b_ids), _p(i_ids), _p(j_ids), _p(mkpts1_c), _p(scale1), _p(weights),
+                                         _p(ln_params), _p(expec), _p(mk1), M, _p(count), *geom), "gim_fine_fused_dev")
+        return expec, mk1, None, None
     d0 = torch.empty(M, W * W, C, dtype=torch.float32, device=dev) if debug else None
     d1 = torch.empty(M, W * W, C, dtype=torch.float32, device=dev) if debug else None
     assert weights.numel() * weights.element_size() == lib.gim_fine_fused_weight_bytes()
     with _Timed("fine_fused", 33.6e6 * M):   # SURVEY 8d: 33.6 MFLOP per match
-        check(fn(_p(feat_f0), _p(feat_f1), _p(b_ids), _p(i_ids), _p(j_ids), _p(mkpts1_c), _p(scale1),
-                                 _p(weights), _p(ln_params), _p(expec), _p(mk1), _p(d0), _p(d1), M, hf0, wf0, hf1, wf1, C, C,
-                                 w0c, w1c, stride, W, scale, ln_eps, 1 if has_scale0 else 0, _stream()), "gim_fine_fused")
+        check(lib.gim_fine_fused(_p(feat_f0), _p(feat_f1), _p(b_ids), _p(i_ids), _p(j_ids), _p(mkpts1_c), _p(scale1), _p(weights),
+                                 _p(ln_params), _p(expec), _p(mk1), _p(d0), _p(d1), M, *geom), "gim_fine_fused")
     return expec, mk1, d0, d1
 
 

@@ -29,6 +29,11 @@ extern "C" {
 
 typedef void* gim_stream_t; /* hipStream_t */
 
+/* The dtype tag.  ONE convention for every entry point that handles 16-bit operands: the name declared here takes the tag (a `dtype` /
+ * `out_dtype` / `feat_dtype` argument or struct field) and the library routes the call to its bf16 or its IEEE-fp16 build of the kernel;
+ * no per-dtype symbol is part of this ABI.  The fused kernels (gim_bneck64_fused*, gim_bneck_tail*, gim_token_mlp*, gim_fine_fused*)
+ * work on ONE 16-bit kind -- tensors and packed weights alike -- named by their `dtype`: GIM_BF16 or GIM_F16; any other tag returns
+ * GIM_ERR_INVALID before a pointer is looked at or the device is touched. */
 enum { GIM_F32 = 0, GIM_BF16 = 1, GIM_F16 = 2 };
 enum { GIM_ACT_NONE = 0, GIM_ACT_RELU = 1, GIM_ACT_LEAKY = 2, GIM_ACT_ELU1 = 3 /* elu(x)+1 */, GIM_ACT_GELU = 4 /* exact erf GELU */ };
 enum { GIM_OK = 0, GIM_ERR_INVALID = -1, GIM_ERR_LAUNCH = -2, GIM_ERR_UNSUPPORTED = -3 };
@@ -42,7 +47,10 @@ enum { GIM_OK = 0, GIM_ERR_INVALID = -1, GIM_ERR_LAUNCH = -2, GIM_ERR_UNSUPPORTE
  * 112 (round 6): gim_coarse_args.precand_per_row appended (zero it for the old behaviour); the library reads no environment variable.
  * 113 (round 6): gim_conv_args.split16 appended (zero it for the old behaviour).
  * 114: health bit 8 -- a split16 launch handed a `health` word reports an operand that left the IEEE-fp16 range (gim_conv_args.split16);
- * fp32-operand launches with split16 = 0 and a 16-bit output take exact fp32 products (version 113 sent some of them to the split loop). */
+ * fp32-operand launches with split16 = 0 and a 16-bit output take exact fp32 products (version 113 sent some of them to the split loop).
+ * 115: the fused kernels take a `dtype` tag (in front of `health`, else of `stream`; gim_token_mlp_emit: in front of `emit`) like every other
+ * entry point, and the `*_f16` twins (gim_stem7x7_f16, gim_bneck64_fused*_f16, gim_bneck_tail*_f16, gim_token_mlp*_f16, gim_fine_fused*_f16)
+ * left this header: call the plain name with GIM_F16 -- a caller bound to version 114 must be rebuilt. */
 int gim_version(void);
 /* fp16 range guard.  `health` (NULL: no check): a device word into which the fp16 flavour of the kernels that store un-normalised
  * residual streams (gim_bneck64_fused*, gim_bneck_tail*, gim_conv2d_bn_act with a residual operand) OR 4 when a converted value exceeds
@@ -77,8 +85,6 @@ int gim_nchw_to_nhwc_split(const float* src, void* dst, int B, int C, int H, int
 int64_t gim_stem7x7_weight_bytes(int split);
 int gim_stem7x7(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int split, int dtype, int out_dtype,
                 gim_stream_t stream);
-int gim_stem7x7_f16(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int split, int dtype, int out_dtype,
-                    gim_stream_t stream);
 /* inverse, for exposing feature maps in the reference layout (tests / lazy outputs) */
 int gim_nhwc_to_nchw(const void* src, float* dst, int B, int C, int H, int W, int ld, int dtype,
                      gim_stream_t stream);
@@ -141,7 +147,7 @@ typedef struct gim_conv_args {
 int gim_conv_ups_supported(const gim_conv_args* a);   /* 1 if gim_conv2d_bn_act would take a->ups (set or not) for this launch */
 int gim_conv2d_bn_act(const gim_conv_args* a, gim_stream_t stream);
 /* The 3x3 halo launch of gim_conv2d_bn_act (use_lds_dma = 2: 16-bit, stride 1, pad 1, halo packing) over a device-side list of
- * 8 x 32-pixel output patches (additive: the ABI revision stays 114).  tiles[0 .. min(*n_tiles, tiles_cap)): int32 patch indices
+ * 8 x 32-pixel output patches (added within ABI revision 114).  tiles[0 .. min(*n_tiles, tiles_cap)): int32 patch indices
  * (image * ceil(H / 8) + ty) * ceil(W / 32) + tx, ascending for L2 locality; *n_tiles is read ON THE DEVICE (no host sync, the grid
  * does not depend on it; 0 writes nothing).  Listed patches get exactly what the dense launch writes; pixels of every other patch
  * keep whatever y held.  Entries outside the map are clamped into it. */
@@ -244,6 +250,7 @@ int gim_coarse_conf_matrix(const gim_coarse_args* a, float* conf, gim_stream_t s
 
 /* Tail of a ResNet Bottleneck (planes 64) fused with the head of the next block (resnet.py:109-126), one kernel:
  *     x' = relu(bn3(conv3(relu(bn2(conv2_3x3(t1))))) + identity);   t1' = relu(bn1'(conv1'(x')))   (optional)
+ * Tensors and weights are of `dtype` (GIM_BF16 / GIM_F16), called "bf16" below.
  * t1: [B,H,W,64] bf16 (the block's conv1 output), res: [B,H,W,256] bf16 identity / downsample branch, x_out: [B,H,W,256],
  * t1_next: [B,H,W,n_next] or NULL (n_next = 64: the next block of the layer; 128: the next layer's first conv1; 0: none).
  * Weights bf16 with eval-BN folded in (biases fp32): w2 [64][576] with K = (ky, kx, c);
@@ -251,20 +258,13 @@ int gim_coarse_conf_matrix(const gim_coarse_args* a, float* conf, gim_stream_t s
  * products are chained through registers.  H % 8 == 0, W % 32 == 0. */
 int gim_bneck64_fused(const void* t1, const void* res, void* x_out, void* t1_next, const void* w2, const void* w3,
                       const void* w1n, const float* b2, const float* b3, const float* b1n, int B, int H, int W,
-                      int n_next, int32_t* health, gim_stream_t stream);
+                      int n_next, int dtype, int32_t* health, gim_stream_t stream);
 /* First block of layer 1 (resnet.py:120-124: identity = bn(conv1x1(x)), 64 -> 256, stride 1): the downsample convolution runs INSIDE
  * the kernel as extra K of conv3 -- x' = relu([W3 | Wds] [t2 ; x] + b3 + bds) -- so neither its launch nor the 256-channel identity
  * tensor exist.  x_in: [B,H,W,64] the block's input; wds [256][64] bf16 (BN folded, K in channel order); b3ds = b3 + bds; n_next = 64. */
 int gim_bneck64_fused_ds(const void* t1, const void* x_in, void* x_out, void* t1_next, const void* w2, const void* w3,
                          const void* wds, const void* w1n, const float* b2, const float* b3ds, const float* b1n, int B, int H, int W,
-                         int32_t* health, gim_stream_t stream);
-int gim_bneck64_fused_ds_f16(const void* t1, const void* x_in, void* x_out, void* t1_next, const void* w2, const void* w3,
-                             const void* wds, const void* w1n, const float* b2, const float* b3ds, const float* b1n, int B, int H, int W,
-                             int32_t* health, gim_stream_t stream);
-/* the same kernel on IEEE fp16 tensors / weights (GIM_F16 mode) */
-int gim_bneck64_fused_f16(const void* t1, const void* res, void* x_out, void* t1_next, const void* w2, const void* w3,
-                          const void* w1n, const float* b2, const float* b3, const float* b1n, int B, int H, int W,
-                          int n_next, int32_t* health, gim_stream_t stream);
+                         int dtype, int32_t* health, gim_stream_t stream);
 
 /* The same fusion one layer up (planes 128: layer 2), without the 3x3 -- x' = relu(bn3(conv3_1x1(t2)) + identity), t1' =
  * act(bn1'(conv1'_1x1(x'))) of the NEXT block (resnet.py:117-124, 109-111) -- so that x' [M,512], the widest tensor of the block, is
@@ -273,9 +273,8 @@ int gim_bneck64_fused_f16(const void* t1, const void* res, void* x_out, void* t1
  * order, w1n [8][n_next][64]: per 64-channel chunk of x', K in accumulator order (gim_amd/packing.py::pack_bneck_tail); the 256+ KiB
  * of weights stream through LDS two chunks ahead of the MFMAs.  act_next: GIM_ACT_RELU / GIM_ACT_NONE. */
 int gim_bneck_tail128(const void* t2, const void* res, void* x_out, void* t1_next, const void* w3, const void* w1n,
-                      const float* b3, const float* b1n, int M, int n_next, int act_next, int32_t* health, gim_stream_t stream);
-int gim_bneck_tail128_f16(const void* t2, const void* res, void* x_out, void* t1_next, const void* w3, const void* w1n,
-                          const float* b3, const float* b1n, int M, int n_next, int act_next, int32_t* health, gim_stream_t stream);
+                      const float* b3, const float* b1n, int M, int n_next, int act_next, int dtype, int32_t* health,
+                      gim_stream_t stream);
 /* First block of layer 2 with its `downsample` branch INSIDE the kernel (round 5; resnet.py:120-124: identity = bn(conv1x1, stride 2 (x))):
  *     x' = relu([W3 | Wds] [t2 ; x_in(b, 2y, 2x)] + b3 + bds);   t1' = act(bn1'(conv1'(x')))
  * -- neither the downsample launch nor its 512-channel output exist.  t2 [B,Ho,Wo,128] (conv2 output, stride 2), x_in [B,Hin,Win,256] the
@@ -284,19 +283,16 @@ int gim_bneck_tail128_f16(const void* t2, const void* res, void* x_out, void* t1
  * accumulator order), b3ds = b3 + bds (gim_amd/packing.py::pack_bneck_tail(..., ds=True)). */
 int gim_bneck_tail128_ds(const void* t2, const void* x_in, void* x_out, void* t1_next, const void* w3ds, const void* w1n,
                          const float* b3ds, const float* b1n, int B, int Ho, int Wo, int Hin, int Win, int n_next, int act_next,
-                         int32_t* health, gim_stream_t stream);
-int gim_bneck_tail128_ds_f16(const void* t2, const void* x_in, void* x_out, void* t1_next, const void* w3ds, const void* w1n,
-                             const float* b3ds, const float* b1n, int B, int Ho, int Wo, int Hin, int Win, int n_next, int act_next,
-                             int32_t* health, gim_stream_t stream);
+                         int dtype, int32_t* health, gim_stream_t stream);
 /* Planes 256 (layer 3): t2 [M,256], res / x_out [M,1024], t1_next [M,256] (n_next = 256); w3 [1024][256], w1n [32][256][32] (chunks of
  * 32 channels).  x_out may be NULL: the last block's output is read by nothing but the fused 1x1 convolution -- the FPN's
  * layer3_outconv (resnet.py:316), act_next = GIM_ACT_NONE, zero bias -- so it is never written. */
 int gim_bneck_tail256(const void* t2, const void* res, void* x_out, void* t1_next, const void* w3, const void* w1n,
-                      const float* b3, const float* b1n, int M, int n_next, int act_next, int32_t* health, gim_stream_t stream);
-int gim_bneck_tail256_f16(const void* t2, const void* res, void* x_out, void* t1_next, const void* w3, const void* w1n,
-                          const float* b3, const float* b1n, int M, int n_next, int act_next, int32_t* health, gim_stream_t stream);
+                      const float* b3, const float* b1n, int M, int n_next, int act_next, int dtype, int32_t* health,
+                      gim_stream_t stream);
 
-/* Token-wise tail of a LoFTREncoderLayer in ONE kernel (bf16 operand mode, d_model 256; transformer.py:52-58):
+/* Token-wise tail of a LoFTREncoderLayer in ONE kernel (16-bit operand modes, d_model 256; transformer.py:52-58; "bf16" below = the
+ * 16-bit kind named by `dtype`, GIM_BF16 / GIM_F16):
  *     x += norm2(mlp.2(relu(mlp.0(cat[x, norm1(merge(msg))]))))
  * msg: [R][ldm] bf16 attention output; xb: [R][ldxb] bf16 operand copy of x (read, then overwritten with the new x);
  * x32: [R][ldx32] fp32 residual stream (read-modify-write).  `weights`: gim_token_mlp_weight_bytes() bytes of bf16 in the
@@ -308,11 +304,7 @@ int gim_bneck_tail256_f16(const void* t2, const void* res, void* x_out, void* t1
 int64_t gim_token_mlp_weight_bytes(void);
 int gim_token_mlp(const void* msg, void* xb, float* x32, const void* weights, const float* ln_params, const float* kv,
                   const uint8_t* q_mask, int R, int C, int L, int S, int ldm, int ldxb, int ldx32, float ln_eps,
-                  gim_stream_t stream);
-/* the same kernel with fp16 operand rows / weights (GIM_F16 mode) */
-int gim_token_mlp_f16(const void* msg, void* xb, float* x32, const void* weights, const float* ln_params, const float* kv,
-                      const uint8_t* q_mask, int R, int C, int L, int S, int ldm, int ldxb, int ldx32, float ln_eps,
-                      gim_stream_t stream);
+                  int dtype, gim_stream_t stream);
 
 /* gim_token_mlp + projection blocks of the NEW x, computed on the tile while it is still in LDS: the q / k / v projections of
  * the following LoFTREncoderLayer (transformer.py:42-44; in a cross layer also the k / v of the same layer's second call), each
@@ -351,10 +343,7 @@ typedef struct gim_token_emit {
 } gim_token_emit;
 int gim_token_mlp_emit(const void* msg, void* xb, float* x32, const void* weights, const float* ln_params, const float* kv,
                        const uint8_t* q_mask, int R, int C, int L, int S, int ldm, int ldxb, int ldx32, float ln_eps,
-                       const gim_token_emit* emit, gim_stream_t stream);
-int gim_token_mlp_emit_f16(const void* msg, void* xb, float* x32, const void* weights, const float* ln_params, const float* kv,
-                           const uint8_t* q_mask, int R, int C, int L, int S, int ldm, int ldxb, int ldx32, float ln_eps,
-                           const gim_token_emit* emit, gim_stream_t stream);
+                       int dtype, const gim_token_emit* emit, gim_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * Fine level.  gim_fine_gather = F.unfold(k=W,stride,pad=W/2) + [b_ids,i_ids] pick
@@ -371,7 +360,8 @@ int gim_fine_gather(const void* feat_f0, const void* feat_f1, const int64_t* b_i
 int gim_fine_match(const float* f0, const float* f1, const float* mkpts1_c, const int64_t* b_ids,
                    const float* scale1, float* expec_f, float* mkpts1_f, int M, int WW, int C, int ld,
                    float scale, int has_scale0, gim_stream_t stream);
-/* The whole fine level in ONE kernel (bf16 operand mode, d_model 128, 5x5 windows, layer_names ['self','cross']):
+/* The whole fine level in ONE kernel (16-bit operand modes, d_model 128, 5x5 windows, layer_names ['self','cross']; "bf16" below = the
+ * 16-bit kind named by `dtype`, GIM_BF16 / GIM_F16):
  * window gather (fine_preprocess.py:40-47) + LocalFeatureTransformer (transformer.py:35-58,80-101, LinearAttention
  * attentions.py:20-47) + FineMatching (fine_matching.py:43-74); 2 matches per workgroup, activations never leave the CU.
  * feat_f0/feat_f1: NHWC bf16 fine maps (row stride ldf).  `weights`: gim_fine_fused_weight_bytes() bytes, bf16, per layer
@@ -384,7 +374,7 @@ int gim_fine_fused(const void* feat_f0, const void* feat_f1, const int64_t* b_id
                    const int64_t* j_ids, const float* mkpts1_c, const float* scale1, const void* weights,
                    const float* ln_params, float* expec_f, float* mkpts1_f, float* dbg_fine0, float* dbg_fine1,
                    int M, int hf0, int wf0, int hf1, int wf1, int C, int ldf, int w0c, int w1c, int stride, int W,
-                   float scale, float ln_eps, int has_scale0, gim_stream_t stream);
+                   float scale, float ln_eps, int has_scale0, int dtype, gim_stream_t stream);
 /* The same launch without the host knowing the match count: it covers M_cap = the capacity of the match lists and processes the first
  * min(M_cap, *count_dev) of them (count_dev = gim_coarse_match's count[0]); expec_f / mkpts1_f hold M_cap rows.  The reference
  * synchronises on the count (torch.where, coarse_matching.py:193) before the fine level; here the read-back overlaps this kernel. */
@@ -392,18 +382,7 @@ int gim_fine_fused_dev(const void* feat_f0, const void* feat_f1, const int64_t* 
                        const int64_t* j_ids, const float* mkpts1_c, const float* scale1, const void* weights,
                        const float* ln_params, float* expec_f, float* mkpts1_f, int M_cap, const int* count_dev,
                        int hf0, int wf0, int hf1, int wf1, int C, int ldf, int w0c, int w1c, int stride, int W,
-                       float scale, float ln_eps, int has_scale0, gim_stream_t stream);
-int gim_fine_fused_dev_f16(const void* feat_f0, const void* feat_f1, const int64_t* b_ids, const int64_t* i_ids,
-                           const int64_t* j_ids, const float* mkpts1_c, const float* scale1, const void* weights,
-                           const float* ln_params, float* expec_f, float* mkpts1_f, int M_cap, const int* count_dev,
-                           int hf0, int wf0, int hf1, int wf1, int C, int ldf, int w0c, int w1c, int stride, int W,
-                           float scale, float ln_eps, int has_scale0, gim_stream_t stream);
-/* the same kernel on fp16 fine maps / weights (GIM_F16 mode) */
-int gim_fine_fused_f16(const void* feat_f0, const void* feat_f1, const int64_t* b_ids, const int64_t* i_ids,
-                       const int64_t* j_ids, const float* mkpts1_c, const float* scale1, const void* weights,
-                       const float* ln_params, float* expec_f, float* mkpts1_f, float* dbg_fine0, float* dbg_fine1,
-                       int M, int hf0, int wf0, int hf1, int wf1, int C, int ldf, int w0c, int w1c, int stride, int W,
-                       float scale, float ln_eps, int has_scale0, gim_stream_t stream);
+                       float scale, float ln_eps, int has_scale0, int dtype, gim_stream_t stream);
 
 
 /* ======================================================================================================
@@ -522,7 +501,7 @@ int gim_copy_segments(const gim_copy_segs* segs, gim_stream_t stream);
 int gim_pack_matches(const int64_t* m_bids, const float* mkpts0, const float* mkpts1, const float* mconf,
                      const int64_t* pair_ids, int64_t pid_base, float* out, int M, gim_stream_t stream);
 /* The patches of the 1/2-resolution fine maps [2 bs, H, W, .] (images of side 0, then of side 1) that the fine level of the first
- * min(count[0], cap) matches can read, for gim_conv3x3_halo_tiles (additive: the ABI revision stays 114).  A patch is listed when it
+ * min(count[0], cap) matches can read, for gim_conv3x3_halo_tiles (added within ABI revision 114).  A patch is listed when it
  * holds a pixel of [stride cy - 3, stride cy + 3] x [stride cx - 3, stride cx + 3] clipped to the map, (cy, cx) = the match's coarse cell
  * (i_ids / w0c on side 0, j_ids / w1c on side 1): the 5 x 5 fine window (fine_preprocess.py:40-47) plus the one-pixel reach of a 3 x 3
  * convolution.  tiles: ascending int32 patch indices ((side * bs + b) * ceil(H / 8) + ty) * ceil(W / 32) + tx, n_tiles[0] their number;
@@ -641,8 +620,8 @@ int gim_seg_head_argmax(const float* logits, uint8_t* cls, float* prob, int* fla
                         gim_stream_t stream);
 
 /* ======================================================================================================
- * Feature bank (gim_loftr): the backbone maps of an image are extracted once and matched in many pairs (additive: the ABI
- * revision stays 114).  The reference recomputes them per pair (networks/loftr/loftr.py:59-72).
+ * Feature bank (gim_loftr): the backbone maps of an image are extracted once and matched in many pairs (added within ABI
+ * revision 114).  The reference recomputes them per pair (networks/loftr/loftr.py:59-72).
  * ====================================================================================================== */
 
 /* Indexed block copy between two slabs of equally sized slots, ONE launch: for i in [0, n) the block_bytes bytes (a positive multiple
@@ -656,8 +635,8 @@ int gim_slot_copy(const void* src, void* dst, const int32_t* src_idx, const int3
                   int dst_slots, gim_stream_t stream);
 
 /* ======================================================================================================
- * root_sift baseline: descriptor matching (additive: the ABI revision stays 114 -- no existing structure or prototype changes, a
- * caller bound to 114 keeps working).
+ * root_sift baseline: descriptor matching (added within ABI revision 114: no existing structure or prototype
+ * changed with it).
  * ====================================================================================================== */
 
 /* RootSIFT normalisation, similarity, mutual nearest neighbour and Lowe's ratio test of root_sift_inference --
@@ -675,7 +654,7 @@ int gim_nn_match(const float* desc0, const float* desc1, int n0, int n1, int D, 
                  float* score0, int32_t* count, void* ws, gim_stream_t stream);
 
 /* ======================================================================================================
- * RANSAC hypothesis scoring for the pose half of the ZEB loop (additive: the ABI revision stays 114).  Sampling, the minimal
+ * RANSAC hypothesis scoring for the pose half of the ZEB loop (added within ABI revision 114).  Sampling, the minimal
  * solvers, the iteration bound and recoverPose stay on the host (gim_amd/pose.py); this is the inlier count that was 90 % of its step.
  * ====================================================================================================== */
 

@@ -57,10 +57,11 @@ def test_ctypes_mirror_matches_the_header(tmp_path, struct, mirror):
 
 
 def test_abi_version_114():
-    """version 114: health bit 8 of the split launches (gim_conv_args.split16).  The library, the ctypes mirror and the header's revision list
-    agree on it: a caller bound to 113 would not know that the word it hands a split launch can come back with bit 8."""
+    """version 114: health bit 8 of the split launches (gim_conv_args.split16); version 115: a dtype tag on the fused kernels, no `*_f16`
+    name declared.  The library, the ctypes mirror and the header's revision list agree on the revision: a caller bound to 113 would not know
+    that the word it hands a split launch can come back with bit 8, one bound to 114 would shift the fused kernels' arguments."""
     from gim_amd import _lib
-    assert _lib.ABI_VERSION == 114 and _lib.lib.gim_version() == 114
+    assert _lib.ABI_VERSION == 115 and _lib.lib.gim_version() == 115
     src = open(HEADER).read()
-    assert re.findall(r"^ \* (\d{3})\b", src, re.M)[-1] == "114"
+    assert re.findall(r"^ \* (\d{3})\b", src, re.M)[-1] == "115"
     assert "ORs 8 into `health`" in re.search(r"int split16;(.*?)\*/", src, re.S).group(1)

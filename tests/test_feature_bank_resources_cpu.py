@@ -1,5 +1,5 @@
 """gim_slot_copy (csrc/feature_bank.hip) in the built libgimhip.so, without a GPU: the symbol is exported and bound, its ctypes
-signature is the header's prototype, the ABI revision is still 114, and the kernel is a gfx950 code object with no scratch and no
+signature is the header's prototype, it moved no ABI revision (the library is at 115), and the kernel is a gfx950 code object with no scratch and no
 spills (read from the AMDGPU metadata notes like tests/test_semseg_resources_cpu.py)."""
 import ctypes
 import importlib.util
@@ -41,10 +41,11 @@ def test_slot_copy_is_exported_with_the_headers_signature():
 
 
 def test_abi_revision_is_still_114():
+    """(named after the revision this export arrived in; 115 gave the fused kernels their dtype tag)"""
     from gim_amd import _lib
-    assert _lib.ABI_VERSION == 114 and _lib.lib.gim_version() == 114
+    assert _lib.ABI_VERSION == 115 and _lib.lib.gim_version() == 115
     src = open(HEADER).read()
-    assert re.findall(r"^ \* (\d{3})\b", src, re.M)[-1] == "114"
+    assert re.findall(r"^ \* (\d{3})\b", src, re.M)[-1] == "115"
 
 
 def test_host_argument_checks_need_no_gpu():

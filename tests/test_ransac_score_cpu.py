@@ -1,5 +1,5 @@
 """gim_ransac_score / gim_ransac_mask (csrc/ransac_score.hip) and the scorer hook of gim_amd/pose.py, without a GPU: the symbols are
-exported and bound with the header's signatures, the ABI revision is still 114, the kernels are gfx950 code objects without scratch or
+exported and bound with the header's signatures, they moved no ABI revision (the library is at 115), the kernels are gfx950 code objects without scratch or
 spills (AMDGPU metadata notes, like tests/test_feature_bank_resources_cpu.py), and the RANSAC loop driven through a scorer object --
 here a numpy one that calls pose.sampson_error -- returns what the host path returns for the same seed, one pair at a time and
 several pairs in lockstep (find_essential_mat_batch)."""
@@ -45,9 +45,10 @@ def test_both_symbols_are_exported_with_the_headers_signatures():
 
 
 def test_abi_revision_is_still_114():
+    """(named after the revision these exports arrived in; 115 gave the fused kernels their dtype tag)"""
     from gim_amd import _lib
-    assert _lib.ABI_VERSION == 114 and _lib.lib.gim_version() == 114
-    assert re.findall(r"^ \* (\d{3})\b", open(HEADER).read(), re.M)[-1] == "114"
+    assert _lib.ABI_VERSION == 115 and _lib.lib.gim_version() == 115
+    assert re.findall(r"^ \* (\d{3})\b", open(HEADER).read(), re.M)[-1] == "115"
 
 
 def test_host_argument_checks_need_no_gpu():
