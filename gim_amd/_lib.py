@@ -172,6 +172,10 @@ PROTOTYPES = {
     # RANSAC hypothesis scoring of gim_amd/pose.py (added within ABI revision 114)
     "gim_ransac_score": (c_int, [c_void_p] * 5 + [c_int, c_int, ctypes.c_double, c_void_p, c_void_p]),
     "gim_ransac_mask": (c_int, [c_void_p] * 4 + [c_int, ctypes.c_double, c_void_p, c_void_p]),
+    # keypoint bank of gim_lightglue (added within ABI revision 115)
+    "gim_lg_bank_put": (c_int, [c_void_p] * 8 + [c_int] * 4 + [c_void_p]),
+    "gim_lg_gather_pairs": (c_int, [c_void_p] * 7 + [c_int] * 7 + [c_void_p]),
+    "gim_lg_emit_hloc": (c_int, [c_void_p] * 4 + [c_int] * 2 + [c_void_p]),
 }
 
 

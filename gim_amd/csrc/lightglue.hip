@@ -17,6 +17,7 @@
 //     LDS reads per fragment from a V^T tile stored [d][key] (hence lg_transpose).
 //   * LDS tiles are XOR-swizzled so that both the 16-byte K reads and the 8-byte V^T reads are conflict-free.
 #include "gim_common.h"
+#include "lg_posenc.h"
 #include <math.h>
 
 namespace {
@@ -29,13 +30,10 @@ __global__ void lg_posenc_kernel(const float* __restrict__ kpts, const float* __
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= rows * F) return;
     const int f = idx % F, r = idx / F, b = r / K;
-    const float w = size_wh[b * 2 + 0], h = size_wh[b * 2 + 1];
-    const float scale = fmaxf(w, h) / 2.f;
-    const float x = (kpts[(size_t)r * 2 + 0] - w / 2.f) / scale;
-    const float y = (kpts[(size_t)r * 2 + 1] - h / 2.f) / scale;
-    const float p = x * Wr[f * 2 + 0] + y * Wr[f * 2 + 1];
-    enc[(size_t)r * 2 * F + f] = cosf(p);
-    enc[(size_t)r * 2 * F + F + f] = sinf(p);
+    float c, s;
+    lg_posenc_freq(kpts + (size_t)r * 2, size_wh[b * 2 + 0], size_wh[b * 2 + 1], Wr, f, c, s);   // lg_posenc.h: shared with the keypoint bank
+    enc[(size_t)r * 2 * F + f] = c;
+    enc[(size_t)r * 2 * F + F + f] = s;
 }
 
 // x[row][c..c+3] (two rotary pairs) for c < ncols; head dim 64 = 32 pairs, the same table for every head:

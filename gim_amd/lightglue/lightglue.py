@@ -125,13 +125,17 @@ class LightGlue(nn.Module):
         self.log_assignment = nn.ModuleList([_MatchAssignment(d) for _ in range(n)])
         self.token_confidence = nn.ModuleList([_TokenConfidence(d) for _ in range(n - 1)])
         self._packed = None
+        self._pack_epoch = 0      # counts the repacks: a KeypointBank's encoding table is valid for one (module, epoch) only
+        self.input_hook = None    # debugging: callable(X32, CAT, enc), called with the first block's outputs before the first GEMM
 
     def load_state_dict(self, state_dict, *args, **kwargs):
         self._packed = None
+        self._pack_epoch += 1
         return super().load_state_dict(state_dict, *args, **kwargs)
 
     def _apply(self, fn, *a, **k):
         self._packed = None
+        self._pack_epoch += 1
         return super()._apply(fn, *a, **k)
 
     # ---- one-time weight packing ----------------------------------------------------------------------------
@@ -186,10 +190,7 @@ class LightGlue(nn.Module):
         if not kp0.is_cuda:
             raise GimHipError("gim_amd LightGlue needs device (cuda/HIP) tensors: there is no CPU fallback")
         dev = kp0.device
-        dt_want = PRECISION_DTYPE[self.precision]
-        if self._packed is None or self._packed[4] != dev or self._packed[3] != dt_want:
-            self._prepack(dev)
-        layers, head, wr, dt, _ = self._packed
+        layers, head, wr, dt = self._packed_for(dev)
         tdt = torch_dtype(dt)
         B, M, _ = kp0.shape
         N = kp1.shape[1]
@@ -197,7 +198,6 @@ class LightGlue(nn.Module):
         size1 = (data["image_size1"] if "image_size1" in data else data["resize1"])[:, [1, 0]]
         d0, d1 = data["descriptors0"], data["descriptors1"]
         assert d0.shape[-1] == self.conf["input_dim"] and d1.shape[-1] == self.conf["input_dim"]
-        n_layers = self.conf["n_layers"]
         if M == 0 or N == 0:
             raise GimHipError("LightGlue needs at least one keypoint per image")
         enc0 = ops.lg_posenc(kp0.float().contiguous(), size0.to(device=dev, dtype=torch.float32).contiguous(), wr)
@@ -212,6 +212,25 @@ class LightGlue(nn.Module):
         X32[R0:].copy_(d1.reshape(R1, 256))
         if not alias:
             ops.cast_rows(X32, CAT[:, :256])
+        return self._match_rows(layers, head, dt, B, M, N, CAT, X32, enc, kp0, kp1, data.get("_adapter"))[0]
+
+    def _packed_for(self, dev):
+        """(layers, head, Wr, dtype tag) packed for `dev` in the module's precision (packed on first use and after a repack)"""
+        dt_want = PRECISION_DTYPE[self.precision]
+        if self._packed is None or self._packed[4] != dev or self._packed[3] != dt_want:
+            self._prepack(dev)
+        return self._packed[:4]
+
+    def _match_rows(self, layers, head, dt, B, M, N, CAT, X32, enc, kp0, kp1, kscale):
+        """Everything behind the first block, shared by forward() and match_pairs(): the stacked rows CAT[:, :256] / X32 (image-0 rows
+        first) and their encoding table `enc` -> (the reference's result dict, the lg_assign result).  kscale: see below."""
+        dev, tdt = CAT.device, torch_dtype(dt)
+        R0, R1 = B * M, B * N
+        R = R0 + R1
+        alias = dt == GIM_F32
+        n_layers = self.conf["n_layers"]
+        if self.input_hook is not None:
+            self.input_hook(X32, CAT, enc)
         QKV = torch.empty(R, 768, dtype=tdt, device=dev)
         CTX = torch.empty(R, 256, dtype=tdt, device=dev)
         HID = torch.empty(R, 512, dtype=torch.float32, device=dev)
@@ -246,7 +265,7 @@ class LightGlue(nn.Module):
                           MD[R0:].view(B, N, 256), head["mw"], head["mb"], float(self.conf["filter_threshold"]))
         counts = r.count.tolist()  # the one read-back: sizes of the per-pair match lists (torch.where, lightglue.py:500)
         total = sum(counts)
-        kscale = data.get("_adapter")  # set by gim_lightglue_inference: (scale0, scale1) -> fused caller-side adapter
+        # kscale: data["_adapter"], set by gim_lightglue_inference: (scale0, scale1) -> fused caller-side adapter
         if kscale is not None:
             packed = ops.lg_emit_matches(r, total, kp0.float().contiguous(), kp1.float().contiguous(), kscale[0], kscale[1])
         else:
@@ -266,4 +285,28 @@ class LightGlue(nn.Module):
         }
         if kscale is not None:
             pred["_packed"] = packed
+        return pred, r
+
+    @torch.no_grad()
+    def match_pairs(self, bank, idx0, idx1, hloc=False):
+        """forward() for B pairs of images resident in a `KeypointBank`: pair b matches the image in slot idx0[b] against the one in slot
+        idx1[b] (int32 device tensors, or sequences of ints as `bank.slots(keys)` returns them).  One gim_lg_gather_pairs launch builds
+        what forward()'s first block builds per call; the rest is the same code.  Returns forward()'s dict; hloc=True adds `matches0_i16`
+        [B,K] int16 and `matching_scores0_f16` [B,K] fp16, hloc's match-file datasets for the batch."""
+        dev = bank.device
+        layers, head, wr, dt = self._packed_for(dev)
+        bank.ensure_encodings(self, wr)
+        idx0, idx1 = bank.slot_tensor(idx0), bank.slot_tensor(idx1)
+        B, K = idx0.numel(), bank.num_keypoints
+        if B == 0 or idx1.numel() != B:
+            raise GimHipError(f"match_pairs needs as many slots on both sides and at least one pair, got {B} and {idx1.numel()}")
+        alias = dt == GIM_F32
+        R = 2 * B * K
+        CAT = torch.empty(R, 512, dtype=torch_dtype(dt), device=dev)
+        X32 = CAT[:, :256] if alias else torch.empty(R, 256, dtype=torch.float32, device=dev)
+        enc = torch.empty(R, 64, dtype=torch.float32, device=dev)
+        ops.lg_gather_pairs(bank.desc, bank.enc, idx0, idx1, X32, None if alias else CAT, enc)
+        pred, r = self._match_rows(layers, head, dt, B, K, K, CAT, X32, enc, None, None, None)
+        if hloc:
+            pred["matches0_i16"], pred["matching_scores0_f16"] = ops.lg_emit_hloc(r)
         return pred

@@ -5,7 +5,7 @@ Drop-in contract:
   * `SuperPoint(conf_dict)` with the reference's `default_conf` keys; `state_dict()` has the reference's 24
     tensors (conv1a ... convDb), so the `superpoint.`-stripped halves of gim_lightglue checkpoints load
     unchanged (`demo.py:378-386`);
-  * `model({'image': [B,1|3,H,W]})` -> `{'keypoints': [B,K,2] (x, y) + 0.5, 'descriptors': [B,K,256]}`;
+  * `model({'image': [B,1|3,H,W]})` -> `{'keypoints': [B,K,2] (x, y) + 0.5, 'descriptors': [B,K,256], 'keypoint_scores': [B,K]}`;
   * quirks kept: a caller-supplied `image_size` is ignored (the reference overwrites it with the canvas size,
     superpoint.py:207), `legacy_sampling` descriptor interpolation, keypoints padded with uniform random
     points when fewer than `max_num_keypoints` survive (`pad_and_stack(mode='random_c')`, misc.py:44-55).
@@ -149,6 +149,6 @@ class SuperPoint(nn.Module):
         desc = torch.empty(B, K, 256, dtype=torch.float32, device=dev)
         if K > 0:
             ops.sp_sample_desc(dense, kpts, h, w, desc.view(B * K, 256), None)
-        pred = {"keypoints": kpts + 0.5, "descriptors": desc}
+        pred = {"keypoints": kpts + 0.5, "descriptors": desc, "keypoint_scores": ksc}   # superpoint.py:331-336; hloc stores all three
         self._debug = {"scores": scores, "nms": nms, "keypoint_scores": ksc, "nvalid": nv, "dense_raw": dense, "logits": logits}
         return pred

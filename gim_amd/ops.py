@@ -905,6 +905,42 @@ def lg_emit_matches(r, total, kpts0=None, kpts1=None, scale0=None, scale1=None):
     return matches, scores, mk0, mk1, bids
 
 
+# ---- gim_lightglue: keypoint bank (csrc/lg_bank.hip) ---------------------------------------------------------
+def lg_bank_put(kpts, desc, size_wh, Wr, slots, bank_kpts, bank_desc, bank_enc):
+    """kpts [n,K,2] fp32, desc [n,K,256] fp32 | None, size_wh [n,2] (w, h) | None, Wr [32,2] | None, slots int32 [n] (device) -> the bank
+    arrays bank_kpts [S,K,2] | None, bank_desc [S,K,256] fp32 / fp16, bank_enc [S,K,64]; a None part is left untouched"""
+    _req_cuda(kpts, desc, size_wh, Wr, slots, bank_kpts, bank_desc, bank_enc)
+    n, K, _ = kpts.shape
+    assert kpts.dtype == torch.float32 and kpts.is_contiguous() and slots.dtype == torch.int32 and slots.numel() == n
+    assert desc is None or (desc.dtype == torch.float32 and desc.is_contiguous() and desc.shape == (n, K, 256))
+    assert bank_desc.is_contiguous() and bank_enc.is_contiguous() and bank_desc.shape[1:] == (K, 256) and bank_enc.shape[1:] == (K, 64)
+    check(lib.gim_lg_bank_put(_p(kpts), _p(desc), _p(size_wh), _p(Wr), _p(slots), _p(bank_kpts), _p(bank_desc), _p(bank_enc), n, K,
+                              bank_desc.shape[0], gim_dtype(bank_desc), _stream()), "gim_lg_bank_put")
+
+
+def lg_gather_pairs(bank_desc, bank_enc, idx0, idx1, X32, CAT, enc):
+    """bank slots idx0[b] / idx1[b] (int32 device, [B]) -> X32 [2BK, >=256] fp32 row view, CAT [2BK, >=256] 16-bit row view (None in fp32
+    mode, where X32 is CAT[:, :256] itself) and enc [2BK, 64]"""
+    _req_cuda(bank_desc, bank_enc, idx0, idx1, X32, CAT, enc)
+    B, K = idx0.numel(), bank_desc.shape[1]
+    assert idx0.dtype == torch.int32 and idx1.dtype == torch.int32 and idx1.numel() == B
+    assert X32.dtype == torch.float32 and X32.shape[0] == 2 * B * K and enc.is_contiguous() and enc.shape == (2 * B * K, 64)
+    check(lib.gim_lg_gather_pairs(_p(bank_desc), _p(bank_enc), _p(idx0), _p(idx1), _p(X32), _p(CAT), _p(enc), B, K, bank_desc.shape[0],
+                                  gim_dtype(bank_desc), gim_dtype(CAT) if CAT is not None else GIM_F32, X32.stride(0),
+                                  CAT.stride(0) if CAT is not None else 0, _stream()), "gim_lg_gather_pairs")
+
+
+def lg_emit_hloc(r):
+    """an lg_assign result -> (matches0 int16 [B,M], matching_scores0 fp16 [B,M]): hloc's match-file datasets for the whole batch"""
+    B, M = r.matches0.shape
+    if M > 32767:
+        raise _lib.GimHipError(f"hloc stores matches0 as int16: {M} keypoints per image do not fit (at most 32767)")
+    m16 = torch.empty(B, M, dtype=torch.int16, device=r.matches0.device)
+    s16 = torch.empty(B, M, dtype=torch.float16, device=r.matches0.device)
+    check(lib.gim_lg_emit_hloc(_p(r.matches0), _p(r.mscores0), _p(m16), _p(s16), B, M, _stream()), "gim_lg_emit_hloc")
+    return m16, s16
+
+
 # ---- gim_dkm -------------------------------------------------------------------------------------------------
 def maxpool3x3s2(x):
     """x [B,H,W,C] NHWC -> new [B,(H-1)//2+1,(W-1)//2+1,C] (kernel 3, stride 2, padding 1)"""

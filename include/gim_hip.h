@@ -635,6 +635,41 @@ int gim_slot_copy(const void* src, void* dst, const int32_t* src_idx, const int3
                   int dst_slots, gim_stream_t stream);
 
 /* ======================================================================================================
+ * Keypoint bank (gim_lightglue): the SuperPoint features of an image are stored once and matched in many pairs (added within
+ * ABI revision 115: no existing structure or prototype changed with it).  The reference reloads both images' features and
+ * recomputes both positional encodings for every pair (hloc/match_features.py:124-160, lightglue.py:414-430).
+ * Bank arrays, `n_slots` images of K keypoints, dense and slot-major: kpts fp32 [n_slots][K][2], desc [n_slots][K][256] in the
+ * `storage` dtype (GIM_F32 or GIM_F16 = IEEE fp16), enc fp32 [n_slots][K][64] (the table of gim_lg_posenc).  Slot indices are
+ * DEVICE int32 arrays read by the kernels; an index outside [0, n_slots) is never used as an address.
+ * ====================================================================================================== */
+
+/* Inserts n images: image i goes to slot slots[i] (an out-of-range slot skips the image).  kpts [n][K][2] fp32, desc [n][K][256]
+ * fp32 (16-byte aligned), size_wh [n][2] = (w, h), Wr [32][2].  Writes the slot's keypoints, its descriptors rounded to the storage
+ * dtype (round to nearest even, as .half()) and its encoding -- bit for bit what gim_lg_posenc writes for the same fp32 keypoints,
+ * size and Wr (one shared device function), so it is never computed again per pair.  Parts can be left out: desc == NULL leaves the
+ * descriptors, bank_kpts == NULL the keypoints, Wr == NULL the encoding (size_wh, bank_enc unused) untouched -- a changed Wr rebuilds
+ * the encodings of resident images with desc == bank_kpts == NULL.  Slots must be distinct. */
+int gim_lg_bank_put(const float* kpts, const float* desc, const float* size_wh, const float* Wr, const int32_t* slots,
+                    float* bank_kpts, void* bank_desc, float* bank_enc, int n, int K, int n_slots, int storage,
+                    gim_stream_t stream);
+
+/* The stacked row block of B pairs in ONE launch: rows [0, B*K) are the images idx0[b], rows [B*K, 2*B*K) the images idx1[b] (the
+ * layout LightGlue.forward builds with two gim_lg_posenc launches, a concatenation, two copies and a gim_cast_rows).  x32 rows
+ * [2*B*K][ld_x32] fp32 = the descriptors (fp16 storage: converted exactly), cat rows [2*B*K][ld_cat] = the same values in the compute
+ * dtype `dtype` (GIM_BF16 / GIM_F16; the rounding of gim_cast_rows), enc [2*B*K][64] = the slots' encodings.  dtype GIM_F32: x32 is
+ * the GEMM operand itself (it aliases CAT[:, :256], ld_x32 = 512) and cat must be NULL -- the row is written once.  A pair whose slot is
+ * out of range gets zero rows.  16-byte loads and stores; all buffers 16-byte aligned. */
+int gim_lg_gather_pairs(const void* bank_desc, const float* bank_enc, const int32_t* idx0, const int32_t* idx1, float* x32,
+                        void* cat, float* enc, int B, int K, int n_slots, int storage, int dtype, int ld_x32, int ld_cat,
+                        gim_stream_t stream);
+
+/* hloc's sparse match-file datasets (hloc/match_features.py:150-160) of a whole batch from a gim_lg_assign result: matches0 int64
+ * [B][K] -> int16 (the low 16 bits, as .short()), mscores0 fp32 [B][K] -> IEEE fp16 (round to nearest even, as .half()).  K > 32767
+ * does not fit the int16 format and is refused before the launch.  All buffers 16-byte aligned. */
+int gim_lg_emit_hloc(const int64_t* matches0, const float* mscores0, int16_t* matches0_i16, void* mscores0_f16, int B, int K,
+                     gim_stream_t stream);
+
+/* ======================================================================================================
  * root_sift baseline: descriptor matching (added within ABI revision 114: no existing structure or prototype
  * changed with it).
  * ====================================================================================================== */
