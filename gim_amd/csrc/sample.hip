@@ -40,7 +40,11 @@ __global__ void __launch_bounds__(256) ws_keys_kernel(const float* __restrict__ 
             // ((r >> 8) + 0.5 needs 25 bits at the top end and rounds up to 1.0 -> e = 0 -> key = +inf)
             const float u = ((float)(r >> 9) + 0.5f) * (1.0f / 8388608.0f);
             const float e = -logf(u);
-            key = __float_as_uint(wi / e);                                       // > 0: bit order = value order
+            // > 0: bit order = value order.  The floor keeps a subnormal weight drawable: wi / e rounds to 0 for wi = 1.4e-45 and
+            // e > 2 (subnormals are kept, the division is IEEE), key 0 is never taken by ws_compact_kernel, and a caller that counts
+            // the weight as positive (balanced_sample: k = n_pos) would get an output whose tail was never written.  Floored keys
+            // tie and go by ascending index like every tie
+            key = max(__float_as_uint(wi / e), 1u);
         }
         keys[i] = key;
         atomicAdd(&h[key >> 20], 1u);
@@ -123,6 +127,9 @@ __global__ void __launch_bounds__(256) ws_ties_kernel(WsState* __restrict__ st, 
 
 }  // namespace
 
+// Workspace layout: n key words, the 4096-bin histogram, the WsState block (256 bytes), the tie list.  After the call the first
+// n words are the keys of this (weights, seed) -- the bit patterns of w_i / e_i (at least 1), 0 where w_i <= 0 -- which callers may read
+// (tests/test_gpu_dense_tail.py compares the returned set with the top-k of exactly these words).
 extern "C" int64_t gim_weighted_sample_ws_bytes(int n) { return (int64_t)n * 4 + 4096 * 4 + 256 + TIE_CAP * 4; }
 
 extern "C" int gim_weighted_sample(const float* w, int64_t* out, void* ws, int n, int k, uint32_t seed, gim_stream_t stream) {

@@ -1160,13 +1160,24 @@ def cls_to_flow(logits, B, h, w, ncls):
     return flow, cert
 
 
-def weighted_sample(w, k, seed):
-    """k distinct indices drawn with probability ~ w (fp32 [n], >= k positive entries) -> int64 [k], unordered"""
-    _req_cuda(w)
+def weighted_sample_ws_bytes(n):
+    return lib.gim_weighted_sample_ws_bytes(n)
+
+
+def weighted_sample(w, k, seed, ws=None, out=None):
+    """k distinct indices drawn with probability ~ w (fp32 [n], >= k positive entries) -> int64 [k], unordered.
+    ws: caller's workspace (contiguous, >= weighted_sample_ws_bytes(n) bytes; its first n 32-bit words are the keys after the
+    call); out: caller's int64 [k] result buffer."""
+    _req_cuda(w, ws, out)
     assert w.dim() == 1 and w.is_contiguous() and w.dtype == torch.float32
     n = w.shape[0]
-    ws = torch.empty(lib.gim_weighted_sample_ws_bytes(n), dtype=torch.uint8, device=w.device)
-    out = torch.empty(k, dtype=torch.int64, device=w.device)
+    need = weighted_sample_ws_bytes(n)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=w.device)
+    assert ws.is_contiguous() and ws.numel() * ws.element_size() >= need, (ws.shape, ws.dtype, need)
+    if out is None:
+        out = torch.empty(k, dtype=torch.int64, device=w.device)
+    assert out.dtype == torch.int64 and out.shape == (k,) and out.is_contiguous(), (out.dtype, out.shape)
     check(lib.gim_weighted_sample(_p(w), _p(out), _p(ws), n, k, seed & 0xffffffff, _stream()), "gim_weighted_sample")
     return out
 
