@@ -176,6 +176,10 @@ PROTOTYPES = {
     "gim_lg_bank_put": (c_int, [c_void_p] * 8 + [c_int] * 4 + [c_void_p]),
     "gim_lg_gather_pairs": (c_int, [c_void_p] * 7 + [c_int] * 7 + [c_void_p]),
     "gim_lg_emit_hloc": (c_int, [c_void_p] * 4 + [c_int] * 2 + [c_void_p]),
+    # sparse lateral of gim_loftr's fine FPN head (added within ABI revision 115)
+    "gim_conv_ups_tiles_supported": (c_int, [ctypes.POINTER(ConvArgs)]),
+    "gim_conv2d_ups_tiles": (c_int, [ctypes.POINTER(ConvArgs), c_void_p, c_void_p, c_int, c_void_p]),
+    "gim_fine_tile_lists": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p] * 4 + [c_int, c_void_p]),
 }
 
 
@@ -197,7 +201,12 @@ def _load():
         pass
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in PROTOTYPES.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            # entry points are also added WITHIN a revision (no structure or prototype changes with them): a library built from an older tree of
+            # the same revision passes the version check below and lacks the symbol -- the same answer as for a wrong revision
+            raise ImportError(f"{LIB_PATH} does not export {name}: it was built from an older tree, rebuild with `python -m gim_amd.build`") from None
         fn.restype = res
         fn.argtypes = args
     # the ctypes mirrors above are bound to ONE revision of include/gim_hip.h: same-named entry points changed their argument lists between

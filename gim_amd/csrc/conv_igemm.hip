@@ -144,8 +144,11 @@ igemm_kernel(const gim_conv_args a, const int mtiles, const int ntiles, const in
 // extra LDS), so that residual loads and output stores are 16 bytes per lane with a whole 128/256-byte row
 // segment per 8/16 adjacent lanes.  Bias enters as the accumulator's initial value; activation kind,
 // bounds and dtypes are tile-uniform branches; bf16 rounding is one v_cvt_pk_bf16_f32 per pair.
-template <typename G, bool OUT_BF16, bool HAS_RES, bool UPS = false>
+// LIST (igemm_persistent_tiles_kernel): the tile is an 8 x 32 pixel patch of a flat launch -- m0 is the flat index of the patch's first pixel and
+// the wave's pass j is patch row wm * TM + j of a map 2 ups_w pixels wide (pass_row); everything else is the dense epilogue.
+template <typename G, bool OUT_BF16, bool HAS_RES, bool UPS = false, bool LIST = false>
 struct Epilogue {
+    static_assert(!LIST || (UPS && OUT_BF16 && !HAS_RES), "the patch walk is built for the upsample-carrying 16-bit tile only");
     static constexpr int TM = G::TM, TN = G::TN, WTM = G::WTM, WTN = G::WTN, WN = G::WTN == 0 ? 1 : (G::B_BYTES / KTB) / G::WTN;
     static_assert(WTM % 32 == 0 && WTN % 64 == 0, "epilogue transposition works on 32 px x 64 ch passes of the wave tile");
     static constexpr int NH = WTN / 64;            // 64-channel halves of the wave tile
@@ -167,6 +170,12 @@ struct Epilogue {
         l31 = lane & 31; lh = lane >> 5;
         G::wave_mn(wave, wm, wn);
         rrow = lane / LPR; rslot = lane % LPR;
+    }
+
+    // first output row of the wave's 32-pixel pass j of the tile at m0
+    __device__ __forceinline__ int pass_row(const gim_conv_args& a, int m0, int j) const {
+        if constexpr (LIST) return m0 + (wm * TM + j) * (2 * a.ups_w);
+        else return m0 + wm * WTM + j * 32;
     }
 
     // acc := bias (the MFMAs accumulate on top of it)
@@ -233,7 +242,7 @@ struct Epilogue {
         // (16-byte slot of channel group g in row s: g ^ 2 ((s >> 1) & 1) -- the four rows of a transposed read then cover 128 B of distinct banks)
         auto issue = [&](const int p) __attribute__((always_inline)) {
             const int jj = p / NH, nn = p % NH;
-            const int mb = m0 + wm * WTM + jj * 32;
+            const int mb = pass_row(a, m0, jj);
             const int pr = mb / W2, X0 = mb - pr * W2, ib = pr / H2, Y = pr - ib * H2;
             const float fy = sy * Y;
             const int y0 = (int)fy, y1 = y0 + (y0 < h - 1 ? 1 : 0);
@@ -256,7 +265,7 @@ struct Epilogue {
         for (int p = 0; p < NP; ++p) {
             const int j = p / NH, nh = p % NH;   // compile-time
             // ---- this pass's weights: pixel l31 of the pass, source row = lane half --------------------------------------------
-            const int mb = m0 + wm * WTM + j * 32;
+            const int mb = pass_row(a, m0, j);
             const int pr = mb / W2, uX0 = mb - pr * W2, uY = pr - (pr / H2) * H2;
             const float fy = sy * uY;
             const float ly1 = fy - (float)(int)fy;
@@ -334,7 +343,7 @@ struct Epilogue {
             }
         }
         char* wl = stage + wave * WAVE_BYTES;  // this wave's transposition tile [32 px][RB]
-        const bool full = (m0 + G::A_BYTES / KTB <= M) && (n0 + G::B_BYTES / KTB <= a.N);
+        const bool full = (LIST || m0 + G::A_BYTES / KTB <= M) && (n0 + G::B_BYTES / KTB <= a.N);   // (LIST: whole patches inside the map)
         const int act = (a.act_cols > 0 && n0 >= a.act_cols) ? GIM_ACT_NONE : a.act;  // tile-uniform
         // kind of a 16-bit output: the flavour of this translation unit, except that the fp16 objects can also write bf16
         // (no residual / upsample operand then: checked at launch)
@@ -423,7 +432,7 @@ struct Epilogue {
 #pragma unroll
                 for (int k = 0; k < NI; ++k) {
                     const int row = k * RPI + rrow;
-                    const int m = m0 + wm * WTM + j * 32 + row;
+                    const int m = pass_row(a, m0, j) + row;
                     const uint4 o = *(const uint4*)(wl + row * RB + ((rslot ^ (row & 7)) << 4));
                     if (ncol_ok && (full || m < M)) {
                         *(uint4*)((char*)a.y + ((size_t)m * a.ldy + ncol) * OES) = o;
@@ -473,84 +482,32 @@ template <int N> struct IntC { static constexpr int value = N; };
 
 // SKIP: waves whose last 32-channel fragment lies entirely beyond N run a K loop without it (a second copy of the loop,
 // selected per tile by a wave-uniform branch; see Igemm::mma)
+//
+// LIST (gim_conv2d_ups_tiles: the upsample-carrying 256 x 256 tile of a flat 1 x 1 launch): the M tiles are 8 x 32 pixel patches of the
+// [images, 2 ups_h, 2 ups_w] output map, taken from a device-side list as conv3x3_halo_body<TN, LIST> takes them -- `tlist` holds `*tcount`
+// patch indices (image * tiles_y + ty) * tiles_x + tx, the count is read here, the grid stays the resident-slot grid, workgroups whose share
+// of the list is empty return, patches outside the list are never written.  Tile row r is pixel (8 ty + r / 32, 32 tx + r % 32): only the
+// row addresses of the pixel operand (Igemm::decode_patch) and of the output (Epilogue::pass_row) differ from the dense walk; a patch row
+// is one 32-pixel pass of ups_accumulate, which the dense launch also starts at a multiple of 32 of one map row, so a listed patch comes out
+// bit for bit as the dense launch writes it.
 template <int BM, int BN, int WM, int WN, bool BF16, bool OUT_BF16, bool HAS_RES, bool SKIP = false, bool UPS = false>
 __global__ void __launch_bounds__(WM * WN * 64, 2)  // 2 waves per SIMD: 2 x 4-wave or 1 x 8-wave workgroup per CU
 igemm_persistent_kernel(const gim_conv_args a, const int mtiles, const int ntiles, const int M) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef gim::Igemm<BM, BN, WM, WN, BF16, true> G;
-    typedef Epilogue<G, OUT_BF16, HAS_RES, UPS> E;
-
-    unsigned first, step, end;
-    tile_list((unsigned)(mtiles * ntiles), first, step, end);
-    if (first >= end) return;
-    const gim::MainloopArgs ml = mainloop_args(a, M, G::ES);
-    const int nkt = a.kpad * G::ES / KTB;
-
-    E epi;
-    if constexpr (!BF16) { if (a.split16) epi.wscale = 4096.f; }
-    GIM_TT(conv, epi.wave, 0);
-    unsigned long long tt_k = 0, tt_e = 0, tt_n = 0, tt_a = 0, tt_b = 0;   // GIM_TIMING: K-loop / epilogue totals over this workgroup's tiles
-    (void)tt_k; (void)tt_e; (void)tt_n; (void)tt_a; (void)tt_b;
-    G g, gn;  // staging coordinates of the current / the next tile
-    typename G::Acc acc;
-    typename E::Res rres;
-    int buf = 0;
-    int m0 = (int)(first / ntiles) * BM, n0 = (int)(first % ntiles) * BN;
-    epi.init_acc(a, acc, n0);
-    g.decode(ml, m0, n0);
-    g.stage_issue(ml, smem, 0, 0, a.ktab[G::ktab_index(0)]);
-    int e_nxt = a.ktab[G::ktab_index(nkt > 1 ? 1 : 0)];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    for (unsigned tile = first; tile < end; tile += step) {
-        const unsigned tile_n = tile + step;
-        const bool has_next = tile_n < end;
-        const int m0n = (int)(tile_n / ntiles) * BM, n0n = (int)(tile_n % ntiles) * BN;
-        if (has_next) gn.decode(ml, m0n, n0n);
-        tt_a = GIM_TT_NOW();
-        // ---- K loop: only MFMAs touch the accumulators in here ------------------------------------------
-        auto kloop = [&](auto live, auto split16) __attribute__((always_inline)) {
-            for (int kt = 0; kt < nkt; ++kt) {
-                const bool last = kt + 1 == nkt;
-                int k2 = kt + 2;
-                if (k2 >= nkt) k2 -= nkt;
-                if (k2 >= nkt) k2 = 0;  // nkt == 1
-                const int e_n2 = a.ktab[G::ktab_index(k2)];
-                if (!last) g.stage_issue(ml, smem, buf ^ 1, kt + 1, e_nxt);
-                else if (has_next) gn.stage_issue(ml, smem, buf ^ 1, 0, e_nxt);  // first slab of the next tile
-                if (last) epi.prefetch_res(a, rres, m0, n0, M);
-                if constexpr (decltype(split16)::value != 0) G::template compute_split16<decltype(live)::value>(smem, buf, acc, epi.wscale);
-                else G::template compute<decltype(live)::value>(smem, buf, acc);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-                buf ^= 1;
-                e_nxt = e_n2;
-            }
-        };
-        if constexpr (SKIP && G::TN > 1) {
-            // the wave's last channel fragment holds only padding channels (wave-uniform)
-            if (n0 + epi.wn * G::WTN + (G::TN - 1) * 32 >= a.N) kloop(IntC<G::TN - 1>(), IntC<BF16 ? 0 : 1>());   // (fp32 operands reach this tile as split launches only: dispatch_persistent checks a.split16 on both branches)
-            else kloop(IntC<G::TN>(), IntC<BF16 ? 0 : 1>());
-        } else if constexpr (!BF16) {
-            if constexpr (BM == 256 && BN == 256) kloop(IntC<G::TN>(), IntC<1>());   // (only split launches are sent to this tile: dispatch_persistent checks a.split16 on both branches)
-            else if (a.split16) kloop(IntC<G::TN>(), IntC<1>());   // (a second copy of the loop, selected per launch)
-            else kloop(IntC<G::TN>(), IntC<0>());
-        } else {
-            kloop(IntC<G::TN>(), IntC<0>());
-        }
-        tt_b = GIM_TT_NOW(); tt_k += tt_b - tt_a;
-        epi.run(a, acc, rres, smem + (buf ^ 1) * G::STAGE, m0, n0, M, smem + 2 * G::STAGE);  // buf ^ 1: the stage just consumed; UPS: patch rows behind the stages
-        epi.init_acc(a, acc, n0n < a.npad ? n0n : 0);
-        g = gn;
-        m0 = m0n; n0 = n0n;
-        __syncthreads();  // the transposition tile lives in a stage buffer the next slab's DMA will overwrite
-        tt_e += GIM_TT_NOW() - tt_b; ++tt_n;
-    }
-    GIM_TT(conv, epi.wave, 1);
-    GIM_TT_SET(conv, epi.wave, 4, tt_k); GIM_TT_SET(conv, epi.wave, 5, tt_e); GIM_TT_SET(conv, epi.wave, 6, tt_n);
+    constexpr bool LIST = false;
+    constexpr const int* tlist = nullptr;
+    constexpr const int* tcount = nullptr;
+    constexpr int tcap = 0;
+#include "igemm_persistent_body.h"
 }
 
+// the upsample-carrying tile over a patch list (mtiles = the patches of the map): the same body with LIST on
+template <int BM, int BN, int WM, int WN, bool SKIP>
+__global__ void __launch_bounds__(WM * WN * 64, 2)
+igemm_persistent_tiles_kernel(const gim_conv_args a, const int mtiles, const int ntiles, const int M,
+                              const int* __restrict__ tlist, const int* __restrict__ tcount, const int tcap) {
+    constexpr bool BF16 = true, OUT_BF16 = true, HAS_RES = false, UPS = true, LIST = true;
+#include "igemm_persistent_body.h"
+}
 
 template <int BM, int BN, int WM, int WN, bool BF16, bool OUT_BF16, bool HAS_RES, bool SKIP = false, bool UPS = false>
 int launch_persistent(const gim_conv_args& a, hipStream_t stream) {
@@ -577,6 +534,31 @@ int launch_persistent(const gim_conv_args& a, hipStream_t stream) {
     const int grid = T < RESIDENT ? T : RESIDENT;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), smem, stream, a, mtiles, ntiles, M);
     return gim_check_launch("igemm_persistent_kernel");
+}
+
+// the upsample-carrying 256 x 256 tile over a device-side patch list (igemm_persistent_tiles_kernel; cf. launch_halo<TN, true>)
+template <bool SKIP>
+int launch_persistent_tiles(const gim_conv_args& a, hipStream_t stream, const int* tlist, const int* tcount, int tcap) {
+    constexpr int smem = 2 * (256 + 256) * KTB + 8 * 4096;
+    static_assert(smem <= 160 * 1024, "LDS");
+    auto kern = igemm_persistent_tiles_kernel<256, 256, 4, 2, SKIP>;
+    static GimPerDevice attr_done;
+    if (attr_done.needed()) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        if (e != hipSuccess) {
+            gim_set_error("hipFuncSetAttribute(%d B LDS): %s", smem, hipGetErrorString(e));
+            return GIM_ERR_LAUNCH;
+        }
+        attr_done.done();
+    }
+    const int M = a.B * a.Ho * a.Wo;
+    const int npatch = M / 256, ntiles = a.npad / 256;   // whole 8 x 32 patches (ups_tiles_supported)
+    const int T = (tcap < npatch ? tcap : npatch) * ntiles;   // the most the list can hold; the count itself stays on the device
+    if (T <= 0) return GIM_OK;
+    constexpr int RESIDENT = 256;  // one 8-wave workgroup per CU
+    const int grid = T < RESIDENT ? T : RESIDENT;   // (see launch_persistent)
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, stream, a, npatch, ntiles, M, tlist, tcount, tcap);
+    return gim_check_launch("igemm_persistent_tiles_kernel");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -926,7 +908,8 @@ int dispatch_tile(const gim_conv_args& a, hipStream_t s) {
 }  // namespace
 
 // a->ups is only built into the 256 x 256 / 8-wave bf16 tile: the launch must be one that dispatch_persistent sends there
-static bool ups_supported(const gim_conv_args& a) {
+// (floor = false: without the tile-count floor of that dispatch -- the patch-list launch, whose list decides the count)
+static bool ups_supported(const gim_conv_args& a, const bool floor = true) {
     if (a.dtype != GIM_H16 || a.out_dtype != GIM_H16 || a.res || (a.use_lds_dma != 1 && a.use_lds_dma != 3) || a.npad % 256 != 0) return false;
     // output rows are (image, Y, X) with Y < 2 ups_h, X < 2 ups_w whatever geometry the launch states (a 1x1 conv is launched flat)
     const long long Mo = (long long)a.B * a.Ho * a.Wo;
@@ -934,11 +917,19 @@ static bool ups_supported(const gim_conv_args& a) {
     if (a.act_cols != 0 || a.act != GIM_ACT_NONE) return false;   // the upsampled map is added in front of the activation slot: only the FPN's bare lateral conv
     const int nkt = a.kpad * 2 / KTB;
     const long long M = (long long)a.B * a.Ho * a.Wo;
-    return a.use_lds_dma == 3 || (nkt >= BIG_MIN_NKT && big_tile_count(((M + 255) / 256) * (a.npad / 256), nkt));
+    return a.use_lds_dma == 3 || (nkt >= BIG_MIN_NKT && (!floor || big_tile_count(((M + 255) / 256) * (a.npad / 256), nkt)));
+}
+
+// ... and over a patch list (gim_conv2d_ups_tiles): a 1 x 1 conv launched flat (pixel index == row index) onto an output map
+// [images, 2 ups_h, 2 ups_w] of whole 8 x 32 patches
+static bool ups_tiles_supported(const gim_conv_args& a) {
+    if (!ups_supported(a, false)) return false;
+    if (a.B != 1 || a.H != 1 || a.Ho != 1 || a.stride != 1 || a.pad != 0 || a.W != a.Wo) return false;
+    return (2 * a.ups_h) % 8 == 0 && (2 * a.ups_w) % 32 == 0;
 }
 
 // argument checks every launch of this file shares
-static int conv_check(const gim_conv_args& a) {
+static int conv_check(const gim_conv_args& a, const bool ups_tiles = false) {
     const int es = a.dtype == GIM_H16 ? 2 : 4;
     GIM_REQUIRE(a.dtype == GIM_H16 || a.dtype == GIM_F32, "conv: bad dtype %d", a.dtype);
     GIM_REQUIRE(a.x && a.w && a.y && a.ktab, "conv: NULL x/w/y/ktab");
@@ -953,7 +944,7 @@ static int conv_check(const gim_conv_args& a) {
     GIM_REQUIRE(a.act_cols >= 0 && a.act_cols % 128 == 0, "conv: act_cols=%d must be a multiple of 128", a.act_cols);
     GIM_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0 && a.Ho > 0 && a.Wo > 0 && a.stride > 0, "conv: bad geometry");
     GIM_REQUIRE((int64_t)a.B * a.Ho * a.Wo < (int64_t)0x7fffffff, "conv: too many output rows");
-    GIM_REQUIRE(!a.ups || ups_supported(a), "conv: this launch cannot take the fused upsample-add (see gim_conv_ups_supported)");
+    GIM_REQUIRE(!a.ups || (ups_tiles ? ups_tiles_supported(a) : ups_supported(a)), "conv: this launch cannot take the fused upsample-add (see gim_conv_ups_supported)");
     return GIM_OK;
 }
 
@@ -972,6 +963,8 @@ static int halo_launch(const gim_conv_args& a, const int* tiles, const int* n_ti
 GIM_TWIN(gim_conv_ups_supported)
 GIM_TWIN(gim_conv2d_bn_act)
 GIM_TWIN(gim_conv3x3_halo_tiles)
+GIM_TWIN(gim_conv_ups_tiles_supported)
+GIM_TWIN(gim_conv2d_ups_tiles)
 extern "C" int GIM_FN(gim_conv_ups_supported)(const gim_conv_args* ap) {
     GIM_TO_F16(ap && ap->dtype == GIM_F16, gim_conv_ups_supported, ap);
     return ap && ups_supported(*ap) ? 1 : 0;
@@ -1010,4 +1003,22 @@ extern "C" int GIM_FN(gim_conv3x3_halo_tiles)(const gim_conv_args* ap, const int
     GIM_REQUIRE(a.use_lds_dma == 2 && !a.ups, "gim_conv3x3_halo_tiles: the args must describe a halo launch (use_lds_dma = 2, halo packing)");
     if (const int rc = conv_check(a)) return rc;
     return halo_launch(a, tiles, n_tiles, tiles_cap, (hipStream_t)stream);
+}
+
+extern "C" int GIM_FN(gim_conv_ups_tiles_supported)(const gim_conv_args* ap) {
+    GIM_TO_F16(ap && ap->dtype == GIM_F16, gim_conv_ups_tiles_supported, ap);
+    return ap && ups_tiles_supported(*ap) ? 1 : 0;
+}
+
+// gim_conv2d_bn_act's lateral launch (a 1 x 1 conv with a->ups, stated flat) over a device-side list of 8 x 32 patches of its output map
+// [images, 2 ups_h, 2 ups_w]: tiles[0 .. min(*n_tiles, tiles_cap)) are patch indices (image * (2 ups_h / 8) + ty) * (2 ups_w / 32) + tx; the
+// count is read on the device (no host sync, fixed grid), 0 writes nothing, and pixels of patches outside the list keep whatever y held
+extern "C" int GIM_FN(gim_conv2d_ups_tiles)(const gim_conv_args* ap, const int* tiles, const int* n_tiles, int tiles_cap, gim_stream_t stream) {
+    GIM_REQUIRE(ap && tiles && n_tiles && tiles_cap >= 0, "gim_conv2d_ups_tiles: NULL args / tiles / n_tiles or a negative capacity");
+    GIM_TO_F16(ap->dtype == GIM_F16, gim_conv2d_ups_tiles, ap, tiles, n_tiles, tiles_cap, stream);
+    const gim_conv_args& a = *ap;
+    GIM_REQUIRE(a.ups && ups_tiles_supported(a), "gim_conv2d_ups_tiles: not a launch this entry takes (see gim_conv_ups_tiles_supported)");
+    if (const int rc = conv_check(a, true)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    return a.N <= a.npad - 32 ? launch_persistent_tiles<true>(a, s, tiles, n_tiles, tiles_cap) : launch_persistent_tiles<false>(a, s, tiles, n_tiles, tiles_cap);
 }

@@ -7,7 +7,8 @@
 //
 // `gim_fine_tile_list` turns the match lists into the ascending list of 8 x 32 patches of the 1/2-resolution maps that the fine level
 // can read (5 x 5 windows at stride 4 around every coarse match, plus the 3 x 3 receptive field of the FPN's last convolution): the last
-// two FPN layers then run on those patches only (conv_igemm.hip: gim_conv3x3_halo_tiles).
+// two FPN layers then run on those patches only (conv_igemm.hip: gim_conv3x3_halo_tiles).  `gim_fine_tile_lists` also emits the list one
+// pixel wider, for the lateral sum those layers read (gim_conv2d_ups_tiles).
 //
 // Replaces (reference file:line): the tensor construction at networks/loftr/utils/coarse_matching.py:236-259 as far as it
 // only moves data, and the per-pair metric rows of trainer/lightning.py:258-270 (packed form).
@@ -49,14 +50,21 @@ __global__ void __launch_bounds__(256) pack_matches_kernel(const int64_t* __rest
 // The reach of match cell (cy, cx) is [stride * cy - 3, stride * cy + 3] x [stride * cx - 3, stride * cx + 3] clipped to the map: the fine
 // window's +-2 (fine_fused.hip, gather) and one more pixel for the input of the last 3 x 3 convolution.  Rows whose ids lie outside the
 // batch or the coarse map are skipped.
+//
+// REACH2 (gim_fine_tile_lists): a second list from the same launch -- the patches of the reach grown by one more pixel, +-4: what the
+// INPUT of the last-but-one 3 x 3 convolution has to hold (the lateral sum x1_out, gim_conv2d_ups_tiles).  Flag bit 0 = the +-3 reach,
+// bit 1 = the +-4 reach (a superset); one scan over the pair of counts, two compactions.
 constexpr int TL_THREADS = 1024, TL_MAX_FLAGS = 32768;
 
+template <bool REACH2>
 __global__ void __launch_bounds__(TL_THREADS) fine_tile_list_kernel(const int64_t* __restrict__ b_ids, const int64_t* __restrict__ i_ids,
                                                                   const int64_t* __restrict__ j_ids, const int* __restrict__ count, int cap,
                                                                   int bs, int w0c, int w1c, int stride, int H, int W,
-                                                                  int* __restrict__ tiles, int* __restrict__ n_tiles, int tiles_cap) {
-    __shared__ unsigned char flags[TL_MAX_FLAGS];
+                                                                  int* __restrict__ tiles, int* __restrict__ n_tiles, int tiles_cap,
+                                                                  int* __restrict__ tiles2, int* __restrict__ n_tiles2) {
+    __shared__ __attribute__((aligned(16))) unsigned char flags[TL_MAX_FLAGS];
     __shared__ int part[TL_THREADS];
+    __shared__ int part2[REACH2 ? TL_THREADS : 1];
     const int t = threadIdx.x;
     const int tiles_x = (W + 31) / 32, tiles_y = (H + 7) / 8, per_img = tiles_x * tiles_y, nflags = 2 * bs * per_img;
     for (int i = t; i < nflags; i += TL_THREADS) flags[i] = 0;
@@ -77,31 +85,57 @@ __global__ void __launch_bounds__(TL_THREADS) fine_tile_list_kernel(const int64_
             y1 = y1 > H - 1 ? H - 1 : y1; x1 = x1 > W - 1 ? W - 1 : x1;
             if (y0 > y1 || x0 > x1) continue;
             const int img = side * bs + (int)b;
+            if constexpr (REACH2) {
+                // a patch of the +-3 reach gets 3, one that only the fourth pixel touches gets 2: bytes of different writers differ, so they
+                // are OR-ed into the flag's 32-bit word
+                int Y0 = cy * stride - 4, Y1 = cy * stride + 4, X0 = cx * stride - 4, X1 = cx * stride + 4;
+                Y0 = Y0 < 0 ? 0 : Y0; X0 = X0 < 0 ? 0 : X0;
+                Y1 = Y1 > H - 1 ? H - 1 : Y1; X1 = X1 > W - 1 ? W - 1 : X1;
+                for (int ty = Y0 >> 3; ty <= (Y1 >> 3); ++ty)
+                    for (int tx = X0 >> 5; tx <= (X1 >> 5); ++tx) {
+                        const bool in3 = ty >= (y0 >> 3) && ty <= (y1 >> 3) && tx >= (x0 >> 5) && tx <= (x1 >> 5);
+                        const int f = (img * tiles_y + ty) * tiles_x + tx;
+                        atomicOr((unsigned*)flags + (f >> 2), (in3 ? 3u : 2u) << (8 * (f & 3)));
+                    }
+            } else {
             for (int ty = y0 >> 3; ty <= (y1 >> 3); ++ty)
                 for (int tx = x0 >> 5; tx <= (x1 >> 5); ++tx) flags[(img * tiles_y + ty) * tiles_x + tx] = 1;   // (every writer stores the same byte)
+            }
         }
     }
     __syncthreads();
     // ordered compaction: thread t owns flags [t * per, (t + 1) * per)
     const int per = (nflags + TL_THREADS - 1) / TL_THREADS;
     const int lo = t * per < nflags ? t * per : nflags, hi = lo + per < nflags ? lo + per : nflags;
-    int n = 0;
-    for (int i = lo; i < hi; ++i) n += flags[i];
+    int n = 0, n2 = 0;
+    for (int i = lo; i < hi; ++i) { n += flags[i] & 1; n2 += flags[i] >> 1; }
     part[t] = n;
+    if constexpr (REACH2) part2[t] = n2;
     __syncthreads();
     for (int d = 1; d < TL_THREADS; d <<= 1) {   // inclusive scan
         const int v = t >= d ? part[t - d] : 0;
+        const int v2 = REACH2 && t >= d ? part2[t - d] : 0;
         __syncthreads();
         part[t] += v;
+        if constexpr (REACH2) part2[t] += v2;
         __syncthreads();
     }
     int o = part[t] - n;
     for (int i = lo; i < hi; ++i)
-        if (flags[i]) {
+        if (flags[i] & 1) {
             if (o < tiles_cap) tiles[o] = i;
             ++o;
         }
     if (t == TL_THREADS - 1) n_tiles[0] = part[t] < tiles_cap ? part[t] : tiles_cap;
+    if constexpr (REACH2) {
+        int o2 = part2[t] - n2;
+        for (int i = lo; i < hi; ++i)
+            if (flags[i] & 2) {
+                if (o2 < tiles_cap) tiles2[o2] = i;
+                ++o2;
+            }
+        if (t == TL_THREADS - 1) n_tiles2[0] = part2[t] < tiles_cap ? part2[t] : tiles_cap;
+    }
 }
 
 }  // namespace
@@ -115,8 +149,22 @@ extern "C" int gim_fine_tile_list(const int64_t* b_ids, const int64_t* i_ids, co
     const int64_t nflags = 2ll * bs * ((W + 31) / 32) * ((H + 7) / 8);
     GIM_REQUIRE(nflags <= TL_MAX_FLAGS, "gim_fine_tile_list: %lld patches exceed the %d flags of the one-workgroup kernel", (long long)nflags, TL_MAX_FLAGS);
     GIM_REQUIRE(tiles_cap >= nflags, "gim_fine_tile_list: the list holds %d entries, the maps have %lld patches", tiles_cap, (long long)nflags);
-    hipLaunchKernelGGL(fine_tile_list_kernel, dim3(1), dim3(TL_THREADS), 0, (hipStream_t)stream, b_ids, i_ids, j_ids, count, cap, bs, w0c, w1c,
-                       stride, H, W, tiles, n_tiles, tiles_cap);
+    hipLaunchKernelGGL(fine_tile_list_kernel<false>, dim3(1), dim3(TL_THREADS), 0, (hipStream_t)stream, b_ids, i_ids, j_ids, count, cap, bs, w0c, w1c,
+                       stride, H, W, tiles, n_tiles, tiles_cap, nullptr, nullptr);
+    return gim_check_launch("fine_tile_list_kernel");
+}
+
+// gim_fine_tile_list plus, from the same launch, the list of the reach grown to +-4 (tiles4 / n_tiles4, the same capacity)
+extern "C" int gim_fine_tile_lists(const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, const int* count, int cap, int bs,
+                                   int w0c, int w1c, int stride, int H, int W, int* tiles, int* n_tiles, int* tiles4, int* n_tiles4,
+                                   int tiles_cap, gim_stream_t stream) {
+    GIM_REQUIRE(b_ids && i_ids && j_ids && count && tiles && n_tiles && tiles4 && n_tiles4, "gim_fine_tile_lists: NULL pointer");
+    GIM_REQUIRE(cap >= 0 && bs > 0 && w0c > 0 && w1c > 0 && stride > 0 && H > 0 && W > 0, "gim_fine_tile_lists: bad geometry");
+    const int64_t nflags = 2ll * bs * ((W + 31) / 32) * ((H + 7) / 8);
+    GIM_REQUIRE(nflags <= TL_MAX_FLAGS, "gim_fine_tile_lists: %lld patches exceed the %d flags of the one-workgroup kernel", (long long)nflags, TL_MAX_FLAGS);
+    GIM_REQUIRE(tiles_cap >= nflags, "gim_fine_tile_lists: the lists hold %d entries each, the maps have %lld patches", tiles_cap, (long long)nflags);
+    hipLaunchKernelGGL(fine_tile_list_kernel<true>, dim3(1), dim3(TL_THREADS), 0, (hipStream_t)stream, b_ids, i_ids, j_ids, count, cap, bs, w0c, w1c,
+                       stride, H, W, tiles, n_tiles, tiles_cap, tiles4, n_tiles4);
     return gim_check_launch("fine_tile_list_kernel");
 }
 

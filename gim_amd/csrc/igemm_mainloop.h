@@ -74,6 +74,24 @@ struct Igemm {
         wrow = (unsigned)(n0 + srow) * (unsigned)a.ldw * ES + sgrp * 16;
     }
 
+    // the same for a tile that is an 8 x 32 pixel patch of a flat launch (1 x 1 conv, pixel index == row index; BM = 256): tile row r is
+    // pixel p0 + (r >> 5) * lw + (r & 31), p0 = the patch's first pixel, lw = the width of the map it lies in (conv_igemm.hip: LIST)
+    __device__ __forceinline__ void decode_patch(const MainloopArgs& a, int p0, int lw, int n0) {
+        static_assert(BM == 256, "an 8 x 32 patch is a 256-row tile");
+        const int t = (int)threadIdx.x;
+        const int srow = t >> 3, sslot = t & 7;
+        const int sgrp = sslot ^ ((srow >> 1) & 7);
+#pragma unroll
+        for (int i = 0; i < PA; ++i) {
+            const int r = i * RPP + srow;
+            const int m = p0 + (r >> 5) * lw + (r & 31);
+            iy0[i] = m < a.M ? 0 : -(1 << 24);
+            ix0[i] = m;
+            rowoff[i] = (unsigned)m * (unsigned)a.ldx * ES;
+        }
+        wrow = (unsigned)(n0 + srow) * (unsigned)a.ldw * ES + sgrp * 16;
+    }
+
     static __device__ __forceinline__ int ktab_index(int kt) { return ktab_index(kt, (int)threadIdx.x); }
     static __device__ __forceinline__ int ktab_index(int kt, const int t) {
         return kt * 8 + ((t & 7) ^ (((t >> 3) >> 1) & 7));

@@ -285,6 +285,9 @@ class LoFTR(nn.Module):
         # 16-bit modes, forward() on equal image shapes: the FPN's last two 3x3 layers (layer1_outconv2, 1/2 resolution) run behind coarse matching, on
         # the 8 x 32 patches the fine windows of the matches can read and nowhere else (see _fine_tail_sparse; False: the dense maps, as extract() keeps them)
         self.fine_sparse = flag("fine_sparse", True, config)
+        self.lateral_sparse = flag("lateral_sparse", True, config)   # ... and the 1/2-level lateral conv + upsample-add in front of them (_fine_tail_sparse)
+        self.lateral_one_list = flag("lateral_one_list", False, config)   # A/B: all three launches walk the +-4 list (measured slower)
+        self._lat_ok = {}   # _lateral_sparse_ok per shape
         self._packed = None
         self._health = None          # fp16 range guard word of the forward in flight (count[1] of its coarse matching), see _coarse_stage
         self._health_sync_left = 3   # forwards that still wait for the fine kernel to read its health bit at once (fp16 mode)
@@ -535,11 +538,15 @@ class LoFTR(nn.Module):
             off += im.shape[0]
         return out
 
-    def _backbone(self, P, x, dt, fine_tail=True):
+    def _backbone(self, P, x, dt, fine_tail=True, lateral=True):
         """x: NHWC [B,H,W,cstore(3)] images in the compute dtype.  Returns (x3_out NHWC [B,h8,w8,256], feat_f NHWC [B,h2,w2,128])
         in the compute dtype.  (resnet.py:230-235, 306-329)  fine_tail = False: the second tensor is the INPUT of the fine head's last
-        two layers instead ([B,h2,w2,196], see _fpn_fine_tail)."""
+        two layers instead ([B,h2,w2,196], see _fpn_fine_tail); lateral = False as well: the pair (x1, x2_out) that the 1/2-level lateral
+        conv makes that input of (see _fpn_fine)."""
         x1, x2, x3_out = self._backbone_trunk(P, x, dt)
+        if not lateral:
+            assert not fine_tail
+            return x3_out, (x1, self._fpn_fine(P, x1, x2, x3_out, lateral=False))
         x1_out = self._fpn_fine(P, x1, x2, x3_out)
         return x3_out, (self._fpn_fine_tail(P, x1_out) if fine_tail else x1_out)
 
@@ -675,13 +682,16 @@ class LoFTR(nn.Module):
             o = None
         return x, o, x3_out
 
-    def _fpn_fine(self, P, x1, x2, x3_out):
+    def _fpn_fine(self, P, x1, x2, x3_out, lateral=True):
         """the FPN's top-down path to the 1/2 resolution (resnet.py:321-328): four convolutions that nothing of the coarse level (position
-        encoding, transformer, coarse matching) depends on.  Returns the lateral sum x1_out; `_fpn_fine_tail` makes the fine features of it."""
+        encoding, transformer, coarse matching) depends on.  Returns the lateral sum x1_out; `_fpn_fine_tail` makes the fine features of it.
+        lateral = False: stops in front of the 1/2-level lateral conv and returns x2_out (forward's sparse lateral, _fine_tail_sparse)."""
         # lateral 1x1 conv + F.interpolate(scale_factor=2, bilinear, align_corners=True) of the coarser level + add (resnet.py:
         # 321-327): the upsample-add runs in the conv's epilogue when the launch takes it, else as a second pass over the output
         x2_out = self._conv(x2, P["l2o"], ups=x3_out)
         x2_out = self._conv(self._conv(x2_out, P["l2o2a"], ACT_LEAKY), P["l2o2b"])
+        if not lateral:
+            return x2_out
         return self._conv(x1, P["l1o"], ups=x2_out)
 
     def _fine_halo(self, P, h2, w2):
@@ -715,13 +725,46 @@ class LoFTR(nn.Module):
         # the window stride the gather uses (4 h8 = h2), and no more patches than the one-workgroup list kernel flags
         return self._fine_halo(P, h2, w2) and h2 == 4 * h8 and w2 == 4 * w8 and B * (h2 // 8) * (w2 // 32) <= ops.FINE_TILE_MAX_FLAGS
 
+    def _lateral_sparse_ok(self, P, xs):
+        """may this forward (one that `_fine_sparse_ok` accepts) also compute the lateral sum x1_out under the matched windows only?  The
+        launch must be one the patch-list entry takes, and one whose dense form fuses the upsample-add as well -- extract() runs that one,
+        and forward() must stay bit-identical to extract() + match_features() (ops.conv_ups_tiles_supported); x1 is [B,h2,w2,.], x2_out
+        [B,h2/2,w2/2,.]."""
+        if not self.lateral_sparse:
+            return False
+        B, H, W = xs[0].shape[:3]
+        pk = P["l1o"]
+        key = (B, H, W, pk.dtype, pk.cin_pad, pk.n_store, ops.FORCE_BIG_TILE, ops.UPS_FUSED)   # all the predicates look at
+        ok = self._lat_ok.get(key)
+        if ok is None:
+            h2, w2 = _half(H), _half(W)
+            ok = self._lat_ok[key] = ops.conv_ups_tiles_supported((B, h2, w2, pk.cin_pad), pk, (B, h2 // 2, w2 // 2, pk.n_store), dense_too=True)
+        return ok
+
     def _fine_tail_sparse(self, P, x1_out, cr, bs):
         """`_fpn_fine_tail` on the 8 x 32 patches that the fine level can read, behind coarse matching.  The fine map has ONE consumer: the
         gather of a 5 x 5 window per match and side at rows 4 cy - 2 .. 4 cy + 2 (fine_fused.hip / gim_fine_gather; zeros outside the image).
         A window pixel of the second layer reads the first layer at +-1 more, so both launches walk one list: the patches that hold a pixel
         of [4 cy - 3, 4 cy + 3] x [4 cx - 3, 4 cx + 3] for some match (gim_fine_tile_list, from the device-side match count -- no host sync,
         same captured graph).  Every input of a listed first-layer pixel lies in x1_out, which is dense.  Pixels of other patches are never
-        written and never read: the buffers are NOT cleared (a replayed graph leaves the previous forward's values there)."""
+        written and never read: the buffers are NOT cleared (a replayed graph leaves the previous forward's values there).
+        x1_out = (x1, x2_out) (`_lateral_sparse_ok`): the lateral conv + upsample-add that makes x1_out runs here too, on a patch list."""
+        if isinstance(x1_out, tuple):
+            x1, x2_out = x1_out
+            _, H, W, _ = x1.shape
+            # Two lists from one launch: the +-3 list above for the two 3 x 3 layers, and the patches of the reach one pixel wider, +-4, for
+            # the lateral -- every x1_out pixel a CONSUMED first-layer output (+-3) reads lies within +-4, hence in a patch of the second
+            # list.  A listed first-layer patch also reads a one-pixel ring that may lie in patches the lateral never wrote (stale or
+            # uninitialised values): those reach only first-layer outputs outside every +-3 box, which the second layer's consumed
+            # outputs (+-2) never read -- convolution outputs do not mix across pixels.  The alternative, ONE +-4 list for all three
+            # launches, rests on the same argument but grows the two 3 x 3 launches (the expensive ones: a patch row is added below
+            # every match on an odd coarse row, 4 cy + 4 = 8 k) and shrinks nothing; the second list costs one more compaction in the
+            # one-workgroup kernel (DESIGN.md 7d).
+            tiles, n_tiles, tiles4, n_tiles4 = ops.fine_tile_lists(cr.b_ids, cr.i_ids, cr.j_ids, cr.count, bs, cr.args.w0c, cr.args.w1c, 4, H, W)
+            x1_out = ops.conv2d_ups_tiles(x1, P["l1o"], x2_out, tiles4, n_tiles4)
+            if self.lateral_one_list:
+                tiles, n_tiles = tiles4, n_tiles4
+            return self._fpn_fine_tail(P, x1_out, tiles, n_tiles)
         _, H, W, _ = x1_out.shape
         tiles, n_tiles = ops.fine_tile_list(cr.b_ids, cr.i_ids, cr.j_ids, cr.count, bs, cr.args.w0c, cr.args.w1c, 4, H, W)
         return self._fpn_fine_tail(P, x1_out, tiles, n_tiles)
@@ -1062,7 +1105,8 @@ class LoFTR(nn.Module):
             # the two branches fight over L2 and LDS instead of complementing each other; one stream it is)
             if self._fine_sparse_ok(P, xs):
                 # the fine head stops in front of its last two layers; they run behind coarse matching, under the matched windows only
-                c_all, x1_out = self._extract_stage(P, xs[0], fine_tail=False)
+                # (... and, where the launch allows, in front of the 1/2-level lateral conv: x1_out is then the pair (x1, x2_out))
+                c_all, x1_out = self._extract_stage(P, xs[0], fine_tail=False, lateral=not self._lateral_sparse_ok(P, xs))
                 st = self._match_stage(P, c_all[:bs], c_all[bs:], None, None, c_all, bs, xs[0].shape[1], scale0, scale1, mask0, mask1, count)
                 f_all = self._fine_tail_sparse(P, x1_out, st["cr"], bs)
                 st["f0"], st["f1"] = f_all[:bs], f_all[bs:]
@@ -1082,11 +1126,12 @@ class LoFTR(nn.Module):
         split = ops.FP32_SPLIT if self._split16 is None else self._split16
         return word if (self.precision == "fp16" or (self.precision == "fp32" and split)) else None
 
-    def _extract_stage(self, P, x, fine_tail=True):
+    def _extract_stage(self, P, x, fine_tail=True, lateral=True):
         """the per-image half: NHWC images [B,H,W,cstore(3)] -> (coarse map [B,H/8,W/8,256], fine map [B,H/2,W/2,128]) in the compute dtype.
         No image's maps depend on another image of the batch (eval-mode BatchNorm is folded into the weights).
-        fine_tail = False (forward's sparse fine tail): the fine head's last two layers are left to the caller, see _backbone."""
-        return self._backbone(P, x, self._dt(), fine_tail)
+        fine_tail = False (forward's sparse fine tail): the fine head's last two layers are left to the caller, see _backbone;
+        lateral = False: the 1/2-level lateral conv too."""
+        return self._backbone(P, x, self._dt(), fine_tail, lateral)
 
     def _match_stage(self, P, c0, c1, f0, f1, c_all, bs, H0, scale0, scale1, mask0, mask1, count):
         """the per-pair half: coarse maps c0 / c1 [bs,h,w,256] and fine maps f0 / f1 of the bs pairs -> position encoding, coarse
@@ -1131,7 +1176,7 @@ class LoFTR(nn.Module):
 
     def _graph_key(self, color0, color1, scale0, mask0):
         return (tuple(color0.shape), tuple(color1.shape), scale0 is not None, mask0 is not None, self.precision, bool(self.fp32_split),
-                bool(self.fine_sparse), self.coarse_sim, self._img_dt(), self._split(), self._stem_k(), str(color0.device))
+                bool(self.fine_sparse), bool(self.lateral_sparse), bool(self.lateral_one_list), self.coarse_sim, self._img_dt(), self._split(), self._stem_k(), str(color0.device))
 
     def _stage_graphed(self, key, fill, warm, stage, bs, dev, scale0, scale1, mask0, mask1):
         """HIP-graph replay of a shape-static stage (one graph per `key`: input shapes / precision): forward's `_coarse_stage` (~140 kernel

@@ -332,6 +332,68 @@ def conv3x3_halo(x, pk, y, act=ACT_NONE, tiles=None, n_tiles=None):
             check(lib.gim_conv3x3_halo_tiles(ctypes.byref(a), _p(tiles), _p(n_tiles), tiles.numel(), _stream()), "gim_conv3x3_halo_tiles")
 
 
+def _ups_tiles_args(x, pk, ups, y):
+    """gim_conv_args of the lateral 1x1 conv + upsample-add, stated flat, as gim_conv2d_ups_tiles takes it.  x / ups / y: tensors, or
+    their shapes (the predicate needs no pointer)."""
+    xs, us = tuple(getattr(x, "shape", x)), tuple(getattr(ups, "shape", ups))
+    B, H, W, cs = xs
+    rows = B * H * W
+    a = _lib.ConvArgs()
+    if torch.is_tensor(x):
+        a.x, a.ups, a.y = x.data_ptr(), ups.data_ptr(), y.data_ptr()
+    a.w, a.ktab = pk.w.data_ptr(), pk.ktab.data_ptr()
+    a.bias = pk.bias.data_ptr() if pk.bias is not None else None
+    a.res = None
+    a.x_bytes = ((rows - 1) * cs + pk.cin_pad) * elem_size(pk.dtype)
+    a.B, a.H, a.W, a.Ho, a.Wo = 1, 1, rows, 1, rows
+    a.stride, a.pad = pk.stride, pk.pad
+    a.ldx, a.ldy, a.ldres = cs, pk.n_store, 0
+    a.N, a.npad, a.kpad = pk.n_store, pk.npad, pk.kpad
+    a.act, a.res_mod, a.act_cols = ACT_NONE, 0, 0
+    a.dtype = a.out_dtype = pk.dtype
+    a.res_dtype = GIM_F32
+    a.use_lds_dma = 3 if FORCE_BIG_TILE else 1
+    a.ups_h, a.ups_w, a.ups_ld = us[1], us[2], us[3]
+    return a
+
+
+def conv_ups_tiles_supported(x, pk, ups, act=ACT_NONE, res=None, dense_too=False):
+    """does `conv2d_ups_tiles` take this lateral launch?  x [B,H,W,cin_pad] / ups [B,H/2,W/2,n_store]: tensors or shapes
+    (gim_conv_ups_tiles_supported: a bare 16-bit 1x1 conv onto a map of whole 8 x 32 patches).  dense_too: ... and would `conv2d` fuse the
+    upsample-add into the dense launch of the same shape as well (gim_conv_ups_supported: enough tiles for the 256 x 256 tile)?  Only then
+    are the two bit-identical: the two-pass path rounds the conv output before the add."""
+    xs, us = tuple(getattr(x, "shape", x)), tuple(getattr(ups, "shape", ups))
+    if not (UPS_FUSED and pk.kh == 1 and pk.kw == 1 and pk.stride == 1 and pk.pad == 0 and xs[3] == pk.cin_pad):
+        return False
+    if us != (xs[0], xs[1] // 2, xs[2] // 2, pk.n_store) or xs[1] % 2 or xs[2] % 2:
+        return False
+    a = _ups_tiles_args(xs, pk, us, None)
+    a.act = act
+    a.res = 1 if res is not None else None   # (the predicate looks at whether there is one)
+    return bool(lib.gim_conv_ups_tiles_supported(ctypes.byref(a)) and (not dense_too or lib.gim_conv_ups_supported(ctypes.byref(a))))
+
+
+def conv2d_ups_tiles(x, pk, ups, tiles, n_tiles, y=None):
+    """`conv2d(x, pk, ups=ups)` -- the FPN's lateral 1x1 conv + bilinear x2 of `ups` + add -- on the 8 x 32 patches tiles[:n_tiles[0]] of
+    y [B,H,W,n_store] only (int32 device tensors, `fine_tile_lists`; the count stays on the device): listed patches get the bits the dense
+    launch writes, every other pixel of y keeps what it held (gim_conv2d_ups_tiles).  A launch the entry does not take
+    (`conv_ups_tiles_supported`) runs dense."""
+    _req_cuda(x, ups, tiles, n_tiles, y)
+    if not (x.is_contiguous() and ups.is_contiguous() and x.dtype in HALF and ups.dtype == x.dtype and conv_ups_tiles_supported(x, pk, ups)):
+        return conv2d(x, pk, ups=ups)
+    B, H, W, _ = x.shape
+    if y is None:
+        y = torch.empty(B, H, W, pk.n_store, dtype=x.dtype, device=x.device)
+    assert y.shape == (B, H, W, pk.n_store) and y.is_contiguous() and y.dtype == x.dtype
+    assert tiles.dtype == n_tiles.dtype == torch.int32 and tiles.is_contiguous() and n_tiles.numel() >= 1
+    a = _ups_tiles_args(x, pk, ups, y)
+    # sparse: the live measurement alone reads the count back -- computed patches x per-patch flops
+    with _Timed(lambda: f"{pk.cin}->{pk.cout} k1s1 M={B * H * W} +ups sparse",
+                lambda: 2.0 * int(n_tiles[0].item()) * 256 * pk.cout * pk.cin, conv=True):
+        check(lib.gim_conv2d_ups_tiles(ctypes.byref(a), _p(tiles), _p(n_tiles), tiles.numel(), _stream()), "gim_conv2d_ups_tiles")
+    return y
+
+
 FINE_TILE_MAX_FLAGS = lib.gim_fine_tile_list_max_flags()
 
 
@@ -352,6 +414,21 @@ def fine_tile_list(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W, tiles
     check(lib.gim_fine_tile_list(_p(b_ids), _p(i_ids), _p(j_ids), _p(count), cap, bs, w0c, w1c, stride, H, W, _p(tiles), _p(n_tiles),
                                  tiles.numel(), _stream()), "gim_fine_tile_list")
     return tiles, n_tiles
+
+
+def fine_tile_lists(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W):
+    """`fine_tile_list` and, from the same launch, the list of the reach grown by one pixel (+-4 instead of +-3 around stride * cell): the
+    patches whose lateral sum the last-but-one 3 x 3 layer reads.  Returns (tiles, n_tiles, tiles4, n_tiles4)  (gim_fine_tile_lists)"""
+    _req_cuda(b_ids, i_ids, j_ids, count)
+    assert b_ids.dtype == i_ids.dtype == j_ids.dtype == torch.int64 and count.dtype == torch.int32
+    assert b_ids.is_contiguous() and i_ids.is_contiguous() and j_ids.is_contiguous()
+    cap = min(b_ids.numel(), i_ids.numel(), j_ids.numel())
+    total = 2 * bs * ((H + 7) // 8) * ((W + 31) // 32)
+    tiles = torch.empty(2, total, dtype=torch.int32, device=b_ids.device)
+    n = torch.empty(2, dtype=torch.int32, device=b_ids.device)
+    check(lib.gim_fine_tile_lists(_p(b_ids), _p(i_ids), _p(j_ids), _p(count), cap, bs, w0c, w1c, stride, H, W, _p(tiles[0]), _p(n[0:1]),
+                                  _p(tiles[1]), _p(n[1:2]), total, _stream()), "gim_fine_tile_lists")
+    return tiles[0], n[0:1], tiles[1], n[1:2]
 
 
 def linear(x, pk, y, act=ACT_NONE, lds_dma=True, act_cols=0, health=None, split16=None):

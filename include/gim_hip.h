@@ -152,6 +152,16 @@ int gim_conv2d_bn_act(const gim_conv_args* a, gim_stream_t stream);
  * does not depend on it; 0 writes nothing).  Listed patches get exactly what the dense launch writes; pixels of every other patch
  * keep whatever y held.  Entries outside the map are clamped into it. */
 int gim_conv3x3_halo_tiles(const gim_conv_args* a, const int* tiles, const int* n_tiles, int tiles_cap, gim_stream_t stream);
+/* The upsample-carrying launch of gim_conv2d_bn_act (a 1x1 conv with a->ups: the FPN's lateral conv + bilinear x2 + add) over a device-side
+ * list of 8 x 32-pixel patches of its output map [images, 2 ups_h, 2 ups_w] (added within ABI revision 115: no existing structure or
+ * prototype changed with it).  The list is that of gim_conv3x3_halo_tiles: int32 patch indices (image * (2 ups_h / 8) + ty) * (2 ups_w / 32)
+ * + tx, ascending, *n_tiles read ON THE DEVICE and clipped to tiles_cap, entries outside the map clamped into it.  Listed patches get exactly
+ * the bits the dense launch writes; pixels of every other patch keep whatever y held.
+ * gim_conv_ups_tiles_supported(): 1 if the launch is one this entry takes -- the conditions of gim_conv_ups_supported() without its
+ * tile-count floor (the list decides the count), a 16-bit dtype, the 1x1 conv stated flat (B = H = Ho = 1, W = Wo = the pixel count,
+ * stride 1, pad 0) and an output map of whole patches: (2 ups_h) % 8 == 0, (2 ups_w) % 32 == 0. */
+int gim_conv_ups_tiles_supported(const gim_conv_args* a);
+int gim_conv2d_ups_tiles(const gim_conv_args* a, const int* tiles, const int* n_tiles, int tiles_cap, gim_stream_t stream);
 
 /* y[m,:] += bilinear_upsample_2x(x)[m,:], align_corners=True (resnet.py:321,325: F.interpolate +
  * the `x2_out+x3_out_2x` add).  x: [B,h,w,C] rows (ldx), y: [B,2h,2w,C] rows (ldy), in place. */
@@ -509,6 +519,13 @@ int gim_pack_matches(const int64_t* m_bids, const float* mkpts0, const float* mk
 int gim_fine_tile_list_max_flags(void);
 int gim_fine_tile_list(const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, const int* count, int cap, int bs,
                        int w0c, int w1c, int stride, int H, int W, int* tiles, int* n_tiles, int tiles_cap, gim_stream_t stream);
+/* gim_fine_tile_list and, from the same launch, a second list of the same form for the reach grown by one pixel (added within ABI
+ * revision 115): tiles4 / n_tiles4 list the patches that hold a pixel of [stride cy - 4, stride cy + 4] x [stride cx - 4, stride cx + 4]
+ * clipped to the map -- what the INPUT of the last-but-one 3 x 3 convolution must hold, for gim_conv2d_ups_tiles.  tiles / n_tiles get
+ * exactly what gim_fine_tile_list writes; both lists have tiles_cap entries. */
+int gim_fine_tile_lists(const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, const int* count, int cap, int bs,
+                        int w0c, int w1c, int stride, int H, int W, int* tiles, int* n_tiles, int* tiles4, int* n_tiles4, int tiles_cap,
+                        gim_stream_t stream);
 
 /* ======================================================================================================
  * gim_dkm path (kernels D1-D9).  Convolutions / 1x1 projections / the cosine-kernel and
