@@ -180,6 +180,11 @@ PROTOTYPES = {
     "gim_conv_ups_tiles_supported": (c_int, [ctypes.POINTER(ConvArgs)]),
     "gim_conv2d_ups_tiles": (c_int, [ctypes.POINTER(ConvArgs), c_void_p, c_void_p, c_int, c_void_p]),
     "gim_fine_tile_lists": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p] * 4 + [c_int, c_void_p]),
+    # sparse 1/4-level part of gim_loftr's fine FPN head (added within ABI revision 115)
+    "gim_conv2d_tiles_supported": (c_int, [ctypes.POINTER(ConvArgs)]),
+    "gim_conv2d_big_tile": (c_int, [ctypes.POINTER(ConvArgs)]),
+    "gim_conv2d_tiles": (c_int, [ctypes.POINTER(ConvArgs), c_void_p, c_void_p, c_int, c_void_p]),
+    "gim_fine_tile_lists4": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p] * 4 + [c_int, c_void_p, c_void_p, c_int, c_void_p]),
 }
 
 

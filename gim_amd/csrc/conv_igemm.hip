@@ -146,9 +146,10 @@ igemm_kernel(const gim_conv_args a, const int mtiles, const int ntiles, const in
 // bounds and dtypes are tile-uniform branches; bf16 rounding is one v_cvt_pk_bf16_f32 per pair.
 // LIST (igemm_persistent_tiles_kernel): the tile is an 8 x 32 pixel patch of a flat launch -- m0 is the flat index of the patch's first pixel and
 // the wave's pass j is patch row wm * TM + j of a map 2 ups_w pixels wide (pass_row); everything else is the dense epilogue.
+// LIST without UPS (igemm_conv_tiles_kernel): the same patch of the output map [B, Ho, Wo] of a 3 x 3 / stride 1 / pad 1 launch, Wo pixels wide.
 template <typename G, bool OUT_BF16, bool HAS_RES, bool UPS = false, bool LIST = false>
 struct Epilogue {
-    static_assert(!LIST || (UPS && OUT_BF16 && !HAS_RES), "the patch walk is built for the upsample-carrying 16-bit tile only");
+    static_assert(!LIST || (OUT_BF16 && !HAS_RES), "the patch walk is built for the 16-bit tile without residual only");
     static constexpr int TM = G::TM, TN = G::TN, WTM = G::WTM, WTN = G::WTN, WN = G::WTN == 0 ? 1 : (G::B_BYTES / KTB) / G::WTN;
     static_assert(WTM % 32 == 0 && WTN % 64 == 0, "epilogue transposition works on 32 px x 64 ch passes of the wave tile");
     static constexpr int NH = WTN / 64;            // 64-channel halves of the wave tile
@@ -174,7 +175,7 @@ struct Epilogue {
 
     // first output row of the wave's 32-pixel pass j of the tile at m0
     __device__ __forceinline__ int pass_row(const gim_conv_args& a, int m0, int j) const {
-        if constexpr (LIST) return m0 + (wm * TM + j) * (2 * a.ups_w);
+        if constexpr (LIST) return m0 + (wm * TM + j) * (UPS ? 2 * a.ups_w : a.Wo);
         else return m0 + wm * WTM + j * 32;
     }
 
@@ -509,6 +510,18 @@ igemm_persistent_tiles_kernel(const gim_conv_args a, const int mtiles, const int
 #include "igemm_persistent_body.h"
 }
 
+// the plain 256 x 256 tile of a 3 x 3 / stride 1 / pad 1 convolution over a patch list (gim_conv2d_tiles; mtiles = the patches of the output map
+// [B, Ho, Wo] = the input map): the same body with LIST on and UPS off.  Tile row r is pixel (8 ty + r / 32, 32 tx + r % 32) of image b, staged from
+// (Y - 1, X - 1) on (Igemm::decode_patch<true>); K loop, ktab, weight packing and K order are the dense launch's, and an accumulator does not
+// depend on which row of a tile its pixel sits in -- a listed pixel comes out bit for bit as igemm_persistent_kernel<256, 256, 4, 2, ..> writes it.
+template <int BM, int BN, int WM, int WN, bool SKIP>
+__global__ void __launch_bounds__(WM * WN * 64, 2)
+igemm_conv_tiles_kernel(const gim_conv_args a, const int mtiles, const int ntiles, const int M,
+                        const int* __restrict__ tlist, const int* __restrict__ tcount, const int tcap) {
+    constexpr bool BF16 = true, OUT_BF16 = true, HAS_RES = false, UPS = false, LIST = true;
+#include "igemm_persistent_body.h"
+}
+
 template <int BM, int BN, int WM, int WN, bool BF16, bool OUT_BF16, bool HAS_RES, bool SKIP = false, bool UPS = false>
 int launch_persistent(const gim_conv_args& a, hipStream_t stream) {
     constexpr int smem = 2 * (BM + BN) * KTB + (UPS ? WM * WN * 4096 : 0);   // UPS: rows 32..47 of the two upsample patches of every wave (Epilogue::ups_accumulate)
@@ -559,6 +572,30 @@ int launch_persistent_tiles(const gim_conv_args& a, hipStream_t stream, const in
     const int grid = T < RESIDENT ? T : RESIDENT;   // (see launch_persistent)
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, stream, a, npatch, ntiles, M, tlist, tcount, tcap);
     return gim_check_launch("igemm_persistent_tiles_kernel");
+}
+
+// the plain 256 x 256 tile of a 3 x 3 convolution over a device-side patch list (igemm_conv_tiles_kernel)
+template <bool SKIP>
+int launch_conv_tiles(const gim_conv_args& a, hipStream_t stream, const int* tlist, const int* tcount, int tcap) {
+    constexpr int smem = 2 * (256 + 256) * KTB;
+    auto kern = igemm_conv_tiles_kernel<256, 256, 4, 2, SKIP>;
+    static GimPerDevice attr_done;
+    if (attr_done.needed()) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        if (e != hipSuccess) {
+            gim_set_error("hipFuncSetAttribute(%d B LDS): %s", smem, hipGetErrorString(e));
+            return GIM_ERR_LAUNCH;
+        }
+        attr_done.done();
+    }
+    const int M = a.B * a.Ho * a.Wo;
+    const int npatch = M / 256, ntiles = a.npad / 256;   // whole 8 x 32 patches (conv_tiles_supported)
+    const int T = (tcap < npatch ? tcap : npatch) * ntiles;   // the most the list can hold; the count itself stays on the device
+    if (T <= 0) return GIM_OK;
+    constexpr int RESIDENT = 256;  // one 8-wave workgroup per CU
+    const int grid = T < RESIDENT ? T : RESIDENT;   // (see launch_persistent)
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), smem, stream, a, npatch, ntiles, M, tlist, tcount, tcap);
+    return gim_check_launch("igemm_conv_tiles_kernel");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -823,6 +860,13 @@ constexpr int BIG_MIN_TILES = 1024, BIG_MIN_NKT = 4;
 // 128 x 128 tiles in 1.17 rounds do.  Same box, two chains: 9.59 vs 9.73 ms per step.  Between one and four rounds the smaller tile's finer quantisation wins.
 // (deep K only -- 16 slabs, i.e. the 3 x 3 layers: gim_lightglue's 128- and 256-tile Linears, K = 256 / 512, measured 1.5 % slower on the big tile)
 static bool big_tile_count(long long tiles, int nkt) { return tiles >= BIG_MIN_TILES || (tiles >= 128 && tiles <= 256 && nkt >= 16); }
+// does dispatch_persistent send this launch of 16-bit operands (or of split fp32 ones) to the 256 x 256 tile?  `es`: operand element size
+static bool big_tile_launch(const gim_conv_args& a, const int es) {
+    const int nkt = a.kpad * es / KTB;
+    const long long M = (long long)a.B * a.Ho * a.Wo;
+    return a.npad % 256 == 0 && out_is16(a) && !a.res &&
+           (a.use_lds_dma == 3 || (nkt >= BIG_MIN_NKT && big_tile_count(((M + 255) / 256) * (a.npad / 256), nkt)));   // 3: the tests' way onto this tile
+}
 
 template <int BM, int BN, int WM, int WN, bool BF16>
 int dispatch_res(const gim_conv_args& a, hipStream_t s) {
@@ -847,8 +891,7 @@ int dispatch_persistent(const gim_conv_args& a, hipStream_t s) {
         // 256 x 256 tile, 8 waves, 64 x 128 wave tile: twice the MFMAs per wave and slab against nearly the same
         // staging / addressing overhead -- for the MFMA-bound layers (no residual, bf16 out, N % 256 == 0).  fp32 operands only as split
         // launches: this tile has no exact-product loop (split16 = 0 goes to the 128 x 128 tile, which picks the loop per launch)
-        if (a.npad % 256 == 0 && out_is16(a) && !a.res && (BF16 || a.split16) &&
-            (a.use_lds_dma == 3 || (nkt >= BIG_MIN_NKT && big_tile_count(((M + 255) / 256) * (a.npad / 256), nkt))))   // 3: the tests' way onto this tile
+        if ((BF16 || a.split16) && big_tile_launch(a, es))
         {
             // N <= 224 (the FPN's 196-channel layers): the second column half's last fragment is pure padding
             const bool skip = a.N <= a.npad - 32;
@@ -928,6 +971,16 @@ static bool ups_tiles_supported(const gim_conv_args& a) {
     return (2 * a.ups_h) % 8 == 0 && (2 * a.ups_w) % 32 == 0;
 }
 
+// the plain 256 x 256 tile over a patch list (gim_conv2d_tiles): a 16-bit 3 x 3 / stride 1 / pad 1 convolution (the output map is the input
+// map: with pad 1 and stride 1 that is k = 3) without residual, upsample operand or split products, on a map of whole 8 x 32 patches
+static bool conv_tiles_supported(const gim_conv_args& a) {
+    if (a.dtype != GIM_H16 || a.out_dtype != GIM_H16 || a.res || a.ups || a.split16 || (a.use_lds_dma != 1 && a.use_lds_dma != 3)) return false;
+    if (a.npad <= 0 || a.npad % 256 != 0 || a.act_cols != 0) return false;
+    if (a.B <= 0 || a.H <= 0 || a.W <= 0 || a.stride != 1 || a.pad != 1 || a.Ho != a.H || a.Wo != a.W) return false;
+    if (a.H % 8 != 0 || a.W % 32 != 0) return false;
+    return (long long)a.B * (a.H / 8) * (a.W / 32) <= 32768;
+}
+
 // argument checks every launch of this file shares
 static int conv_check(const gim_conv_args& a, const bool ups_tiles = false) {
     const int es = a.dtype == GIM_H16 ? 2 : 4;
@@ -965,6 +1018,9 @@ GIM_TWIN(gim_conv2d_bn_act)
 GIM_TWIN(gim_conv3x3_halo_tiles)
 GIM_TWIN(gim_conv_ups_tiles_supported)
 GIM_TWIN(gim_conv2d_ups_tiles)
+GIM_TWIN(gim_conv2d_tiles_supported)
+GIM_TWIN(gim_conv2d_big_tile)
+GIM_TWIN(gim_conv2d_tiles)
 extern "C" int GIM_FN(gim_conv_ups_supported)(const gim_conv_args* ap) {
     GIM_TO_F16(ap && ap->dtype == GIM_F16, gim_conv_ups_supported, ap);
     return ap && ups_supported(*ap) ? 1 : 0;
@@ -1021,4 +1077,30 @@ extern "C" int GIM_FN(gim_conv2d_ups_tiles)(const gim_conv_args* ap, const int* 
     if (const int rc = conv_check(a, true)) return rc;
     hipStream_t s = (hipStream_t)stream;
     return a.N <= a.npad - 32 ? launch_persistent_tiles<true>(a, s, tiles, n_tiles, tiles_cap) : launch_persistent_tiles<false>(a, s, tiles, n_tiles, tiles_cap);
+}
+
+extern "C" int GIM_FN(gim_conv2d_tiles_supported)(const gim_conv_args* ap) {
+    GIM_TO_F16(ap && ap->dtype == GIM_F16, gim_conv2d_tiles_supported, ap);
+    return ap && conv_tiles_supported(*ap) ? 1 : 0;
+}
+
+// does gim_conv2d_bn_act run the DENSE launch of these args (16-bit operands, LDS-DMA path) on the 256 x 256 tile -- the tile, K loop and K
+// order of gim_conv2d_tiles?  Only then is a listed patch the dense launch's patch bit for bit.
+extern "C" int GIM_FN(gim_conv2d_big_tile)(const gim_conv_args* ap) {
+    GIM_TO_F16(ap && ap->dtype == GIM_F16, gim_conv2d_big_tile, ap);
+    return ap && ap->dtype == GIM_H16 && !ap->ups && (ap->use_lds_dma == 1 || ap->use_lds_dma == 3) && ap->npad > 0 && ap->kpad > 0 &&
+           big_tile_launch(*ap, 2) ? 1 : 0;
+}
+
+// gim_conv2d_bn_act's plain 3 x 3 / stride 1 / pad 1 launch on the 256 x 256 tile over a device-side list of 8 x 32 patches of its output map
+// [B, H, W]: tiles[0 .. min(*n_tiles, tiles_cap)) are patch indices (image * (H / 8) + ty) * (W / 32) + tx; the count is read on the device (no
+// host sync, fixed grid), 0 writes nothing, and pixels of patches outside the list keep whatever y held
+extern "C" int GIM_FN(gim_conv2d_tiles)(const gim_conv_args* ap, const int* tiles, const int* n_tiles, int tiles_cap, gim_stream_t stream) {
+    GIM_REQUIRE(ap && tiles && n_tiles && tiles_cap >= 0, "gim_conv2d_tiles: NULL args / tiles / n_tiles or a negative capacity");
+    GIM_TO_F16(ap->dtype == GIM_F16, gim_conv2d_tiles, ap, tiles, n_tiles, tiles_cap, stream);
+    const gim_conv_args& a = *ap;
+    GIM_REQUIRE(conv_tiles_supported(a), "gim_conv2d_tiles: not a launch this entry takes (see gim_conv2d_tiles_supported)");
+    if (const int rc = conv_check(a)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    return a.N <= a.npad - 32 ? launch_conv_tiles<true>(a, s, tiles, n_tiles, tiles_cap) : launch_conv_tiles<false>(a, s, tiles, n_tiles, tiles_cap);
 }

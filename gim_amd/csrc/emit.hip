@@ -8,7 +8,8 @@
 // `gim_fine_tile_list` turns the match lists into the ascending list of 8 x 32 patches of the 1/2-resolution maps that the fine level
 // can read (5 x 5 windows at stride 4 around every coarse match, plus the 3 x 3 receptive field of the FPN's last convolution): the last
 // two FPN layers then run on those patches only (conv_igemm.hip: gim_conv3x3_halo_tiles).  `gim_fine_tile_lists` also emits the list one
-// pixel wider, for the lateral sum those layers read (gim_conv2d_ups_tiles).
+// pixel wider, for the lateral sum those layers read (gim_conv2d_ups_tiles); `gim_fine_tile_lists4` adds, still from that launch, the three
+// patch lists of the 1/4-resolution maps that this lateral's upsample operand and the two 3 x 3 layers in front of it need (gim_conv2d_tiles).
 //
 // Replaces (reference file:line): the tensor construction at networks/loftr/utils/coarse_matching.py:236-259 as far as it
 // only moves data, and the per-pair metric rows of trainer/lightning.py:258-270 (packed form).
@@ -54,20 +55,37 @@ __global__ void __launch_bounds__(256) pack_matches_kernel(const int64_t* __rest
 // REACH2 (gim_fine_tile_lists): a second list from the same launch -- the patches of the reach grown by one more pixel, +-4: what the
 // INPUT of the last-but-one 3 x 3 convolution has to hold (the lateral sum x1_out, gim_conv2d_ups_tiles).  Flag bit 0 = the +-3 reach,
 // bit 1 = the +-4 reach (a superset); one scan over the pair of counts, two compactions.
+//
+// QUARTER (gim_fine_tile_lists4): three more lists from the same launch, of 8 x 32 patches of the 1/4-resolution maps [2 bs, H / 2, W / 2]
+// (h x w below).  The lateral launch that walks the +-4 list reads its upsample operand x2_out where Epilogue::ups_accumulate (conv_igemm.hip,
+// lambda `issue`) STAGES it: for every 32-pixel pass (row Y, columns X0 .. X0 + 31) of a listed patch, source rows y0 = (int)(sy Y) and
+// y1 = y0 + (y0 < h - 1), columns xa .. min(xa + 23, w - 1), xa = (int)(sx X0), in fp32 with sy = (float)(h - 1) / (float)(H - 1), sx
+// likewise.  All 2 x 24 of them enter the MFMA, most with weight 0 -- and 0 x NaN = NaN, so every staged source must hold a computed value,
+// not only those a pixel interpolates from.  S = the union of the staged sources, computed here with the same fp32 expressions.  Quarter
+// flag bit 0 = the patch holds a pixel of S (list C: the last 3 x 3 layer in front of the lateral), bit 1 = of S dilated by 1 (list B: the
+// 3 x 3 layer before it), bit 2 = of S dilated by 2 (list A: the 1/4-level lateral), dilations clipped to the map; C <= B <= A.  The
+// dilation of a union is the union of the dilations, and the staged set of one half-level patch is a product rows x column range, so
+// each listed patch marks rectangles of quarter patches.
 constexpr int TL_THREADS = 1024, TL_MAX_FLAGS = 32768;
 
-template <bool REACH2>
-__global__ void __launch_bounds__(TL_THREADS) fine_tile_list_kernel(const int64_t* __restrict__ b_ids, const int64_t* __restrict__ i_ids,
-                                                                  const int64_t* __restrict__ j_ids, const int* __restrict__ count, int cap,
-                                                                  int bs, int w0c, int w1c, int stride, int H, int W,
-                                                                  int* __restrict__ tiles, int* __restrict__ n_tiles, int tiles_cap,
-                                                                  int* __restrict__ tiles2, int* __restrict__ n_tiles2) {
+template <bool REACH2, bool QUARTER>
+__device__ __forceinline__ void fine_tile_list_body(const int64_t* __restrict__ b_ids, const int64_t* __restrict__ i_ids,
+                                                    const int64_t* __restrict__ j_ids, const int* __restrict__ count, int cap,
+                                                    int bs, int w0c, int w1c, int stride, int H, int W,
+                                                    int* __restrict__ tiles, int* __restrict__ n_tiles, int tiles_cap,
+                                                    int* __restrict__ tiles2, int* __restrict__ n_tiles2,
+                                                    int* __restrict__ tilesq, int* __restrict__ n_tilesq, int tilesq_cap) {
+    static_assert(!QUARTER || REACH2, "the quarter-level lists are derived from the +-4 flags");
     __shared__ __attribute__((aligned(16))) unsigned char flags[TL_MAX_FLAGS];
     __shared__ int part[TL_THREADS];
     __shared__ int part2[REACH2 ? TL_THREADS : 1];
+    __shared__ int partq[QUARTER ? TL_THREADS : 1][2];   // [0]: |A| << 16 | |B| (each <= TL_MAX_FLAGS / 5 < 2^16), [1]: |C|
     const int t = threadIdx.x;
     const int tiles_x = (W + 31) / 32, tiles_y = (H + 7) / 8, per_img = tiles_x * tiles_y, nflags = 2 * bs * per_img;
-    for (int i = t; i < nflags; i += TL_THREADS) flags[i] = 0;
+    // QUARTER: the quarter-level flags live behind the half-level ones, from the next multiple of four on (word-wise atomicOr)
+    const int h = H / 2, w = W / 2, qtiles_x = w / 32, qtiles_y = h / 8, qper_img = qtiles_x * qtiles_y;
+    const int qbase = (nflags + 3) & ~3, nqflags = QUARTER ? 2 * bs * qper_img : 0;
+    for (int i = t; i < (QUARTER ? qbase + nqflags : nflags); i += TL_THREADS) flags[i] = 0;
     __syncthreads();
     int M = count[0];
     M = M < 0 ? 0 : (M < cap ? M : cap);
@@ -104,6 +122,32 @@ __global__ void __launch_bounds__(TL_THREADS) fine_tile_list_kernel(const int64_
         }
     }
     __syncthreads();
+    if constexpr (QUARTER) {
+        unsigned char* const qf = flags + qbase;
+        const float sy = (float)(h - 1) / (float)(H - 1), sx = (float)(w - 1) / (float)(W - 1);   // ups_accumulate's, to the letter
+        for (int i = t; i < nflags; i += TL_THREADS) {
+            if (!(flags[i] & 2)) continue;
+            const int img = i / per_img, r = i - img * per_img, ty = r / tiles_x, tx = r - ty * tiles_x;
+            const int xa = (int)(sx * (32 * tx));
+            const int xe = xa + 23 < w - 1 ? xa + 23 : w - 1;
+            for (int Y = 8 * ty; Y < 8 * ty + 8 && Y < H; ++Y) {
+                const float fy = sy * Y;
+                const int y0 = (int)fy, y1 = y0 + (y0 < h - 1 ? 1 : 0);
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    const int ra = y0 - d > 0 ? y0 - d : 0, rb = y1 + d < h - 1 ? y1 + d : h - 1;
+                    const int ca = xa - d > 0 ? xa - d : 0, cb = xe + d < w - 1 ? xe + d : w - 1;
+                    const unsigned bits = d == 0 ? 7u : (d == 1 ? 6u : 4u);
+                    for (int qy = ra >> 3; qy <= (rb >> 3); ++qy)
+                        for (int qx = ca >> 5; qx <= (cb >> 5); ++qx) {
+                            const int f = (img * qtiles_y + qy) * qtiles_x + qx;
+                            if ((qf[f] & bits) != bits) atomicOr((unsigned*)qf + (f >> 2), bits << (8 * (f & 3)));
+                        }
+                }
+            }
+        }
+        __syncthreads();
+    }
     // ordered compaction: thread t owns flags [t * per, (t + 1) * per)
     const int per = (nflags + TL_THREADS - 1) / TL_THREADS;
     const int lo = t * per < nflags ? t * per : nflags, hi = lo + per < nflags ? lo + per : nflags;
@@ -111,13 +155,27 @@ __global__ void __launch_bounds__(TL_THREADS) fine_tile_list_kernel(const int64_
     for (int i = lo; i < hi; ++i) { n += flags[i] & 1; n2 += flags[i] >> 1; }
     part[t] = n;
     if constexpr (REACH2) part2[t] = n2;
+    // QUARTER: thread t owns quarter flags [t * qper, (t + 1) * qper); the three counts ride the same scan
+    const int qper = (nqflags + TL_THREADS - 1) / TL_THREADS;
+    const int qlo = t * qper < nqflags ? t * qper : nqflags, qhi = qlo + qper < nqflags ? qlo + qper : nqflags;
+    int nab = 0, nc = 0;
+    if constexpr (QUARTER) {
+        for (int i = qlo; i < qhi; ++i) {
+            const int f = flags[qbase + i];
+            nab += ((f >> 2) & 1) << 16 | ((f >> 1) & 1);
+            nc += f & 1;
+        }
+        partq[t][0] = nab; partq[t][1] = nc;
+    }
     __syncthreads();
     for (int d = 1; d < TL_THREADS; d <<= 1) {   // inclusive scan
         const int v = t >= d ? part[t - d] : 0;
         const int v2 = REACH2 && t >= d ? part2[t - d] : 0;
+        const int vab = QUARTER && t >= d ? partq[t - d][0] : 0, vc = QUARTER && t >= d ? partq[t - d][1] : 0;
         __syncthreads();
         part[t] += v;
         if constexpr (REACH2) part2[t] += v2;
+        if constexpr (QUARTER) { partq[t][0] += vab; partq[t][1] += vc; }
         __syncthreads();
     }
     int o = part[t] - n;
@@ -136,6 +194,42 @@ __global__ void __launch_bounds__(TL_THREADS) fine_tile_list_kernel(const int64_
             }
         if (t == TL_THREADS - 1) n_tiles2[0] = part2[t] < tiles_cap ? part2[t] : tiles_cap;
     }
+    if constexpr (QUARTER) {
+        // tilesq: three lists of tilesq_cap entries each -- A, B, C; n_tilesq: their three counts
+        int oa = (partq[t][0] >> 16) - (nab >> 16), ob = (partq[t][0] & 0xffff) - (nab & 0xffff), oc = partq[t][1] - nc;
+        for (int i = qlo; i < qhi; ++i) {
+            const int f = flags[qbase + i];
+            if (f & 4) { if (oa < tilesq_cap) tilesq[oa] = i; ++oa; }
+            if (f & 2) { if (ob < tilesq_cap) tilesq[tilesq_cap + ob] = i; ++ob; }
+            if (f & 1) { if (oc < tilesq_cap) tilesq[2 * tilesq_cap + oc] = i; ++oc; }
+        }
+        if (t == TL_THREADS - 1) {
+            const int ta = partq[t][0] >> 16, tb = partq[t][0] & 0xffff, tc = partq[t][1];
+            n_tilesq[0] = ta < tilesq_cap ? ta : tilesq_cap;
+            n_tilesq[1] = tb < tilesq_cap ? tb : tilesq_cap;
+            n_tilesq[2] = tc < tilesq_cap ? tc : tilesq_cap;
+        }
+    }
+}
+
+template <bool REACH2>
+__global__ void __launch_bounds__(TL_THREADS) fine_tile_list_kernel(const int64_t* __restrict__ b_ids, const int64_t* __restrict__ i_ids,
+                                                                  const int64_t* __restrict__ j_ids, const int* __restrict__ count, int cap,
+                                                                  int bs, int w0c, int w1c, int stride, int H, int W,
+                                                                  int* __restrict__ tiles, int* __restrict__ n_tiles, int tiles_cap,
+                                                                  int* __restrict__ tiles2, int* __restrict__ n_tiles2) {
+    fine_tile_list_body<REACH2, false>(b_ids, i_ids, j_ids, count, cap, bs, w0c, w1c, stride, H, W, tiles, n_tiles, tiles_cap, tiles2, n_tiles2,
+                                       nullptr, nullptr, 0);
+}
+
+__global__ void __launch_bounds__(TL_THREADS) fine_tile_lists4_kernel(const int64_t* __restrict__ b_ids, const int64_t* __restrict__ i_ids,
+                                                                    const int64_t* __restrict__ j_ids, const int* __restrict__ count, int cap,
+                                                                    int bs, int w0c, int w1c, int stride, int H, int W,
+                                                                    int* __restrict__ tiles, int* __restrict__ n_tiles, int tiles_cap,
+                                                                    int* __restrict__ tiles2, int* __restrict__ n_tiles2,
+                                                                    int* __restrict__ tilesq, int* __restrict__ n_tilesq, int tilesq_cap) {
+    fine_tile_list_body<true, true>(b_ids, i_ids, j_ids, count, cap, bs, w0c, w1c, stride, H, W, tiles, n_tiles, tiles_cap, tiles2, n_tiles2,
+                                    tilesq, n_tilesq, tilesq_cap);
 }
 
 }  // namespace
@@ -166,6 +260,24 @@ extern "C" int gim_fine_tile_lists(const int64_t* b_ids, const int64_t* i_ids, c
     hipLaunchKernelGGL(fine_tile_list_kernel<true>, dim3(1), dim3(TL_THREADS), 0, (hipStream_t)stream, b_ids, i_ids, j_ids, count, cap, bs, w0c, w1c,
                        stride, H, W, tiles, n_tiles, tiles_cap, tiles4, n_tiles4);
     return gim_check_launch("fine_tile_list_kernel");
+}
+
+// gim_fine_tile_lists plus, from the same launch, the three patch lists of the 1/4-resolution maps [2 bs, H / 2, W / 2] (see QUARTER above):
+// tilesq = int32 [3][tilesq_cap], lists A, B, C in that order; n_tilesq = int32 [3]
+extern "C" int gim_fine_tile_lists4(const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, const int* count, int cap, int bs,
+                                    int w0c, int w1c, int stride, int H, int W, int* tiles, int* n_tiles, int* tiles4, int* n_tiles4,
+                                    int tiles_cap, int* tilesq, int* n_tilesq, int tilesq_cap, gim_stream_t stream) {
+    GIM_REQUIRE(b_ids && i_ids && j_ids && count && tiles && n_tiles && tiles4 && n_tiles4 && tilesq && n_tilesq, "gim_fine_tile_lists4: NULL pointer");
+    GIM_REQUIRE(cap >= 0 && bs > 0 && w0c > 0 && w1c > 0 && stride > 0 && H > 0 && W > 0, "gim_fine_tile_lists4: bad geometry");
+    GIM_REQUIRE(H % 16 == 0 && W % 64 == 0, "gim_fine_tile_lists4: the 1/4-resolution maps (%d x %d) must be whole 8 x 32 patches", H / 2, W / 2);
+    const int64_t nflags = 2ll * bs * (W / 32) * (H / 8), nq = 2ll * bs * (W / 64) * (H / 16);
+    GIM_REQUIRE(((nflags + 3) & ~3ll) + nq <= TL_MAX_FLAGS, "gim_fine_tile_lists4: %lld + %lld patches exceed the %d flags of the one-workgroup kernel",
+                (long long)nflags, (long long)nq, TL_MAX_FLAGS);
+    GIM_REQUIRE(tiles_cap >= nflags && tilesq_cap >= nq, "gim_fine_tile_lists4: the lists hold %d / %d entries each, the maps have %lld / %lld patches",
+                tiles_cap, tilesq_cap, (long long)nflags, (long long)nq);
+    hipLaunchKernelGGL(fine_tile_lists4_kernel, dim3(1), dim3(TL_THREADS), 0, (hipStream_t)stream, b_ids, i_ids, j_ids, count, cap, bs, w0c, w1c,
+                       stride, H, W, tiles, n_tiles, tiles_cap, tiles4, n_tiles4, tilesq, n_tilesq, tilesq_cap);
+    return gim_check_launch("fine_tile_lists4_kernel");
 }
 
 extern "C" int gim_copy_segments(const gim_copy_segs* sp, gim_stream_t stream) {

@@ -75,19 +75,32 @@ struct Igemm {
     }
 
     // the same for a tile that is an 8 x 32 pixel patch of a flat launch (1 x 1 conv, pixel index == row index; BM = 256): tile row r is
-    // pixel p0 + (r >> 5) * lw + (r & 31), p0 = the patch's first pixel, lw = the width of the map it lies in (conv_igemm.hip: LIST)
+    // pixel p0 + (r >> 5) * lw + (r & 31), p0 = the patch's first pixel, lw = the width of the map it lies in (conv_igemm.hip: LIST).
+    // SPATIAL: the launch is not flat but a stride-1 convolution whose output map is its input map (k = 2 pad + 1; lw = W = Wo): pixel
+    // m = (b, Y, X) of that map stages from (Y - pad, X - pad) exactly as decode() has it, so the K loop's tap bounds checks hold as they are
+    template <bool SPATIAL = false>
     __device__ __forceinline__ void decode_patch(const MainloopArgs& a, int p0, int lw, int n0) {
         static_assert(BM == 256, "an 8 x 32 patch is a 256-row tile");
         const int t = (int)threadIdx.x;
         const int srow = t >> 3, sslot = t & 7;
         const int sgrp = sslot ^ ((srow >> 1) & 7);
+        const int HW = a.H * a.W;
 #pragma unroll
         for (int i = 0; i < PA; ++i) {
             const int r = i * RPP + srow;
             const int m = p0 + (r >> 5) * lw + (r & 31);
-            iy0[i] = m < a.M ? 0 : -(1 << 24);
-            ix0[i] = m;
-            rowoff[i] = (unsigned)m * (unsigned)a.ldx * ES;
+            if constexpr (SPATIAL) {
+                const int b = m / HW, q = m - b * HW;
+                const int ho = q / a.W, wo = q - ho * a.W;
+                const int y = ho - a.pad, x = wo - a.pad;
+                iy0[i] = m < a.M ? y : -(1 << 24);
+                ix0[i] = x;
+                rowoff[i] = ((unsigned)b * (unsigned)HW + (unsigned)(y * a.W + x)) * (unsigned)a.ldx * ES;
+            } else {
+                iy0[i] = m < a.M ? 0 : -(1 << 24);
+                ix0[i] = m;
+                rowoff[i] = (unsigned)m * (unsigned)a.ldx * ES;
+            }
         }
         wrow = (unsigned)(n0 + srow) * (unsigned)a.ldw * ES + sgrp * 16;
     }

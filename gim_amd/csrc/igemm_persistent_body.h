@@ -1,4 +1,4 @@
-// Body of igemm_persistent_kernel / igemm_persistent_tiles_kernel (conv_igemm.hip), included INSIDE both kernel definitions: the text between
+// Body of igemm_persistent_kernel / igemm_persistent_tiles_kernel / igemm_conv_tiles_kernel (conv_igemm.hip), included INSIDE each kernel definition: the text between
 // the braces, written once.  The including kernel provides BM, BN, WM, WN, BF16, OUT_BF16, HAS_RES, SKIP, UPS, LIST as constants and
 // a, mtiles, ntiles, M, tlist, tcount, tcap as values.  Not a device function that the two kernels call: that form (the halo kernel's)
 // changed the register allocation of the dense instantiations -- 0 -> 44 B of scratch on the 196-channel 3 x 3 tile, 24 -> 64 B on the
@@ -18,13 +18,15 @@
     tile_list((unsigned)(nwalk * ntiles), first, step, end);   // (LIST: XCD-contiguous chunks of the ascending list -- neighbouring patches share upsample sources in one L2)
     if (first >= end) return;
     // LIST: walked tile index -> flat index of its patch's first pixel, through the list (clamped: an entry outside the map must not become
-    // an address).  lw: width of the output map, tiles_x / per_img: patches per map row / per image
-    const int lw = LIST ? 2 * a.ups_w : 0, tiles_x = LIST ? lw / 32 : 1, per_img = LIST ? tiles_x * (2 * a.ups_h / 8) : 1;
+    // an address).  lw / lhgt: width / height of the output map (UPS: twice the upsample source's; else the 3 x 3 launch's own), tiles_x / per_img:
+    // patches per map row / per image
+    const int lw = LIST ? (UPS ? 2 * a.ups_w : a.Wo) : 0, lhgt = LIST ? (UPS ? 2 * a.ups_h : a.Ho) : 0;
+    const int tiles_x = LIST ? lw / 32 : 1, per_img = LIST ? tiles_x * (lhgt / 8) : 1;
     auto list_entry = [&](const unsigned tile) -> int { return tlist[tile / (unsigned)ntiles]; };
     auto patch_row0 = [&](int e) -> int {
         e = e < 0 ? 0 : (e < mtiles ? e : mtiles - 1);
         const int b = e / per_img, r = e - b * per_img, ty = r / tiles_x, tx = r - ty * tiles_x;
-        return (b * (2 * a.ups_h) + ty * 8) * lw + tx * 32;
+        return (b * lhgt + ty * 8) * lw + tx * 32;
     };
     const gim::MainloopArgs ml = mainloop_args(a, M, G::ES);
     const int nkt = a.kpad * G::ES / KTB;
@@ -45,7 +47,7 @@
         if (first + step < end) le_n = list_entry(first + step);
     }
     epi.init_acc(a, acc, n0);
-    if constexpr (LIST) g.decode_patch(ml, m0, lw, n0);
+    if constexpr (LIST) g.template decode_patch<!UPS>(ml, m0, lw, n0);
     else g.decode(ml, m0, n0);
     g.stage_issue(ml, smem, 0, 0, a.ktab[G::ktab_index(0)]);
     int e_nxt = a.ktab[G::ktab_index(nkt > 1 ? 1 : 0)];
@@ -60,7 +62,7 @@
         if constexpr (LIST) {
             m0n = has_next ? patch_row0(le_n) : m0;
             if (tile_n + step < end) le_n = list_entry(tile_n + step);   // consumed at the top of the next tile: a whole K loop away
-            if (has_next) gn.decode_patch(ml, m0n, lw, n0n);
+            if (has_next) gn.template decode_patch<!UPS>(ml, m0n, lw, n0n);
         } else {
             if (has_next) gn.decode(ml, m0n, n0n);
         }

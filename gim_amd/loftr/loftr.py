@@ -287,7 +287,11 @@ class LoFTR(nn.Module):
         self.fine_sparse = flag("fine_sparse", True, config)
         self.lateral_sparse = flag("lateral_sparse", True, config)   # ... and the 1/2-level lateral conv + upsample-add in front of them (_fine_tail_sparse)
         self.lateral_one_list = flag("lateral_one_list", False, config)   # A/B: all three launches walk the +-4 list (measured slower)
+        # ... and the 1/4-level part of the head in front of that lateral (layer2_outconv + upsample-add, layer2_outconv2) where the lateral's
+        # listed patches stage it as upsample sources (_fine_tail_sparse; effective only where lateral_sparse is)
+        self.quarter_sparse = flag("quarter_sparse", True, config)
         self._lat_ok = {}   # _lateral_sparse_ok per shape
+        self._q_ok = {}     # _quarter_sparse_ok per shape
         self._packed = None
         self._health = None          # fp16 range guard word of the forward in flight (count[1] of its coarse matching), see _coarse_stage
         self._health_sync_left = 3   # forwards that still wait for the fine kernel to read its health bit at once (fp16 mode)
@@ -538,14 +542,16 @@ class LoFTR(nn.Module):
             off += im.shape[0]
         return out
 
-    def _backbone(self, P, x, dt, fine_tail=True, lateral=True):
+    def _backbone(self, P, x, dt, fine_tail=True, lateral=True, quarter=True):
         """x: NHWC [B,H,W,cstore(3)] images in the compute dtype.  Returns (x3_out NHWC [B,h8,w8,256], feat_f NHWC [B,h2,w2,128])
         in the compute dtype.  (resnet.py:230-235, 306-329)  fine_tail = False: the second tensor is the INPUT of the fine head's last
         two layers instead ([B,h2,w2,196], see _fpn_fine_tail); lateral = False as well: the pair (x1, x2_out) that the 1/2-level lateral
-        conv makes that input of (see _fpn_fine)."""
+        conv makes that input of (see _fpn_fine); quarter = False on top of that: the FPN stops behind the trunk, the triple (x1, x2, x3_out)."""
         x1, x2, x3_out = self._backbone_trunk(P, x, dt)
         if not lateral:
             assert not fine_tail
+            if not quarter:
+                return x3_out, (x1, x2, x3_out)
             return x3_out, (x1, self._fpn_fine(P, x1, x2, x3_out, lateral=False))
         x1_out = self._fpn_fine(P, x1, x2, x3_out)
         return x3_out, (self._fpn_fine_tail(P, x1_out) if fine_tail else x1_out)
@@ -741,6 +747,28 @@ class LoFTR(nn.Module):
             ok = self._lat_ok[key] = ops.conv_ups_tiles_supported((B, h2, w2, pk.cin_pad), pk, (B, h2 // 2, w2 // 2, pk.n_store), dense_too=True)
         return ok
 
+    def _quarter_sparse_ok(self, P, xs):
+        """may this forward (one that `_lateral_sparse_ok` accepts) also compute the 1/4-level part of the head -- layer2_outconv + upsample-add
+        of x3_out, then the two 3 x 3 layers of layer2_outconv2 -- on patch lists behind coarse matching?  Each of the three launches must be one
+        its list entry takes AND one whose dense form runs on the same 256 x 256 tile in the same K order: extract() and every fall-back run
+        the dense launches, and forward() must stay bit-identical to extract() + match_features().  x2 is [B,h4,w4,.], x3_out [B,h8,w8,.]."""
+        if not (self.quarter_sparse and self._lateral_sparse_ok(P, xs)):
+            return False
+        B, H, W = xs[0].shape[:3]
+        key = (B, H, W, P["l2o"].dtype, ops.FORCE_BIG_TILE, ops.UPS_FUSED, ops.HALO, ops.HALO_MIN_TILES)   # all the predicates look at
+        ok = self._q_ok.get(key)
+        if ok is None:
+            h2, w2 = _half(H), _half(W)
+            h4, w4 = _half(h2), _half(w2)
+            pk, pa, pb = P["l2o"], P["l2o2a"], P["l2o2b"]
+            ok = self._q_ok[key] = bool(
+                h2 == 2 * h4 and w2 == 2 * w4 and h4 % 2 == 0 and w4 % 2 == 0 and ops.fine_tile_lists4_fits(B // 2, h2, w2)
+                and pa.cin_pad == pk.n_store and pb.cin_pad == pa.n_store
+                and ops.conv_ups_tiles_supported((B, h4, w4, pk.cin_pad), pk, (B, h4 // 2, w4 // 2, pk.n_store), dense_too=True)
+                and ops.conv_tiles_supported((B, h4, w4, pa.cin_pad), pa, dense_too=True)
+                and ops.conv_tiles_supported((B, h4, w4, pb.cin_pad), pb, dense_too=True))
+        return ok
+
     def _fine_tail_sparse(self, P, x1_out, cr, bs):
         """`_fpn_fine_tail` on the 8 x 32 patches that the fine level can read, behind coarse matching.  The fine map has ONE consumer: the
         gather of a 5 x 5 window per match and side at rows 4 cy - 2 .. 4 cy + 2 (fine_fused.hip / gim_fine_gather; zeros outside the image).
@@ -748,7 +776,24 @@ class LoFTR(nn.Module):
         of [4 cy - 3, 4 cy + 3] x [4 cx - 3, 4 cx + 3] for some match (gim_fine_tile_list, from the device-side match count -- no host sync,
         same captured graph).  Every input of a listed first-layer pixel lies in x1_out, which is dense.  Pixels of other patches are never
         written and never read: the buffers are NOT cleared (a replayed graph leaves the previous forward's values there).
-        x1_out = (x1, x2_out) (`_lateral_sparse_ok`): the lateral conv + upsample-add that makes x1_out runs here too, on a patch list."""
+        x1_out = (x1, x2_out) (`_lateral_sparse_ok`): the lateral conv + upsample-add that makes x1_out runs here too, on a patch list.
+        x1_out = (x1, x2, x3_out) (`_quarter_sparse_ok`): so do the three 1/4-level launches that make x2_out, on lists of their own."""
+        if isinstance(x1_out, tuple) and len(x1_out) == 3:
+            x1, x2, x3_out = x1_out
+            _, H, W, _ = x1.shape
+            # x2_out has ONE consumer, the list-walking lateral below, which reads it where Epilogue::ups_accumulate stages upsample sources
+            # for the +-4 patches: S, weight-0 sources included (0 x NaN = NaN, and an unlisted pixel may hold anything).  x2_out is valid on S
+            # if layer2_outconv2's first layer is valid on S dilated by 1, and that if the 1/4-level lateral is valid on S dilated by 2: lists
+            # C, B, A of gim_fine_tile_lists4 (C <= B <= A), from the same one-workgroup launch.  The ring a listed patch reads outside its
+            # list reaches only outputs outside S and its dilations, which nothing consumed reads (DESIGN.md 7d).
+            tiles, n_tiles, tiles4, n_tiles4, tq, nq = ops.fine_tile_lists4(cr.b_ids, cr.i_ids, cr.j_ids, cr.count, bs, cr.args.w0c, cr.args.w1c, 4, H, W)
+            x2_out = ops.conv2d_ups_tiles(x2, P["l2o"], x3_out, tq[0], nq[0:1])
+            x2_out = ops.conv2d_tiles(x2_out, P["l2o2a"], tq[1], nq[1:2], ACT_LEAKY)
+            x2_out = ops.conv2d_tiles(x2_out, P["l2o2b"], tq[2], nq[2:3])
+            x1_out = ops.conv2d_ups_tiles(x1, P["l1o"], x2_out, tiles4, n_tiles4)
+            if self.lateral_one_list:
+                tiles, n_tiles = tiles4, n_tiles4
+            return self._fpn_fine_tail(P, x1_out, tiles, n_tiles)
         if isinstance(x1_out, tuple):
             x1, x2_out = x1_out
             _, H, W, _ = x1.shape
@@ -1106,7 +1151,9 @@ class LoFTR(nn.Module):
             if self._fine_sparse_ok(P, xs):
                 # the fine head stops in front of its last two layers; they run behind coarse matching, under the matched windows only
                 # (... and, where the launch allows, in front of the 1/2-level lateral conv: x1_out is then the pair (x1, x2_out))
-                c_all, x1_out = self._extract_stage(P, xs[0], fine_tail=False, lateral=not self._lateral_sparse_ok(P, xs))
+                # (... and, where those launches allow too, behind the trunk: the triple (x1, x2, x3_out))
+                c_all, x1_out = self._extract_stage(P, xs[0], fine_tail=False, lateral=not self._lateral_sparse_ok(P, xs),
+                                                    quarter=not self._quarter_sparse_ok(P, xs))
                 st = self._match_stage(P, c_all[:bs], c_all[bs:], None, None, c_all, bs, xs[0].shape[1], scale0, scale1, mask0, mask1, count)
                 f_all = self._fine_tail_sparse(P, x1_out, st["cr"], bs)
                 st["f0"], st["f1"] = f_all[:bs], f_all[bs:]
@@ -1126,12 +1173,12 @@ class LoFTR(nn.Module):
         split = ops.FP32_SPLIT if self._split16 is None else self._split16
         return word if (self.precision == "fp16" or (self.precision == "fp32" and split)) else None
 
-    def _extract_stage(self, P, x, fine_tail=True, lateral=True):
+    def _extract_stage(self, P, x, fine_tail=True, lateral=True, quarter=True):
         """the per-image half: NHWC images [B,H,W,cstore(3)] -> (coarse map [B,H/8,W/8,256], fine map [B,H/2,W/2,128]) in the compute dtype.
         No image's maps depend on another image of the batch (eval-mode BatchNorm is folded into the weights).
         fine_tail = False (forward's sparse fine tail): the fine head's last two layers are left to the caller, see _backbone;
-        lateral = False: the 1/2-level lateral conv too."""
-        return self._backbone(P, x, self._dt(), fine_tail, lateral)
+        lateral = False: the 1/2-level lateral conv too; quarter = False: and the 1/4-level part of the head."""
+        return self._backbone(P, x, self._dt(), fine_tail, lateral, quarter)
 
     def _match_stage(self, P, c0, c1, f0, f1, c_all, bs, H0, scale0, scale1, mask0, mask1, count):
         """the per-pair half: coarse maps c0 / c1 [bs,h,w,256] and fine maps f0 / f1 of the bs pairs -> position encoding, coarse
@@ -1176,7 +1223,7 @@ class LoFTR(nn.Module):
 
     def _graph_key(self, color0, color1, scale0, mask0):
         return (tuple(color0.shape), tuple(color1.shape), scale0 is not None, mask0 is not None, self.precision, bool(self.fp32_split),
-                bool(self.fine_sparse), bool(self.lateral_sparse), bool(self.lateral_one_list), self.coarse_sim, self._img_dt(), self._split(), self._stem_k(), str(color0.device))
+                bool(self.fine_sparse), bool(self.lateral_sparse), bool(self.quarter_sparse), bool(self.lateral_one_list), self.coarse_sim, self._img_dt(), self._split(), self._stem_k(), str(color0.device))
 
     def _stage_graphed(self, key, fill, warm, stage, bs, dev, scale0, scale1, mask0, mask1):
         """HIP-graph replay of a shape-static stage (one graph per `key`: input shapes / precision): forward's `_coarse_stage` (~140 kernel

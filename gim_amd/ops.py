@@ -394,6 +394,66 @@ def conv2d_ups_tiles(x, pk, ups, tiles, n_tiles, y=None):
     return y
 
 
+def _conv_tiles_args(x, pk, y, act):
+    """gim_conv_args of a plain 3 x 3 / stride 1 / pad 1 convolution as gim_conv2d_tiles (and the dense gim_conv2d_bn_act launch of
+    `conv2d`) takes it.  x / y: tensors, or x's shape alone (the predicates need no pointer)."""
+    B, H, W, cs = tuple(getattr(x, "shape", x))
+    a = _lib.ConvArgs()
+    if torch.is_tensor(x):
+        a.x, a.y = x.data_ptr(), y.data_ptr()
+    a.w, a.ktab = pk.w.data_ptr(), pk.ktab.data_ptr()
+    a.bias = pk.bias.data_ptr() if pk.bias is not None else None
+    a.res = None
+    a.x_bytes = ((B * H * W - 1) * cs + pk.cin_pad) * elem_size(pk.dtype)
+    a.B, a.H, a.W, a.Ho, a.Wo = B, H, W, H, W
+    a.stride, a.pad = pk.stride, pk.pad
+    a.ldx, a.ldy, a.ldres = cs, pk.n_store, 0
+    a.N, a.npad, a.kpad = pk.n_store, pk.npad, pk.kpad
+    a.act, a.res_mod, a.act_cols = act, 0, 0
+    a.dtype = a.out_dtype = pk.dtype
+    a.res_dtype = GIM_F32
+    a.use_lds_dma = 3 if FORCE_BIG_TILE else 1
+    return a
+
+
+def conv_tiles_supported(x, pk, dense_too=False):
+    """does `conv2d_tiles` take this launch?  x [B,H,W,cin_pad]: a tensor or its shape (gim_conv2d_tiles_supported: a 16-bit 3 x 3 /
+    stride 1 / pad 1 conv without residual onto a map of whole 8 x 32 patches, 256-channel tile columns).  dense_too: ... and does `conv2d`
+    run the dense launch of the same shape on the same 256 x 256 tile (gim_conv2d_big_tile; not the halo kernel, whose K order differs)?
+    Only then are the two bit-identical."""
+    xs = tuple(getattr(x, "shape", x))
+    if not (pk.kh == 3 and pk.kw == 3 and pk.stride == 1 and pk.pad == 1 and getattr(pk, "dil", 1) == 1 and xs[3] == pk.cin_pad
+            and pk.dtype in (GIM_BF16, GIM_F16)):
+        return False
+    a = _conv_tiles_args(xs, pk, None, ACT_NONE)
+    if not lib.gim_conv2d_tiles_supported(ctypes.byref(a)):
+        return False
+    if dense_too and ((HALO and pk.halo is not None and _halo_pays(pk, xs[0], xs[1], xs[2])) or not lib.gim_conv2d_big_tile(ctypes.byref(a))):
+        return False
+    return True
+
+
+def conv2d_tiles(x, pk, tiles, n_tiles, act=ACT_NONE, out=None):
+    """`conv2d(x, pk, act)` for a 3 x 3 / stride 1 / pad 1 layer on the 8 x 32 patches tiles[:n_tiles[0]] of out [B,H,W,n_store] only
+    (int32 device tensors, `fine_tile_lists4`; the count stays on the device): listed patches get the bits the dense launch writes on the
+    256 x 256 tile, every other pixel of `out` keeps what it held (gim_conv2d_tiles).  A launch the entry does not take
+    (`conv_tiles_supported`) runs dense."""
+    _req_cuda(x, tiles, n_tiles, out)
+    if not (x.is_contiguous() and x.dtype in HALF and conv_tiles_supported(x, pk)):
+        return conv2d(x, pk, act)
+    B, H, W, _ = x.shape
+    if out is None:
+        out = torch.empty(B, H, W, pk.n_store, dtype=x.dtype, device=x.device)
+    assert out.shape == (B, H, W, pk.n_store) and out.is_contiguous() and out.dtype == x.dtype
+    assert tiles.dtype == n_tiles.dtype == torch.int32 and tiles.is_contiguous() and n_tiles.numel() >= 1
+    a = _conv_tiles_args(x, pk, out, act)
+    # sparse: the live measurement alone reads the count back -- computed patches x per-patch flops
+    with _Timed(lambda: f"{pk.cin}->{pk.cout} k3s1 M={B * H * W} sparse",
+                lambda: 2.0 * int(n_tiles[0].item()) * 256 * pk.cout * pk.cin * 9, conv=True):
+        check(lib.gim_conv2d_tiles(ctypes.byref(a), _p(tiles), _p(n_tiles), tiles.numel(), _stream()), "gim_conv2d_tiles")
+    return out
+
+
 FINE_TILE_MAX_FLAGS = lib.gim_fine_tile_list_max_flags()
 
 
@@ -429,6 +489,34 @@ def fine_tile_lists(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W):
     check(lib.gim_fine_tile_lists(_p(b_ids), _p(i_ids), _p(j_ids), _p(count), cap, bs, w0c, w1c, stride, H, W, _p(tiles[0]), _p(n[0:1]),
                                   _p(tiles[1]), _p(n[1:2]), total, _stream()), "gim_fine_tile_lists")
     return tiles[0], n[0:1], tiles[1], n[1:2]
+
+
+def fine_tile_lists4(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W):
+    """`fine_tile_lists` and, from the same launch, the three patch lists of the 1/4-resolution maps [2 bs, H/2, W/2] in front of the
+    lateral that walks tiles4: every upsample source that launch stages (S), S dilated by 1 and by 2.  Returns (tiles, n_tiles, tiles4,
+    n_tiles4, tilesq [3, total/4] = lists A (dilated by 2), B (by 1), C (S itself), n_tilesq [3])  (gim_fine_tile_lists4; H % 16 == 0,
+    W % 64 == 0)"""
+    _req_cuda(b_ids, i_ids, j_ids, count)
+    assert b_ids.dtype == i_ids.dtype == j_ids.dtype == torch.int64 and count.dtype == torch.int32
+    assert b_ids.is_contiguous() and i_ids.is_contiguous() and j_ids.is_contiguous()
+    assert H % 16 == 0 and W % 64 == 0, (H, W)
+    cap = min(b_ids.numel(), i_ids.numel(), j_ids.numel())
+    total = 2 * bs * (H // 8) * (W // 32)
+    totq = 2 * bs * (H // 16) * (W // 64)
+    tiles = torch.empty(2 * total + 3 * totq, dtype=torch.int32, device=b_ids.device)
+    n = torch.empty(5, dtype=torch.int32, device=b_ids.device)
+    tq = tiles[2 * total:].view(3, totq)
+    check(lib.gim_fine_tile_lists4(_p(b_ids), _p(i_ids), _p(j_ids), _p(count), cap, bs, w0c, w1c, stride, H, W, _p(tiles[:total]), _p(n[0:1]),
+                                   _p(tiles[total:2 * total]), _p(n[1:2]), total, _p(tq), _p(n[2:5]), totq, _stream()), "gim_fine_tile_lists4")
+    return tiles[:total], n[0:1], tiles[total:2 * total], n[1:2], tq, n[2:5]
+
+
+def fine_tile_lists4_fits(bs, H, W):
+    """do the half- and quarter-level patch flags of [2 bs, H, W] fit the one-workgroup list kernel, and is the quarter map whole patches?"""
+    if H % 16 or W % 64:
+        return False
+    total = 2 * bs * (H // 8) * (W // 32)
+    return ((total + 3) & ~3) + total // 4 <= FINE_TILE_MAX_FLAGS
 
 
 def linear(x, pk, y, act=ACT_NONE, lds_dma=True, act_cols=0, health=None, split16=None):

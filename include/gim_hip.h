@@ -162,6 +162,18 @@ int gim_conv3x3_halo_tiles(const gim_conv_args* a, const int* tiles, const int* 
  * stride 1, pad 0) and an output map of whole patches: (2 ups_h) % 8 == 0, (2 ups_w) % 32 == 0. */
 int gim_conv_ups_tiles_supported(const gim_conv_args* a);
 int gim_conv2d_ups_tiles(const gim_conv_args* a, const int* tiles, const int* n_tiles, int tiles_cap, gim_stream_t stream);
+/* The plain 3 x 3 / stride 1 / pad 1 launch of gim_conv2d_bn_act on its 256 x 256 tile over a device-side list of 8 x 32-pixel patches of its
+ * output map [B, H, W] (added within ABI revision 115: no existing structure or prototype changed with it).  The list is that of
+ * gim_conv3x3_halo_tiles: int32 patch indices (image * (H / 8) + ty) * (W / 32) + tx, ascending, *n_tiles read ON THE DEVICE and clipped to
+ * tiles_cap, entries outside the map clamped into it.  Same K loop, weight packing and K order as the dense launch on that tile: listed
+ * patches get exactly the bits it writes; pixels of every other patch keep whatever y held.
+ * gim_conv2d_tiles_supported(): 1 if the launch is one this entry takes -- a 16-bit dtype in and out, stride 1, pad 1, Ho = H, Wo = W (k = 3),
+ * no residual, no `ups`, no split16, no act_cols, use_lds_dma 1 or 3, H % 8 == 0, W % 32 == 0, npad % 256 == 0, at most 32 768 patches.
+ * gim_conv2d_big_tile(): 1 if gim_conv2d_bn_act runs the DENSE launch of these 16-bit args on that 256 x 256 tile as well (enough tiles and
+ * K slabs, or use_lds_dma = 3) -- only then are the two bit-identical. */
+int gim_conv2d_tiles_supported(const gim_conv_args* a);
+int gim_conv2d_big_tile(const gim_conv_args* a);
+int gim_conv2d_tiles(const gim_conv_args* a, const int* tiles, const int* n_tiles, int tiles_cap, gim_stream_t stream);
 
 /* y[m,:] += bilinear_upsample_2x(x)[m,:], align_corners=True (resnet.py:321,325: F.interpolate +
  * the `x2_out+x3_out_2x` add).  x: [B,h,w,C] rows (ldx), y: [B,2h,2w,C] rows (ldy), in place. */
@@ -526,6 +538,16 @@ int gim_fine_tile_list(const int64_t* b_ids, const int64_t* i_ids, const int64_t
 int gim_fine_tile_lists(const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, const int* count, int cap, int bs,
                         int w0c, int w1c, int stride, int H, int W, int* tiles, int* n_tiles, int* tiles4, int* n_tiles4, int tiles_cap,
                         gim_stream_t stream);
+/* gim_fine_tile_lists and, from the same launch, three patch lists of the 1/4-resolution maps [2 bs, H / 2, W / 2] (added within ABI
+ * revision 115; H % 16 == 0, W % 64 == 0).  S = every pixel of the 1/4-resolution map that the lateral launch gim_conv2d_ups_tiles stages as
+ * an upsample source for a patch of tiles4: per 32-pixel pass (row Y, first column X0) rows y0 = (int)(sy Y), y0 + (y0 < h - 1) and columns
+ * xa .. min(xa + 23, w - 1), xa = (int)(sx X0), fp32, sy = (float)(h - 1) / (float)(H - 1), sx likewise -- weight-0 sources included.
+ * tilesq = int32 [3][tilesq_cap]: the ascending lists of 8 x 32 patches ((side * bs + b) * (h / 8) + ty) * (w / 32) + tx that hold a pixel of
+ * S dilated by 2 (list A), by 1 (list B) and of S itself (list C), dilations clipped to the map; n_tilesq = int32 [3] their counts.  The
+ * half- and quarter-level patches together must not exceed gim_fine_tile_list_max_flags(). */
+int gim_fine_tile_lists4(const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, const int* count, int cap, int bs,
+                         int w0c, int w1c, int stride, int H, int W, int* tiles, int* n_tiles, int* tiles4, int* n_tiles4, int tiles_cap,
+                         int* tilesq, int* n_tilesq, int tilesq_cap, gim_stream_t stream);
 
 /* ======================================================================================================
  * gim_dkm path (kernels D1-D9).  Convolutions / 1x1 projections / the cosine-kernel and
