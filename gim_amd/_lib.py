@@ -184,6 +184,11 @@ PROTOTYPES = {
     "gim_conv2d_tiles_supported": (c_int, [ctypes.POINTER(ConvArgs)]),
     "gim_conv2d_big_tile": (c_int, [ctypes.POINTER(ConvArgs)]),
     "gim_conv2d_tiles": (c_int, [ctypes.POINTER(ConvArgs), c_void_p, c_void_p, c_int, c_void_p]),
+    # descriptor bank of the root_sift baseline: a pair list per launch sequence (added within ABI revision 115)
+    "gim_nn_bank_put": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p] * 2 + [c_int] * 2 + [c_void_p]),
+    "gim_nn_match_pairs_plan": (c_int, [c_void_p] * 3 + [c_int] * 2 + [c_void_p] * 3 + [c_int] + [c_void_p] * 2),
+    "gim_nn_match_pairs_ws_bytes": (c_int64, [c_int] * 2),
+    "gim_nn_match_pairs": (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_float] + [c_void_p] * 3 + [c_int] + [c_void_p] * 4),
     "gim_fine_tile_lists4": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p] * 4 + [c_int, c_void_p, c_void_p, c_int, c_void_p]),
 }
 

@@ -12,13 +12,24 @@ Restates (reference file:line):
 
 The matching has no CPU fallback.  The detector is OpenCV's and is imported when `inference` first needs it: where cv2 does not
 import, `inference` raises GimHipError before anything touches the device and `match_descriptors` still works on descriptors from
-elsewhere.  One pair per launch; batching several pairs per launch is the obvious follow-up if the video labeller wants it.
+elsewhere.
+
+Pair lists (an exhaustive SfM pairing, the video labeller's neighbouring frames): the descriptors of every image are normalised ONCE into
+a `DescriptorBank` and stay on the device; the pairs are matched by slot index, many per launch sequence (gim_nn_match_pairs), with one
+host read per batch.  Every pair gets the bits the single-pair call gives it.
+
+    bank = DescriptorBank(capacity_images=32, max_rows=4800)
+    bank.put(name, kpts, desc)                                        # once per image
+    m.match_pairs(bank, bank.slots(keys0), bank.slots(keys1))         # the batched dict; m_bids = index of the pair
+    match_descriptor_pair_list(bank, pairs, batch_pairs=32, writer=h5)  # hloc's matches0 int16 / matching_scores0 fp16 per pair
 """
 import numpy as np
 import torch
 
 from . import ops
 from ._lib import GimHipError
+from .hloc_formats import write_sparse_matches
+from .loftr.bank import SlotTable
 
 NO_DETECTOR = ("root_sift needs OpenCV's SIFT detector (cv2.SIFT_create) to find keypoints, and cv2 does not import here: {}. "
                "Install opencv-python, or call RootSiftMatcher.match_descriptors with descriptors of your own.")
@@ -31,6 +42,98 @@ def _cv2():
     except Exception as e:  # noqa: BLE001
         raise GimHipError(NO_DETECTOR.format(f"{type(e).__name__}: {e}")) from e
     return cv2
+
+
+class DescriptorBank:
+    """`capacity_images` slots of at most `max_rows` descriptors of width D on the device (csrc/nn_match.hip for the layout):
+        desc [S, R, D] fp32 (RootSIFT-normalised at insertion when `rootsift`), kpts [S, R, 2] fp32, n [S] int32
+    plus caller-supplied hashable image key -> slot with LRU eviction (gim_amd/loftr/bank.py `SlotTable`, as the keypoint bank of
+    gim_lightglue).  `counts` is the host mirror of n: sizing a batch never reads the device."""
+
+    def __init__(self, capacity_images, max_rows, D=128, rootsift=True, device="cuda"):
+        if capacity_images < 1 or max_rows < 1:
+            raise ValueError("a descriptor bank needs at least one slot and one row per image")
+        if D % 16 or not 16 <= D <= 256:
+            raise GimHipError(f"descriptor bank: D={D} is not a multiple of 16 in [16, 256]")
+        self.capacity, self.max_rows, self.D, self.rootsift = int(capacity_images), int(max_rows), int(D), bool(rootsift)
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        S, R = self.capacity, self.max_rows
+        self.table = SlotTable(S)
+        self.desc = torch.empty(S, R, self.D, dtype=torch.float32, device=self.device)
+        self.kpts = torch.zeros(S, R, 2, dtype=torch.float32, device=self.device)
+        self.n = torch.zeros(S, dtype=torch.int32, device=self.device)
+        self.counts = np.zeros(S, dtype=np.int32)
+
+    # ---- bookkeeping (plain Python: no device work) -----------------------------------------------------------------------------
+    @property
+    def stats(self):
+        return self.table.stats
+
+    def __len__(self):
+        return len(self.table)
+
+    def __contains__(self, key):
+        return key in self.table
+
+    @property
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.desc, self.kpts, self.n))
+
+    def slots(self, keys):
+        """slots of resident images, one per key (duplicates allowed); marks them most recently used.  An image that was never
+        inserted, or has been evicted since, raises: a pair must not read whatever lives in its old slot now."""
+        keys = list(keys)
+        gone = [k for k in dict.fromkeys(keys) if k not in self.table]
+        if gone:
+            raise GimHipError(f"descriptor bank: image {gone[0]!r} is not resident (never inserted, or evicted from the {self.capacity} "
+                              "slots)" + (f"; {len(gone) - 1} more" if len(gone) > 1 else ""))
+        out = []
+        for i in range(0, len(keys), self.capacity):   # SlotTable.assign takes at most `capacity` distinct keys at a time
+            out += self.table.assign(keys[i:i + self.capacity])[0]
+        self.table.unpin()
+        return out
+
+    def check_slots(self, idx):
+        """a host sequence of slot indices, range-checked"""
+        idx = [int(i) for i in idx]
+        bad = [i for i in idx if not 0 <= i < self.capacity]
+        if bad:
+            raise GimHipError(f"descriptor bank: slot {bad[0]} is outside [0, {self.capacity})")
+        return idx
+
+    # ---- device work --------------------------------------------------------------------------------------------------------------
+    def put(self, key, kpts, desc):
+        """one image: kpts [n, 2] pixels, desc [n, D] raw descriptors (device tensors; n == 0: an image without keypoints).  A
+        resident key keeps its slot and is overwritten; otherwise the least recently used image makes room.  Returns the slot."""
+        if desc.dim() != 2 or desc.shape[1] != self.D:
+            raise GimHipError(f"descriptor bank of width {self.D}: got descriptors {tuple(desc.shape)} for image {key!r}")
+        n = desc.shape[0]
+        if n > self.max_rows:
+            raise GimHipError(f"descriptor bank: image {key!r} has {n} descriptors, a slot holds max_rows={self.max_rows}")
+        if tuple(kpts.shape) != (n, 2):
+            raise GimHipError(f"descriptor bank: keypoints {tuple(kpts.shape)} for {n} descriptors of image {key!r}")
+        slot = self.table.assign([key])[0][0]
+        self.table.unpin()
+        ops.nn_bank_put(desc.to(self.device).float(), slot, self.desc, self.n, rootsift=self.rootsift)
+        if n:
+            self.kpts[slot, :n] = kpts.to(self.device).float()
+        self.counts[slot] = n
+        return slot
+
+
+def _pair_scale(scale, P, bids, dev):
+    """scale [2] | [1, 2] (every pair) or [P, 2] / a sequence of P of them (per pair) -> the factor of every matched row"""
+    if not torch.is_tensor(scale):
+        scale = torch.stack([torch.as_tensor(x, dtype=torch.float32).reshape(2) for x in scale]) if len(scale) == P and P and \
+            not isinstance(scale[0], (int, float)) else torch.as_tensor(scale, dtype=torch.float32)
+    scale = scale.to(device=dev, dtype=torch.float32).reshape(-1, 2)
+    if scale.shape[0] == 1:
+        return scale
+    if scale.shape[0] != P:
+        raise GimHipError(f"match_pairs: {scale.shape[0]} scales for {P} pairs")
+    return scale[bids]
 
 
 class RootSiftMatcher:
@@ -68,6 +171,30 @@ class RootSiftMatcher:
         return {"mkpts0_f": mk0, "mkpts1_f": mk1, "m_bids": torch.zeros(rows.shape[0], dtype=torch.int64, device=desc0.device),
                 "mconf": score0[rows]}
 
+    @torch.no_grad()
+    def match_pairs(self, bank, slots0, slots1, scale0=None, scale1=None):
+        """P pairs (slots0[p], slots1[p]) of a `DescriptorBank` in one launch sequence -> the matchers' batched dict {mkpts0_f [M,2],
+        mkpts1_f [M,2], m_bids [M] int64 = index of the pair, mconf [M]}, rows ordered by pair, then by ascending desc0 row; restricted
+        to m_bids == p it is what `match_descriptors` returns for that pair.  scale: [2] | [1,2] for all pairs or [P,2] per pair.
+        The one host read is the P match counts."""
+        s0, s1 = bank.check_slots(slots0), bank.check_slots(slots1)
+        dev = bank.device
+        r = ops.nn_match_pairs(bank.desc, bank.n, bank.counts, s0, s1, ratio=self.ratio)
+        P = len(s0)
+        counts = r.count.cpu()                                              # the read-back of the batch
+        M = int(counts.sum())
+        rows = torch.nonzero_static(r.match0 >= 0, size=M)[:, 0]            # ragged row of every match, ascending: pair, then row
+        bids = torch.repeat_interleave(torch.arange(P, device=dev), counts.to(dev, torch.int64), output_size=M)
+        tab = torch.from_numpy(np.stack([np.asarray(s0, dtype=np.int64), np.asarray(s1, dtype=np.int64),
+                                         r.row_off[:P].astype(np.int64)]).reshape(3, P)).to(dev)
+        mk0 = bank.kpts[tab[0][bids], rows - tab[2][bids]]
+        mk1 = bank.kpts[tab[1][bids], r.match0[rows].long()]
+        if scale0 is not None:
+            mk0 = mk0 * _pair_scale(scale0, P, bids, dev)
+        if scale1 is not None:
+            mk1 = mk1 * _pair_scale(scale1, P, bids, dev)
+        return {"mkpts0_f": mk0, "mkpts1_f": mk1, "m_bids": bids, "mconf": r.score0[rows]}
+
     def detect(self, color):
         """lightning.py:197-212 for one image [1,3,H,W] in [0,1] -> (kpts [n,2] float64, desc [n,128] float32) numpy, on the host"""
         cv2 = _cv2()
@@ -91,3 +218,28 @@ class RootSiftMatcher:
         out = self.match_descriptors(k0, d0, k1, d1, data.get("scale0"), data.get("scale1"))
         data.update({"hw0_i": data["image0"].shape[2:], "hw1_i": data["image1"].shape[2:], **out})
         return data
+
+
+@torch.no_grad()
+def match_descriptor_pair_list(bank, pairs, batch_pairs=32, ratio=0.8, writer=None, names=None):
+    """pairs: a sequence of (key0, key1) of images resident in `bank`, matched as given, in the order given, `batch_pairs` per launch
+    sequence (gim_amd.lightglue.match_pair_list for the sparse learned matcher).  Returns [(key0, key1, matches0 int16 [n0],
+    matching_scores0 fp16 [n0])] as numpy arrays -- hloc's datasets, which leave the device in that format, one copy per batch; with
+    `writer` (h5py's group protocol) every pair is also written through hloc_formats.write_sparse_matches (group name from names[key] if
+    `names` is given, else str(key))."""
+    if batch_pairs < 1:
+        raise ValueError("batch_pairs must be >= 1")
+    pairs = list(pairs)
+    name = (lambda k: names[k]) if names is not None else str
+    out = []
+    for i in range(0, len(pairs), batch_pairs):
+        batch = pairs[i:i + batch_pairs]
+        s0, s1 = bank.slots([p[0] for p in batch]), bank.slots([p[1] for p in batch])
+        r = ops.nn_match_pairs(bank.desc, bank.n, bank.counts, s0, s1, ratio=ratio, hloc=True)
+        m, s = r.matches0_i16.cpu().numpy(), r.matching_scores0_f16.cpu().numpy()
+        for b, (k0, k1) in enumerate(batch):
+            lo, hi = int(r.row_off[b]), int(r.row_off[b + 1])
+            if writer is not None:
+                write_sparse_matches(writer, name(k0), name(k1), m[lo:hi], s[lo:hi])
+            out.append((k0, k1, m[lo:hi], s[lo:hi]))
+    return out

@@ -1,9 +1,11 @@
 """Thin torch-tensor wrappers over the libgimhip C ABI (device pointers + current stream; torch is only
 the allocator / stream owner).  Every function launches HIP kernels from `gim_amd/csrc`; none of them
 has a torch or CPU fallback."""
+import collections
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1388,6 +1390,90 @@ def nn_match(desc0, desc1, rootsift=False, ratio=0.8, count=None):
         check(lib.gim_nn_match(_p(desc0), _p(desc1), n0, n1, D, int(bool(rootsift)), float(ratio), _p(match0), _p(score0), _p(count),
                                _p(ws), _stream()), "gim_nn_match")
     return match0, score0
+
+
+def nn_bank_put(desc, slot, bank_desc, bank_n, rootsift=True):
+    """one image's descriptors [n, D] fp32 (n == 0 allowed) -> slot `slot` of bank_desc [S, R, D] fp32, bank_n [S] int32 (its count), in
+    one launch of gim_nn_bank_put.  rootsift: the stored rows are sqrt(d / sum d), bit-equal to what `nn_match` normalises per call."""
+    _req_cuda(desc, bank_desc, bank_n)
+    assert desc.dim() == 2 and bank_desc.dim() == 3 and desc.dtype == bank_desc.dtype == torch.float32 and bank_n.dtype == torch.int32
+    assert bank_desc.is_contiguous() and bank_n.is_contiguous() and bank_n.numel() == bank_desc.shape[0]
+    S, R, D = bank_desc.shape
+    if desc.shape[1] != D:
+        raise _lib.GimHipError(f"nn_bank_put: descriptors of width {desc.shape[1]} into a bank of width {D}")
+    desc = desc.contiguous()
+    check(lib.gim_nn_bank_put(_p(desc) if desc.shape[0] else None, int(desc.shape[0]), D, int(bool(rootsift)), int(slot), _p(bank_desc),
+                              _p(bank_n), S, R, _stream()), "gim_nn_bank_put")
+
+
+NnPairsPlan = collections.namedtuple("NnPairsPlan", "idx0 idx1 row_off col_off work nsplit")
+NnPairsResult = collections.namedtuple("NnPairsResult", "match0 score0 count row_off matches0_i16 matching_scores0_f16")
+
+
+def nn_pairs_plan(idx0, idx1, counts):
+    """The host half of `nn_match_pairs` (gim_nn_match_pairs_plan; no device): slot pairs (idx0[p], idx1[p]) and the per-slot descriptor
+    counts [S] -> NnPairsPlan of int32 numpy arrays: row_off / col_off [P + 1] (prefix sums of the counts of the pairs' sides), work
+    [W, 4] = (pair, row block, first column tile, one past the last) and the batch's column split.  A slot outside [0, S) raises."""
+    i0 = np.ascontiguousarray(np.asarray(idx0, dtype=np.int32).reshape(-1))
+    i1 = np.ascontiguousarray(np.asarray(idx1, dtype=np.int32).reshape(-1))
+    n = np.ascontiguousarray(np.asarray(counts, dtype=np.int32).reshape(-1))
+    if i0.shape != i1.shape:
+        raise _lib.GimHipError(f"nn_match_pairs: {i0.shape[0]} first slots, {i1.shape[0]} second slots")
+    P = i0.shape[0]
+    row_off, col_off = np.zeros(P + 1, dtype=np.int32), np.zeros(P + 1, dtype=np.int32)
+    nw, ns = ctypes.c_int32(0), ctypes.c_int32(0)
+
+    def ptr(a):
+        return a.ctypes.data_as(ctypes.c_void_p)
+
+    def plan(work):
+        check(lib.gim_nn_match_pairs_plan(ptr(i0), ptr(i1), ptr(n), P, int(n.shape[0]), ptr(row_off), ptr(col_off),
+                                          ptr(work) if work is not None else None, 0 if work is None else work.shape[0],
+                                          ctypes.addressof(nw), ctypes.addressof(ns)), "gim_nn_match_pairs_plan")
+    plan(None)                                      # counts the work items
+    work = np.zeros((nw.value, 4), dtype=np.int32)
+    if nw.value:
+        plan(work)
+    return NnPairsPlan(i0, i1, row_off, col_off, work, ns.value)
+
+
+def _upload_i32(a, dev):
+    return torch.from_numpy(a).to(dev)
+
+
+def nn_match_pairs(bank_desc, bank_n, counts, idx0, idx1, ratio=0.8, hloc=False):
+    """P pairs of bank slots in one launch sequence of gim_nn_match_pairs (reset, sweep over the work table, final) with no host
+    synchronisation.  bank_desc [S, R, D] fp32 / bank_n [S] int32 as `nn_bank_put` filled them, counts: the HOST mirror of bank_n,
+    idx0 / idx1: host sequences of slots.  -> NnPairsResult: ragged match0 int32 / score0 fp32 [row_off[P]] (pair p owns
+    row_off[p]:row_off[p + 1]; bit-equal to `nn_match` on that pair), count int32 [P] on the device, row_off as a host array, and with
+    `hloc` the same rows as hloc stores them: matches0_i16 int16, matching_scores0_f16 fp16 = (1 + score0) / 2 on matches, else 0."""
+    _req_cuda(bank_desc, bank_n)
+    assert bank_desc.dim() == 3 and bank_desc.dtype == torch.float32 and bank_desc.is_contiguous() and bank_n.dtype == torch.int32
+    S, R, D = bank_desc.shape
+    dev = bank_desc.device
+    if hloc and R > 32767:
+        raise _lib.GimHipError(f"nn_match_pairs: max_rows={R} descriptors do not fit hloc's int16 matches0 (at most 32767)")
+    pl = nn_pairs_plan(idx0, idx1, counts)
+    P, W = pl.idx0.shape[0], pl.work.shape[0]
+    rows0, rows1 = int(pl.row_off[P]), int(pl.col_off[P])
+    match0 = torch.empty(rows0, dtype=torch.int32, device=dev)
+    score0 = torch.empty(rows0, dtype=torch.float32, device=dev)
+    count = torch.empty(P, dtype=torch.int32, device=dev)
+    m16 = torch.empty(rows0, dtype=torch.int16, device=dev) if hloc else None
+    s16 = torch.empty(rows0, dtype=torch.float16, device=dev) if hloc else None
+    if P == 0:
+        return NnPairsResult(match0, score0, count, pl.row_off, m16, s16)
+    # one upload: the index arrays, the offsets and the work table
+    tab = _upload_i32(np.concatenate([pl.idx0, pl.idx1, pl.row_off, pl.col_off, pl.work.reshape(-1)]), dev)
+    o = [0, P, 2 * P, 3 * P + 1, 4 * P + 2]
+    i0, i1, ro, co, wk = (tab[o[k]:] for k in range(5))
+    ws = torch.empty(lib.gim_nn_match_pairs_ws_bytes(rows0, rows1), dtype=torch.uint8, device=dev) if rows0 else None
+    flops = 2.0 * D * float(np.sum((pl.row_off[1:] - pl.row_off[:-1]).astype(np.float64) * (pl.col_off[1:] - pl.col_off[:-1])))
+    with _Timed("nn_match_pairs", flops):
+        check(lib.gim_nn_match_pairs(_p(bank_desc), _p(bank_n), _p(i0), _p(i1), _p(ro), _p(co), _p(wk) if W else None, P, W, pl.nsplit,
+                                     rows0, rows1, S, R, D, float(ratio), _p(match0), _p(score0), _p(count), int(bool(hloc)), _p(m16),
+                                     _p(s16), _p(ws), _stream()), "gim_nn_match_pairs")
+    return NnPairsResult(match0, score0, count, pl.row_off, m16, s16)
 
 
 # ---- RANSAC hypothesis scoring (gim_amd/pose.py) -----------------------------------------------------------------

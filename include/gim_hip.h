@@ -727,6 +727,45 @@ int64_t gim_nn_match_ws_bytes(int n0, int n1, int D, int rootsift);
 int gim_nn_match(const float* desc0, const float* desc1, int n0, int n1, int D, int rootsift, float ratio, int32_t* match0,
                  float* score0, int32_t* count, void* ws, gim_stream_t stream);
 
+/* ---- descriptor bank: the same matcher over a pair list (added within ABI revision 115: no existing structure or prototype changed
+ * with it).  Bank arrays, `n_slots` images of at most `max_rows` descriptors, slot-major: bank_desc fp32 [n_slots][max_rows][D]
+ * (16-byte aligned; slot s owns rows s * max_rows .. s * max_rows + bank_n[s] - 1), bank_n int32 [n_slots] on the DEVICE.  The
+ * descriptors are stored as the sweep reads them (normalised once), so an image is never normalised again per pair. ---- */
+
+/* Inserts one image: desc [n][D] fp32 DEVICE rows (16-byte aligned; NULL allowed when n == 0: an image without keypoints) into slot
+ * `slot`, and bank_n[slot] = n, in ONE launch.  rootsift = 1 stores sqrt(d / sum d) per row -- the device function gim_nn_match's
+ * normalisation calls, so the stored rows are bit-equal to the copies that call keeps in its workspace; rootsift = 0 is a plain copy.
+ * slot outside [0, n_slots), n outside [0, max_rows] and a bad D are refused before the launch. */
+int gim_nn_bank_put(const float* desc, int n, int D, int rootsift, int slot, float* bank_desc, int32_t* bank_n, int n_slots,
+                    int max_rows, gim_stream_t stream);
+
+/* HOST-only planning of a batch of P pairs (idx0[p], idx1[p]) of slots; every pointer is HOST memory and no device is touched.
+ * n [n_slots] = the caller's mirror of bank_n.  Writes row_off [P + 1] / col_off [P + 1] = prefix sums of n[idx0[p]] / n[idx1[p]],
+ * *nsplit = the column split of the batch (chosen from the TOTAL number of 128-row blocks: about 512 workgroups, at most 16; a pair
+ * uses min(*nsplit, its column tiles)), *n_work = the number of work items, and, when work != NULL, the work table
+ * work [n_work][4] = (pair, row block, first column tile, one past the last column tile) in pair, row block, split order
+ * (work_cap = its capacity in items; too small is an error, work == NULL only counts).  A pair with n0 == 0 or n1 == 0 has no work
+ * items.  A slot index outside [0, n_slots), a negative count and sums that do not fit int32 are refused. */
+int gim_nn_match_pairs_plan(const int32_t* idx0, const int32_t* idx1, const int32_t* n, int P, int n_slots, int32_t* row_off,
+                            int32_t* col_off, int32_t* work, int work_cap, int32_t* n_work, int32_t* nsplit);
+
+/* gim_nn_match for P pairs of slots in at most three launches whatever P is (reset, sweep over the work table, final), no host
+ * synchronisation.  idx0, idx1 [P], row_off, col_off [P + 1], work [n_work][4]: DEVICE copies of what gim_nn_match_pairs_plan made
+ * (rows0 = row_off[P], rows1 = col_off[P], nsplit as planned); the kernels re-check every entry against n_slots, max_rows, bank_n and
+ * the offsets and skip an item that does not fit, so nothing is read or written out of bounds.  The sweep is gim_nn_match's tile, the
+ * same k-ordered exact-fp32 chain: every similarity, and so match0 / score0 / count, has the bits the single-pair call gives that
+ * pair.  Ragged outputs: match0 int32 [rows0], score0 fp32 [rows0] (pair p owns row_off[p] .. row_off[p + 1] - 1), count int32 [P].
+ * hloc != 0: the final kernel also writes hloc's match-file datasets in the same pass, matches0_i16 int16 [rows0] and
+ * scores_f16 IEEE fp16 [rows0] = (1 + score0) / 2 on matched rows, 0 elsewhere (round to nearest even); max_rows > 32767 does not
+ * fit int16 and is refused.  The same slot may appear on both sides and in many pairs; slots are only read.  Rules for n1 == 0,
+ * n1 == 1 and ratio <= 0 as in gim_nn_match; a pair with n0 == 0 owns no rows.  P == 0 returns without a launch.
+ * ws: gim_nn_match_pairs_ws_bytes(rows0, rows1) bytes, 16-byte aligned -- O(rows0 + rows1), never n0 x n1. */
+int64_t gim_nn_match_pairs_ws_bytes(int rows0, int rows1);
+int gim_nn_match_pairs(const float* bank_desc, const int32_t* bank_n, const int32_t* idx0, const int32_t* idx1, const int32_t* row_off,
+                       const int32_t* col_off, const int32_t* work, int P, int n_work, int nsplit, int rows0, int rows1, int n_slots,
+                       int max_rows, int D, float ratio, int32_t* match0, float* score0, int32_t* count, int hloc,
+                       int16_t* matches0_i16, void* scores_f16, void* ws, gim_stream_t stream);
+
 /* ======================================================================================================
  * RANSAC hypothesis scoring for the pose half of the ZEB loop (added within ABI revision 114).  Sampling, the minimal
  * solvers, the iteration bound and recoverPose stay on the host (gim_amd/pose.py); this is the inlier count that was 90 % of its step.
