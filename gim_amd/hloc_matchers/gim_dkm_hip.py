@@ -77,3 +77,18 @@ class GimDkmHip(BaseModel):
             if m is not None:
                 d["mask" + i] = m
         return self.adapter(d)
+
+    def match_and_assign_from_images(self, images, pairs, features, matches, max_kps=8192, scales=None, max_error=2, cell_size=8,
+                                     write_dense=True):
+        """hloc/match_dense.py `match_and_assign` for the SfM branch with the bookkeeping on the device (gim_amd/dense_sfm.py): matches
+        every pair of `pairs` ([(name0, name1)]) over `images` ({name: [1,3,H,W] device tensor}; `scales`: {name: (sx, sy)} back to the
+        original size), aggregates the dense matches into at most `max_kps` keypoints per image and writes hloc's datasets into the
+        h5py-like files `features` (`keypoints`, `score`) and `matches` (`matches0`, `matching_scores0`; with write_dense the dense
+        `keypoints0`, `keypoints1`, `scores` too).  max_error / cell_size: the conf of match_dense.py:37-38.  Returns the aggregator."""
+        from ..dense_sfm import DenseMatchAggregator, match_dense_pair_list
+        device = next(iter(images.values())).device if images else "cuda"
+        agg = DenseMatchAggregator(max_error=max_error, cell_size=cell_size, device=device)
+        match_dense_pair_list(self, images, pairs, agg, scales)
+        agg.finalize(max_kps)
+        agg.write(features, matches, write_dense=write_dense)
+        return agg

@@ -1584,3 +1584,140 @@ def seg_head_argmax(logits, C, size, prob=False, flag=None):
     with _Timed("seg_head_argmax", 10.0 * B * H * W * C):   # 4 taps (7 flops) + the exponential / compare per class and pixel
         check(lib.gim_seg_head_argmax(_p(logits), _p(cls), _p(pr), _p(flag), B, h, w, C, ld, H, W, _stream()), "gim_seg_head_argmax")
     return (cls, pr) if prob else cls
+
+
+# ---- dense SfM: dense matches of a pair list -> keypoints and keypoint-indexed matches (gim_amd/dense_sfm.py) ------------------
+AggState = collections.namedtuple("AggState", "kpts0 kpts1 scores geom votes cell_n cell_off max_error patch")
+AggBatch = collections.namedtuple("AggBatch", "P row_lo row_hi offsets slot0 slot1 host_offsets host_slot0 host_slot1")
+AggKeypoints = collections.namedtuple("AggKeypoints", "id_grid keypoints score cells kp_off host_kp_off nearest")
+AggMatches = collections.namedtuple("AggMatches", "matches0 scores_f16 row_len koff0")
+
+
+def agg_patch(max_error, cell_size):
+    """patch = max(cell_size, max_error) of match_dense.py:64-65 as the integer the kernels take; GimHipError for a geometry they refuse
+    (patch / int(max_error) not an integer in 1..8, max_error > patch / 2) -- checked by the library, no device involved"""
+    ps = max(cell_size if cell_size is not None else max_error, max_error)
+    if not (ps == int(ps) and 1 <= ps <= 4096):
+        raise _lib.GimHipError(f"dense aggregation: patch = max(cell_size, max_error) = {ps} must be an integer in 1..4096")
+    if lib.gim_agg_bins(float(max_error), int(ps)) == 0:
+        msg = lib.gim_last_error()
+        raise _lib.GimHipError(f"dense aggregation: max_error={max_error} cell_size={cell_size}: {msg.decode() if msg else ''}")
+    return int(ps)
+
+
+def agg_bins(max_error, patch):
+    return int(lib.gim_agg_bins(float(max_error), int(patch)))
+
+
+def agg_grid(width, height, patch):
+    """(Gw, Gh) of an image: cells 0 .. W // patch + 1 per axis"""
+    return int(width) // patch + 2, int(height) // patch + 2
+
+
+def agg_batch(offsets, slot0, slot1, n_slots, pool_rows, device):
+    """host lists of a batch of pairs -- offsets [P + 1] rising pool rows, slot0 / slot1 [P] -- checked here (the kernels get a launch
+    shape from them) and uploaded in one copy -> AggBatch"""
+    o = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+    s0 = np.ascontiguousarray(np.asarray(slot0, dtype=np.int64).reshape(-1))
+    s1 = np.ascontiguousarray(np.asarray(slot1, dtype=np.int64).reshape(-1))
+    P = s0.shape[0]
+    if s1.shape[0] != P or o.shape[0] != P + 1:
+        raise _lib.GimHipError(f"dense aggregation: {P} first slots, {s1.shape[0]} second slots, {o.shape[0]} offsets (P, P, P + 1)")
+    if P and (o[0] < 0 or o[-1] > pool_rows or np.any(o[1:] < o[:-1])):
+        raise _lib.GimHipError(f"dense aggregation: offsets must rise within the pool's {pool_rows} rows, got {o[:8].tolist()}{'...' if P > 7 else ''}")
+    for s in (s0, s1):
+        bad = np.flatnonzero((s < 0) | (s >= n_slots))
+        if bad.size:
+            raise _lib.GimHipError(f"dense aggregation: pair {int(bad[0])} names slot {int(s[bad[0]])} outside [0, {n_slots})")
+    tab = _upload_i32(np.concatenate([o, s0, s1]).astype(np.int32), device)
+    return AggBatch(P, int(o[0]) if P else 0, int(o[-1]) if P else 0, tab[:P + 1], tab[P + 1:2 * P + 1], tab[2 * P + 1:], o, s0, s1)
+
+
+def _agg_state_check(st):
+    _req_cuda(st.kpts0, st.kpts1, st.scores, st.geom, st.votes, st.cell_n)
+    assert st.kpts0.dtype == st.kpts1.dtype == st.scores.dtype == torch.float32 and st.geom.dtype == st.cell_n.dtype == torch.int32
+    assert st.votes.dtype == torch.int64 and all(t.is_contiguous() for t in (st.kpts0, st.kpts1, st.scores, st.geom, st.votes, st.cell_n))
+    rows, S, cells = st.scores.shape[0], st.geom.shape[0], st.cell_n.shape[0]
+    if st.kpts0.shape != (rows, 2) or st.kpts1.shape != (rows, 2) or st.geom.shape != (S, 4):
+        raise _lib.GimHipError(f"dense aggregation: pool {tuple(st.kpts0.shape)} / {tuple(st.kpts1.shape)} / {tuple(st.scores.shape)}, geom {tuple(st.geom.shape)}")
+    if st.votes.numel() != cells * agg_bins(st.max_error, st.patch) or len(st.cell_off) != S + 1 or st.cell_off[-1] != cells:
+        raise _lib.GimHipError(f"dense aggregation: {st.votes.numel()} vote sums for {cells} cells of {agg_bins(st.max_error, st.patch)} bins")
+    return rows, S, cells
+
+
+def agg_vote(st, batch):
+    """gim_agg_vote: the matches of the batch's pairs vote in the cells of both images -> dropped int32 [P] on the device (matches that
+    did not count: outside their image, or a score that is not finite and in [0, 65536))"""
+    rows, S, cells = _agg_state_check(st)
+    dropped = torch.empty(batch.P, dtype=torch.int32, device=st.scores.device)
+    if batch.P:
+        check(lib.gim_agg_vote(_p(st.kpts0), _p(st.kpts1), _p(st.scores), _p(batch.offsets), _p(batch.slot0), _p(batch.slot1), _p(st.geom),
+                               _p(st.votes), _p(st.cell_n), _p(dropped), batch.P, batch.row_lo, batch.row_hi, rows, S, cells,
+                               float(st.max_error), int(st.patch), _stream()), "gim_agg_vote")
+    return dropped
+
+
+def agg_finalize(st, max_kps=None):
+    """gim_agg_finalize + the per-image ordering + gim_agg_keypoints -> AggKeypoints.  Ids: without max_kps the raster order of the
+    voted cells; with max_kps the first max_kps cells in (score descending, raster) order.  One read-back: the voted cells per image."""
+    rows, S, cells = _agg_state_check(st)
+    if max_kps is not None and max_kps < 1:
+        raise _lib.GimHipError(f"dense aggregation: max_kps={max_kps} (None or >= 1)")
+    dev = st.scores.device
+    key = torch.empty(cells, dtype=torch.int64, device=dev)
+    cbin = torch.empty(cells, dtype=torch.int32, device=dev)
+    check(lib.gim_agg_finalize(_p(st.votes), _p(st.cell_n), cells, float(st.max_error), int(st.patch), _p(key), _p(cbin), _stream()),
+          "gim_agg_finalize")
+    off = [int(x) for x in st.cell_off]
+    voted = key > 0
+    counts = torch.stack([voted[off[s]:off[s + 1]].sum() for s in range(S)]).tolist() if S else []
+    keep = [c if not max_kps else min(c, int(max_kps)) for c in counts]
+    kp_off = np.concatenate([[0], np.cumsum(keep)]).astype(np.int64)
+    n_sel = int(kp_off[-1])
+    if not max_kps:
+        sel = torch.nonzero(voted).reshape(-1).to(torch.int32)             # raster order within a slot, slots in order
+    else:
+        parts = []
+        for s in range(S):
+            if keep[s]:
+                order = torch.sort(key[off[s]:off[s + 1]], descending=True, stable=True).indices[:keep[s]]
+                parts.append((order + off[s]).to(torch.int32))
+        sel = torch.cat(parts) if parts else torch.empty(0, dtype=torch.int32, device=dev)
+    sel = sel.contiguous()
+    kp_off_dev = _upload_i32(kp_off.astype(np.int32), dev)
+    sel_slot = torch.repeat_interleave(torch.arange(S, dtype=torch.int32, device=dev), torch.as_tensor(keep, dtype=torch.int64, device=dev),
+                                       output_size=n_sel) if n_sel else torch.empty(0, dtype=torch.int32, device=dev)
+    id_grid = torch.empty(cells, dtype=torch.int32, device=dev)
+    keypoints = torch.empty(n_sel, 2, dtype=torch.float32, device=dev)
+    score = torch.empty(n_sel, dtype=torch.float64, device=dev)
+    kcells = torch.empty(n_sel, 2, dtype=torch.int32, device=dev)
+    check(lib.gim_agg_keypoints(_p(st.votes), _p(cbin), _p(st.geom), _p(sel), _p(sel_slot), _p(kp_off_dev), n_sel, S, cells,
+                                float(st.max_error), int(st.patch), _p(id_grid), _p(keypoints), _p(score), _p(kcells), _stream()),
+          "gim_agg_keypoints")
+    return AggKeypoints(id_grid, keypoints, score, kcells, kp_off_dev, kp_off, bool(max_kps))
+
+
+def agg_assign(st, kp, batch):
+    """gim_agg_assign: keypoint-indexed one-to-one matches of the batch's pairs -> AggMatches: matches0 int32 / scores_f16 fp16 rows
+    padded to the keypoint count of each pair's first image (pair p owns koff0[p]:koff0[p + 1], a host array), row_len int32 [P] on the
+    device = max matched id0 + 1, the length hloc's matches0 has.  No host synchronisation."""
+    rows, S, cells = _agg_state_check(st)
+    _req_cuda(kp.id_grid, kp.keypoints, kp.kp_off)
+    dev = st.scores.device
+    K = np.diff(kp.host_kp_off)
+    koff0 = np.concatenate([[0], np.cumsum(K[batch.host_slot0])]).astype(np.int64)
+    koff1 = np.concatenate([[0], np.cumsum(K[batch.host_slot1])]).astype(np.int64)
+    rows0, rows1, n = int(koff0[-1]), int(koff1[-1]), batch.row_hi - batch.row_lo
+    if max(rows0, rows1) > 0x7fffffff:
+        raise _lib.GimHipError(f"dense aggregation: {rows0} / {rows1} keypoint rows in one batch do not fit int32: use fewer pairs per batch")
+    matches0 = torch.empty(rows0, dtype=torch.int32, device=dev)
+    s16 = torch.empty(rows0, dtype=torch.float16, device=dev)
+    row_len = torch.empty(batch.P, dtype=torch.int32, device=dev)
+    if batch.P:
+        ko = _upload_i32(np.concatenate([koff0, koff1]).astype(np.int32), dev)
+        ws = torch.empty(max(int(lib.gim_agg_assign_ws_bytes(n, rows0, rows1)), 8), dtype=torch.uint8, device=dev)
+        check(lib.gim_agg_assign(_p(st.kpts0), _p(st.kpts1), _p(st.scores), _p(batch.offsets), _p(batch.slot0), _p(batch.slot1), _p(st.geom),
+                                 _p(kp.id_grid), _p(kp.keypoints), _p(kp.kp_off), _p(ko[:batch.P + 1]), _p(ko[batch.P + 1:]), batch.P,
+                                 batch.row_lo, batch.row_hi, rows, S, cells, int(kp.keypoints.shape[0]), rows0, rows1, float(st.max_error),
+                                 int(st.patch), int(kp.nearest), _p(matches0), _p(s16), _p(row_len), _p(ws), _stream()), "gim_agg_assign")
+    return AggMatches(matches0, s16, row_len, koff0)

@@ -787,6 +787,69 @@ int gim_ransac_score(const double* models, const uint8_t* valid, const double* x
 int gim_ransac_mask(const double* models, const double* x0, const double* x1, const int32_t* offsets, int B, double thr2,
                     uint8_t* mask, gim_stream_t stream);
 
+/* ======================================================================================================
+ * Dense SfM: the dense matches of a pair list aggregated into keypoints and keypoint-indexed matches on the device (added
+ * within ABI revision 115: no existing structure or prototype changed with it).  The reference does this on the host, one
+ * match at a time (hloc/match_dense.py:43-130, 298-419: assign_keypoints, aggregate_matches, assign_matches, kpids_to_matches0).
+ *
+ * Geometry: patch = max(cell_size, max_error) (an integer), vote = int(max_error), r = patch / vote an integer in 1..8,
+ * max_error <= patch / 2 (so 2 <= r), h = (r + 1) / 2, nb = 2 h + 1 bins per axis and cell (r + 1 when r is even).  Per axis and in
+ * IEEE fp32 with round-half-to-even, a point x has cell c = rint((x + 0.5) / patch) and bin b = rint((x + 0.5) / vote), b - r c + h
+ * in [0, nb); bin index = by * nb + bx.  Every call takes (max_error, patch) and refuses another geometry before it launches.
+ * State, all DEVICE memory, indexed by image slot:
+ *   geom int32 [n_slots][4] = (W, H, first cell, 0): slot s owns the Gh * Gw cells from its first cell on, raster order (cy * Gw + cx),
+ *     Gw = W / patch + 2, Gh = H / patch + 2 (integer division); total_cells = the cells of all slots;
+ *   votes uint64 [total_cells][nb * nb] and cell_n int32 [total_cells] (votes per cell), zeroed by the caller before the first vote;
+ *   the pool of stored matches kpts0, kpts1 fp32 [pool_rows][2] (pixel coordinates, 8-byte aligned), scores fp32 [pool_rows];
+ *   a batch of P pairs: offsets int32 [P + 1] rising pool rows (pair p owns offsets[p] .. offsets[p + 1] - 1), slot0, slot1 int32 [P];
+ *   row_lo = offsets[0], row_hi = offsets[P] as the HOST knows them (the launch shape; one lane per row of [row_lo, row_hi)).
+ * A match counts iff both slots are usable, its score is finite and in [0, 65536), and both points lie in [-0.5, W - 0.5] x
+ * [-0.5, H - 0.5] of their image.  The kernels re-check every slot, cell, bin, id and row against n_slots, total_cells and the offsets
+ * and never turn one that does not fit into an address.
+ * ====================================================================================================== */
+
+/* nb * nb for (max_error, patch), or 0 for a geometry the calls below refuse (the reason is in gim_last_error). */
+int gim_agg_bins(float max_error, int patch);
+
+/* Votes of the batch: every counting match adds llrint(score * 2^32) to its bin's 64-bit sum and 1 to its cell's count, on both sides
+ * (ordinary integer atomicAdd: only integer sums cross threads, so the sums do not depend on the launch shape or on the order of the
+ * pairs).  dropped int32 [P] is FULLY written: the matches of pair p that did not count. */
+int gim_agg_vote(const float* kpts0, const float* kpts1, const float* scores, const int32_t* offsets, const int32_t* slot0,
+                 const int32_t* slot1, const int32_t* geom, uint64_t* votes, int32_t* cell_n, int32_t* dropped, int P, int row_lo,
+                 int row_hi, int pool_rows, int n_slots, int64_t total_cells, float max_error, int patch, gim_stream_t stream);
+
+/* Per cell (one lane each) the bin with the largest sum; the lowest bin index wins an exact tie.  cell_bin int32 [total_cells] = that bin,
+ * -1 for a cell without votes; cell_key int64 [total_cells] = 0 for a cell without votes, else min(sum, 2^63 - 2) + 1: a stable
+ * descending sort of a slot's keys is (score descending, raster cell index) with the cells without votes last. */
+int gim_agg_finalize(const uint64_t* votes, const int32_t* cell_n, int64_t total_cells, float max_error, int patch, int64_t* cell_key,
+                     int32_t* cell_bin, gim_stream_t stream);
+
+/* The final keypoints of all slots from the cells the host selected: sel int32 [n_sel] = cell indices (into [0, total_cells)), the
+ * selected cells of slot s at kp_off[s] .. kp_off[s + 1] - 1 in id order (kp_off int32 [n_slots + 1]), sel_slot int32 [n_sel] = the
+ * slot of each entry.  Writes id_grid int32 [total_cells] (FULLY: the id of the cell's keypoint within its image, -1 = none),
+ * keypoints fp32 [n_sel][2] = b * vote - 0.5, score fp64 [n_sel] = the integer sum * 2^-32, cells int32 [n_sel][2] = (cx, cy).  An
+ * entry that does not fit its slot or names a cell without votes writes keypoint (0, 0), score 0, cell (-1, -1) and no id. */
+int gim_agg_keypoints(const uint64_t* votes, const int32_t* cell_bin, const int32_t* geom, const int32_t* sel, const int32_t* sel_slot,
+                      const int32_t* kp_off, int n_sel, int n_slots, int64_t total_cells, float max_error, int patch, int32_t* id_grid,
+                      float* keypoints, double* score, int32_t* cells, gim_stream_t stream);
+
+/* Keypoint-indexed one-to-one matches of a batch of pairs in two launches.  Per counting match and side the keypoint id is, with
+ * nearest == 0, the id of the point's own cell (assign_keypoints(update=True)), else that of the nearest final keypoint among the 3 x 3
+ * cells around it whose fp64 distance (correctly rounded sqrt) is <= max_error, the lowest id on a tie, -1 when there is none
+ * (assign_keypoints(update=False): the KDTree query; max_error <= patch / 2 keeps every candidate within one cell).  Among the matches
+ * with both ids a match stays iff it has the best score of its id on BOTH sides (the lowest match index wins equal scores):
+ * (score bits << 32) | ~index is maximised per id with 64-bit atomicMax, a second pass keeps the holders of both maxima.
+ * koff0, koff1 int32 [P + 1]: prefix sums of the keypoint counts of the pairs' first / second images (rows0 = koff0[P],
+ * rows1 = koff1[P]).  FULLY written: matches0 int32 [rows0] (pair p owns koff0[p] .. koff0[p + 1] - 1; -1 = unmatched), scores_f16
+ * IEEE fp16 [rows0] (the score rounded to nearest even; 0 = unmatched), row_len int32 [P] = max matched id0 + 1: hloc's matches0 of
+ * pair p is its row cut to row_len[p].  ws: gim_agg_assign_ws_bytes(row_hi - row_lo, rows0, rows1) bytes, 8-byte aligned. */
+int64_t gim_agg_assign_ws_bytes(int n_rows, int rows0, int rows1);
+int gim_agg_assign(const float* kpts0, const float* kpts1, const float* scores, const int32_t* offsets, const int32_t* slot0,
+                   const int32_t* slot1, const int32_t* geom, const int32_t* id_grid, const float* keypoints, const int32_t* kp_off,
+                   const int32_t* koff0, const int32_t* koff1, int P, int row_lo, int row_hi, int pool_rows, int n_slots,
+                   int64_t total_cells, int n_kp, int rows0, int rows1, float max_error, int patch, int nearest, int32_t* matches0,
+                   void* scores_f16, int32_t* row_len, void* ws, gim_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
