@@ -70,6 +70,18 @@ class LgAssignArgs(ctypes.Structure):
     ]
 
 
+class DenseGatherArgs(ctypes.Structure):
+    """struct gim_dense_gather_args (include/gim_hip.h)."""
+    MAX = 8
+    _fields_ = [("slab", c_void_p * 8), ("dst", c_void_p * 8), ("slot_bytes", c_int64 * 8), ("n_levels", c_int), ("pad_", c_int)]
+
+
+class DensePairGeom(ctypes.Structure):
+    """struct gim_dense_pair_geom (include/gim_hip.h): one row of the [B, 16] fp32 geometry table of gim_dense_emit_pairs."""
+    _fields_ = [(n, c_float) for n in ("wp0", "hp0", "wp1", "hp1", "pl0", "pt0", "pl1", "pt1", "ow0", "oh0", "ow1", "oh1",
+                                       "sx0", "sy0", "sx1", "sy1")]
+
+
 ABI_VERSION = 115   # gim_version() of the include/gim_hip.h revision the structures and prototypes here mirror
 
 # name -> (restype, argtypes); every symbol declared in include/gim_hip.h
@@ -197,6 +209,9 @@ PROTOTYPES = {
     "gim_agg_keypoints": (c_int, [c_void_p] * 6 + [c_int] * 2 + [c_int64, c_float, c_int] + [c_void_p] * 5),
     "gim_agg_assign_ws_bytes": (c_int64, [c_int] * 3),
     "gim_agg_assign": (c_int, [c_void_p] * 12 + [c_int] * 5 + [c_int64] + [c_int] * 3 + [c_float] + [c_int] * 2 + [c_void_p] * 5),
+    # feature bank of the dense matchers: a pair list from per-image state (added within ABI revision 115)
+    "gim_dense_gather_pairs": (c_int, [ctypes.POINTER(DenseGatherArgs), c_void_p, c_int, c_int, c_void_p]),
+    "gim_dense_emit_pairs": (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_void_p]),
 }
 
 

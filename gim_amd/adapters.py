@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
+from ._lib import GimHipError
 
 
 def get_padding_size(image, h, w):
@@ -52,6 +53,23 @@ def dense_demo_inference(model, image0, image1, h, w, num=5000):
     return kpts0[mask], kpts1[mask], b_ids[mask], mconf[mask]
 
 
+def pair_geometry_row(geo0, geo1, scale_out0=(1.0, 1.0), scale_out1=(1.0, 1.0)):
+    """one row of gim_dense_emit_pairs' geometry table (struct gim_dense_pair_geom).  geo0 / geo1: the `image_geometry` of the MODEL's
+    first / second image (the caller's image1 / image0); scale_out0 / scale_out1: (sx, sy) of the OUTPUT keypoints0 / keypoints1, i.e.
+    of the caller's image0 / image1."""
+    (hp0, wp0), (ow0, oh0, pl0, _, pt0, _) = geo0["hw"], geo0["pads"]
+    (hp1, wp1), (ow1, oh1, pl1, _, pt1, _) = geo1["hw"], geo1["pads"]
+    return (float(wp0), float(hp0), float(wp1), float(hp1), float(pl0), float(pt0), float(pl1), float(pt1),
+            float(ow0), float(oh0), float(ow1), float(oh1),
+            float(scale_out0[0]), float(scale_out0[1]), float(scale_out1[0]), float(scale_out1[1]))
+
+
+def image_geometry(image, h, w):
+    """what the tail needs to know of one image [1,C,H,W]: `pads` = get_padding_size(image, h, w), `hw` = its padded size"""
+    pads = get_padding_size(image, h, w)
+    return {"pads": pads, "hw": (image.shape[2] + pads[4] + pads[5], image.shape[3] + pads[2] + pads[3])}
+
+
 class HlocDenseMatcher(torch.nn.Module):
     """hloc/matchers/dkm.py:15-154 without the file I/O: `forward({'image0', 'image1'[, 'mask0', 'mask1']})` ->
     `{'keypoints0', 'keypoints1', 'scores'[, 'batch_indexes']}`.  The plugin matches the pair in swapped order ("we refine
@@ -87,3 +105,55 @@ class HlocDenseMatcher(torch.nn.Module):
             kpts0, kpts1, scores = kpts0[keep], kpts1[keep], scores[keep]
         # names switched back: the model's first image is the caller's image1
         return {"keypoints0": kpts1, "keypoints1": kpts0, "scores": scores, "batch_indexes": b_ids}
+
+    # ---- a pair list from a bank: every image is masked, padded and extracted once -----------------------------------------------------
+    @torch.no_grad()
+    def extract(self, image, mask=None):
+        """one image [1,3,H,W] as `forward` gets it (and its class-id map) -> (DenseFeatures of the masked, padded image, its
+        `image_geometry`)"""
+        if mask is not None:
+            image = image * (torch.as_tensor(mask, device=image.device) != 0)[None, None]
+        geo = image_geometry(image, self.h, self.w)
+        pads = geo["pads"]
+        return self.net.extract(F.pad(image, (pads[2], pads[3], pads[4], pads[5]))), geo
+
+    def bank_put(self, bank, key, image, mask=None):
+        """extracts the image and stores it in `bank` (a gim_amd.dense_bank.DenseFeatureBank of self.net) under `key`"""
+        feats, geo = self.extract(image, mask)
+        return bank.put_features([key], feats, meta=[geo])[0]
+
+    @torch.no_grad()
+    def match_pairs(self, bank, pairs, batch_pairs=1, scales=None):
+        """`forward` for a list of pairs [(key0, key1)] of images stored with `bank_put`: per batch of `batch_pairs` pairs one
+        `match_features`, the net's `sample()` per pair (seeds from torch's CPU generator in pair order, exactly as single calls draw
+        them), ONE gim_dense_emit_pairs for the tail and one read of the counts.  Returns one {'keypoints0', 'keypoints1', 'scores',
+        'batch_indexes'} per pair, equal to `forward`'s.  scales: None, or per pair ((sx, sy) of key0, (sx, sy) of key1) -- the
+        keypoints then carry the rescale of dense_sfm.match_dense_pair_list, (k + 0.5) * s - 0.5."""
+        pairs = list(pairs)
+        bp = max(1, min(int(batch_pairs), self.net.max_batch))
+        out = []
+        for lo in range(0, len(pairs), bp):
+            chunk = pairs[lo:lo + bp]
+            B = len(chunk)
+            # the model's first image is the caller's image1 (the swap of `forward`)
+            slots = bank.slots([k1 for _, k1 in chunk] + [k0 for k0, _ in chunk])    # raises for an image that is not resident
+            geos = [(bank.meta[k1], bank.meta[k0]) for k0, k1 in chunk]
+            warp, cert = self.net.match_features(bank, slots[:B], slots[B:])
+            samples = [self.net.sample(warp[b], cert[b], self.num_samples) for b in range(B)]
+            num = max(1, max(m.shape[0] for _, m in samples))
+            sparse = torch.zeros(B, num, 4, dtype=torch.float32, device=warp.device)
+            mconf = torch.zeros(B, num, dtype=torch.float32, device=warp.device)    # rows past a pair's samples: rejected by mconf > 0
+            for b, (sm, mc) in enumerate(samples):
+                sparse[b, :sm.shape[0]].copy_(sm)
+                mconf[b, :mc.shape[0]].copy_(mc)
+            rows = [pair_geometry_row(g0, g1, *(scales[lo + b] if scales is not None else ((1.0, 1.0), (1.0, 1.0))))
+                    for b, (g0, g1) in enumerate(geos)]
+            k0, k1, sc, count = ops.dense_emit_pairs(sparse, mconf, ops.dense_pair_geometry(rows, warp.device), rescale=scales is not None)
+            for b, n in enumerate(count.tolist()):                                  # the one read-back of the batch
+                kp0, kp1, scores = k0[b, :n], k1[b, :n], sc[b, :n]
+                if self.max_num_matches is not None and n > self.max_num_matches:
+                    keep = torch.argsort(scores, descending=True)[:self.max_num_matches]
+                    kp0, kp1, scores = kp0[keep], kp1[keep], scores[keep]
+                out.append({"keypoints0": kp0, "keypoints1": kp1, "scores": scores,
+                            "batch_indexes": torch.zeros(n, dtype=torch.long, device=scores.device)})   # as `forward`: not cut by the top-k
+        return out

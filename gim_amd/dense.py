@@ -167,9 +167,25 @@ def gp_posterior(a32, nb, h, w, f, out, exact):
 
 
 # ---------------------------------------------------------------------------------------- the matcher surface
+class DenseFeatures:
+    """What `DenseMatcher.extract` returns: `tensors` {kind: [N, ...]} -- the per-image state of N images -- and the `tag`
+    (`DenseMatcher.feature_tag()`) it was computed under."""
+
+    def __init__(self, tensors, tag):
+        self.tensors, self.tag = tensors, tag
+
+    def __len__(self):
+        return next(iter(self.tensors.values())).shape[0]
+
+    @property
+    def nbytes_per_image(self):
+        return sum(t[0].numel() * t.element_size() for t in self.tensors.values())
+
+
 class DenseMatcher(nn.Module):
     """What `RegressionMatcher` of gim_dkm and gim_roma have in common.  A subclass sets `engine`, `max_batch`, `kde_half`, creates
-    `self.precision` and its parameter tree, and provides `_prepack(device)` (-> `self._packed = (P, dt, device)`) and `match_batch`."""
+    `self.precision` and its parameter tree, and provides `_prepack(device)` (-> `self._packed = (P, dt, device)`), `_state` (everything computed from one image alone) and
+    `_match_state` (everything that depends on both images of a pair); `match_batch` and `match_features` are built from the two."""
     engine = None       # name in messages
     max_batch = None    # pairs per match_batch call
     kde_half = False    # sample(): the KDE on fp16-rounded coordinates (roma.py:1018-1023)
@@ -189,18 +205,162 @@ class DenseMatcher(nn.Module):
         # 16-bit modes: the 144- and 24-channel ConvRefiner blocks (scales 2 and 1, both passes) as ONE launch each (gim_dwconv5x5_pw, round 5)
         self.refiner_fused = flag("refiner_fused", True)
         self._packed = None
+        self._epoch = 0      # moves with every weight change / device move: per-image state extracted before it is stale (feature_tag)
 
     def _gp_is_exact(self):
         return (self.precision == "fp32") if self.gp_exact is None else self.gp_exact
 
     def _images(self, dt, im1, im2, hs, ws):
         """[B,3,H,W] x 2 -> NHWC [2B, hs, ws, cpad]: queries first, then supports (extract_backbone_features, dkm.py:572-581,
-        roma.py:668-678)"""
-        B = im1.shape[0]
-        x = torch.empty(2 * B, hs, ws, cstore(3, dt), dtype=torch_dtype(dt), device=im1.device)
-        ops.resize_image(im1, x, 0)
-        ops.resize_image(im2, x, B)
+        roma.py:668-678); im2 None: the images of im1 alone (extract)"""
+        ims = [im1] if im2 is None else [im1, im2]
+        x = torch.empty(sum(im.shape[0] for im in ims), hs, ws, cstore(3, dt), dtype=torch_dtype(dt), device=im1.device)
+        off = 0
+        for im in ims:
+            ops.resize_image(im, x, off)
+            off += im.shape[0]
         return x
+
+    def _black(self, ims, hs, ws):
+        """the black-pixel masks of the match() tail (dkm.py:726-729), one per image: uint8 [sum B_i, hs, ws]"""
+        return torch.stack([ops.dkm_black_mask(im[b:b + 1], (hs, ws)) for im in ims for b in range(im.shape[0])])
+
+    # ---- weight / device changes move the epoch of the per-image state ----------------------------------------------------------------
+    def load_state_dict(self, state_dict, *a, **k):
+        self._epoch = getattr(self, "_epoch", 0) + 1
+        return super().load_state_dict(state_dict, *a, **k)
+
+    def _apply(self, fn, *a, **k):
+        self._epoch = getattr(self, "_epoch", 0) + 1
+        return super()._apply(fn, *a, **k)
+
+    def _ensure_packed(self, device):
+        if self._packed is None or self._packed[2] != device or self._packed[1] != PRECISION_DTYPE[self.precision]:
+            self._prepack(device)
+        return self._packed[0], self._packed[1]
+
+    def _tag_extra(self):
+        return ()
+
+    def feature_tag(self):
+        """what per-image state depends on besides the image: weights (epoch), precision, the two resolutions and the engine's switches.
+        A DenseFeatureBank holds state of ONE tag."""
+        return (id(self), self._epoch, self.precision, self.h_resized, self.w_resized, bool(self.upsample_preds),
+                tuple(self.upsample_res) if self.upsample_preds else None) + tuple(self._tag_extra())
+
+    def _out_size(self):
+        return tuple(self.upsample_res) if self.upsample_preds else (self.h_resized, self.w_resized)
+
+    # ---- per-image state: extract once, match many times ---------------------------------------------------------------------------------
+    @torch.no_grad()
+    def extract(self, images):
+        """[N,3,H,W] images, padded and masked as match() gets them -> DenseFeatures: everything match_batch computes from ONE image
+        alone, at the module's precision, as tensors with a leading N -- the low-resolution levels `_decode` reads (the coarse scales as
+        their projections), the high-resolution levels of the upsampling pass (scales 8, 4, 2, 1 only) and the black-pixel mask of the
+        match() tail.  gim_amd.dense_bank.DenseFeatureBank stores them; `match_features` matches pairs of stored images."""
+        if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 3 or images.shape[0] < 1:
+            raise GimHipError(f"extract takes [N,3,H,W] images, got {tuple(getattr(images, 'shape', ()))}")
+        if not images.is_cuda:
+            raise GimHipError(f"gim_amd {self.engine} needs device (cuda/HIP) tensors: there is no CPU fallback")
+        if not self.symmetric:
+            raise NotImplementedError("only symmetric matching is built")
+        P, dt = self._ensure_packed(images.device)
+        st = self._state(P, dt, images.contiguous().float(), None)
+        return DenseFeatures({k: v for k, v in st.items() if not k.endswith(".rows")}, self.feature_tag())
+
+    def _pair_index(self, slots0, slots1, n_slots, device):
+        if torch.is_tensor(slots0) != torch.is_tensor(slots1):
+            raise GimHipError("match_features: slots0 and slots1 must both be sequences of ints or both int32 device tensors")
+        if torch.is_tensor(slots0):
+            if slots0.dtype != torch.int32 or slots1.dtype != torch.int32 or slots0.device != device or slots1.device != device:
+                raise GimHipError(f"match_features: slot tensors must be int32 on {device}")
+            s0, s1 = slots0.reshape(-1), slots1.reshape(-1)
+        else:
+            s0, s1 = [int(v) for v in slots0], [int(v) for v in slots1]
+            bad = [v for v in s0 + s1 if not 0 <= v < n_slots]
+            if bad:
+                raise GimHipError(f"match_features: slot {bad[0]} is outside [0, {n_slots})")
+            both = torch.tensor(s0 + s1 + s1 + s0, dtype=torch.int32).to(device, non_blocking=True)
+            B = len(s0)
+            if len(s1) != B:
+                raise GimHipError(f"match_features: {B} slots on side 0, {len(s1)} on side 1")
+            return B, both[:2 * B], both[2 * B:]
+        if s0.numel() != s1.numel():
+            raise GimHipError(f"match_features: {s0.numel()} slots on side 0, {s1.numel()} on side 1")
+        return s0.numel(), torch.cat((s0, s1)), torch.cat((s1, s0))
+
+    @torch.no_grad()
+    def match_features(self, bank, slots0, slots1):
+        """`match_batch` from stored state: pair b matches the images in slots0[b] / slots1[b] of `bank` (a DenseFeatureBank of this
+        module) -> (warp [B,Hs,2Ws,4], certainty [B,Hs,2Ws]), B <= max_batch.  Two gim_dense_gather_pairs launch sequences build the
+        query batch (slots0 | slots1) and the support batch (slots1 | slots0) of every level; everything behind them is match_batch's."""
+        bank.check(self)                       # raises for another module's bank, empties a stale one (then the slots name nothing)
+        if bank.slabs is None:
+            raise GimHipError("match_features: the bank is empty (never filled, or invalidated by a weight / device / precision change)")
+        dev = bank.device
+        P, dt = self._ensure_packed(dev)
+        B, iq, isup = self._pair_index(slots0, slots1, bank.capacity, dev)
+        if not 1 <= B <= self.max_batch:
+            raise GimHipError(f"match_features takes 1..{self.max_batch} pairs per call, got {B}")
+        q, sup = {}, {}
+
+        def gather(names, idx, out):
+            levels = []
+            for nm in names:
+                slab = bank.slabs[nm]
+                if nm in self.slack_names:   # GEMM operand rows: 64 zero rows behind the last image
+                    rows = torch.zeros(2 * B * slab.shape[1] + 64, slab.shape[2], dtype=slab.dtype, device=dev)
+                    out[nm + ".rows"] = rows
+                    out[nm] = rows[:2 * B * slab.shape[1]].view(2 * B, *slab.shape[1:])
+                else:
+                    out[nm] = torch.empty(2 * B, *slab.shape[1:], dtype=slab.dtype, device=dev)
+                levels.append((slab, out[nm]))
+            ops.dense_gather_pairs(levels, idx, bank.capacity)
+
+        first = [nm for nm in bank.slabs if nm in self.first_names]
+        gather(first, iq, q)
+        pending = self._begin(P, dt, q, B)
+        gather([nm for nm in bank.slabs if nm not in self.first_names], iq, q)
+        gather([nm for nm in bank.slabs if nm in self.support_names], isup, sup)
+        out = self._match_state(P, dt, q, sup, B, pending)
+        return self._after_match(out, lambda: self.match_features(bank, slots0, slots1))
+
+    first_names = ()      # state the work of `_begin` reads (gathered first)
+    support_names = ()    # state the refiners read as the OTHER image of the pair
+    slack_names = ()      # state that is a GEMM row operand (64 slack rows)
+
+    def _begin(self, P, dt, q, B):
+        return None
+
+    def _after_match(self, out, again):
+        return out
+
+    def _finish(self, im1, im2, flow, cert, low, hs, ws):
+        """`_finish_state` with the black masks computed from the two image batches"""
+        return DenseMatcher._finish_state(self, DenseMatcher._black(self, [im1, im2], hs, ws), flow, cert, low, hs, ws)
+
+    def _finish_state(self, black, flow, cert, low, hs, ws):
+        """tail of match_batch (dkm.py:686-752, roma.py:880-917): flow / cert / low [2B,hs,ws,*] of both directions and the black masks
+        [2B,hs,ws] of the images -> (warp [B,hs,2ws,4], certainty [B,hs,2ws])"""
+        B, dev = flow.shape[0] // 2, flow.device
+        warp = torch.empty(B, hs, 2 * ws, 4, dtype=torch.float32, device=dev)
+        certainty = torch.empty(B, hs, 2 * ws, dtype=torch.float32, device=dev)
+        for b in range(B):
+            ops.dkm_match_post((flow[b], flow[b + B]), (cert[b], cert[b + B]), (low[b], low[b + B]), black[b], black[b + B], warp[b], certainty[b])
+        return warp, certainty
+
+    @torch.no_grad()
+    def match_batch(self, ims1, ims2):
+        """B independent pairs in one pass ([B,3,H,W] x 2 -> warp [B,Hs,2Ws,4], certainty [B,Hs,2Ws]); result b equals
+        `match(ims1[b:b+1], ims2[b:b+1])`.  (The reference's own batched mode cannot upsample and masks with pair 0's black pixels,
+        dkm.py:662,723-724; batching here is the engine's, as SURVEY 8d prescribes for the batch-4 config.)  It is "extract both, then
+        the body `match_features` shares": one decode path."""
+        P, dt, im1, im2 = self._enter(ims1, ims2)
+        B = im1.shape[0]
+        pending = []
+        st = self._state(P, dt, im1, im2, after_low=lambda q: pending.append(self._begin(P, dt, q, B)))
+        out = self._match_state(P, dt, st, None, B, pending[0] if pending else None)
+        return self._after_match(out, lambda: self.match_batch(ims1, ims2))
 
     @torch.no_grad()
     def match(self, im1, im2, *args, batched=False):
@@ -222,21 +382,8 @@ class DenseMatcher(nn.Module):
         if im1.dim() != 4 or im1.shape[1] != 3 or im1.shape != im2.shape or not 1 <= im1.shape[0] <= self.max_batch:
             raise GimHipError(f"match takes two [B,3,H,W] batches of equal shape with B <= {self.max_batch}, "
                               f"got {tuple(im1.shape)} / {tuple(im2.shape)}")
-        if self._packed is None or self._packed[2] != im1.device or self._packed[1] != PRECISION_DTYPE[self.precision]:
-            self._prepack(im1.device)
-        P, dt, _ = self._packed
+        P, dt = self._ensure_packed(im1.device)
         return P, dt, im1.contiguous().float(), im2.contiguous().float()
-
-    def _finish(self, im1, im2, flow, cert, low, hs, ws):
-        """tail of match_batch (dkm.py:686-752, roma.py:880-917): flow / cert / low [2B,hs,ws,*] of both directions ->
-        (warp [B,hs,2ws,4], certainty [B,hs,2ws])"""
-        B, dev = im1.shape[0], im1.device
-        warp = torch.empty(B, hs, 2 * ws, 4, dtype=torch.float32, device=dev)
-        certainty = torch.empty(B, hs, 2 * ws, dtype=torch.float32, device=dev)
-        for b in range(B):
-            ops.dkm_match_post((flow[b], flow[b + B]), (cert[b], cert[b + B]), (low[b], low[b + B]),
-                               ops.dkm_black_mask(im1[b:b + 1], (hs, ws)), ops.dkm_black_mask(im2[b:b + 1], (hs, ws)), warp[b], certainty[b])
-        return warp, certainty
 
     @torch.no_grad()
     def sample(self, dense_matches, dense_certainty, num=10000):

@@ -211,13 +211,16 @@ def _scale_of(scales, name):
 
 
 @torch.no_grad()
-def match_dense_pair_list(matcher, images, pairs, aggregator, scales=None):
+def match_dense_pair_list(matcher, images, pairs, aggregator, scales=None, bank=None, batch_pairs=1):
     """The loop of match_dense.py:221-257 with the matches kept on the device.  matcher: an `adapters.HlocDenseMatcher`, an hloc plugin
     or any callable with their dict contract ({'image0', 'image1', 'name0', 'name1'} -> {'keypoints0', 'keypoints1', 'scores'});
     images: {name: [1,C,H,W] device tensor}; pairs: [(name0, name1)]; scales: {name: (sx, sy)} = original size / matched size
     (ImagePairDataset.preprocess), default 1.  Every pair gets the rescale of :242-243, scale_keypoints(k + 0.5, s) - 0.5 in fp32 on
     the device, and goes to `aggregator.add_pair`; images the aggregator does not know are added with their original size.  Returns
-    nothing: `aggregator.finalize` / `assign` / `write` follow."""
+    nothing: `aggregator.finalize` / `assign` / `write` follow.
+    bank (a gim_amd.dense_bank.DenseFeatureBank of the matcher's net; the matcher then needs `bank_put` / `match_pairs`, as
+    HlocDenseMatcher and the dense hloc plugins have them): every image is extracted on first use instead of once per pair, pairs go
+    out `batch_pairs` at a time, the tail and the rescale are one launch per batch; `add_pair` gets the same rows in the same order."""
     for name0, name1 in pairs:
         for name in (name0, name1):
             if name not in images:
@@ -226,6 +229,24 @@ def match_dense_pair_list(matcher, images, pairs, aggregator, scales=None):
                 s = _scale_of(scales, name)
                 h, w = images[name].shape[-2:]
                 aggregator.add_image(name, int(round(w * s[0])), int(round(h * s[1])))
+    if bank is not None:
+        pairs = list(pairs)
+        bp = max(1, int(batch_pairs))
+        for lo in range(0, len(pairs), bp):
+            chunk = pairs[lo:lo + bp]
+            names = list(dict.fromkeys(n for pr in chunk for n in pr))
+            if len(names) > bank.capacity:
+                raise GimHipError(f"match_dense_pair_list: a batch of {len(chunk)} pairs names {len(names)} images, the bank has {bank.capacity} slots")
+            resident = [n for n in names if n in bank]
+            if resident:
+                bank.slots(resident)                     # most recently used: making room below does not evict them
+            for n in names:
+                if n not in bank:
+                    matcher.bank_put(bank, n, images[n])
+            sc = [(tuple(np.float32(_scale_of(scales, n0))), tuple(np.float32(_scale_of(scales, n1)))) for n0, n1 in chunk]
+            for (n0, n1), pred in zip(chunk, matcher.match_pairs(bank, chunk, batch_pairs=bp, scales=sc)):
+                aggregator.add_pair(n0, n1, pred["keypoints0"], pred["keypoints1"], pred["scores"])
+        return
     for name0, name1 in pairs:
         pred = matcher({"image0": images[name0], "image1": images[name1], "name0": name0, "name1": name1})
         out = []

@@ -151,8 +151,9 @@ class RegressionMatcher(DenseMatcher):
         return self._gp_f[key]
 
     # ---- stages ---------------------------------------------------------------------------------------------------
-    def _encode(self, P, x):
-        """x [2,hs,ws,cpad] NHWC -> {1: x, 2, 4, 8, 16, 32} (encoders.py:43-62)"""
+    def _encode(self, P, x, top=32):
+        """x [nb,hs,ws,cpad] NHWC -> {1: x, 2, 4, 8, 16, 32} (encoders.py:43-62); top = 8: layers 3 and 4 are not computed (the
+        upsampling pass reads scales 8, 4, 2, 1 only)"""
         feats = {1: x}
         x = ops.conv2d(x, P["stem"], ACT_RELU)
         feats[2] = x
@@ -161,6 +162,8 @@ class RegressionMatcher(DenseMatcher):
             for bi in range(nblk):
                 x = bottleneck(x, P, f"l{li}.{bi}.")
             feats[2 ** (li + 1)] = x
+            if 2 ** (li + 1) >= top:
+                break
         return feats
 
     def _rrb(self, P, nm, x):
@@ -175,27 +178,108 @@ class RegressionMatcher(DenseMatcher):
     def _refine(self, P, s, dt, x, y, flow, cert, ins, full_hw):
         refine(P, s, dt, x, y, flow, cert, ins, full_hw, REFINER[s], self.refiner_fused)
 
-    def _gp_stage(self, P, dt, f1, s):
-        """proj + GP + DFN feature input of scale s: everything of that scale that does not depend on the coarser
-        scales' flow (GP.forward ignores `dense_flow`, dkm.py:340) -> (projected features a, emb_in = [feats | mu])"""
-        tdt = torch_dtype(dt)
-        feat = f1[int(s)]
-        nb, h, w, _ = feat.shape
-        n, dev = h * w, feat.device
-        a32 = torch.zeros(nb * n + 64, 512, dtype=torch.float32, device=dev)
-        ops.linear(feat.view(nb * n, feat.shape[3]), P["proj" + s], a32)
-        if dt == GIM_F32:
-            a = a32[:nb * n].view(nb, h, w, 512)
-        else:
-            a = torch.empty(nb, h, w, 512, dtype=tdt, device=dev)
-            ops.cast_rows(a32[:nb * n], a.view(nb * n, 512))
-        emb_in = torch.empty(nb * n, FEAT_DIM + GP_DIM, dtype=tdt, device=dev)
-        ops.linear(a.view(nb * n, 512), P["fin" + s], emb_in[:, :FEAT_DIM])
-        self._gp(P, s, a32, nb, h, w, tdt, emb_in[:, FEAT_DIM:])
-        return a, emb_in
+    first_names = ("a32_32", "a32_16", "fin32", "fin16")
+    support_names = ("lo1", "lo2", "lo4", "lo8", "a16", "hi1", "hi2", "hi4", "hi8")
+    slack_names = ("a32_32", "a32_16")
 
-    def _decode(self, P, dt, f1, upsample=False, dense_flow=None, dense_certainty=None, gp=None):
-        """Decoder.forward on the symmetric pair (f2 = f1 with the two images swapped) -> {scale: (flow, certainty)}"""
+    def _tag_extra(self):
+        return ()
+
+    def _state(self, P, dt, im1, im2, after_low=None):
+        """everything match_batch computes from one image alone, for the images of im1 (and im2 behind them): {kind: [nb, ...]}
+          lo1 / lo2 / lo4 / lo8     low-resolution pyramid levels the refiners read
+          a32_32 / a32_16           proj32 / proj16 rows in fp32 (what the GP reads; `.rows`: the same buffer with its 64 slack rows)
+          a16                       proj16 at the module's precision (refiner 16)
+          fin32 / fin16             the feature half of the DFN's input, feat_input_modules(proj)
+          hi1 / hi2 / hi4 / hi8     the pyramid of the upsampling pass (layers 3, 4 of that ResNet are never read: not computed)
+          black                     the black-pixel mask of the match() tail at the output resolution
+        after_low(state): called when the low-resolution part stands (match_batch starts the GP on its side stream there)."""
+        tdt = torch_dtype(dt)
+        hs, ws = self.h_resized, self.w_resized
+        if hs % 32 or ws % 32:
+            raise GimHipError(f"h_resized / w_resized must be multiples of 32, got {(hs, ws)}")
+        dev = im1.device
+        st = {}
+        pyr = self._encode(P, self._images(dt, im1, im2, hs, ws))
+        for sc in (1, 2, 4, 8):
+            st[f"lo{sc}"] = pyr[sc]
+        for s in ("32", "16"):
+            feat = pyr[int(s)]
+            nb, h, w, _ = feat.shape
+            n = h * w
+            a32 = torch.zeros(nb * n + 64, 512, dtype=torch.float32, device=dev)
+            ops.linear(feat.view(nb * n, feat.shape[3]), P["proj" + s], a32)
+            if dt == GIM_F32:
+                a = a32[:nb * n].view(nb, h, w, 512)
+            else:
+                a = torch.empty(nb, h, w, 512, dtype=tdt, device=dev)
+                ops.cast_rows(a32[:nb * n], a.view(nb * n, 512))
+            fin = torch.empty(nb * n, FEAT_DIM, dtype=tdt, device=dev)
+            ops.linear(a.view(nb * n, 512), P["fin" + s], fin)
+            st["a32_" + s], st["a32_" + s + ".rows"] = a32[:nb * n].view(nb, n, 512), a32
+            st["fin" + s] = fin.view(nb, h, w, FEAT_DIM)
+            if s == "16":
+                st["a16"] = a
+        if after_low is not None:
+            after_low(st)
+        if self.upsample_preds:
+            hi = self._encode(P, self._images(dt, im1, im2, *self.upsample_res), top=8)
+            for sc in (1, 2, 4, 8):
+                st[f"hi{sc}"] = hi[sc]
+        st["black"] = self._black([im1] if im2 is None else [im1, im2], *self._out_size())
+        return st
+
+    def _gp_pair(self, P, dt, q, s):
+        """GP + DFN input of scale s for the stacked pair batch q: everything of that scale that needs both images and not the coarser
+        scales' flow (GP.forward ignores `dense_flow`, dkm.py:340) -> emb_in = [feats | mu]"""
+        tdt = torch_dtype(dt)
+        nb, h, w, _ = q["fin" + s].shape
+        n = h * w
+        emb_in = torch.empty(nb * n, FEAT_DIM + GP_DIM, dtype=tdt, device=q["fin" + s].device)
+        emb_in[:, :FEAT_DIM].copy_(q["fin" + s].view(nb * n, FEAT_DIM))
+        self._gp(P, s, q["a32_" + s + ".rows"], nb, h, w, tdt, emb_in[:, FEAT_DIM:])
+        return emb_in
+
+    def _begin(self, P, dt, q, B):
+        """The GP of both coarse scales (a latency-bound chain of ~150 small launches) needs the low-resolution state only: with the
+        upsampling pass it runs on a side stream while the main stream encodes (match_batch) or gathers (match_features) the rest."""
+        if not (self.upsample_preds and self.overlap_gp):
+            return {s: self._gp_pair(P, dt, q, s) for s in ("32", "16")}, None
+        main = torch.cuda.current_stream()
+        side = self._side_stream(q["fin16"].device)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            gp = {s: self._gp_pair(P, dt, q, s) for s in ("32", "16")}
+        for s in ("32", "16"):
+            q["a32_" + s + ".rows"].record_stream(side)
+            q["fin" + s].record_stream(side)
+            gp[s].record_stream(main)
+        return gp, side
+
+    def _match_state(self, P, dt, q, sup, B, pending):
+        gp, side = pending if pending is not None else self._begin(P, dt, q, B)
+        if side is not None:
+            torch.cuda.current_stream().wait_stream(side)
+        hs, ws = self.h_resized, self.w_resized
+        f1 = {1: q["lo1"], 2: q["lo2"], 4: q["lo4"], 8: q["lo8"], 16: q["a16"], 32: q["fin32"]}
+        y1 = None if sup is None else {1: sup["lo1"], 2: sup["lo2"], 4: sup["lo4"], 8: sup["lo8"], 16: sup["a16"]}
+        cor = self._decode(P, dt, f1, gp=gp, sup=y1)
+        if self.upsample_preds:
+            hs, ws = self.upsample_res
+        low = ops.resize_bilinear(cor[16][1], (hs, ws))
+        if self.upsample_preds:
+            f1 = {sc: q[f"hi{sc}"] for sc in (1, 2, 4, 8)}
+            y1 = None if sup is None else {sc: sup[f"hi{sc}"] for sc in (1, 2, 4, 8)}
+            cor = self._decode(P, dt, f1, upsample=True, dense_flow=cor[1][0], dense_certainty=cor[1][1], sup=y1)
+        flow, cert = cor[1]
+        warp, certainty = self._finish_state(q["black"], flow, cert, low, hs, ws)
+        self._debug = {"corresps": cor}
+        return warp, certainty
+
+    def _decode(self, P, dt, f1, upsample=False, dense_flow=None, dense_certainty=None, gp=None, sup=None):
+        """Decoder.forward on the symmetric pair (f2 = f1 with the two images swapped) -> {scale: (flow, certainty)}.  f1: per scale the
+        tensor the refiner reads (16: the projection; 32: anything of that size), gp: {scale: emb_in} of `_gp_pair`, sup: f1 in support
+        order (match_features gathers it; None: the two halves of f1 are swapped with a copy)"""
         tdt = torch_dtype(dt)
         scales = ["8", "4", "2", "1"] if upsample else ["32", "16", "8", "4", "2", "1"]
         sizes = {s: tuple(f1[s].shape[1:3]) for s in f1}
@@ -218,7 +302,7 @@ class RegressionMatcher(DenseMatcher):
             n = h * w
             a = f1[ins]
             if s in ("32", "16"):
-                a, emb_in = gp[s] if gp is not None else self._gp_stage(P, dt, f1, s)
+                emb_in = gp[s]
                 emb = self._rrb(P, "rd" + s, emb_in.view(nb, h, w, FEAT_DIM + GP_DIM))
                 if old is not None:
                     old = ops.resize_bilinear(old, (h, w))
@@ -239,7 +323,8 @@ class RegressionMatcher(DenseMatcher):
                 cert = torch.empty(nb, h, w, 1, dtype=torch.float32, device=dev)
                 ops.dkm_flow_update(flow, cert, preds, 1.0, 1.0, cert_init=True)       # flow, certainty = preds
             if s in REFINER:
-                self._refine(P, s, dt, a, torch.cat((a[half:], a[:half])), flow, cert, ins, full)   # support = the other image of each pair
+                y = sup[ins] if sup is not None else torch.cat((a[half:], a[:half]))    # support = the other image of each pair
+                self._refine(P, s, dt, a, y, flow, cert, ins, full)
             out[ins] = (flow, cert)
             if s != "1":
                 flow = ops.resize_bilinear(flow, sizes[ins // 2])
@@ -250,45 +335,6 @@ class RegressionMatcher(DenseMatcher):
         if getattr(self, "_side", None) is None or self._side.device != dev:
             self._side = torch.cuda.Stream(device=dev)
         return self._side
-
-    @torch.no_grad()
-    def match_batch(self, ims1, ims2):
-        """B independent pairs in one pass ([B,3,H,W] x 2 -> warp [B,Hs,2Ws,4], certainty [B,Hs,2Ws]); result b equals
-        `match(ims1[b:b+1], ims2[b:b+1])`.  (The reference's own batched mode cannot upsample and masks with pair 0's
-        black pixels, dkm.py:662,723-724; batching here is the engine's, as SURVEY 8d prescribes for the batch-4 config.)"""
-        P, dt, im1, im2 = self._enter(ims1, ims2)
-        dev = im1.device
-        hs, ws = self.h_resized, self.w_resized
-        if hs % 32 or ws % 32:
-            raise GimHipError(f"h_resized / w_resized must be multiples of 32, got {(hs, ws)}")
-        # The GP of both coarse scales (a latency-bound chain of ~150 small launches) only needs the low-resolution
-        # pyramid: it runs on a side stream while the main stream encodes the high-resolution images.
-        pyr = self._encode(P, self._images(dt, im1, im2, hs, ws))
-        main = torch.cuda.current_stream()
-        if self.upsample_preds and self.overlap_gp:
-            side = self._side_stream(dev)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                gp = {s: self._gp_stage(P, dt, pyr, s) for s in ("32", "16")}
-            for s in ("32", "16"):
-                pyr[int(s)].record_stream(side)
-                for t in gp[s]:
-                    t.record_stream(main)
-            pyr_hi = self._encode(P, self._images(dt, im1, im2, *self.upsample_res))
-            main.wait_stream(side)
-        else:
-            gp = None
-            pyr_hi = self._encode(P, self._images(dt, im1, im2, *self.upsample_res)) if self.upsample_preds else None
-        cor = self._decode(P, dt, pyr, gp=gp)
-        if self.upsample_preds:
-            hs, ws = self.upsample_res
-        low = ops.resize_bilinear(cor[16][1], (hs, ws))
-        if self.upsample_preds:
-            cor = self._decode(P, dt, pyr_hi, upsample=True, dense_flow=cor[1][0], dense_certainty=cor[1][1])
-        flow, cert = cor[1]
-        warp, certainty = self._finish(im1, im2, flow, cert, low, hs, ws)
-        self._debug = {"corresps": cor}
-        return warp, certainty
 
 
 def DKMv3(weights, h, w, symmetric=True, sample_mode="threshold_balanced", **kwargs):

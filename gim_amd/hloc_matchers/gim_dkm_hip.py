@@ -78,17 +78,32 @@ class GimDkmHip(BaseModel):
                 d["mask" + i] = m
         return self.adapter(d)
 
+    def bank_put(self, bank, name, image, mask=None):
+        """HlocDenseMatcher.bank_put with the plugin's segment-mask lookup: once per image, not once per pair"""
+        if mask is None:
+            mask = self._segment_mask(name, image.shape[-2:])
+        return self.adapter.bank_put(bank, name, image, mask)
+
+    def match_pairs(self, bank, pairs, batch_pairs=1, scales=None):
+        return self.adapter.match_pairs(bank, pairs, batch_pairs=batch_pairs, scales=scales)
+
     def match_and_assign_from_images(self, images, pairs, features, matches, max_kps=8192, scales=None, max_error=2, cell_size=8,
-                                     write_dense=True):
+                                     write_dense=True, bank_images=None, batch_pairs=1):
         """hloc/match_dense.py `match_and_assign` for the SfM branch with the bookkeeping on the device (gim_amd/dense_sfm.py): matches
         every pair of `pairs` ([(name0, name1)]) over `images` ({name: [1,3,H,W] device tensor}; `scales`: {name: (sx, sy)} back to the
         original size), aggregates the dense matches into at most `max_kps` keypoints per image and writes hloc's datasets into the
         h5py-like files `features` (`keypoints`, `score`) and `matches` (`matches0`, `matching_scores0`; with write_dense the dense
-        `keypoints0`, `keypoints1`, `scores` too).  max_error / cell_size: the conf of match_dense.py:37-38.  Returns the aggregator."""
+        `keypoints0`, `keypoints1`, `scores` too).  max_error / cell_size: the conf of match_dense.py:37-38.  bank_images: slots of a
+        gim_amd.dense_bank.DenseFeatureBank -- every image is then encoded once instead of once per pair (None: the per-pair loop) and
+        `batch_pairs` pairs share a launch sequence.  Returns the aggregator."""
         from ..dense_sfm import DenseMatchAggregator, match_dense_pair_list
         device = next(iter(images.values())).device if images else "cuda"
         agg = DenseMatchAggregator(max_error=max_error, cell_size=cell_size, device=device)
-        match_dense_pair_list(self, images, pairs, agg, scales)
+        bank = None
+        if bank_images:
+            from ..dense_bank import DenseFeatureBank
+            bank = DenseFeatureBank(self.net, bank_images)
+        match_dense_pair_list(self, images, pairs, agg, scales, bank=bank, batch_pairs=batch_pairs)
         agg.finalize(max_kps)
         agg.write(features, matches, write_dense=write_dense)
         return agg

@@ -1721,3 +1721,50 @@ def agg_assign(st, kp, batch):
                                  batch.row_lo, batch.row_hi, rows, S, cells, int(kp.keypoints.shape[0]), rows0, rows1, float(st.max_error),
                                  int(st.patch), int(kp.nearest), _p(matches0), _p(s16), _p(row_len), _p(ws), _stream()), "gim_agg_assign")
     return AggMatches(matches0, s16, row_len, koff0)
+
+
+# ---- feature bank of the dense matchers (csrc/dense_bank.hip) ------------------------------------------------------------------------------
+def dense_gather_pairs(levels, idx, n_slots):
+    """levels: [(slab [n_slots, ...], dst [n_entries, ...])] contiguous device tensors with equal bytes per block (a multiple of 16);
+    idx: int32 device tensor [n_entries].  Block d of every dst receives slot idx[d] of its slab (gim_dense_gather_pairs: one launch
+    per 8 levels; an index outside [0, n_slots) leaves its blocks untouched; nothing waits for the indices)."""
+    _req_cuda(idx, *[t for lv in levels for t in lv])
+    if idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous():
+        raise _lib.GimHipError(f"dense_gather_pairs: idx must be a contiguous int32 vector, got {idx.dtype} {tuple(idx.shape)}")
+    n = idx.numel()
+    for i in range(0, len(levels), _lib.DenseGatherArgs.MAX):
+        args = _lib.DenseGatherArgs()
+        chunk = levels[i:i + _lib.DenseGatherArgs.MAX]
+        for k, (slab, dst) in enumerate(chunk):
+            bb = slab[0].numel() * slab.element_size()
+            if not (slab.is_contiguous() and dst.is_contiguous() and slab.shape[0] == n_slots and dst.shape[0] == n
+                    and (n == 0 or dst[0].numel() * dst.element_size() == bb)):
+                raise _lib.GimHipError(f"dense_gather_pairs: level {i + k}: slab {tuple(slab.shape)} / destination {tuple(dst.shape)} for "
+                                       f"{n_slots} slots and {n} entries")
+            args.slab[k], args.dst[k], args.slot_bytes[k] = slab.data_ptr(), dst.data_ptr(), bb
+        args.n_levels = len(chunk)
+        check(lib.gim_dense_gather_pairs(ctypes.byref(args), _p(idx), n, int(n_slots), _stream()), "gim_dense_gather_pairs")
+
+
+def dense_pair_geometry(rows, device):
+    """rows: one 16-tuple per pair in the field order of struct gim_dense_pair_geom -> fp32 [B, 16] on the device"""
+    t = torch.tensor(rows, dtype=torch.float32).reshape(-1, 16)
+    return t.to(device, non_blocking=True)
+
+
+def dense_emit_pairs(sparse, mconf, geom, rescale):
+    """sparse [B,num,4], mconf [B,num] fp32, geom [B,16] (dense_pair_geometry) -> (keypoints0 [B,num,2], keypoints1 [B,num,2],
+    scores [B,num], count int32 [B]) on the device: per pair the kept rows in input order at the front (gim_dense_emit_pairs)."""
+    _req_cuda(sparse, mconf, geom)
+    B, num = mconf.shape
+    assert sparse.shape == (B, num, 4) and geom.shape == (B, 16)
+    assert sparse.dtype == mconf.dtype == geom.dtype == torch.float32
+    assert sparse.is_contiguous() and mconf.is_contiguous() and geom.is_contiguous()
+    dev = sparse.device
+    k0 = torch.empty(B, num, 2, dtype=torch.float32, device=dev)
+    k1 = torch.empty(B, num, 2, dtype=torch.float32, device=dev)
+    sc = torch.empty(B, num, dtype=torch.float32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    check(lib.gim_dense_emit_pairs(_p(sparse), _p(mconf), _p(geom), _p(k0), _p(k1), _p(sc), _p(count), B, num, int(bool(rescale)), _stream()),
+          "gim_dense_emit_pairs")
+    return k0, k1, sc, count

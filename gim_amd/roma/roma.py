@@ -151,6 +151,7 @@ class RegressionMatcher(DenseMatcher):
         if tuple(state_dict["pos_embed"].shape) != (1, VIT_GRID ** 2 + 1, VIT_DIM):
             raise GimHipError(f"DINOv2 weights: pos_embed {tuple(state_dict['pos_embed'].shape)} is not ViT-L/14 @518")
         self._dino[0] = {k: state_dict[k].detach().float().cpu() for k in need}
+        self._epoch += 1
         self._fp16_checked = False
         self._packed = None
         self._tables = {}
@@ -322,36 +323,66 @@ class RegressionMatcher(DenseMatcher):
         """GP.forward (dense.gp_posterior): a32 fp32 rows [nb*hw (+64 slack), 512] -> mu into `out` (row view [nb*hw, 512])"""
         gp_posterior(a32, nb, h, w, self._gp_features(h, w, a32.device), out, self._gp_is_exact())
 
-    def _coarse(self, P, dt, feat16):
-        """scale 16 of Decoder.forward (roma.py:263-296): proj -> GP -> TransformerDecoder -> cls_to_flow_refine
-        -> (projected features a [nb,h,w,512], flow [nb,h,w,2], certainty [nb,h,w,1])"""
+    def _coarse(self, P, dt, a32, nb, h, w):
+        """scale 16 of Decoder.forward behind its projection (roma.py:263-296): a32 = the fp32 proj16 rows [nb*hw + 64 slack, 512] of
+        the stacked pair batch -> GP -> TransformerDecoder -> cls_to_flow_refine -> (flow [nb,h,w,2], certainty [nb,h,w,1])"""
         tdt = torch_dtype(dt)
-        nb, h, w, _ = feat16.shape
-        n, dev = h * w, feat16.device
-        a32 = self._project(P, dt, feat16, "16", out32=True)
+        n, dev = h * w, a32.device
         x32 = torch.empty(nb * n, DEC_DIM, dtype=torch.float32, device=dev)
         self._gp(a32, nb, h, w, x32[:, :GP_DIM])
         ops.cast_rows(a32[:nb * n], x32[:, GP_DIM:])                       # tokens = cat(gp_posterior, features)
-        if dt == GIM_F32:
-            a = a32[:nb * n].view(nb, h, w, 512)
-        else:
-            a = torch.empty(nb, h, w, 512, dtype=tdt, device=dev)
-            ops.cast_rows(a32[:nb * n], a.view(nb * n, 512))
         wsp = _Workspace(nb, n, DEC_DIM, tdt, dev)
         for i in range(DEC_BLOCKS):
             self._vit_block(P, f"dec{i}.", x32, wsp, nb, n, DEC_HEADS, 1e-5)
         ops.cast_rows(x32, wsp.xn)
         logits = torch.empty(nb * n, P["to_out"].n_store, dtype=torch.float32, device=dev)
         ops.linear(wsp.xn, P["to_out"], logits)
-        flow, cert = ops.cls_to_flow(logits, nb, h, w, CLS_RES ** 2)
-        return a, flow, cert
+        return ops.cls_to_flow(logits, nb, h, w, CLS_RES ** 2)
 
     def _refine(self, P, s, dt, x, y, flow, cert, ins, full_hw, scale_factor):
         refine(P, s, dt, x, y, flow, cert, ins, full_hw, REFINER[s], self.refiner_fused, emb_scale=40.0 / 32.0 * scale_factor,
                roma_layout=True)
 
-    def _decode(self, P, dt, f1, upsample=False, flow=None, cert=None, scale_factor=1.0):
-        """Decoder.forward on the symmetric pair (f2 = f1 with the two images swapped) -> {scale: (flow, certainty)}"""
+    support_names = ("lo1", "lo2", "lo4", "lo8", "a16", "hi1", "hi2", "hi4", "hi8")
+    slack_names = ("a32_16",)
+
+    def _tag_extra(self):
+        return (id(self._dino[0]),)
+
+    def _state(self, P, dt, im1, im2, after_low=None):
+        """everything match_batch computes from one image alone, for the images of im1 (and im2 behind them): {kind: [nb, ...]}
+          lo1 / lo2 / lo4 / lo8     proj[s] of the low-resolution VGG levels -- what the refiners read, smaller than what it projects
+          a32_16                    proj16 of the DINOv2 tokens as fp32 rows (GP and decoder tokens; `.rows`: with the 64 slack rows)
+          a16                       the same at the module's precision (refiner 16)
+          hi1 / hi2 / hi4 / hi8     proj[s] of the upsampling pass's VGG levels
+          black                     the black-pixel mask of the match() tail at the output resolution"""
+        tdt = torch_dtype(dt)
+        st = {}
+        feats = self._encode(P, dt, self._images(dt, im1, im2, self.h_resized, self.w_resized))
+        for sc in (1, 2, 4, 8):
+            st[f"lo{sc}"] = self._project(P, dt, feats[sc], str(sc))
+        nb, h, w, _ = feats[16].shape
+        a32 = self._project(P, dt, feats[16], "16", out32=True)
+        st["a32_16"], st["a32_16.rows"] = a32[:nb * h * w].view(nb, h * w, 512), a32
+        if dt == GIM_F32:
+            st["a16"] = a32[:nb * h * w].view(nb, h, w, 512)
+        else:
+            st["a16"] = torch.empty(nb, h, w, 512, dtype=tdt, device=a32.device)
+            ops.cast_rows(a32[:nb * h * w], st["a16"].view(nb * h * w, 512))
+        del feats
+        if after_low is not None:
+            after_low(st)
+        if self.upsample_preds:
+            feats = self._encode(P, dt, self._images(dt, im1, im2, *self.upsample_res), upsample=True)
+            for sc in (1, 2, 4, 8):
+                st[f"hi{sc}"] = self._project(P, dt, feats[sc], str(sc))
+        st["black"] = self._black([im1] if im2 is None else [im1, im2], *self._out_size())
+        return st
+
+    def _decode(self, P, dt, f1, upsample=False, flow=None, cert=None, scale_factor=1.0, a32=None, sup=None):
+        """Decoder.forward on the symmetric pair (f2 = f1 with the two images swapped) -> {scale: (flow, certainty)}.  f1: per scale
+        the PROJECTED features the refiner reads, a32: the fp32 proj16 rows of `_coarse`, sup: f1 in support order (match_features
+        gathers it; None: the two halves of f1 are swapped with a copy)"""
         scales = ["8", "4", "2", "1"] if upsample else ["16", "8", "4", "2", "1"]
         sizes = {s: tuple(f1[s].shape[1:3]) for s in f1}
         full = sizes[1]
@@ -364,26 +395,24 @@ class RegressionMatcher(DenseMatcher):
         out = {}
         for s in scales:
             ins = int(s)
+            a = f1[ins]
             if s == "16":
-                a, flow, cert = self._coarse(P, dt, f1[16])
+                flow, cert = self._coarse(P, dt, a32, nb, *sizes[16])
                 out["gm"] = (flow.clone(), cert.clone())
-            else:
-                a = self._project(P, dt, f1[ins], s)
-            self._refine(P, s, dt, a, torch.cat((a[half:], a[:half])), flow, cert, ins, full, scale_factor)
+            y = sup[ins] if sup is not None else torch.cat((a[half:], a[:half]))
+            self._refine(P, s, dt, a, y, flow, cert, ins, full, scale_factor)
             out[ins] = (flow, cert)
             if s != "1":
                 flow = ops.resize_bilinear(flow, sizes[ins // 2])
                 cert = ops.resize_bilinear(cert, sizes[ins // 2])
         return out
 
-    @torch.no_grad()
-    def match_batch(self, ims_A, ims_B):
-        """B independent pairs in one pass ([B,3,H,W] x 2 -> warp [B,Hs,2Ws,4], certainty [B,Hs,2Ws]); result b equals
-        `match(ims_A[b:b+1], ims_B[b:b+1])` (the engine's batching, like gim_amd.dkm)."""
-        P, dt, im1, im2 = self._enter(ims_A, ims_B)
-        B, dev = im1.shape[0], im1.device
+    def _match_state(self, P, dt, q, sup, B, pending):
+        dev = q["lo1"].device
         hs, ws = self.h_resized, self.w_resized
-        cor = self._decode(P, dt, self._encode(P, dt, self._images(dt, im1, im2, hs, ws)))
+        f1 = {1: q["lo1"], 2: q["lo2"], 4: q["lo4"], 8: q["lo8"], 16: q["a16"]}
+        y1 = None if sup is None else {1: sup["lo1"], 2: sup["lo2"], 4: sup["lo4"], 8: sup["lo8"], 16: sup["a16"]}
+        cor = self._decode(P, dt, f1, a32=q["a32_16.rows"], sup=y1)
         stages = {"low": cor}
         if self.upsample_preds:
             hs, ws = self.upsample_res
@@ -393,16 +422,23 @@ class RegressionMatcher(DenseMatcher):
             low = torch.zeros(2 * B, hs, ws, 1, dtype=torch.float32, device=dev)
         if self.upsample_preds:
             sf = math.sqrt(self.upsample_res[0] * self.upsample_res[1] / (self.w_resized * self.h_resized))
-            pyr_hi = self._encode(P, dt, self._images(dt, im1, im2, hs, ws), upsample=True)
-            cor = self._decode(P, dt, pyr_hi, upsample=True, flow=cor[1][0], cert=cor[1][1], scale_factor=sf)
+            f1 = {sc: q[f"hi{sc}"] for sc in (1, 2, 4, 8)}
+            y1 = None if sup is None else {sc: sup[f"hi{sc}"] for sc in (1, 2, 4, 8)}
+            cor = self._decode(P, dt, f1, upsample=True, flow=cor[1][0], cert=cor[1][1], scale_factor=sf, sup=y1)
             stages["high"] = cor
         flow, cert = cor[1]
-        warp, certainty = self._finish(im1, im2, flow, cert, low, hs, ws)
+        warp, certainty = self._finish_state(q["black"], flow, cert, low, hs, ws)
         self._debug = stages
-        # fp16 as the DEFAULT mode carries a range check of what it hands out (an explicit precision='fp16' is the caller's decision):
-        # every stored activation of this engine sits behind a BatchNorm / LayerNorm, so an overflow needs pathological weights -- it then
-        # surfaces as inf / nan in the flow or certainty logits (no ReLU between the refiners' last convolution and these outputs).  One
-        # reduction + host sync on the first calls after a weight change; a trip switches the module to bf16 for good and re-runs the batch
+        return warp, certainty
+
+    def _after_match(self, out, again):
+        """fp16 as the DEFAULT mode carries a range check of what it hands out (an explicit precision='fp16' is the caller's decision):
+        every stored activation of this engine sits behind a BatchNorm / LayerNorm, so an overflow needs pathological weights -- it then
+        surfaces as inf / nan in the flow or certainty logits (no ReLU between the refiners' last convolution and these outputs).  One
+        reduction + host sync on the first calls after a weight change; a trip switches the module to bf16 for good and runs the call
+        again (`again`: match_batch re-encodes; match_features finds its bank stale -- the precision is part of the tag -- and raises,
+        the caller extracts again)."""
+        warp, certainty = out
         if self._fp16_default and self.precision == "fp16" and not self._fp16_checked:
             if bool(torch.isfinite(warp).all()) and bool(torch.isfinite(certainty).all()):
                 self._fp16_checked = True
@@ -410,7 +446,7 @@ class RegressionMatcher(DenseMatcher):
                 import warnings
                 warnings.warn("gim_amd RoMa: non-finite outputs in the default fp16 mode (activations beyond 65504?); switching this module to bf16")
                 self.precision, self._packed = "bf16", None
-                return self.match_batch(ims_A, ims_B)
+                return again()
         return warp, certainty
 
 

@@ -850,6 +850,47 @@ int gim_agg_assign(const float* kpts0, const float* kpts1, const float* scores, 
                    int64_t total_cells, int n_kp, int rows0, int rows1, float max_error, int patch, int nearest, int32_t* matches0,
                    void* scores_f16, int32_t* row_len, void* ws, gim_stream_t stream);
 
+/* ======================================================================================================
+ * Feature bank of the dense matchers (gim_dkm, gim_roma): everything match_batch computes from one image is stored once and
+ * matched in many pairs (added within ABI revision 115: no existing structure or prototype changed with it).  The reference
+ * encodes both images of every pair (networks/dkm/models/dkm.py:572-581, networks/roma/roma.py:668-678).
+ * ====================================================================================================== */
+
+#define GIM_DENSE_MAX_LEVELS 8
+/* The level table of one gather: level l copies slot_bytes[l] bytes per entry from slab[l] (slots of slot_bytes[l] bytes) to dst[l]
+ * (n_entries blocks of slot_bytes[l] bytes).  Entries past n_levels are ignored. */
+typedef struct gim_dense_gather_args {
+    const void* slab[GIM_DENSE_MAX_LEVELS];
+    void* dst[GIM_DENSE_MAX_LEVELS];
+    int64_t slot_bytes[GIM_DENSE_MAX_LEVELS];
+    int n_levels;
+    int pad_;
+} gim_dense_gather_args;
+/* A whole pyramid of a pair batch in ONE launch: for every level l < n_levels and every entry d < n_entries, block d of dst[l]
+ * receives slot idx[d] of slab[l], as 16-byte vector loads and stores.  idx: DEVICE int32 [n_entries], read by the kernel (the host
+ * waits for nothing); an index outside [0, n_slots) skips its blocks whole -- nothing is read or written for it.  Every slab has
+ * n_slots slots; slabs and destinations are 16-byte aligned and do not overlap, slot_bytes are positive multiples of 16, 1 <=
+ * n_levels <= GIM_DENSE_MAX_LEVELS, n_entries <= 65535: anything else returns GIM_ERR_INVALID before the launch. */
+int gim_dense_gather_pairs(const gim_dense_gather_args* args, const int32_t* idx, int n_entries, int n_slots, gim_stream_t stream);
+
+/* Geometry of one pair for gim_dense_emit_pairs, all fp32 (sizes are integers below 2^24).  Side 0 / 1 = the model's first / second
+ * image, which are the caller's image1 / image0 (hloc/matchers/dkm.py:44-55 matches the pair swapped). */
+typedef struct gim_dense_pair_geom {
+    float wp0, hp0, wp1, hp1;   /* padded sizes: what the model saw */
+    float pl0, pt0, pl1, pt1;   /* left / top padding of get_padding_size */
+    float ow0, oh0, ow1, oh1;   /* sizes before padding */
+    float sx0, sy0, sx1, sy1;   /* rescale of the OUTPUT keypoints0 / keypoints1 (the caller's image0 / image1) */
+} gim_dense_pair_geom;
+/* The tail of the hloc dense plugin for B pairs in ONE launch -- hloc/matchers/dkm.py:95-150 + hloc/match_dense.py:242-243.  sparse
+ * [B][num][4] normalised matches and mconf [B][num] of RegressionMatcher.sample.  Row r of pair b is kept iff mconf > 0 and its pixel
+ * coordinates k = size_padded * (x + 1) / 2 - pad (gim_dense_to_pixels, then the un-padding) satisfy 0 < k <= original size - 1 on
+ * both axes of both sides.  Kept rows are written IN INPUT ORDER to the front of keypoints0 [B][num][2] (side 1: the caller's image0),
+ * keypoints1 [B][num][2] (side 0) and scores [B][num]; count int32 [B] = kept rows per pair; rows past count are not written.
+ * rescale != 0: every output coordinate becomes (k + 0.5) * s - 0.5.  fp32, the operations of the per-pair host path in its order,
+ * nothing contracted: the rows equal that path's bit for bit.  One workgroup per pair with a block scan; no atomics. */
+int gim_dense_emit_pairs(const float* sparse, const float* mconf, const gim_dense_pair_geom* geom, float* keypoints0, float* keypoints1,
+                         float* scores, int32_t* count, int B, int num, int rescale, gim_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
