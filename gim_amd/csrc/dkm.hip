@@ -825,7 +825,7 @@ __global__ void __launch_bounds__(256) kde_kernel(const float* __restrict__ x, f
 
 GIM_TWIN(gim_maxpool3x3s2)
 extern "C" int GIM_FN(gim_maxpool3x3s2)(const void* x, void* y, int B, int H, int W, int C, int ldx, int ldy, int dtype, gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_maxpool3x3s2, x, y, B, H, W, C, ldx, ldy, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_maxpool3x3s2, x, y, B, H, W, C, ldx, ldy, dtype, stream);
     const int G = dtype == GIM_H16 ? 8 : 4;
     GIM_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && C > 0 && C % G == 0 && ldx % G == 0 && ldy % G == 0, "maxpool3x3s2: bad args");
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
@@ -838,7 +838,7 @@ extern "C" int GIM_FN(gim_maxpool3x3s2)(const void* x, void* y, int B, int H, in
 GIM_TWIN(gim_resize_bilinear)
 extern "C" int GIM_FN(gim_resize_bilinear)(const void* x, void* y, int B, int h, int w, int Ho, int Wo, int C, int ldx, int ldy,
                                    int dtype, int out_dtype, gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16 || out_dtype == GIM_F16, gim_resize_bilinear, x, y, B, h, w, Ho, Wo, C, ldx, ldy, dtype, out_dtype, stream);
+    GIM_ROUTE_ANY2(dtype, out_dtype, gim_resize_bilinear, x, y, B, h, w, Ho, Wo, C, ldx, ldy, dtype, out_dtype, stream);
     GIM_REQUIRE(x && y && B > 0 && h > 0 && w > 0 && Ho > 0 && Wo > 0 && C > 0 && ldx >= C && ldy >= C, "resize_bilinear: bad args");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(nblocks((size_t)B * Ho * Wo * C, 256));
@@ -853,7 +853,7 @@ extern "C" int GIM_FN(gim_resize_bilinear)(const void* x, void* y, int B, int h,
 GIM_TWIN(gim_resize_image)
 extern "C" int GIM_FN(gim_resize_image)(const float* x, void* y, int B, int C, int h, int w, int Ho, int Wo, int cpad, int b_off,
                                 int out_dtype, gim_stream_t stream) {
-    GIM_TO_F16(out_dtype == GIM_F16, gim_resize_image, x, y, B, C, h, w, Ho, Wo, cpad, b_off, out_dtype, stream);
+    GIM_ROUTE_ANY(out_dtype, gim_resize_image, x, y, B, C, h, w, Ho, Wo, cpad, b_off, out_dtype, stream);
     GIM_REQUIRE(x && y && B > 0 && C > 0 && h > 0 && w > 0 && Ho > 0 && Wo > 0 && cpad >= C, "resize_image: bad args");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(nblocks((size_t)B * Ho * Wo, 256));
@@ -864,7 +864,7 @@ extern "C" int GIM_FN(gim_resize_image)(const float* x, void* y, int B, int C, i
 GIM_TWIN(gim_grid_sample)
 extern "C" int GIM_FN(gim_grid_sample)(const void* feat, const float* grid_xy, void* out, int B, int h, int w, int Ho, int Wo, int C,
                                int ldf, int ldo, int dtype, gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_grid_sample, feat, grid_xy, out, B, h, w, Ho, Wo, C, ldf, ldo, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_grid_sample, feat, grid_xy, out, B, h, w, Ho, Wo, C, ldf, ldo, dtype, stream);
     const int G = dtype == GIM_H16 ? 8 : 4;
     GIM_REQUIRE(feat && grid_xy && out && B > 0 && h > 0 && w > 0 && Ho > 0 && Wo > 0 && C > 0, "grid_sample: bad args");
     GIM_REQUIRE(C % G == 0 && ldf % G == 0 && ldo % G == 0, "grid_sample: C / strides must keep 16-byte groups (C=%d)", C);
@@ -877,7 +877,7 @@ extern "C" int GIM_FN(gim_grid_sample)(const void* feat, const float* grid_xy, v
 GIM_TWIN(gim_dkm_disp_emb)
 extern "C" int GIM_FN(gim_dkm_disp_emb)(const float* flow, const float* wgt, const float* bias, void* out, int B, int h, int w, int E,
                                 int ldo, int out_dtype, gim_stream_t stream) {
-    GIM_TO_F16(out_dtype == GIM_F16, gim_dkm_disp_emb, flow, wgt, bias, out, B, h, w, E, ldo, out_dtype, stream);
+    GIM_ROUTE_ANY(out_dtype, gim_dkm_disp_emb, flow, wgt, bias, out, B, h, w, E, ldo, out_dtype, stream);
     GIM_REQUIRE(flow && wgt && bias && out && B > 0 && h > 0 && w > 0 && E > 0 && ldo >= E, "dkm_disp_emb: bad args");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(nblocks((size_t)B * h * w * E, 256));
@@ -888,7 +888,7 @@ extern "C" int GIM_FN(gim_dkm_disp_emb)(const float* flow, const float* wgt, con
 GIM_TWIN(gim_local_corr)
 extern "C" int GIM_FN(gim_local_corr)(const void* f0, const void* f1, const float* flow, void* out, int B, int h, int w, int C, int r,
                               int ld0, int ld1, int ldo, int dtype, int out_dtype, gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16 || out_dtype == GIM_F16, gim_local_corr, f0, f1, flow, out, B, h, w, C, r, ld0, ld1, ldo, dtype, out_dtype, stream);
+    GIM_ROUTE_ANY2(dtype, out_dtype, gim_local_corr, f0, f1, flow, out, B, h, w, C, r, ld0, ld1, ldo, dtype, out_dtype, stream);
     GIM_REQUIRE(f0 && f1 && flow && out && B > 0 && h > 0 && w > 0 && C > 0 && C % 4 == 0, "local_corr: bad args");
     GIM_REQUIRE(r >= 1 && r <= 7, "local_corr: radius %d unsupported (1..7)", r);
     GIM_REQUIRE(ld0 % 4 == 0 && ld1 % 4 == 0 && ldo >= (2 * r + 1) * (2 * r + 1), "local_corr: strides");
@@ -913,7 +913,7 @@ extern "C" int GIM_FN(gim_local_corr)(const void* f0, const void* f1, const floa
 GIM_TWIN(gim_dwconv5x5_bn_relu)
 extern "C" int GIM_FN(gim_dwconv5x5_bn_relu)(const void* x, const float* wgt, const float* scale, const float* shift, void* y, int B,
                                      int H, int W, int Cin, int Cout, int cpad, int ldx, int ldy, int dtype, gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_dwconv5x5_bn_relu, x, wgt, scale, shift, y, B, H, W, Cin, Cout, cpad, ldx, ldy, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_dwconv5x5_bn_relu, x, wgt, scale, shift, y, B, H, W, Cin, Cout, cpad, ldx, ldy, dtype, stream);
     GIM_REQUIRE(x && wgt && scale && shift && y && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout % Cin == 0, "dwconv5x5: bad args");
     GIM_REQUIRE(cpad % 4 == 0 && cpad >= Cout && ldx % 4 == 0 && ldy % 4 == 0 && ldy >= cpad, "dwconv5x5: cpad / strides");
     GIM_REQUIRE((int64_t)ldx * (Cout / Cin) >= cpad, "dwconv5x5: input rows too narrow for the padded channel range");
@@ -947,7 +947,7 @@ extern "C" int GIM_FN(gim_dwconv5x5_bn_relu)(const void* x, const float* wgt, co
 GIM_TWIN(gim_dwconv5x5_pw)
 extern "C" int GIM_FN(gim_dwconv5x5_pw)(const void* x, const float* wgt, const float* scale, const float* shift, const void* pw_w, const float* pw_b, void* y,
                                        int B, int H, int W, int cs, int ldx, int ldy, int dtype, gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_dwconv5x5_pw, x, wgt, scale, shift, pw_w, pw_b, y, B, H, W, cs, ldx, ldy, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_dwconv5x5_pw, x, wgt, scale, shift, pw_w, pw_b, y, B, H, W, cs, ldx, ldy, dtype, stream);
     GIM_REQUIRE(x && wgt && scale && shift && pw_w && pw_b && y && B > 0 && H > 0 && W > 0, "dwconv5x5_pw: bad args");
     GIM_REQUIRE(dtype == GIM_H16, "dwconv5x5_pw: 16-bit operands only");
     GIM_REQUIRE((cs == 24 || cs == 32 || cs == 144) && ldx % 8 == 0 && ldx >= cs && ldy % 8 == 0 && ldy >= cs,
@@ -978,7 +978,7 @@ extern "C" int GIM_FN(gim_dwconv5x5_pw)(const void* x, const float* wgt, const f
 
 GIM_TWIN(gim_row_norms)
 extern "C" int GIM_FN(gim_row_norms)(const void* x, float* out, int rows, int C, int ld, int dtype, gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_row_norms, x, out, rows, C, ld, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_row_norms, x, out, rows, C, ld, dtype, stream);
     GIM_REQUIRE(x && out && rows > 0 && C > 0 && C % 4 == 0 && ld % 4 == 0, "row_norms: bad args");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((rows + 3) / 4);
@@ -998,7 +998,7 @@ extern "C" int gim_cos_kernel_finish(float* k, const float* nx, const float* ny,
 GIM_TWIN(gim_global_avgpool)
 extern "C" int GIM_FN(gim_global_avgpool)(const void* x, float* out, int B, int HW, int C, int ld, int ldo, int c_off, int dtype,
                                   gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_global_avgpool, x, out, B, HW, C, ld, ldo, c_off, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_global_avgpool, x, out, B, HW, C, ld, ldo, c_off, dtype, stream);
     GIM_REQUIRE(x && out && B > 0 && HW > 0 && C > 0, "global_avgpool: bad args");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((C + 63) / 64, B);
@@ -1009,7 +1009,7 @@ extern "C" int GIM_FN(gim_global_avgpool)(const void* x, float* out, int B, int 
 GIM_TWIN(gim_cab_scale_add)
 extern "C" int GIM_FN(gim_cab_scale_add)(const float* g, const void* x1, const void* x2, void* out, int B, int HW, int C, int ldg, int ld1,
                                  int ld2, int ldo, int dtype, gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_cab_scale_add, g, x1, x2, out, B, HW, C, ldg, ld1, ld2, ldo, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_cab_scale_add, g, x1, x2, out, B, HW, C, ldg, ld1, ld2, ldo, dtype, stream);
     GIM_REQUIRE(g && x2 && out && B > 0 && HW > 0 && C > 0 && C % 4 == 0 && ldg % 4 == 0 && ld2 % 4 == 0 && ldo % 4 == 0 && (!x1 || ld1 % 4 == 0), "cab_scale_add: bad args");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(nblocks((size_t)B * HW * (C / 4), 256));
@@ -1020,7 +1020,7 @@ extern "C" int GIM_FN(gim_cab_scale_add)(const float* g, const void* x1, const v
 GIM_TWIN(gim_dkm_flow_update)
 extern "C" int GIM_FN(gim_dkm_flow_update)(float* flow, float* cert, const void* d, int64_t npix, int ldd, float sx, float sy, int cert_init,
                                    int dtype, gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_dkm_flow_update, flow, cert, d, npix, ldd, sx, sy, cert_init, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_dkm_flow_update, flow, cert, d, npix, ldd, sx, sy, cert_init, dtype, stream);
     GIM_REQUIRE(flow && cert && d && npix > 0 && ldd >= 3, "dkm_flow_update: bad args");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(nblocks((size_t)npix, 256));

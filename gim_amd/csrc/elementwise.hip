@@ -188,7 +188,7 @@ inline unsigned nblocks(size_t n, int bs) { return (unsigned)((n + bs - 1) / bs)
 GIM_TWIN(gim_nchw_to_nhwc)
 extern "C" int GIM_FN(gim_nchw_to_nhwc)(const float* src, void* dst, int B, int C, int H, int W, int cpad, int ld,
                                 int b_off, int dtype, gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_nchw_to_nhwc, src, dst, B, C, H, W, cpad, ld, b_off, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_nchw_to_nhwc, src, dst, B, C, H, W, cpad, ld, b_off, dtype, stream);
     GIM_REQUIRE(src && dst && B > 0 && C > 0 && H > 0 && W > 0, "nchw_to_nhwc: bad args");
     GIM_REQUIRE(cpad % 4 == 0 && cpad >= C && ld >= cpad && ld % 4 == 0, "nchw_to_nhwc: cpad=%d ld=%d", cpad, ld);
     const size_t n = (size_t)B * H * W;
@@ -202,7 +202,7 @@ extern "C" int GIM_FN(gim_nchw_to_nhwc)(const float* src, void* dst, int B, int 
 
 GIM_TWIN(gim_nchw_to_nhwc_split)
 extern "C" int GIM_FN(gim_nchw_to_nhwc_split)(const float* src, void* dst, int B, int C, int H, int W, int ld, int b_off, int dtype, gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_nchw_to_nhwc_split, src, dst, B, C, H, W, ld, b_off, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_nchw_to_nhwc_split, src, dst, B, C, H, W, ld, b_off, dtype, stream);
     GIM_REQUIRE(src && dst && B > 0 && C > 0 && H > 0 && W > 0, "nchw_to_nhwc_split: bad args");
     GIM_REQUIRE(dtype == GIM_H16, "nchw_to_nhwc_split: 16-bit output only (dtype %d)", dtype);
     // ld >= 3 C: [hi | lo | hi | 0 ...] (the implicit-GEMM form of the split convolution); 2 C <= ld < 3 C: [hi | lo | 0 ...] (gim_stem7x7)
@@ -223,7 +223,7 @@ extern "C" int GIM_FN(gim_nchw_to_nhwc_split)(const float* src, void* dst, int B
 GIM_TWIN(gim_nhwc_to_nchw)
 extern "C" int GIM_FN(gim_nhwc_to_nchw)(const void* src, float* dst, int B, int C, int H, int W, int ld, int dtype,
                                 gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_nhwc_to_nchw, src, dst, B, C, H, W, ld, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_nhwc_to_nchw, src, dst, B, C, H, W, ld, dtype, stream);
     GIM_REQUIRE(src && dst && B > 0 && C > 0 && H > 0 && W > 0 && ld >= C, "nhwc_to_nchw: bad args");
     const int HW = H * W;
     dim3 grid((HW + 63) / 64, (C + 63) / 64, B);
@@ -236,7 +236,7 @@ extern "C" int GIM_FN(gim_nhwc_to_nchw)(const void* src, float* dst, int B, int 
 GIM_TWIN(gim_upsample2x_add)
 extern "C" int GIM_FN(gim_upsample2x_add)(const void* x, void* y, int B, int h, int w, int C, int ldx, int ldy, int dtype,
                                   gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_upsample2x_add, x, y, B, h, w, C, ldx, ldy, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_upsample2x_add, x, y, B, h, w, C, ldx, ldy, dtype, stream);
     GIM_REQUIRE(x && y && B > 0 && h > 0 && w > 0 && C > 0 && C % 4 == 0, "upsample2x_add: bad args (C=%d)", C);
     GIM_REQUIRE(ldx % 4 == 0 && ldy % 4 == 0, "upsample2x_add: ld must be a multiple of 4");
     const int G = dtype == GIM_H16 ? 8 : 4;
@@ -253,7 +253,7 @@ extern "C" int GIM_FN(gim_upsample2x_add)(const void* x, void* y, int B, int h, 
 GIM_TWIN(gim_posenc_add)
 extern "C" int GIM_FN(gim_posenc_add)(const void* x, const float* pe, float* out_f32, void* out_t, int rows, int hw, int C,
                               int ldx, int ld_f32, int ld_t, int dtype, gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_posenc_add, x, pe, out_f32, out_t, rows, hw, C, ldx, ld_f32, ld_t, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_posenc_add, x, pe, out_f32, out_t, rows, hw, C, ldx, ld_f32, ld_t, dtype, stream);
     GIM_REQUIRE(x && pe && (out_f32 || out_t) && rows > 0 && hw > 0 && C > 0 && C % 4 == 0, "posenc_add: bad args");
     GIM_REQUIRE(ldx % 4 == 0 && ld_f32 % 4 == 0 && ld_t % 4 == 0, "posenc_add: ld must be a multiple of 4");
     const size_t n = (size_t)rows * (C / 4);
@@ -269,7 +269,7 @@ GIM_TWIN(gim_layernorm_residual)
 extern "C" int GIM_FN(gim_layernorm_residual)(const void* x, const float* gamma, const float* beta, const float* res,
                                       float* out_f32, void* out_t, int rows, int C, int ldx, int ldres, int ld_f32,
                                       int ld_t, int x_dtype, int dtype, float eps, gim_stream_t stream) {
-    GIM_TO_F16(x_dtype == GIM_F16 || dtype == GIM_F16, gim_layernorm_residual, x, gamma, beta, res, out_f32, out_t, rows, C, ldx, ldres, ld_f32, ld_t, x_dtype, dtype, eps, stream);
+    GIM_ROUTE_ANY2(x_dtype, dtype, gim_layernorm_residual, x, gamma, beta, res, out_f32, out_t, rows, C, ldx, ldres, ld_f32, ld_t, x_dtype, dtype, eps, stream);
     GIM_REQUIRE(x && gamma && beta && (out_f32 || out_t) && rows > 0, "layernorm: bad args");
     GIM_REQUIRE(C > 0 && C % 4 == 0 && C <= 512, "layernorm: C=%d unsupported (multiple of 4, <= 512)", C);
     GIM_REQUIRE(ldx % 4 == 0 && ld_f32 % 4 == 0 && ld_t % 4 == 0 && (!res || ldres % 4 == 0), "layernorm: ld alignment");

@@ -90,7 +90,7 @@ extern "C" int GIM_FN(gim_fine_gather)(const void* feat_f0, const void* feat_f1,
                                const int64_t* j_ids, float* out_f32, void* out_t, int M, int hf0, int wf0, int hf1,
                                int wf1, int C, int ldf, int w0c, int w1c, int stride, int W, int ld_f32, int ld_t,
                                int dtype, gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_fine_gather, feat_f0, feat_f1, b_ids, i_ids, j_ids, out_f32, out_t, M, hf0, wf0, hf1, wf1, C, ldf, w0c, w1c, stride, W, ld_f32, ld_t, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_fine_gather, feat_f0, feat_f1, b_ids, i_ids, j_ids, out_f32, out_t, M, hf0, wf0, hf1, wf1, C, ldf, w0c, w1c, stride, W, ld_f32, ld_t, dtype, stream);
     if (M == 0) return GIM_OK;
     GIM_REQUIRE(feat_f0 && feat_f1 && b_ids && i_ids && j_ids && (out_f32 || out_t), "fine_gather: NULL pointer");
     GIM_REQUIRE(M > 0 && hf0 > 0 && wf0 > 0 && hf1 > 0 && wf1 > 0 && C > 0 && C % 4 == 0 && W > 0 && (W & 1) && stride > 0, "fine_gather: bad sizes");

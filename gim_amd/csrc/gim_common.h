@@ -72,6 +72,11 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) { return cvt
 // C function).  GIM_TO_F16 hands the call to the twin when `cond` holds; in the fp16 object it is empty.
 // GIM_ROUTE_H16 is the form of the entry points that work on one 16-bit kind only (the fused kernels): forward GIM_F16, run GIM_BF16,
 // refuse everything else -- placed FIRST in the body, so that a wrong tag never reaches a pointer check or the HIP runtime.
+// GIM_ROUTE_ANY / GIM_ROUTE_ANY2 are its counterparts for the entry points that accept GIM_F32 too (one tag / two tags), FIRST in the body
+// as well: a tag that names no kind is refused (every flavour decides with `tag == GIM_H16`, so it would run as fp32: 4-byte accesses to
+// whatever the caller's buffers are), and so is a call whose two tags name BOTH 16-bit kinds (it lands in the fp16 object, where the
+// bf16 operand counts as "not GIM_H16" = fp32: twice the bytes read or written).  Then GIM_F16 on either tag forwards to the twin.
+// GIM_TAG_ANY is the check alone, for entry points that exist in one flavour.
 #ifndef GIM_HALF_KIND
 #define GIM_HALF_KIND 0
 #endif
@@ -88,6 +93,17 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) { return cvt
 #define GIM_ROUTE_H16(dtype, name, ...)                          \
     GIM_TO_F16((dtype) == GIM_F16, name, __VA_ARGS__);           \
     GIM_REQUIRE((dtype) == GIM_H16, #name ": dtype tag %d: the 16-bit kinds GIM_BF16 / GIM_F16 only", (int)(dtype))
+inline bool gim_tag_known(int t) { return t == GIM_F32 || t == GIM_BF16 || t == GIM_F16; }
+inline bool gim_tags_one_kind(int a, int b) { return gim_tag_known(a) && gim_tag_known(b) && (a == GIM_F32 || b == GIM_F32 || a == b); }
+#define GIM_TAG_ANY(dtype, name) \
+    GIM_REQUIRE(gim_tag_known(dtype), #name ": dtype tag %d: GIM_F32 / GIM_BF16 / GIM_F16 only", (int)(dtype))
+#define GIM_ROUTE_ANY(dtype, name, ...)                          \
+    GIM_TAG_ANY(dtype, name);                                    \
+    GIM_TO_F16((dtype) == GIM_F16, name, __VA_ARGS__)
+#define GIM_ROUTE_ANY2(tag0, tag1, name, ...)                                                                                          \
+    GIM_REQUIRE(gim_tags_one_kind(tag0, tag1), #name ": dtype tags %d, %d: each GIM_F32 / GIM_BF16 / GIM_F16, and one 16-bit kind per call", \
+                (int)(tag0), (int)(tag1));                                                                                             \
+    GIM_TO_F16((tag0) == GIM_F16 || (tag1) == GIM_F16, name, __VA_ARGS__)
 typedef _Float16 gim_f16x2_t __attribute__((ext_vector_type(2)));
 typedef _Float16 gim_f16x8_t __attribute__((ext_vector_type(8)));
 typedef __attribute__((ext_vector_type(4))) float gim_f32x4v_t;

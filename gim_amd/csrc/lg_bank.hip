@@ -150,9 +150,9 @@ extern "C" int gim_lg_bank_put(const float* kpts, const float* desc, const float
 extern "C" int gim_lg_gather_pairs(const void* bank_desc, const float* bank_enc, const int32_t* idx0, const int32_t* idx1, float* x32,
                                    void* cat, float* enc, int B, int K, int n_slots, int storage, int dtype, int ld_x32, int ld_cat,
                                    gim_stream_t stream) {
+    GIM_TAG_ANY(dtype, gim_lg_gather_pairs);   // the compute dtype; one object serves every kind, nothing to route
     GIM_REQUIRE(B >= 0 && K > 0 && n_slots > 0, "lg_gather_pairs: B=%d K=%d n_slots=%d", B, K, n_slots);
     GIM_REQUIRE(storage_ok(storage), "lg_gather_pairs: storage dtype tag %d (GIM_F32 or GIM_F16)", storage);
-    GIM_REQUIRE(dtype == GIM_F32 || dtype == GIM_BF16 || dtype == GIM_F16, "lg_gather_pairs: compute dtype tag %d", dtype);
     if (B == 0) return GIM_OK;
     GIM_REQUIRE(bank_desc && bank_enc && idx0 && idx1 && x32 && enc, "lg_gather_pairs: NULL argument");
     // fp32 compute: the residual stream IS the GEMM operand (x32 aliases CAT[:, :256]) -- written once, no 16-bit copy

@@ -383,7 +383,7 @@ extern "C" int gim_lg_posenc(const float* kpts, const float* size_wh, const floa
 
 GIM_TWIN(gim_lg_rotary)
 extern "C" int GIM_FN(gim_lg_rotary)(void* x, const float* enc, int rows, int ncols, int ld, int dtype, gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_lg_rotary, x, enc, rows, ncols, ld, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_lg_rotary, x, enc, rows, ncols, ld, dtype, stream);
     GIM_REQUIRE(x && enc && rows > 0 && ncols > 0 && ncols % 64 == 0 && ld >= ncols && ld % 4 == 0, "lg_rotary: bad args");
     const size_t n = (size_t)rows * (ncols / 4);
     hipStream_t s = (hipStream_t)stream;
@@ -395,7 +395,7 @@ extern "C" int GIM_FN(gim_lg_rotary)(void* x, const float* enc, int rows, int nc
 GIM_TWIN(gim_lg_transpose)
 extern "C" int GIM_FN(gim_lg_transpose)(const void* src, void* dst, int nb, int S, int Sp, int C, int ld, int dtype,
                                 gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_lg_transpose, src, dst, nb, S, Sp, C, ld, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_lg_transpose, src, dst, nb, S, Sp, C, ld, dtype, stream);
     GIM_REQUIRE(src && dst && nb > 0 && S > 0 && Sp >= S && Sp % 64 == 0 && C > 0 && ld >= C, "lg_transpose: bad args");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(Sp / 64, (C + 63) / 64, nb);
@@ -407,7 +407,7 @@ extern "C" int GIM_FN(gim_lg_transpose)(const void* src, void* dst, int nb, int 
 GIM_TWIN(gim_cast_rows)
 extern "C" int GIM_FN(gim_cast_rows)(const float* src, void* dst, int rows, int C, int ld_src, int ld_dst, int dtype,
                              gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_cast_rows, src, dst, rows, C, ld_src, ld_dst, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_cast_rows, src, dst, rows, C, ld_src, ld_dst, dtype, stream);
     GIM_REQUIRE(src && dst && rows > 0 && C > 0 && C % 4 == 0 && ld_src % 4 == 0 && ld_dst % 4 == 0, "cast_rows: bad args");
     const size_t n = (size_t)rows * (C / 4);
     hipStream_t s = (hipStream_t)stream;
@@ -419,7 +419,7 @@ extern "C" int GIM_FN(gim_cast_rows)(const float* src, void* dst, int rows, int 
 GIM_TWIN(gim_layernorm_act)
 extern "C" int GIM_FN(gim_layernorm_act)(const float* x, const float* gamma, const float* beta, void* out, int rows, int C,
                                  int ldx, int ldo, int act, int out_dtype, float eps, gim_stream_t stream) {
-    GIM_TO_F16(out_dtype == GIM_F16, gim_layernorm_act, x, gamma, beta, out, rows, C, ldx, ldo, act, out_dtype, eps, stream);
+    GIM_ROUTE_ANY(out_dtype, gim_layernorm_act, x, gamma, beta, out, rows, C, ldx, ldo, act, out_dtype, eps, stream);
     GIM_REQUIRE(x && gamma && beta && out && rows > 0, "layernorm_act: bad args");
     GIM_REQUIRE(C > 0 && C % 4 == 0 && C <= 1024 && ldx % 4 == 0 && ldo % 4 == 0, "layernorm_act: C=%d (multiple of 4, <= 1024)", C);
     GIM_REQUIRE(act == GIM_ACT_NONE || act == GIM_ACT_GELU, "layernorm_act: act must be NONE or GELU");
@@ -436,7 +436,7 @@ extern "C" int GIM_FN(gim_layernorm_act)(const float* x, const float* gamma, con
 GIM_TWIN(gim_sdpa)
 extern "C" int GIM_FN(gim_sdpa)(const void* q, const void* k, const void* vt, void* out, int nb, int H, int L, int S, int Sp,
                         int D, int ldq, int ldk, int ldo, int kv_shift, int dtype, int out_dtype, gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16 || out_dtype == GIM_F16, gim_sdpa, q, k, vt, out, nb, H, L, S, Sp, D, ldq, ldk, ldo, kv_shift, dtype, out_dtype, stream);
+    GIM_ROUTE_ANY2(dtype, out_dtype, gim_sdpa, q, k, vt, out, nb, H, L, S, Sp, D, ldq, ldk, ldo, kv_shift, dtype, out_dtype, stream);
     GIM_REQUIRE(q && k && vt && out && nb > 0 && H > 0 && L > 0 && S > 0, "sdpa: bad args");
     GIM_REQUIRE(D == 64 || D == 128, "sdpa: head dim %d unsupported (64, 128)", D);
     GIM_REQUIRE(Sp >= S && Sp % 64 == 0, "sdpa: Sp=%d must be S rounded up to a multiple of 64", Sp);

@@ -539,7 +539,7 @@ extern "C" int64_t GIM_FN(gim_linear_attention_ws_bytes)(int nb, int S, int H, i
 GIM_TWIN(gim_linear_attention_kv)
 extern "C" int GIM_FN(gim_linear_attention_kv)(const void* k, const void* v, const uint8_t* kv_mask, float* kv_ws, int nb,
                                        int S, int H, int D, int ldk, int ldv, int dtype, gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_linear_attention_kv, k, v, kv_mask, kv_ws, nb, S, H, D, ldk, ldv, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_linear_attention_kv, k, v, kv_mask, kv_ws, nb, S, H, D, ldk, ldv, dtype, stream);
     GIM_REQUIRE(k && v && kv_ws && nb > 0 && S > 0 && H > 0, "linear_attention_kv: bad args");
     GIM_REQUIRE(D == 32 || D == 16, "linear_attention_kv: head dim %d unsupported (16 or 32)", D);
     GIM_REQUIRE(ldk % 4 == 0 && ldv % 4 == 0, "linear_attention_kv: ld alignment");
@@ -614,7 +614,7 @@ GIM_TWIN(gim_linear_attention_apply)
 extern "C" int GIM_FN(gim_linear_attention_apply)(const void* q, const uint8_t* q_mask, const float* kv_ws, void* out, int nb,
                                           int L, int S, int H, int D, int ldq, int ldo, int dtype, int out_dtype,
                                           gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16 || out_dtype == GIM_F16, gim_linear_attention_apply, q, q_mask, kv_ws, out, nb, L, S, H, D, ldq, ldo, dtype, out_dtype, stream);
+    GIM_ROUTE_ANY2(dtype, out_dtype, gim_linear_attention_apply, q, q_mask, kv_ws, out, nb, L, S, H, D, ldq, ldo, dtype, out_dtype, stream);
     GIM_REQUIRE(q && kv_ws && out && nb > 0 && L > 0 && S > 0 && H > 0, "linear_attention_apply: bad args");
     GIM_REQUIRE(D == 32 || D == 16, "linear_attention_apply: head dim %d unsupported (16 or 32)", D);
     GIM_REQUIRE(ldq % 4 == 0 && ldo % 4 == 0, "linear_attention_apply: ld alignment");
@@ -654,7 +654,7 @@ extern "C" int GIM_FN(gim_linear_attention_short)(const void* q, const void* k, 
                                           const uint8_t* kv_mask, void* out, int nb, int L, int S, int H, int D,
                                           int ldq, int ldk, int ldv, int ldo, int dtype, int out_dtype,
                                           gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16 || out_dtype == GIM_F16, gim_linear_attention_short, q, k, v, q_mask, kv_mask, out, nb, L, S, H, D, ldq, ldk, ldv, ldo, dtype, out_dtype, stream);
+    GIM_ROUTE_ANY2(dtype, out_dtype, gim_linear_attention_short, q, k, v, q_mask, kv_mask, out, nb, L, S, H, D, ldq, ldk, ldv, ldo, dtype, out_dtype, stream);
     GIM_REQUIRE(q && k && v && out && nb > 0 && L > 0 && S > 0, "linear_attention_short: bad args");
     GIM_REQUIRE(H == 8 && (D == 16 || D == 32), "linear_attention_short: needs H == 8 and D in {16, 32} (got H=%d D=%d)", H, D);
     GIM_REQUIRE(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0, "linear_attention_short: ld alignment");

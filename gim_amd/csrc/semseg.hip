@@ -168,7 +168,7 @@ __global__ void __launch_bounds__(256) seg_head_kernel(const float* __restrict__
 
 GIM_TWIN(gim_ppm_pool)
 extern "C" int GIM_FN(gim_ppm_pool)(const void* x, float* out, int B, int H, int W, int C, int ldx, int dtype, gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_ppm_pool, x, out, B, H, W, C, ldx, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_ppm_pool, x, out, B, H, W, C, ldx, dtype, stream);
     GIM_REQUIRE(x && out && B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && ldx >= C && ldx % 4 == 0, "ppm_pool: bad args");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(PPM_BINS, B, (C + 63) / 64);
@@ -180,7 +180,7 @@ extern "C" int GIM_FN(gim_ppm_pool)(const void* x, float* out, int B, int H, int
 GIM_TWIN(gim_ppm_upsample_concat)
 extern "C" int GIM_FN(gim_ppm_upsample_concat)(const float* br, void* y, int B, int h, int w, int Cb, int ldy, int c_off, int dtype,
                                                gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_ppm_upsample_concat, br, y, B, h, w, Cb, ldy, c_off, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_ppm_upsample_concat, br, y, B, h, w, Cb, ldy, c_off, dtype, stream);
     GIM_REQUIRE(br && y && B > 0 && h > 0 && w > 0 && Cb > 0 && Cb % 4 == 0 && c_off >= 0 && c_off % 4 == 0 && ldy % 4 == 0 &&
                 c_off + 4 * Cb <= ldy, "ppm_upsample_concat: bad args");
     hipStream_t s = (hipStream_t)stream;

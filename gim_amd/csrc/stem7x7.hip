@@ -145,9 +145,11 @@ extern "C" int64_t gim_stem7x7_weight_bytes(int split) { return split ? StemCfg<
 GIM_TWIN(gim_stem7x7)
 extern "C" int GIM_FN(gim_stem7x7)(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int split, int dtype,
                                    int out_dtype, gim_stream_t stream) {
+    // operands of one 16-bit kind, output of either (the bf16 mode reads an fp16 image and writes bf16): nothing else, before anything else
+    GIM_REQUIRE((dtype == GIM_BF16 || dtype == GIM_F16) && (out_dtype == GIM_BF16 || out_dtype == GIM_F16),
+                "gim_stem7x7: dtype tags %d, %d: 16-bit operands and output only (GIM_BF16 / GIM_F16)", dtype, out_dtype);
     GIM_TO_F16(dtype == GIM_F16, gim_stem7x7, x, w, bias, y, B, H, W, split, dtype, out_dtype, stream);
     GIM_REQUIRE(x && w && bias && y && B > 0 && H > 0 && W > 0, "stem7x7: bad args");
-    GIM_REQUIRE(dtype == GIM_H16 && (out_dtype == GIM_BF16 || out_dtype == GIM_F16), "stem7x7: 16-bit operands and output only (dtype %d -> %d)", dtype, out_dtype);
     GIM_REQUIRE((int64_t)B * H * W * 16 < (int64_t)0xFFFFFFF0ll, "stem7x7: image batch too large for 32-bit buffer offsets");
     Args a;
     a.x = x; a.w = w; a.bias = bias; a.y = y; a.B = B; a.H = H; a.W = W;

@@ -308,7 +308,7 @@ __global__ void __launch_bounds__(256) sp_sample_desc_kernel(const void* __restr
 GIM_TWIN(gim_maxpool2x2)
 extern "C" int GIM_FN(gim_maxpool2x2)(const void* x, void* y, int B, int H, int W, int C, int ldx, int ldy, int dtype,
                               gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_maxpool2x2, x, y, B, H, W, C, ldx, ldy, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_maxpool2x2, x, y, B, H, W, C, ldx, ldy, dtype, stream);
     const int G = dtype == GIM_H16 ? 8 : 4;
     GIM_REQUIRE(x && y && B > 0 && H > 1 && W > 1 && C > 0 && C % G == 0, "maxpool2x2: bad args (C=%d)", C);
     GIM_REQUIRE(ldx % G == 0 && ldy % G == 0, "maxpool2x2: row strides must keep 16-byte groups aligned");
@@ -322,7 +322,7 @@ extern "C" int GIM_FN(gim_maxpool2x2)(const void* x, void* y, int B, int H, int 
 GIM_TWIN(gim_sp_scores)
 extern "C" int GIM_FN(gim_sp_scores)(const void* logits, float* scores, int B, int h, int w, int ld, int dtype,
                              gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_sp_scores, logits, scores, B, h, w, ld, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_sp_scores, logits, scores, B, h, w, ld, dtype, stream);
     GIM_REQUIRE(logits && scores && B > 0 && h > 0 && w > 0 && ld >= 65, "sp_scores: bad args");
     const int cells = B * h * w;
     hipStream_t s = (hipStream_t)stream;
@@ -386,7 +386,7 @@ GIM_TWIN(gim_sp_sample_desc)
 extern "C" int GIM_FN(gim_sp_sample_desc)(const void* dense, const float* kpts, float* out_f32, void* out_t, int B, int K,
                                   int h, int w, int C, int ld, int ld_f32, int ld_t, int cell, int dtype,
                                   gim_stream_t stream) {
-    GIM_TO_F16(dtype == GIM_F16, gim_sp_sample_desc, dense, kpts, out_f32, out_t, B, K, h, w, C, ld, ld_f32, ld_t, cell, dtype, stream);
+    GIM_ROUTE_ANY(dtype, gim_sp_sample_desc, dense, kpts, out_f32, out_t, B, K, h, w, C, ld, ld_f32, ld_t, cell, dtype, stream);
     GIM_REQUIRE(dense && kpts && (out_f32 || out_t) && B > 0 && K > 0 && h > 1 && w > 1, "sp_sample_desc: bad args");
     GIM_REQUIRE(C == 256 && ld % 4 == 0 && ld_f32 % 4 == 0 && ld_t % 4 == 0, "sp_sample_desc: C must be 256, strides % 4");
     hipStream_t s = (hipStream_t)stream;

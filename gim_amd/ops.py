@@ -993,6 +993,8 @@ def sdpa(q, k, vt, out, nb, H, L, S, Sp, kv_shift=0, D=64):
     """q row view [nb*L, ..], k row view [nb*S, ..], vt [nb, H*D, Sp], out row view [nb*L, ..]; head dim D in {64, 128}"""
     _req_cuda(q, k, vt, out)
     assert q.dtype == k.dtype == vt.dtype
+    # one 16-bit kind per call (the library routes by it): out is fp32 or of q's kind -- or anything, next to fp32 operands
+    assert torch.float32 in (q.dtype, out.dtype) or out.dtype == q.dtype, f"sdpa: {q.dtype} operands with a {out.dtype} output"
     check(lib.gim_sdpa(_p(q), _p(k), _p(vt), _p(out), nb, H, L, S, Sp, D, q.stride(0), k.stride(0), out.stride(0),
                        kv_shift, gim_dtype(q), gim_dtype(out), _stream()), "gim_sdpa")
 

@@ -33,7 +33,10 @@ typedef void* gim_stream_t; /* hipStream_t */
  * `out_dtype` / `feat_dtype` argument or struct field) and the library routes the call to its bf16 or its IEEE-fp16 build of the kernel;
  * no per-dtype symbol is part of this ABI.  The fused kernels (gim_bneck64_fused*, gim_bneck_tail*, gim_token_mlp*, gim_fine_fused*)
  * work on ONE 16-bit kind -- tensors and packed weights alike -- named by their `dtype`: GIM_BF16 or GIM_F16; any other tag returns
- * GIM_ERR_INVALID before a pointer is looked at or the device is touched. */
+ * GIM_ERR_INVALID before a pointer is looked at or the device is touched.  The entry points that take their tag(s) as `int` arguments
+ * and accept GIM_F32 too refuse, in the same place and the same way, a tag that is none of the three and -- with two tags -- a call that
+ * names BOTH 16-bit kinds (a 16-bit tag next to GIM_F32 is the mixed-precision form, e.g. gim_sdpa with fp16 operands and an fp32
+ * output).  gim_stem7x7 alone takes the two 16-bit kinds side by side (fp16 image -> bf16 activations) and refuses GIM_F32. */
 enum { GIM_F32 = 0, GIM_BF16 = 1, GIM_F16 = 2 };
 enum { GIM_ACT_NONE = 0, GIM_ACT_RELU = 1, GIM_ACT_LEAKY = 2, GIM_ACT_ELU1 = 3 /* elu(x)+1 */, GIM_ACT_GELU = 4 /* exact erf GELU */ };
 enum { GIM_OK = 0, GIM_ERR_INVALID = -1, GIM_ERR_LAUNCH = -2, GIM_ERR_UNSUPPORTED = -3 };

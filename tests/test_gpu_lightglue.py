@@ -4,7 +4,21 @@ reference's own modules (tests/golden/lg_*.npz).
 
 Bars: keypoint coordinates, arg-max / match indices: exact in fp32 mode (fp32 MFMA); floats 2e-5 of the
 output scale in fp32 mode (summation order only); bf16 mode: 6.5e-3 = 2 x the largest value measured on MI355X (3.2e-3 of scale, one
-bf16 output rounding; profiles/r04_secondary_measured.txt -- the bound was 1.5e-2 ... 2.5e-2 through round 3)."""
+bf16 output rounding; profiles/r04_secondary_measured.txt -- the bound was 1.5e-2 ... 2.5e-2 through round 3); fp16 kernels: the bf16
+bar / 6 (three more significand bits; tests/test_gpu_dkm.py::_t16) = 1.08e-3 of scale.  For sdpa that bar rests on the fp64 emulation of
+the kernel's own roundings (_attention64 with kinds: P and the output rounded where the kernel rounds them), which the tests assert to
+stay below HALF of it on their inputs.
+
+Largest fraction of scale measured on MI355X per kernel, bf16 / fp16 (bars 6.5e-3 / 1.08e-3 unless noted):
+  sdpa D=64, all of test_sdpa*          3.24e-3 (2048 x 2048) / 4.09e-4 (256 x 128)   -- equal to the emulation to 3 digits: the kernel
+                                        adds nothing measurable to its roundings
+  sdpa 16-bit operands -> fp32 out      6.7e-4, 9.2e-4 (D=128) / 8.4e-5, 9.9e-5 (D=128)
+  sdpa fp32 operands -> 16-bit out      2.6e-3 / 3.1e-4
+  sdpa late maximum (keys 195, 70)      0 / 0 (the output is v[planted], a 16-bit value); fp32 8.2e-8
+  layernorm_act (bars 5e-3 / 8.3e-4)    2.2e-3 / 3.5e-4
+  lg_rotary vs the once-rounded fp64    5.6e-5 / 1.1e-4 of scale; 5.9e-5 / 3.9e-5 of the elements differ at all (one unit)
+  maxpool2x2, lg_transpose, cast_rows, sp_sample_desc's out_t: bit-exact; fp32 outputs (bars 2e-6), any kind: sp_scores 5.4e-7, sp_sample_desc 5.0e-7."""
+import math
 import os
 
 import numpy as np
@@ -15,7 +29,8 @@ import torch.nn.functional as F
 import lightglue_oracle as O
 
 pytestmark = pytest.mark.gpu
-DTS = ["fp32", "bf16"]
+DTS = ["fp32", "bf16", "fp16"]   # fp16: the IEEE-fp16 flavour of every kernel (GIM_HALF_KIND = 1 objects)
+H16 = ["bf16", "fp16"]
 
 
 def _dev():
@@ -24,11 +39,16 @@ def _dev():
 
 
 def _tdt(dt):
-    return torch.bfloat16 if dt == "bf16" else torch.float32
+    return {"bf16": torch.bfloat16, "fp16": torch.float16}.get(dt, torch.float32)
+
+
+def _t16(dt, bf16_tol, fp32_tol):
+    """tolerance of a kernel test by operand kind (tests/test_gpu_dkm.py): fp16 keeps 3 more significand bits than bf16"""
+    return {"bf16": bf16_tol, "fp16": bf16_tol / 6}.get(dt, fp32_tol)
 
 
 def _tol(dt):
-    return 6.5e-3 if dt == "bf16" else 2e-5
+    return _t16(dt, 6.5e-3, 2e-5)
 
 
 def _close(got, ref, tol, what=""):
@@ -117,20 +137,25 @@ def test_sp_topk_ties_and_plateau():
     assert kpts[0, 1:].tolist() == exp
 
 
-@pytest.mark.parametrize("dt", ["fp32"])
+@pytest.mark.parametrize("dt", DTS)
 def test_sp_sample_desc(dt):
+    """the dense map in every kind (the 16-bit ld4), both outputs at once: out_f32 against the oracle on the rounded map, out_t = out_f32
+    rounded once to the kind, in rows wider than 256 whose padding stays untouched"""
     from gim_amd import ops
     dev = _dev()
     g = torch.Generator().manual_seed(5)
     B, h, w, K = 2, 8, 12, 70
-    dense = torch.randn(B, 256, h, w, generator=g)
+    dense = torch.randn(B, 256, h, w, generator=g).to(_tdt(dt)).float()
     kp = torch.stack([torch.randint(0, w * 8, (B, K), generator=g), torch.randint(0, h * 8, (B, K), generator=g)], -1).float()
     kp[0, 0] = torch.tensor([0.0, 0.0]); kp[0, 1] = torch.tensor([w * 8 - 1.0, h * 8 - 1.0])   # outside the sample grid
     ref = O.sample_descriptors_legacy(kp.clone(), F.normalize(dense, p=2, dim=1), 8).transpose(-1, -2)
-    rows = dense.permute(0, 2, 3, 1).reshape(B * h * w, 256).contiguous().to(dev)
+    rows = dense.permute(0, 2, 3, 1).reshape(B * h * w, 256).contiguous().to(_tdt(dt)).to(dev)
     out = torch.empty(B * K, 256, device=dev)
-    ops.sp_sample_desc(rows, kp.to(dev), h, w, out, None)
+    out_t = torch.full((B * K, 320), 7.0, dtype=_tdt(dt), device=dev)
+    ops.sp_sample_desc(rows, kp.to(dev), h, w, out, out_t[:, :256])
     _close(out.view(B, K, 256), ref, 2e-6, "sample_desc")
+    assert torch.equal(out_t[:, :256], out.to(_tdt(dt)))
+    assert (out_t[:, 256:] == 7.0).all()
 
 
 # ------------------------------------------------------------------------------------------- LightGlue pieces
@@ -156,6 +181,41 @@ def test_posenc_rotary():
     assert torch.equal(x.view(B, K, 768)[..., 512:].cpu(), q[..., 512:])
 
 
+@pytest.mark.parametrize("dt", H16)
+def test_rotary_16bit(dt):
+    """lg_rotary in place on 16-bit rows (ElemIO ld4 / st4) vs the fp64 rotation of the same 16-bit values with the kernel's own fp32
+    cos / sin table, rounded ONCE to the kind.  The kernel rounds its fp32 result a second time: it lands on the neighbouring 16-bit value
+    only when the exact one lies within the fp32 error (three roundings of 2^-24) of a tie of a grid 2^13 (fp16) / 2^16 (bf16) times
+    coarser -- the same formula in torch fp32 on the CPU differs from the once-rounded value in 2.1e-4 (fp16) / 0.8e-4 (bf16) of 51200
+    elements, so at most 0.1 % may differ at all, and those by one unit of the kind (inside the 16-bit bar of the file).  Columns
+    [512, 768) and, on the row view with ld = 1024, everything outside the view: bit-identical."""
+    from gim_amd import ops
+    dev = _dev()
+    _, lg = O.make_state_dicts(0)
+    g = torch.Generator().manual_seed(6)
+    B, K = 2, 50
+    kp = torch.rand(B, K, 2, generator=g) * torch.tensor([640.0, 480.0])
+    size = torch.tensor([[640.0, 480.0], [500.0, 480.0]])
+    enc = ops.lg_posenc(kp.to(dev), size.to(dev), lg["posenc.Wr.weight"].to(dev))      # [B*K, 64] = cos | sin, pinned by test_posenc_rotary
+    q = torch.randn(B * K, 768, generator=g).to(_tdt(dt))
+    t = q.double()[:, :512].reshape(B * K, 8, 32, 2)
+    c, s_ = enc.cpu().double()[:, None, :32], enc.cpu().double()[:, None, 32:]
+    rot = torch.stack([t[..., 0] * c - t[..., 1] * s_, t[..., 1] * c + t[..., 0] * s_], -1).reshape(B * K, 512)
+    ref = torch.cat([rot.to(_tdt(dt)), q[:, 512:]], 1)
+    x = q.clone().to(dev)
+    ops.lg_rotary(x, enc, 512)
+    wide = torch.full((B * K, 1024), 7.0, dtype=_tdt(dt), device=dev)
+    wide[:, 128:896] = q.to(dev)
+    ops.lg_rotary(wide[:, 128:896], enc, 512)
+    for got, what in ((x.cpu(), f"rotary {dt}"), (wide[:, 128:896].cpu(), f"rotary {dt} ld=1024")):
+        _close(got[:, :512], ref[:, :512], _tol(dt), what)
+        differ = (got[:, :512] != ref[:, :512]).float().mean().item()
+        print(f"[differ] {what}: {differ:.2e} of the elements are not the once-rounded value")
+        assert differ <= 1e-3, (what, differ)
+        assert torch.equal(got[:, 512:], q[:, 512:])
+    assert (wide[:, :128] == 7.0).all() and (wide[:, 896:] == 7.0).all()
+
+
 @pytest.mark.parametrize("dt", DTS)
 def test_transpose_and_cast(dt):
     from gim_amd import ops
@@ -173,6 +233,69 @@ def test_transpose_and_cast(dt):
     out = torch.empty(40, 512, dtype=_tdt(dt), device=dev)
     ops.cast_rows(x.to(dev), out[:, :256])
     assert torch.equal(out[:, :256].float().cpu(), x.to(_tdt(dt)).float())
+
+
+def _rnd(x, dt):
+    return x if dt == "fp32" else x.to(_tdt(dt)).double()
+
+
+def _attention64(qq, kk, vv, D, dt_in="fp32", dt_out="fp32"):
+    """softmax(q k^T / sqrt(D)) v in fp64 on [..., L / S, D] operands.  With the defaults: the exact result.  With kinds: the roundings
+    of the kernel ON TOP of it -- 16-bit operands make it round P to their kind for the second MFMA (the row sum keeps the unrounded
+    P), a 16-bit output is rounded once -- i.e. what a kernel without any error of its own returns."""
+    sc = qq @ kk.transpose(-1, -2) / math.sqrt(D)
+    p = torch.exp(sc - sc.amax(-1, keepdim=True))
+    return _rnd(_rnd(p, dt_in) @ vv / p.sum(-1, keepdim=True), dt_out)
+
+
+def _sdpa_tol(dt_in, dt_out):
+    """1e-5 of scale between fp32 operands and an fp32 output, else the 16-bit bar of the 16-bit kind involved"""
+    return _t16(dt_in if dt_in != "fp32" else dt_out, 6.5e-3, 1e-5)
+
+
+def _sdpa_check(out, qq, kk, vv, D, dt_in, dt_out, what):
+    """out rows [nb*L, H*D] vs the fp64 attention of qq / kk / vv [nb, H, L / S, D] (fp64 copies of the kernel's operands); the
+    emulated roundings alone must stay below HALF the bar, so that a change of inputs cannot quietly eat the margin for real errors"""
+    nb, H, L, _ = qq.shape
+    ref = _attention64(qq, kk, vv, D)
+    tol = _sdpa_tol(dt_in, dt_out)
+    if (dt_in, dt_out) != ("fp32", "fp32"):
+        emu = (_attention64(qq, kk, vv, D, dt_in, dt_out) - ref).abs().max().item() / ref.abs().max().item()
+        print(f"[emulated] {what}: roundings alone {emu:.3e} of scale (half the bar: {tol / 2:g})")
+        assert emu < tol / 2, (what, emu, tol)
+    _close(out, ref.transpose(1, 2).reshape(nb * L, H * D).float(), tol, what)
+
+
+def _heads(x, nb, n, H, D, shift=0):
+    """rows [nb*n, H*D] -> fp64 [nb, H, n, D], sequences rolled the way kv_shift pairs them"""
+    return x.double().reshape(nb, n, H, D).transpose(1, 2).roll(-shift, 0)
+
+
+def _sdpa_run(q, k, v, nb, H, D, L, S, dt_out, shift=0, ld=None, extra_rows=3):
+    """q [nb*L, H*D], k / v [nb*S, H*D]: CPU tensors of the operand kind.  V^T goes into a buffer of NaNs (the padding keys must be
+    zeros lg_transpose wrote), q / k / out are column windows of buffers with row strides `ld` (default: H*D + 64), out's buffer is
+    `extra_rows` longer: everything of it outside the window must keep its sentinel.  -> out [nb*L, H*D] on the device"""
+    from gim_amd import ops
+    dev = _dev()
+    C = H * D
+    Sp = (S + 63) // 64 * 64
+    vt = torch.full((nb, C, Sp), float("nan"), dtype=q.dtype, device=dev)
+    ops.lg_transpose(v.to(dev), vt, nb, S, Sp, C)
+    views = []
+    for t, w, fill, rows in ((q, (ld or (C + 64,) * 3)[0], 0.0, nb * L), (k, (ld or (C + 64,) * 3)[1], 0.0, nb * S),
+                             (None, (ld or (C + 64,) * 3)[2], 7.0, nb * L + extra_rows)):
+        buf = torch.full((rows, w), fill, dtype=_tdt(dt_out) if t is None else t.dtype, device=dev)
+        off = (w - C) // 2 // 8 * 8
+        if t is not None:
+            buf[:, off:off + C] = t.to(dev)
+        views.append((buf, off))
+    (qb, qo), (kb, ko), (ob, oo) = views
+    out = ob[:nb * L, oo:oo + C]
+    ops.sdpa(qb[:, qo:qo + C], kb[:, ko:ko + C], vt, out, nb, H, L, S, Sp, kv_shift=shift, D=D)
+    rest = ob.clone()
+    rest[:nb * L, oo:oo + C] = 7.0
+    assert (rest == 7.0).all(), "sdpa wrote outside its nb*L rows / H*D columns"
+    return out
 
 
 @pytest.mark.parametrize("dt", DTS)
@@ -198,7 +321,106 @@ def test_sdpa(dt, L, S, cross):
     kk = kv.double()[:, 256:512].reshape(nb, S, H, 64).transpose(1, 2).roll(-shift, 0)
     vv = kv.double()[:, 512:].reshape(nb, S, H, 64).transpose(1, 2).roll(-shift, 0)
     ref = (torch.softmax(qq @ kk.transpose(-1, -2) / 8.0, -1) @ vv).transpose(1, 2).reshape(nb * L, 256)
-    _close(out, ref.float(), 1e-5 if dt == "fp32" else 6.5e-3, f"sdpa L={L} S={S}")
+    _close(out, ref.float(), _t16(dt, 6.5e-3, 1e-5), f"sdpa L={L} S={S}")
+    if dt != "fp32":   # the fp16 bar leaves the kernel half of itself: the roundings of an error-free kernel stay below the other half
+        emu = (_attention64(qq, kk, vv, 64, dt, dt).transpose(1, 2).reshape(nb * L, 256) - ref).abs().max().item() / ref.abs().max().item()
+        print(f"[emulated] sdpa {dt} L={L} S={S}: roundings alone {emu:.3e} of scale")
+        # (bf16: printed only -- its bar is 2 x the MEASURED error, and at 2048 x 2048 the emulation sits at 3.24e-3, half of it)
+        assert dt == "bf16" or emu < _t16(dt, 6.5e-3, 1e-5) / 2, emu
+
+
+def _qkv(nb, L, S, C, dt, seed, ksharp=2.0):
+    g = torch.Generator().manual_seed(seed)
+    q = torch.randn(nb * L, C, generator=g).to(_tdt(dt))
+    k = (ksharp * torch.randn(nb * S, C, generator=g)).to(_tdt(dt))
+    v = torch.randn(nb * S, C, generator=g).to(_tdt(dt))
+    return q, k, v
+
+
+@pytest.mark.parametrize("D,L,S", [(64, 100, 77), (128, 80, 80)])
+@pytest.mark.parametrize("dt_in,dt_out", [("fp16", "fp32"), ("bf16", "fp32"), ("fp32", "fp16"), ("fp32", "bf16")])
+def test_sdpa_mixed_kinds(dt_in, dt_out, D, L, S):
+    """launch_sdpa<true, false, D> (16-bit operands, fp32 output) and <false, true, D> (fp32 operands and MFMA, 16-bit output), in the
+    flavour the 16-bit tag routes to"""
+    nb, H = 2, 256 // D
+    q, k, v = _qkv(nb, L, S, H * D, dt_in, 14, 2.0 if D == 64 else 1.5)
+    out = _sdpa_run(q, k, v, nb, H, D, L, S, dt_out)
+    assert out.dtype == _tdt(dt_out)
+    _sdpa_check(out, _heads(q, nb, L, H, D), _heads(k, nb, S, H, D), _heads(v, nb, S, H, D), D, dt_in, dt_out,
+                f"sdpa {dt_in}->{dt_out} D={D}")
+
+
+@pytest.mark.parametrize("dt", ["fp32", "fp16"])
+@pytest.mark.parametrize("L,S", [(128, 64), (129, 65), (127, 63), (256, 128), (1, 1)])
+def test_sdpa_tile_edges(dt, L, S):
+    """L on / one past / one short of the 128-query workgroup tile, S of the 64-key tile; the padding keys of V^T are the zeros of
+    lg_transpose (the buffer held NaNs), the rows behind nb*L and the columns beside H*D keep their sentinel (_sdpa_run)"""
+    nb, H, D = 2, 2, 64
+    q, k, v = _qkv(nb, L, S, H * D, dt, 15)
+    out = _sdpa_run(q, k, v, nb, H, D, L, S, dt, shift=1)
+    _sdpa_check(out, _heads(q, nb, L, H, D), _heads(k, nb, S, H, D, 1), _heads(v, nb, S, H, D, 1), D, dt, dt, f"sdpa {dt} edge L={L} S={S}")
+
+
+@pytest.mark.parametrize("dt", ["fp32", "fp16"])
+@pytest.mark.parametrize("shift", [1, 2])
+def test_sdpa_kv_shift_wraps(dt, shift):
+    """sequence s attends to sequence (s + kv_shift) % nb: nb = 3, so that both shifts wrap at a different sequence"""
+    nb, H, D, L, S = 3, 4, 64, 100, 77
+    q, k, v = _qkv(nb, L, S, H * D, dt, 16)
+    out = _sdpa_run(q, k, v, nb, H, D, L, S, dt, shift=shift)
+    _sdpa_check(out, _heads(q, nb, L, H, D), _heads(k, nb, S, H, D, shift), _heads(v, nb, S, H, D, shift), D, dt, dt,
+                f"sdpa {dt} nb=3 kv_shift={shift}")
+
+
+@pytest.mark.parametrize("dt", ["fp32", "fp16"])
+def test_sdpa_strides_and_16_heads(dt):
+    """q, k and out in three buffers with three row strides (1536 / 1280 / 1096), 16 heads of 64: DINOv2's geometry"""
+    nb, H, D, L, S = 1, 16, 64, 70, 130
+    q, k, v = _qkv(nb, L, S, H * D, dt, 17)
+    out = _sdpa_run(q, k, v, nb, H, D, L, S, dt, ld=(1536, 1280, 1096))
+    assert (out.stride(0), out.shape) == (1096, (L, 1024))
+    _sdpa_check(out, _heads(q, nb, L, H, D), _heads(k, nb, S, H, D), _heads(v, nb, S, H, D), D, dt, dt, f"sdpa {dt} H=16 strided")
+
+
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("planted", [195, 70])
+def test_sdpa_late_maximum(dt, planted):
+    """the online-softmax rescale: one key per head beats every other score of every query by more than 20 (after the 1 / sqrt(D)
+    scale), and it arrives in the LAST tile, which holds 8 valid keys of 64 (key 195 of 200: the rescale branch next to the -inf
+    masking), or in tile 1 of 4 (key 70).  Everything accumulated before it must shrink by exp(-20) or more: a rescale that is
+    skipped, or applied to one half of the lanes only, leaves the output orders of magnitude away from v[planted]."""
+    nb, H, D, L, S = 1, 4, 64, 130, 200
+    g = torch.Generator().manual_seed(18)
+    u = F.normalize(torch.randn(H, D, generator=g), dim=-1)                       # one direction per head
+    q = (torch.randn(L, H, D, generator=g) + 24.0 * u).reshape(L, H * D).to(_tdt(dt))
+    k = torch.randn(S, H, D, generator=g)
+    k[:192] *= 0.25
+    k[planted] = 16.0 * u
+    k = k.reshape(S, H * D).to(_tdt(dt))
+    v = torch.randn(S, H * D, generator=g).to(_tdt(dt))
+    qq, kk, vv = _heads(q, nb, L, H, D), _heads(k, nb, S, H, D), _heads(v, nb, S, H, D)
+    sc = qq @ kk.transpose(-1, -2) / 8.0
+    others = sc.clone()
+    others[..., planted] = -math.inf
+    margin = (sc[..., planted] - others.amax(-1)).min().item()
+    assert margin > 20.0, margin
+    out = _sdpa_run(q, k, v, nb, H, D, L, S, dt)
+    _sdpa_check(out, qq, kk, vv, D, dt, dt, f"sdpa {dt} late maximum at key {planted} (margin {margin:.1f})")
+
+
+def test_sdpa_refuses_two_16bit_kinds():
+    """fp16 operands with a bf16 output: refused in Python before any launch (the library refuses the tags too: GIM_ROUTE_ANY2,
+    tests/test_dtype_dispatch_cpu.py); out keeps its sentinel"""
+    from gim_amd import ops
+    dev = _dev()
+    nb, H, L, S, Sp = 1, 4, 8, 8, 64
+    q = torch.randn(nb * L, 256, dtype=torch.float16, device=dev)
+    vt = torch.zeros(nb, 256, Sp, dtype=torch.float16, device=dev)
+    out = torch.full((nb * L, 256), 7.0, dtype=torch.bfloat16, device=dev)
+    with pytest.raises(AssertionError):
+        ops.sdpa(q, q, vt, out, nb, H, L, S, Sp)
+    torch.cuda.synchronize()
+    assert (out == 7.0).all()
 
 
 @pytest.mark.parametrize("dt", DTS)
@@ -214,7 +436,7 @@ def test_layernorm_gelu(dt):
         ops.layernorm_act(x.to(dev), gamma.to(dev), beta.to(dev), out, act)
         ref = F.layer_norm(x, (512,), gamma, beta)
         ref = F.gelu(ref) if act == ACT_GELU else ref
-        _close(out, ref, 5e-3 if dt == "bf16" else 2e-6, "layernorm_act")
+        _close(out, ref, _t16(dt, 5e-3, 2e-6), "layernorm_act")
 
 
 def _assign_inputs(B, M, N, seed):

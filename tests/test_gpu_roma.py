@@ -2,7 +2,12 @@
 inputs and against the golden vectors recorded from the reference's own modules (tests/golden/roma_*.npz).
 
 Bars: fp32 mode 2e-5 of the output scale for single kernels (summation order only), 1e-4 for the stages of the
-whole pipeline; bf16 kernels 6.5e-3 = 2 x the largest measured error (profiles/r04_secondary_measured.txt)."""
+whole pipeline; bf16 kernels 6.5e-3 = 2 x the largest measured error (profiles/r04_secondary_measured.txt); fp16 kernels -- gim_roma's
+default precision -- the bf16 bar / 6 (tests/test_gpu_dkm.py::_t16) = 1.08e-3 of scale, of which the emulated roundings of an error-free
+sdpa (_attention64) are asserted to take less than half.
+
+Largest fraction of scale measured on MI355X, bf16 / fp16: sdpa D=128 2.5e-3 / 3.0e-4 (= the emulation to 3 digits); layernorm 1024
+3.0e-3 / 3.4e-4; linear + GELU epilogue (bars 5.5e-3 / 9.2e-4) 2.6e-3 / 3.2e-4; dkm_flow_update in RoMa layout 0 / 0 (fp32 bar 1e-6)."""
 import math
 import os
 
@@ -14,7 +19,7 @@ import torch.nn.functional as F
 import roma_oracle as O
 
 pytestmark = pytest.mark.gpu
-DTS = ["fp32", "bf16"]
+DTS = ["fp32", "bf16", "fp16"]   # fp16: gim_roma's default precision (gim_amd/precision.py), the GIM_HALF_KIND = 1 objects
 
 
 def _dev():
@@ -23,7 +28,21 @@ def _dev():
 
 
 def _tdt(dt):
-    return torch.bfloat16 if dt == "bf16" else torch.float32
+    return {"bf16": torch.bfloat16, "fp16": torch.float16}.get(dt, torch.float32)
+
+
+def _t16(dt, bf16_tol, fp32_tol):
+    """tolerance of a kernel test by operand kind (tests/test_gpu_dkm.py): fp16 keeps 3 more significand bits than bf16"""
+    return {"bf16": bf16_tol, "fp16": bf16_tol / 6}.get(dt, fp32_tol)
+
+
+def _attention64(qq, kk, vv, D, dt="fp32"):
+    """softmax(q k^T / sqrt(D)) v in fp64; with a 16-bit kind: plus the roundings of an error-free kernel (P to the kind for the
+    second MFMA while the row sum keeps the unrounded P, the output once) -- tests/test_gpu_lightglue.py::_attention64"""
+    rnd = (lambda x: x) if dt == "fp32" else (lambda x: x.to(_tdt(dt)).double())
+    sc = qq @ kk.transpose(-1, -2) / math.sqrt(D)
+    p = torch.exp(sc - sc.amax(-1, keepdim=True))
+    return rnd(rnd(p) @ vv / p.sum(-1, keepdim=True))
 
 
 def _close(got, ref, tol, what=""):
@@ -59,7 +78,11 @@ def test_sdpa_head_dim_128(dt, L, S):
     kk = q.double()[:, C:2 * C].reshape(nb, S, H, D).transpose(1, 2)
     vv = q.double()[:, 2 * C:].reshape(nb, S, H, D).transpose(1, 2)
     ref = (torch.softmax(qq @ kk.transpose(-1, -2) / math.sqrt(D), -1) @ vv).transpose(1, 2).reshape(nb * L, C)
-    _close(out, ref.float(), 1e-5 if dt == "fp32" else 6.5e-3, f"sdpa D=128 L={L}")
+    _close(out, ref.float(), _t16(dt, 6.5e-3, 1e-5), f"sdpa D=128 L={L}")
+    if dt != "fp32":   # the fp16 bar leaves the kernel half of itself: the roundings of an error-free kernel stay below the other half
+        emu = (_attention64(qq, kk, vv, D, dt).transpose(1, 2).reshape(nb * L, C) - ref).abs().max().item() / ref.abs().max().item()
+        print(f"[emulated] sdpa {dt} D=128 L={L}: roundings alone {emu:.3e} of scale")
+        assert dt == "bf16" or emu < _t16(dt, 6.5e-3, 1e-5) / 2, emu   # bf16: printed only, its bar is 2 x the MEASURED error
 
 
 @pytest.mark.parametrize("dt", DTS)
@@ -72,14 +95,14 @@ def test_layernorm_1024(dt):
     gamma, beta = 1 + 0.1 * torch.randn(1024, generator=g), 0.1 * torch.randn(1024, generator=g)
     out = torch.empty(77, 1024, dtype=_tdt(dt), device=dev)
     ops.layernorm_act(x.to(dev), gamma.to(dev), beta.to(dev), out, ACT_NONE, eps=1e-6)
-    _close(out, F.layer_norm(x, (1024,), gamma, beta, 1e-6), 6.5e-3 if dt == "bf16" else 2e-6, "layernorm 1024")
+    _close(out, F.layer_norm(x, (1024,), gamma, beta, 1e-6), _t16(dt, 6.5e-3, 2e-6), "layernorm 1024")
 
 
 @pytest.mark.parametrize("dt", DTS)
 def test_linear_gelu_epilogue(dt):
     """exact (erf) GELU in the igemm epilogue: fc1 of the ViT MLPs"""
     from gim_amd import ops
-    from gim_amd._lib import ACT_GELU, GIM_BF16, GIM_F32
+    from gim_amd._lib import ACT_GELU, GIM_BF16, GIM_F16, GIM_F32
     from gim_amd.packing import pack_conv
     dev = _dev()
     g = torch.Generator().manual_seed(10)
@@ -87,11 +110,11 @@ def test_linear_gelu_epilogue(dt):
     x = torch.randn(333, 256, generator=g).to(tdt)
     w = (torch.randn(512, 256, generator=g) / 16).to(tdt)
     b = torch.randn(512, generator=g)
-    pk = pack_conv(w.float(), None, GIM_BF16 if dt == "bf16" else GIM_F32, dev, bias=b)
+    pk = pack_conv(w.float(), None, {"bf16": GIM_BF16, "fp16": GIM_F16}.get(dt, GIM_F32), dev, bias=b)
     y = torch.empty(333, pk.n_store, dtype=tdt, device=dev)
     ops.linear(x.to(dev), pk, y, ACT_GELU)
     ref = F.gelu(x.double() @ w.double().t() + b.double()).float()
-    _close(y[:, :512], ref, 5.5e-3 if dt == "bf16" else 2e-5, "linear+gelu")
+    _close(y[:, :512], ref, _t16(dt, 5.5e-3, 2e-5), "linear+gelu")
 
 
 def test_cls_to_flow():
