@@ -212,6 +212,9 @@ PROTOTYPES = {
     # feature bank of the dense matchers: a pair list from per-image state (added within ABI revision 115)
     "gim_dense_gather_pairs": (c_int, [ctypes.POINTER(DenseGatherArgs), c_void_p, c_int, c_int, c_void_p]),
     "gim_dense_emit_pairs": (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_void_p]),
+    # RegressionMatcher.sample for a batch of pairs, no host read (added within ABI revision 115)
+    "gim_balanced_sample_pairs_ws_bytes": (c_int64, [c_int] * 3),
+    "gim_balanced_sample_pairs": (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_float, c_int, c_void_p]),
 }
 
 

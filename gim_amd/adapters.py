@@ -125,9 +125,9 @@ class HlocDenseMatcher(torch.nn.Module):
     @torch.no_grad()
     def match_pairs(self, bank, pairs, batch_pairs=1, scales=None):
         """`forward` for a list of pairs [(key0, key1)] of images stored with `bank_put`: per batch of `batch_pairs` pairs one
-        `match_features`, the net's `sample()` per pair (seeds from torch's CPU generator in pair order, exactly as single calls draw
-        them), ONE gim_dense_emit_pairs for the tail and one read of the counts.  Returns one {'keypoints0', 'keypoints1', 'scores',
-        'batch_indexes'} per pair, equal to `forward`'s.  scales: None, or per pair ((sx, sy) of key0, (sx, sy) of key1) -- the
+        `match_features`, ONE `sample_batch` (seeds from torch's CPU generator in pair order, exactly as single `sample()` calls draw
+        them; its rows are theirs), ONE gim_dense_emit_pairs for the tail and one read of the counts -- the only host read of a batch.
+        Returns one {'keypoints0', 'keypoints1', 'scores', 'batch_indexes'} per pair, equal to `forward`'s.  scales: None, or per pair ((sx, sy) of key0, (sx, sy) of key1) -- the
         keypoints then carry the rescale of dense_sfm.match_dense_pair_list, (k + 0.5) * s - 0.5."""
         pairs = list(pairs)
         bp = max(1, min(int(batch_pairs), self.net.max_batch))
@@ -139,13 +139,7 @@ class HlocDenseMatcher(torch.nn.Module):
             slots = bank.slots([k1 for _, k1 in chunk] + [k0 for k0, _ in chunk])    # raises for an image that is not resident
             geos = [(bank.meta[k1], bank.meta[k0]) for k0, k1 in chunk]
             warp, cert = self.net.match_features(bank, slots[:B], slots[B:])
-            samples = [self.net.sample(warp[b], cert[b], self.num_samples) for b in range(B)]
-            num = max(1, max(m.shape[0] for _, m in samples))
-            sparse = torch.zeros(B, num, 4, dtype=torch.float32, device=warp.device)
-            mconf = torch.zeros(B, num, dtype=torch.float32, device=warp.device)    # rows past a pair's samples: rejected by mconf > 0
-            for b, (sm, mc) in enumerate(samples):
-                sparse[b, :sm.shape[0]].copy_(sm)
-                mconf[b, :mc.shape[0]].copy_(mc)
+            sparse, mconf, _ = self.net.sample_batch(warp, cert, self.num_samples)  # rows past a pair's samples are zero: rejected by mconf > 0
             rows = [pair_geometry_row(g0, g1, *(scales[lo + b] if scales is not None else ((1.0, 1.0), (1.0, 1.0))))
                     for b, (g0, g1) in enumerate(geos)]
             k0, k1, sc, count = ops.dense_emit_pairs(sparse, mconf, ops.dense_pair_geometry(rows, warp.device), rescale=scales is not None)

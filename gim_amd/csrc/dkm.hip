@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "gim_common.h"
+#include "sample_common.h"
 
 namespace {
 
@@ -777,42 +778,14 @@ __global__ void black_mask_kernel(const float* __restrict__ im, uint8_t* __restr
     mask[p] = (im[o] < 0.03125f) && (im[hw + o] < 0.03125f) && (im[2 * hw + o] < 0.03125f);
 }
 
-// kde (utils/kde.py:17-26): density[i] = sum_j exp(-|x_i - x_j|^2 / (2 std^2)), x [n,4]; j tiles staged in LDS
-__device__ __forceinline__ float4 round_half4(float4 v) {
-    return make_float4((float)(_Float16)v.x, (float)(_Float16)v.y, (float)(_Float16)v.z, (float)(_Float16)v.w);
-}
-
-// One block = 64 query points; its 4 waves split the j range (chunks of 64 points, chunk c -> wave c % 4), each staging its
-// chunk in its own LDS slice (wave-local: no block barrier in the loop), partial sums combined in a fixed order.  The first
-// version ran 256 queries per block with the whole block walking all j: 79 blocks for 20 000 samples -- a quarter of the CUs,
-// one wave per SIMD, 1.6 ms per call; exp via v_exp_f32 (relative error ~1e-6 on a sum of 20 000 terms).
+// kde (utils/kde.py:17-26): density[i] = sum_j exp(-|x_i - x_j|^2 / (2 std^2)), x [n,4]; j tiles staged in LDS.  The body is kde_block
+// (sample_common.h), shared with the batched sampler of sample_pairs.hip: one summation order for both
 __global__ void __launch_bounds__(256) kde_kernel(const float* __restrict__ x, float* __restrict__ density, int n, float inv2s2, int half) {
     __shared__ float4 tile[4][64];
     __shared__ float part[4][64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + lane;
-    float4 xi = i < n ? *(const float4*)(x + (size_t)i * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    if (half) xi = round_half4(xi);
-    const float c = -inv2s2 * 1.4426950408889634f;      // exp(-d2 * inv2s2) = exp2(d2 * c)
-    float acc = 0.f;
-    for (int j0 = wv * 64; j0 < n; j0 += 256) {
-        const int j = j0 + lane;
-        float4 xj = j < n ? *(const float4*)(x + (size_t)j * 4) : make_float4(1e18f, 1e18f, 1e18f, 1e18f);
-        if (half && j < n) xj = round_half4(xj);
-        tile[wv][lane] = xj;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // wave-local LDS hand-off
-        const int m = min(64, n - j0);
-#pragma unroll 8
-        for (int k = 0; k < m; ++k) {
-            const float4 v = tile[wv][k];
-            const float dx = xi.x - v.x, dy = xi.y - v.y, dz = xi.z - v.z, dw = xi.w - v.w;
-            acc += __builtin_amdgcn_exp2f(((dx * dx + dy * dy) + (dz * dz + dw * dw)) * c);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // all reads done before the slice is overwritten
-    }
-    part[wv][lane] = acc;
-    __syncthreads();
-    if (wv == 0 && i < n) density[i] = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
+    const int i = blockIdx.x * 64 + (threadIdx.x & 63);
+    const float d = kde_block(x, n, inv2s2, half, blockIdx.x, tile, part);
+    if ((threadIdx.x >> 6) == 0 && i < n) density[i] = d;
 }
 
 }  // namespace

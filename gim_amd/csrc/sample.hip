@@ -10,6 +10,7 @@
 // function of (weights, seed) only: keys tied with the threshold key are taken by ascending index (tie list + one
 // small sorting workgroup), not in atomic arrival order.
 #include "gim_common.h"
+#include "sample_common.h"
 
 namespace {
 
@@ -21,31 +22,13 @@ struct WsState {       // device-side state of the radix select
 };
 constexpr int TIE_CAP = 4096;  // tie list capacity (entries beyond it fall back to arrival order)
 
-__device__ __forceinline__ unsigned hash32(unsigned x) {  // murmur3 finaliser
-    x ^= x >> 16; x *= 0x85ebca6bu; x ^= x >> 13; x *= 0xc2b2ae35u; x ^= x >> 16;
-    return x;
-}
-
 __global__ void __launch_bounds__(256) ws_keys_kernel(const float* __restrict__ w, unsigned* __restrict__ keys, unsigned* __restrict__ hist,
                                                       int n, unsigned seed) {
     __shared__ unsigned h[4096];
     for (int i = threadIdx.x; i < 4096; i += 256) h[i] = 0u;
     __syncthreads();
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const float wi = w[i];
-        unsigned key = 0u;
-        if (wi > 0.f) {
-            const unsigned r = hash32(hash32((unsigned)i ^ (seed * 0x9e3779b9u)) + seed);
-            // 23 random bits + half an ulp: every value is exactly representable and strictly inside (0, 1)
-            // ((r >> 8) + 0.5 needs 25 bits at the top end and rounds up to 1.0 -> e = 0 -> key = +inf)
-            const float u = ((float)(r >> 9) + 0.5f) * (1.0f / 8388608.0f);
-            const float e = -logf(u);
-            // > 0: bit order = value order.  The floor keeps a subnormal weight drawable: wi / e rounds to 0 for wi = 1.4e-45 and
-            // e > 2 (subnormals are kept, the division is IEEE), key 0 is never taken by ws_compact_kernel, and a caller that counts
-            // the weight as positive (balanced_sample: k = n_pos) would get an output whose tail was never written.  Floored keys
-            // tie and go by ascending index like every tie
-            key = max(__float_as_uint(wi / e), 1u);
-        }
+        const unsigned key = ws_key(w[i], (unsigned)i, seed);   // sample_common.h: the batched sampler computes the same key
         keys[i] = key;
         atomicAdd(&h[key >> 20], 1u);
     }

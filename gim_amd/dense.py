@@ -391,6 +391,35 @@ class DenseMatcher(nn.Module):
         from torch's generator), the balanced-sampling density is the HIP KDE kernel; samples come back as an unordered set."""
         return balanced_sample(dense_matches, dense_certainty, num, self.sample_mode, self.sample_thresh, kde_half=self.kde_half)
 
+    @torch.no_grad()
+    def sample_batch(self, dense_matches, dense_certainty, num=10000):
+        """`sample()` of B pairs at once: dense_matches [B,H,2W,4], dense_certainty [B,H,2W] (what `match_batch` / `match_features`
+        return) -> (sparse [B,num,4], mconf [B,num], count int32 [B]), all on the device and with no synchronisation.  Pair b's first
+        count[b] rows are the rows of `sample(dense_matches[b], dense_certainty[b], num)`, bit for bit and in its order; the rows behind
+        them are zero (mconf 0).  The seeds are drawn from torch's CPU generator as B successive `sample()` calls draw them, so
+        `torch.manual_seed` reproduces the batch and leaves the generator where those calls leave it.  One fixed launch sequence per
+        ops.SAMPLE_MAX_PAIRS pairs (gim_balanced_sample_pairs); the workspace is kept on the module per (B, n, num)."""
+        if "threshold" not in self.sample_mode or "balanced" not in self.sample_mode:
+            raise NotImplementedError("gim uses sample_mode='threshold_balanced' (DKMv3.py:5, roma.py:645)")
+        if dense_certainty.dim() != 3 or dense_matches.shape != dense_certainty.shape + (4,) or dense_certainty.shape[0] < 1:
+            raise GimHipError(f"sample_batch takes matches [B,H,2W,4] and certainty [B,H,2W], got {tuple(dense_matches.shape)} / "
+                              f"{tuple(dense_certainty.shape)}")
+        B, dev = dense_certainty.shape[0], dense_certainty.device
+        n = dense_certainty[0].numel()
+        seeds = [torch.randint(0, 2 ** 31 - 1, (2,)).tolist() for _ in range(B)]     # pair order: the stream of B sample() calls
+        sparse = torch.empty(B, num, 4, dtype=torch.float32, device=dev)
+        mconf = torch.empty(B, num, dtype=torch.float32, device=dev)
+        count = torch.empty(B, dtype=torch.int32, device=dev)
+        cache = self.__dict__.setdefault("_sample_ws", {})
+        for lo in range(0, B, ops.SAMPLE_MAX_PAIRS):
+            hi = min(B, lo + ops.SAMPLE_MAX_PAIRS)
+            key = (hi - lo, n, num, str(dev))
+            if key not in cache:
+                cache[key] = torch.empty(ops.balanced_sample_pairs_ws_bytes(hi - lo, n, num), dtype=torch.uint8, device=dev)
+            ops.balanced_sample_pairs(dense_matches[lo:hi], dense_certainty[lo:hi], seeds[lo:hi], num, self.sample_thresh, self.kde_half,
+                                      ws=cache[key], out=(sparse[lo:hi], mconf[lo:hi], count[lo:hi]))
+        return sparse, mconf, count
+
 
 @torch.no_grad()
 def balanced_sample(dense_matches, dense_certainty, num, sample_mode, sample_thresh, kde_half):

@@ -3,6 +3,7 @@ the allocator / stream owner).  Every function launches HIP kernels from `gim_am
 has a torch or CPU fallback."""
 import collections
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -1349,6 +1350,70 @@ def weighted_sample(w, k, seed, ws=None, out=None):
     assert out.dtype == torch.int64 and out.shape == (k,) and out.is_contiguous(), (out.dtype, out.shape)
     check(lib.gim_weighted_sample(_p(w), _p(out), _p(ws), n, k, seed & 0xffffffff, _stream()), "gim_weighted_sample")
     return out
+
+
+SAMPLE_MAX_PAIRS = 16    # GIM_SAMPLE_MAX_PAIRS of include/gim_hip.h
+
+
+def balanced_sample_pairs_ws_bytes(B, n, num):
+    return lib.gim_balanced_sample_pairs_ws_bytes(B, n, num)
+
+
+def balanced_sample_pairs_layout(B, n, num):
+    """the workspace of gim_balanced_sample_pairs as include/gim_hip.h documents it: region name -> (byte offset, dtype, shape),
+    plus "bytes" -> the total.  `state` rows are int32 [16]: n_pos (as counted), k1, k2, then scratch."""
+    npad, K1 = (n + 3) // 4 * 4, min(4 * num, n)
+    nb1, nb2 = (n + 2047) // 2048, (K1 + 2047) // 2048
+    out, off = {}, 0
+    for name, dt, shape in (("keys1", torch.int32, (B, npad)), ("rows", torch.float32, (B, K1, 4)), ("rowcert", torch.float32, (B, K1)),
+                            ("density", torch.float32, (B, K1)), ("keys2", torch.int32, (B, K1)), ("blocks1", torch.int32, (B, nb1, 2)),
+                            ("blocks2", torch.int32, (B, nb2, 2)), ("hist", torch.int32, (B, 4096)), ("state", torch.int32, (B, 16))):
+        out[name] = (off, dt, shape)
+        off += (4 * math.prod(shape) + 255) // 256 * 256
+    out["bytes"] = off
+    return out
+
+
+def balanced_sample_pairs_region(ws, B, n, num, name):
+    """one region of a workspace `balanced_sample_pairs` has filled, as a tensor view (keys as int32 bit patterns)"""
+    off, dt, shape = balanced_sample_pairs_layout(B, n, num)[name]
+    return ws.view(torch.uint8).reshape(-1)[off:off + 4 * math.prod(shape)].view(dt).reshape(shape)
+
+
+def balanced_sample_pairs(matches, cert, seeds, num, thresh, kde_half, ws=None, out=None):
+    """`balanced_sample` of B pairs in one fixed launch sequence with no synchronisation (gim_balanced_sample_pairs): matches [B,n,4]
+    (or [B,H,W2,4]) and cert [B,n] (or [B,H,W2]) fp32 contiguous, seeds: B pairs of ints (host) -> (sparse [B,num,4], mconf [B,num],
+    count int32 [B]) on the device.  Pair b's first count[b] rows are what balanced_sample(matches[b], cert[b], num, ...) returns when
+    its generator draws seeds[b], bit for bit and in its order; the rows behind them are zero.  1 <= B <= SAMPLE_MAX_PAIRS.
+    ws: caller's workspace (uint8, >= balanced_sample_pairs_ws_bytes(B, n, num) bytes); out: caller's (sparse, mconf, count)."""
+    _req_cuda(matches, cert, ws)
+    for t, what in ((matches, "matches"), (cert, "certainty")):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.GimHipError(f"balanced_sample_pairs: {what} must be contiguous fp32, got {t.dtype}, strides {t.stride()}")
+    B = cert.shape[0]
+    n = cert[0].numel() if B else 0
+    if cert.dim() < 2 or matches.shape != cert.shape + (4,) or not 1 <= B <= SAMPLE_MAX_PAIRS or n == 0:
+        raise _lib.GimHipError(f"balanced_sample_pairs: matches {tuple(matches.shape)} / certainty {tuple(cert.shape)} "
+                               f"(1 <= B <= {SAMPLE_MAX_PAIRS})")
+    flat = [int(v) & 0xffffffff for pair in seeds for v in pair]
+    if len(flat) != 2 * B or num < 1:
+        raise _lib.GimHipError(f"balanced_sample_pairs: {len(flat)} seeds for {B} pairs, num = {num}")
+    sd = (ctypes.c_uint32 * (2 * B))(*flat)
+    need = balanced_sample_pairs_ws_bytes(B, n, num)
+    dev = cert.device
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    assert ws.is_contiguous() and ws.numel() * ws.element_size() >= need, (ws.shape, ws.dtype, need)
+    if out is None:
+        out = (torch.empty(B, num, 4, dtype=torch.float32, device=dev), torch.empty(B, num, dtype=torch.float32, device=dev),
+               torch.empty(B, dtype=torch.int32, device=dev))
+    sparse, mconf, count = out
+    assert sparse.shape == (B, num, 4) and mconf.shape == (B, num) and count.shape == (B,)
+    assert sparse.dtype == mconf.dtype == torch.float32 and count.dtype == torch.int32
+    assert sparse.is_contiguous() and mconf.is_contiguous() and count.is_contiguous()
+    check(lib.gim_balanced_sample_pairs(_p(matches), _p(cert), ctypes.cast(sd, ctypes.c_void_p), _p(sparse), _p(mconf), _p(count), _p(ws),
+                                        B, n, int(num), float(thresh), int(bool(kde_half)), _stream()), "gim_balanced_sample_pairs")
+    return sparse, mconf, count
 
 
 def dense_to_pixels(matches, hw0, hw1):

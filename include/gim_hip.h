@@ -894,6 +894,37 @@ typedef struct gim_dense_pair_geom {
 int gim_dense_emit_pairs(const float* sparse, const float* mconf, const gim_dense_pair_geom* geom, float* keypoints0, float* keypoints1,
                          float* scores, int32_t* count, int B, int num, int rescale, gim_stream_t stream);
 
+/* RegressionMatcher.sample (dkm.py:583-620, roma.py:680-714; sample_mode 'threshold_balanced') for B pairs in one fixed launch
+ * sequence, with no host read: what gim_amd.dense.balanced_sample does per pair with gim_weighted_sample, gim_kde and torch.sort.
+ * matches [B][n][4] and certainty [B][n] are the maps of `match`, flattened (n = H * 2W); seeds: HOST uint32 [B][2], the seeds of a
+ * pair's two draws (passed to the kernels by value).  Per pair b:
+ *   w = certainty > thresh ? 1 : certainty;  n_pos = #(w > 0);  if n_pos == 0: w += 1e-8 and n_pos = n;
+ *   first draw:  k1 = min(4 * num, n, n_pos) rows without replacement with probability ~ w (the keys of gim_weighted_sample from
+ *                seeds[b][0] and the flat index), kept in ASCENDING FLAT INDEX;
+ *   density = kde(rows, std 0.1) (kde_half: on fp16-rounded coordinates), p = density < 10 ? 1e-7 : 1 / (density + 1);
+ *   second draw: k2 = min(num, k1) of those rows with probability ~ p (keys from seeds[b][1] and the row's rank), in ascending rank.
+ * sparse [B][num][4] / mconf [B][num] (the un-thresholded certainty) hold the k2 rows, ZERO behind them; count int32 [B] = k2.  Every
+ * element of the three outputs is written.  The rows are those of the per-pair path for the same seeds, bit for bit and in its order.
+ * Keys tied with a draw's threshold key are taken by ascending index, however many there are (the per-pair path falls back to
+ * arrival order behind 4096 ties; there the two paths may differ).
+ * 1 <= B <= GIM_SAMPLE_MAX_PAIRS, n > 0, num > 0, no NULL pointer, sparse 16-byte aligned: anything else returns GIM_ERR_INVALID
+ * before a launch.
+ * Workspace (gim_balanced_sample_pairs_ws_bytes, 256-byte aligned base), consecutive regions, each rounded up to 256 bytes, with
+ * np = n rounded up to 4, K1 = min(4 * num, n), nb1 = ceil(n / 2048), nb2 = ceil(K1 / 2048):
+ *   keys1   uint32 [B][np]     first-draw keys (0: weight <= 0), as gim_weighted_sample leaves them
+ *   rows    float  [B][K1][4]  first-draw rows, k1[b] valid
+ *   rowcert float  [B][K1]     their certainties
+ *   density float  [B][K1]     their KDE densities
+ *   keys2   uint32 [B][K1]     second-draw keys
+ *   blocks1 int32  [B][nb1][2] scan scratch of the first draw
+ *   blocks2 int32  [B][nb2][2] scan scratch of the second draw
+ *   hist    uint32 [B][4096]   radix-select histogram
+ *   state   int32  [B][16]     n_pos (as counted, before the n_pos == 0 replacement), k1, k2, then scratch */
+#define GIM_SAMPLE_MAX_PAIRS 16
+int64_t gim_balanced_sample_pairs_ws_bytes(int B, int n, int num);
+int gim_balanced_sample_pairs(const float* matches, const float* certainty, const uint32_t* seeds, float* sparse, float* mconf,
+                              int32_t* count, void* ws, int B, int n, int num, float thresh, int kde_half, gim_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
