@@ -202,6 +202,8 @@ PROTOTYPES = {
     "gim_nn_match_pairs_ws_bytes": (c_int64, [c_int] * 2),
     "gim_nn_match_pairs": (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_float] + [c_void_p] * 3 + [c_int] + [c_void_p] * 4),
     "gim_fine_tile_lists4": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p] * 4 + [c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    # ... for one pair range of the batch: the forward's fine-head chains (added within ABI revision 115)
+    "gim_fine_tile_lists4_range": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p] * 4 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     # dense SfM: dense matches of a pair list -> keypoints and keypoint-indexed matches (added within ABI revision 115)
     "gim_agg_bins": (c_int, [c_float, c_int]),
     "gim_agg_vote": (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_int64, c_float, c_int, c_void_p]),

@@ -74,7 +74,8 @@ __device__ __forceinline__ void fine_tile_list_body(const int64_t* __restrict__ 
                                                     int bs, int w0c, int w1c, int stride, int H, int W,
                                                     int* __restrict__ tiles, int* __restrict__ n_tiles, int tiles_cap,
                                                     int* __restrict__ tiles2, int* __restrict__ n_tiles2,
-                                                    int* __restrict__ tilesq, int* __restrict__ n_tilesq, int tilesq_cap) {
+                                                    int* __restrict__ tilesq, int* __restrict__ n_tilesq, int tilesq_cap,
+                                                    int b_lo, int b_hi) {
     static_assert(!QUARTER || REACH2, "the quarter-level lists are derived from the +-4 flags");
     __shared__ __attribute__((aligned(16))) unsigned char flags[TL_MAX_FLAGS];
     __shared__ int part[TL_THREADS];
@@ -91,7 +92,7 @@ __device__ __forceinline__ void fine_tile_list_body(const int64_t* __restrict__ 
     M = M < 0 ? 0 : (M < cap ? M : cap);
     for (int m = t; m < M; m += TL_THREADS) {
         const int64_t b = b_ids[m];
-        if (b < 0 || b >= bs) continue;
+        if (b < b_lo || b >= b_hi) continue;   // [b_lo, b_hi) lies inside [0, bs): a match of another pair range marks nothing
 #pragma unroll
         for (int side = 0; side < 2; ++side) {
             const int64_t cell = side ? j_ids[m] : i_ids[m];
@@ -219,7 +220,7 @@ __global__ void __launch_bounds__(TL_THREADS) fine_tile_list_kernel(const int64_
                                                                   int* __restrict__ tiles, int* __restrict__ n_tiles, int tiles_cap,
                                                                   int* __restrict__ tiles2, int* __restrict__ n_tiles2) {
     fine_tile_list_body<REACH2, false>(b_ids, i_ids, j_ids, count, cap, bs, w0c, w1c, stride, H, W, tiles, n_tiles, tiles_cap, tiles2, n_tiles2,
-                                       nullptr, nullptr, 0);
+                                       nullptr, nullptr, 0, 0, bs);
 }
 
 __global__ void __launch_bounds__(TL_THREADS) fine_tile_lists4_kernel(const int64_t* __restrict__ b_ids, const int64_t* __restrict__ i_ids,
@@ -227,9 +228,10 @@ __global__ void __launch_bounds__(TL_THREADS) fine_tile_lists4_kernel(const int6
                                                                     int bs, int w0c, int w1c, int stride, int H, int W,
                                                                     int* __restrict__ tiles, int* __restrict__ n_tiles, int tiles_cap,
                                                                     int* __restrict__ tiles2, int* __restrict__ n_tiles2,
-                                                                    int* __restrict__ tilesq, int* __restrict__ n_tilesq, int tilesq_cap) {
+                                                                    int* __restrict__ tilesq, int* __restrict__ n_tilesq, int tilesq_cap,
+                                                                    int b_lo, int b_hi) {
     fine_tile_list_body<true, true>(b_ids, i_ids, j_ids, count, cap, bs, w0c, w1c, stride, H, W, tiles, n_tiles, tiles_cap, tiles2, n_tiles2,
-                                    tilesq, n_tilesq, tilesq_cap);
+                                    tilesq, n_tilesq, tilesq_cap, b_lo, b_hi);
 }
 
 }  // namespace
@@ -263,12 +265,14 @@ extern "C" int gim_fine_tile_lists(const int64_t* b_ids, const int64_t* i_ids, c
 }
 
 // gim_fine_tile_lists plus, from the same launch, the three patch lists of the 1/4-resolution maps [2 bs, H / 2, W / 2] (see QUARTER above):
-// tilesq = int32 [3][tilesq_cap], lists A, B, C in that order; n_tilesq = int32 [3]
-extern "C" int gim_fine_tile_lists4(const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, const int* count, int cap, int bs,
-                                    int w0c, int w1c, int stride, int H, int W, int* tiles, int* n_tiles, int* tiles4, int* n_tiles4,
-                                    int tiles_cap, int* tilesq, int* n_tilesq, int tilesq_cap, gim_stream_t stream) {
+// tilesq = int32 [3][tilesq_cap], lists A, B, C in that order; n_tilesq = int32 [3].  Only the matches of the pairs [b_lo, b_hi) mark
+// patches (gim_fine_tile_lists4: all of them, [0, bs)): the forward's two pair-range chains each build the lists of their own images.
+extern "C" int gim_fine_tile_lists4_range(const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, const int* count, int cap, int bs,
+                                          int w0c, int w1c, int stride, int H, int W, int* tiles, int* n_tiles, int* tiles4, int* n_tiles4,
+                                          int tiles_cap, int* tilesq, int* n_tilesq, int tilesq_cap, int b_lo, int b_hi, gim_stream_t stream) {
     GIM_REQUIRE(b_ids && i_ids && j_ids && count && tiles && n_tiles && tiles4 && n_tiles4 && tilesq && n_tilesq, "gim_fine_tile_lists4: NULL pointer");
     GIM_REQUIRE(cap >= 0 && bs > 0 && w0c > 0 && w1c > 0 && stride > 0 && H > 0 && W > 0, "gim_fine_tile_lists4: bad geometry");
+    GIM_REQUIRE(0 <= b_lo && b_lo <= b_hi && b_hi <= bs, "gim_fine_tile_lists4: the pair range [%d, %d) is not inside [0, %d)", b_lo, b_hi, bs);
     GIM_REQUIRE(H % 16 == 0 && W % 64 == 0, "gim_fine_tile_lists4: the 1/4-resolution maps (%d x %d) must be whole 8 x 32 patches", H / 2, W / 2);
     const int64_t nflags = 2ll * bs * (W / 32) * (H / 8), nq = 2ll * bs * (W / 64) * (H / 16);
     GIM_REQUIRE(((nflags + 3) & ~3ll) + nq <= TL_MAX_FLAGS, "gim_fine_tile_lists4: %lld + %lld patches exceed the %d flags of the one-workgroup kernel",
@@ -276,8 +280,15 @@ extern "C" int gim_fine_tile_lists4(const int64_t* b_ids, const int64_t* i_ids, 
     GIM_REQUIRE(tiles_cap >= nflags && tilesq_cap >= nq, "gim_fine_tile_lists4: the lists hold %d / %d entries each, the maps have %lld / %lld patches",
                 tiles_cap, tilesq_cap, (long long)nflags, (long long)nq);
     hipLaunchKernelGGL(fine_tile_lists4_kernel, dim3(1), dim3(TL_THREADS), 0, (hipStream_t)stream, b_ids, i_ids, j_ids, count, cap, bs, w0c, w1c,
-                       stride, H, W, tiles, n_tiles, tiles_cap, tiles4, n_tiles4, tilesq, n_tilesq, tilesq_cap);
+                       stride, H, W, tiles, n_tiles, tiles_cap, tiles4, n_tiles4, tilesq, n_tilesq, tilesq_cap, b_lo, b_hi);
     return gim_check_launch("fine_tile_lists4_kernel");
+}
+
+extern "C" int gim_fine_tile_lists4(const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, const int* count, int cap, int bs,
+                                    int w0c, int w1c, int stride, int H, int W, int* tiles, int* n_tiles, int* tiles4, int* n_tiles4,
+                                    int tiles_cap, int* tilesq, int* n_tilesq, int tilesq_cap, gim_stream_t stream) {
+    return gim_fine_tile_lists4_range(b_ids, i_ids, j_ids, count, cap, bs, w0c, w1c, stride, H, W, tiles, n_tiles, tiles4, n_tiles4, tiles_cap,
+                                      tilesq, n_tilesq, tilesq_cap, 0, bs, stream);
 }
 
 extern "C" int gim_copy_segments(const gim_copy_segs* sp, gim_stream_t stream) {

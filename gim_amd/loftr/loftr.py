@@ -290,6 +290,9 @@ class LoFTR(nn.Module):
         # ... and the 1/4-level part of the head in front of that lateral (layer2_outconv + upsample-add, layer2_outconv2) where the lateral's
         # listed patches stage it as upsample sources (_fine_tail_sparse; effective only where lateral_sparse is)
         self.quarter_sparse = flag("quarter_sparse", True, config)
+        # ... as that many pair-range chains on parallel streams where the whole sparse head runs (quarter_sparse's path): each chain builds the
+        # patch lists of its own pairs and walks them, the short last rounds of one chain's launches fill with the other's (_fine_tail_sparse)
+        self.fine_chains = flag("fine_chains", 2, config)
         self._lat_ok = {}   # _lateral_sparse_ok per shape
         self._q_ok = {}     # _quarter_sparse_ok per shape
         self._packed = None
@@ -707,19 +710,33 @@ class LoFTR(nn.Module):
         return bool(self.fine_sparse and is_half(self._dt()) and self.use_lds_dma and ops.HALO and P["l1o2a"].halo is not None
                     and P["l1o2b"].halo is not None and h2 % 8 == 0 and w2 % 32 == 0)
 
-    def _fpn_fine_tail(self, P, x1_out, tiles=None, n_tiles=None):
+    def _fpn_fine_tail(self, P, x1_out, tiles=None, n_tiles=None, out=None):
         """layer1_outconv2 (resnet.py:329): the two 3x3 layers at 1/2 resolution whose output is the fine map.  tiles / n_tiles
-        (ops.fine_tile_list): only those 8 x 32 patches are computed (see _fine_tail_sparse)."""
+        (ops.fine_tile_list): only those 8 x 32 patches are computed (see _fine_tail_sparse); out = (mid, f): the two layers' output maps
+        (the pair-range chains of _fine_tail_sparse share them)."""
         B, H, W, _ = x1_out.shape
         if self._fine_halo(P, H, W):
             # (no health word: these launches add no residual -- ops.conv_rows hands the word to residual / split launches only)
-            mid = torch.empty(B, H, W, P["l1o2a"].n_store, dtype=x1_out.dtype, device=x1_out.device)
-            f = torch.empty(B, H, W, P["l1o2b"].n_store, dtype=x1_out.dtype, device=x1_out.device)
+            mid, f = out if out is not None else self._fine_tail_maps(P, x1_out)
             ops.conv3x3_halo(x1_out, P["l1o2a"], mid, ACT_LEAKY, tiles=tiles, n_tiles=n_tiles)
             ops.conv3x3_halo(mid, P["l1o2b"], f, ACT_NONE, tiles=tiles, n_tiles=n_tiles)
             return f
-        assert tiles is None
+        assert tiles is None and out is None
         return self._conv(self._conv(x1_out, P["l1o2a"], ACT_LEAKY), P["l1o2b"])
+
+    def _fine_head_maps(self, P, x1, x2):
+        """the six (uncleared) maps the sparse head writes between the trunk and the fused fine kernel: layer2_outconv + upsample-add,
+        layer2_outconv2's two layers (1/4 level), the lateral sum x1_out, layer1_outconv2's two layers (1/2 level)"""
+        new = lambda t, pk: torch.empty(*t.shape[:3], pk.n_store, dtype=x1.dtype, device=x1.device)   # noqa: E731
+        x1_out = new(x1, P["l1o"])
+        return (new(x2, P["l2o"]), new(x2, P["l2o2a"]), new(x2, P["l2o2b"]), x1_out) + self._fine_tail_maps(P, x1_out)
+
+    @staticmethod
+    def _fine_tail_maps(P, x1_out):
+        """the (uncleared) output maps of layer1_outconv2's two layers on the halo kernel"""
+        B, H, W, _ = x1_out.shape
+        return (torch.empty(B, H, W, P["l1o2a"].n_store, dtype=x1_out.dtype, device=x1_out.device),
+                torch.empty(B, H, W, P["l1o2b"].n_store, dtype=x1_out.dtype, device=x1_out.device))
 
     def _fine_sparse_ok(self, P, xs):
         """may this forward compute the fine map under the matched windows only?  (the conditions of _fine_tail_sparse)"""
@@ -786,6 +803,9 @@ class LoFTR(nn.Module):
             # if layer2_outconv2's first layer is valid on S dilated by 1, and that if the 1/4-level lateral is valid on S dilated by 2: lists
             # C, B, A of gim_fine_tile_lists4 (C <= B <= A), from the same one-workgroup launch.  The ring a listed patch reads outside its
             # list reaches only outputs outside S and its dilations, which nothing consumed reads.
+            K = min(int(self.fine_chains), bs) if (self.debug is None and self.fine_chains > 1 and self._fine_halo(P, H, W)) else 1
+            if K > 1:
+                return self._fine_tail_chains(P, x1, x2, x3_out, cr, bs, K)
             tiles, n_tiles, tiles4, n_tiles4, tq, nq = ops.fine_tile_lists4(cr.b_ids, cr.i_ids, cr.j_ids, cr.count, bs, cr.args.w0c, cr.args.w1c, 4, H, W)
             x2_out = ops.conv2d_ups_tiles(x2, P["l2o"], x3_out, tq[0], nq[0:1])
             x2_out = ops.conv2d_tiles(x2_out, P["l2o2a"], tq[1], nq[1:2], ACT_LEAKY)
@@ -813,6 +833,46 @@ class LoFTR(nn.Module):
         _, H, W, _ = x1_out.shape
         tiles, n_tiles = ops.fine_tile_list(cr.b_ids, cr.i_ids, cr.j_ids, cr.count, bs, cr.args.w0c, cr.args.w1c, 4, H, W)
         return self._fpn_fine_tail(P, x1_out, tiles, n_tiles)
+
+    def _fine_tail_chains(self, P, x1, x2, x3_out, cr, bs, K):
+        """the whole sparse head of `_fine_tail_sparse` (x1_out = (x1, x2, x3_out)) as K pair-range chains on parallel streams.  Chain g owns
+        the pairs [bs g / K, bs (g + 1) / K), i.e. the images b and bs + b of those pairs: its list launch marks the patches of its own
+        matches only (ops.fine_tile_lists4, b_range), then its six launches walk those lists.  A patch belongs to one image and no
+        convolution, lateral or upsample reads across images, so the chains share no data: they write disjoint patches of the same six
+        (uncleared) maps, every listed patch gets the bits the one-chain launches write, and the one-pixel ring argument of DESIGN.md 7d
+        holds per image.  The launches are persistent (one workgroup per CU walking a list whose length the host does not know): alone
+        on the chip each pays a whole last round, two chains fill each other's.  Fork behind coarse matching, join in front of the fused
+        fine kernel, inside the captured graph; same kernels, same arithmetic."""
+        H, W = x1.shape[1:3]
+        # allocated on the main stream in front of the fork, read by the main stream behind the join
+        qa, qb, qc, x1_out, mid, f = self._fine_head_maps(P, x1, x2)
+        main = torch.cuda.current_stream()
+        sides = self._side_streams(x1.device, K - 1)
+        keep = []   # the chains' patch lists and counts stay referenced until the join (the caching allocator re-uses a freed block per stream)
+
+        def chain(g):
+            lists = ops.fine_tile_lists4(cr.b_ids, cr.i_ids, cr.j_ids, cr.count, bs, cr.args.w0c, cr.args.w1c, 4, H, W,
+                                         b_range=(bs * g // K, bs * (g + 1) // K))
+            keep.append(lists)
+            tiles, n_tiles, tiles4, n_tiles4, tq, nq = lists
+            got = (ops.conv2d_ups_tiles(x2, P["l2o"], x3_out, tq[0], nq[0:1], y=qa),
+                   ops.conv2d_tiles(qa, P["l2o2a"], tq[1], nq[1:2], ACT_LEAKY, out=qb),
+                   ops.conv2d_tiles(qb, P["l2o2b"], tq[2], nq[2:3], out=qc),
+                   ops.conv2d_ups_tiles(x1, P["l1o"], qc, tiles4, n_tiles4, y=x1_out))
+            if not all(a is b for a, b in zip(got, (qa, qb, qc, x1_out))):   # a dense fall-back allocates its own map: _quarter_sparse_ok admitted all four
+                raise RuntimeError("fine_chains: a list launch of the sparse fine head fell back to its dense form")
+            if self.lateral_one_list:
+                tiles, n_tiles = tiles4, n_tiles4
+            self._fpn_fine_tail(P, x1_out, tiles, n_tiles, out=(mid, f))
+
+        for g in range(1, K):
+            sides[g - 1].wait_stream(main)
+            with torch.cuda.stream(sides[g - 1]):
+                chain(g)
+        chain(0)
+        for s_ in sides:
+            main.wait_stream(s_)
+        return f   # (`keep` dies past the join: see the lifetime note at T.init_state, _transformer_emit)
 
     class _TfBuffers:
         """Row buffers of one LocalFeatureTransformer run over R rows of width C.  The q / k / v rows, the message, the pre-LayerNorm
@@ -1223,7 +1283,7 @@ class LoFTR(nn.Module):
 
     def _graph_key(self, color0, color1, scale0, mask0):
         return (tuple(color0.shape), tuple(color1.shape), scale0 is not None, mask0 is not None, self.precision, bool(self.fp32_split),
-                bool(self.fine_sparse), bool(self.lateral_sparse), bool(self.quarter_sparse), bool(self.lateral_one_list), self.coarse_sim, self._img_dt(), self._split(), self._stem_k(), str(color0.device))
+                bool(self.fine_sparse), bool(self.lateral_sparse), bool(self.quarter_sparse), bool(self.lateral_one_list), int(self.fine_chains), self.coarse_sim, self._img_dt(), self._split(), self._stem_k(), str(color0.device))
 
     def _stage_graphed(self, key, fill, warm, stage, bs, dev, scale0, scale1, mask0, mask1):
         """HIP-graph replay of a shape-static stage (one graph per `key`: input shapes / precision): forward's `_coarse_stage` (~140 kernel

@@ -494,11 +494,12 @@ def fine_tile_lists(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W):
     return tiles[0], n[0:1], tiles[1], n[1:2]
 
 
-def fine_tile_lists4(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W):
+def fine_tile_lists4(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W, b_range=None):
     """`fine_tile_lists` and, from the same launch, the three patch lists of the 1/4-resolution maps [2 bs, H/2, W/2] in front of the
     lateral that walks tiles4: every upsample source that launch stages (S), S dilated by 1 and by 2.  Returns (tiles, n_tiles, tiles4,
     n_tiles4, tilesq [3, total/4] = lists A (dilated by 2), B (by 1), C (S itself), n_tilesq [3])  (gim_fine_tile_lists4; H % 16 == 0,
-    W % 64 == 0)"""
+    W % 64 == 0).  b_range = (b_lo, b_hi): only the matches of those pairs mark patches (gim_fine_tile_lists4_range; indices and buffer
+    sizes stay those of the whole batch)."""
     _req_cuda(b_ids, i_ids, j_ids, count)
     assert b_ids.dtype == i_ids.dtype == j_ids.dtype == torch.int64 and count.dtype == torch.int32
     assert b_ids.is_contiguous() and i_ids.is_contiguous() and j_ids.is_contiguous()
@@ -509,8 +510,13 @@ def fine_tile_lists4(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W):
     tiles = torch.empty(2 * total + 3 * totq, dtype=torch.int32, device=b_ids.device)
     n = torch.empty(5, dtype=torch.int32, device=b_ids.device)
     tq = tiles[2 * total:].view(3, totq)
-    check(lib.gim_fine_tile_lists4(_p(b_ids), _p(i_ids), _p(j_ids), _p(count), cap, bs, w0c, w1c, stride, H, W, _p(tiles[:total]), _p(n[0:1]),
-                                   _p(tiles[total:2 * total]), _p(n[1:2]), total, _p(tq), _p(n[2:5]), totq, _stream()), "gim_fine_tile_lists4")
+    if b_range is None:
+        check(lib.gim_fine_tile_lists4(_p(b_ids), _p(i_ids), _p(j_ids), _p(count), cap, bs, w0c, w1c, stride, H, W, _p(tiles[:total]), _p(n[0:1]),
+                                       _p(tiles[total:2 * total]), _p(n[1:2]), total, _p(tq), _p(n[2:5]), totq, _stream()), "gim_fine_tile_lists4")
+    else:
+        check(lib.gim_fine_tile_lists4_range(_p(b_ids), _p(i_ids), _p(j_ids), _p(count), cap, bs, w0c, w1c, stride, H, W, _p(tiles[:total]),
+                                             _p(n[0:1]), _p(tiles[total:2 * total]), _p(n[1:2]), total, _p(tq), _p(n[2:5]), totq,
+                                             int(b_range[0]), int(b_range[1]), _stream()), "gim_fine_tile_lists4_range")
     return tiles[:total], n[0:1], tiles[total:2 * total], n[1:2], tq, n[2:5]
 
 

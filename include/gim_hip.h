@@ -551,6 +551,13 @@ int gim_fine_tile_lists(const int64_t* b_ids, const int64_t* i_ids, const int64_
 int gim_fine_tile_lists4(const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, const int* count, int cap, int bs,
                          int w0c, int w1c, int stride, int H, int W, int* tiles, int* n_tiles, int* tiles4, int* n_tiles4, int tiles_cap,
                          int* tilesq, int* n_tilesq, int tilesq_cap, gim_stream_t stream);
+/* gim_fine_tile_lists4 for the pairs [b_lo, b_hi) alone, 0 <= b_lo <= b_hi <= bs (added within ABI revision 115): a match whose b_ids value
+ * lies outside the range marks nothing; patch indices, list order and buffer sizes stay those of the whole batch, so the lists of disjoint
+ * ranges are disjoint and their sorted union is the list of the union of the ranges.  b_lo = 0, b_hi = bs writes what gim_fine_tile_lists4
+ * writes; an empty range writes the five counts (0) and no list entry.  For launch chains that each own the images of a pair range. */
+int gim_fine_tile_lists4_range(const int64_t* b_ids, const int64_t* i_ids, const int64_t* j_ids, const int* count, int cap, int bs,
+                               int w0c, int w1c, int stride, int H, int W, int* tiles, int* n_tiles, int* tiles4, int* n_tiles4, int tiles_cap,
+                               int* tilesq, int* n_tilesq, int tilesq_cap, int b_lo, int b_hi, gim_stream_t stream);
 
 /* ======================================================================================================
  * gim_dkm path (kernels D1-D9).  Convolutions / 1x1 projections / the cosine-kernel and
