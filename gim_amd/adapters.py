@@ -14,6 +14,7 @@ import torch.nn.functional as F
 
 from . import ops
 from ._lib import GimHipError
+from .bank import pair_batches
 
 
 def get_padding_size(image, h, w):
@@ -129,14 +130,12 @@ class HlocDenseMatcher(torch.nn.Module):
         them; its rows are theirs), ONE gim_dense_emit_pairs for the tail and one read of the counts -- the only host read of a batch.
         Returns one {'keypoints0', 'keypoints1', 'scores', 'batch_indexes'} per pair, equal to `forward`'s.  scales: None, or per pair ((sx, sy) of key0, (sx, sy) of key1) -- the
         keypoints then carry the rescale of dense_sfm.match_dense_pair_list, (k + 0.5) * s - 0.5."""
-        pairs = list(pairs)
         bp = max(1, min(int(batch_pairs), self.net.max_batch))
         out = []
-        for lo in range(0, len(pairs), bp):
-            chunk = pairs[lo:lo + bp]
-            B = len(chunk)
+        for chunk in pair_batches(pairs, bp):
+            lo, B = len(out), len(chunk)
             # the model's first image is the caller's image1 (the swap of `forward`)
-            slots = bank.slots([k1 for _, k1 in chunk] + [k0 for k0, _ in chunk])    # raises for an image that is not resident
+            slots = bank.slots([k1 for _, k1 in chunk] + [k0 for k0, _ in chunk])    # raises unless every image is resident
             geos = [(bank.meta[k1], bank.meta[k0]) for k0, k1 in chunk]
             warp, cert = self.net.match_features(bank, slots[:B], slots[B:])
             sparse, mconf, _ = self.net.sample_batch(warp, cert, self.num_samples)  # rows past a pair's samples are zero: rejected by mconf > 0

@@ -1,6 +1,6 @@
 """Feature bank of the dense matchers: every image of an exhaustive hloc pairing is resized, encoded (at both resolutions) and projected
-ONCE, however many pairs name it -- the dense counterpart of gim_amd/loftr/bank.py and gim_amd/lightglue/bank.py (whose `SlotTable` does
-the bookkeeping here too, unchanged).
+ONCE, however many pairs name it -- the dense counterpart of gim_amd/loftr/bank.py and gim_amd/lightglue/bank.py (gim_amd/bank.py
+`SlotBank` does the bookkeeping here too).
 
   DenseFeatureBank   `capacity_images` slots of the per-image state `DenseMatcher.extract` returns (gim_amd/dense.py: pyramid levels of
                      both resolutions, the coarse projections, the black-pixel mask), one slab [slots, ...] per tensor kind, allocated when
@@ -10,7 +10,7 @@ the bookkeeping here too, unchanged).
 
 The state of a slot belongs to ONE module in ONE state (`DenseMatcher.feature_tag()`: weights, device, precision, resolutions): `check`,
 called by `put`, `slots` and `match_features`, empties the bank when the module has moved on (load_state_dict, a device move, a
-precision change).  A pair that names an image which is not resident -- never inserted, evicted, or dropped by such a reset -- raises
+precision change).  A pair that names an image which is no longer resident -- never inserted, evicted, or dropped by such a reset -- raises
 GimHipError before anything is launched.
 
 Memory per image: `bytes_per_image` (the README has the figures of the two evaluation sizes).
@@ -19,28 +19,19 @@ import torch
 
 from . import ops
 from ._lib import GimHipError
-from .loftr.bank import SlotTable
+from .bank import SlotBank
 
 
-class DenseFeatureBank:
+class DenseFeatureBank(SlotBank):
+    GONE = "never inserted, evicted from the {} slots, or dropped when the module changed"
+
     def __init__(self, model, capacity_images):
-        if capacity_images < 1:
-            raise ValueError("a feature bank needs at least one slot")
+        super().__init__(capacity_images, "dense feature bank")
         self.model = model
-        self.capacity = int(capacity_images)
-        self.table = SlotTable(self.capacity)
         self.tag = None
         self.slabs = None       # {kind: [capacity, ...]} in the order extract returns the kinds
         self.device = None
         self.meta = {}          # key -> whatever the caller stored with the image (adapters.HlocDenseMatcher: its padding geometry)
-
-    # ---- bookkeeping (plain Python: no device work) -----------------------------------------------------------------------------
-    @property
-    def stats(self):
-        return self.table.stats
-
-    def __len__(self):
-        return len(self.table)
 
     def __contains__(self, key):
         return self.tag == self.model.feature_tag() and key in self.table
@@ -75,20 +66,8 @@ class DenseFeatureBank:
         self.tag = tag
         return False
 
-    def slots(self, keys):
-        """slots of resident images, one per key (duplicates allowed); marks them most recently used.  An image that was never inserted,
-        or has been evicted or invalidated since, raises: a pair must not read whatever lives in its old slot now."""
+    def _before_lookup(self):
         self.check()
-        keys = list(keys)
-        gone = [k for k in dict.fromkeys(keys) if k not in self.table]
-        if gone:
-            raise GimHipError(f"dense feature bank: image {gone[0]!r} is not resident (never inserted, evicted from the {self.capacity} "
-                              "slots, or dropped when the module changed)" + (f"; {len(gone) - 1} more" if len(gone) > 1 else ""))
-        out = []
-        for i in range(0, len(keys), self.capacity):   # SlotTable.assign takes at most `capacity` distinct keys at a time
-            out += self.table.assign(keys[i:i + self.capacity])[0]
-        self.table.unpin()
-        return out
 
     # ---- device work --------------------------------------------------------------------------------------------------------------
     def put(self, key, image):
@@ -116,11 +95,7 @@ class DenseFeatureBank:
             self.slabs = {kind: torch.empty(self.capacity, *t.shape[1:], dtype=t.dtype, device=t.device) for kind, t in feats.tensors.items()}
         elif any(tuple(self.slabs[k].shape[1:]) != tuple(t.shape[1:]) or self.slabs[k].dtype != t.dtype for k, t in feats.tensors.items()):
             raise GimHipError("dense feature bank: the images of one bank must have one padded size")   # cannot happen: the model resizes
-        try:
-            slots, _ = self.table.assign(keys)
-        except ValueError as e:
-            raise GimHipError(f"dense feature bank: {e}") from e
-        self.table.unpin()
+        slots = self.reserve(keys)
         for kind, t in feats.tensors.items():
             ops.slot_copy(t.contiguous(), self.slabs[kind], dst_idx=slots)
         for k in [k for k in self.meta if k not in self.table]:    # evicted images

@@ -23,6 +23,7 @@ import torch
 
 from . import hloc_formats, ops
 from ._lib import GimHipError
+from .bank import pair_batches
 
 
 class DenseMatchAggregator:
@@ -171,9 +172,10 @@ class DenseMatchAggregator:
         if batch_pairs < 1:
             raise GimHipError(f"DenseMatchAggregator: batch_pairs={batch_pairs}")
         st = self._state()
-        for b0 in range(0, len(self.pairs), int(batch_pairs)):
-            b1 = min(b0 + int(batch_pairs), len(self.pairs))
-            s0, s1 = zip(*self.pair_slots[b0:b1])
+        b1 = 0
+        for chunk in pair_batches(self.pair_slots, int(batch_pairs)):
+            b0, b1 = b1, b1 + len(chunk)
+            s0, s1 = zip(*chunk)
             batch = ops.agg_batch(self.offsets[b0:b1 + 1], s0, s1, len(self.sizes), st.scores.shape[0], self.device)
             r = ops.agg_assign(st, self._kp, batch)
             rows0, P = r.matches0.shape[0], b1 - b0
@@ -230,10 +232,8 @@ def match_dense_pair_list(matcher, images, pairs, aggregator, scales=None, bank=
                 h, w = images[name].shape[-2:]
                 aggregator.add_image(name, int(round(w * s[0])), int(round(h * s[1])))
     if bank is not None:
-        pairs = list(pairs)
         bp = max(1, int(batch_pairs))
-        for lo in range(0, len(pairs), bp):
-            chunk = pairs[lo:lo + bp]
+        for chunk in pair_batches(pairs, bp):
             names = list(dict.fromkeys(n for pr in chunk for n in pr))
             if len(names) > bank.capacity:
                 raise GimHipError(f"match_dense_pair_list: a batch of {len(chunk)} pairs names {len(names)} images, the bank has {bank.capacity} slots")

@@ -1,5 +1,5 @@
 """Keypoint bank for pair lists: every image of an exhaustive hloc pairing runs SuperPoint ONCE and is uploaded ONCE, however many pairs
-name it -- the sparse counterpart of gim_amd/loftr/bank.py (whose `SlotTable` does the bookkeeping here too, unchanged).
+name it -- the sparse counterpart of gim_amd/loftr/bank.py (gim_amd/bank.py `SlotBank` does the bookkeeping of both kinds of bank).
 
   KeypointBank   `capacity_images` slots of `num_keypoints` keypoints on the device (csrc/lg_bank.hip for the layout):
                      kpts [S, K, 2] fp32, desc [S, K, 256] fp32 | fp16 (`storage`), enc [S, K, 64] fp32
@@ -21,23 +21,21 @@ import torch
 
 from .. import ops
 from .._lib import GimHipError
-from ..loftr.bank import SlotTable
+from ..bank import SlotBank, SlotTable  # noqa: F401  (SlotTable: named from here by earlier callers)
 
 _STORAGE = {"fp16": torch.float16, "fp32": torch.float32}
 
 
-class KeypointBank:
+class KeypointBank(SlotBank):
     def __init__(self, capacity_images, num_keypoints, storage="fp16", device="cuda"):
         if storage not in _STORAGE:
             raise ValueError(f"storage must be 'fp16' or 'fp32', got {storage!r}")
-        if capacity_images < 1 or num_keypoints < 1:
-            raise ValueError("a keypoint bank needs at least one slot and one keypoint per image")
-        self.capacity, self.num_keypoints, self.storage = int(capacity_images), int(num_keypoints), storage
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        if num_keypoints < 1:
+            raise ValueError("a keypoint bank needs at least one keypoint per image")
+        super().__init__(capacity_images, "keypoint bank")
+        self.num_keypoints, self.storage = int(num_keypoints), storage
+        self.device = self.resolve_device(device)
         S, K = self.capacity, self.num_keypoints
-        self.table = SlotTable(S)
         self.kpts = torch.empty(S, K, 2, dtype=torch.float32, device=self.device)
         self.desc = torch.empty(S, K, 256, dtype=_STORAGE[storage], device=self.device)
         self.enc = torch.empty(S, K, 64, dtype=torch.float32, device=self.device)
@@ -45,47 +43,9 @@ class KeypointBank:
         self._owner, self._epoch, self._wr = None, None, None    # the LightGlue module / packing epoch / Wr the encodings belong to
         self._stale = set()                                      # resident slots whose encoding is not of that module
 
-    # ---- bookkeeping (plain Python: no device work) -----------------------------------------------------------------------------
-    @property
-    def stats(self):
-        return self.table.stats
-
-    def __len__(self):
-        return len(self.table)
-
-    def __contains__(self, key):
-        return key in self.table
-
     @property
     def nbytes(self):
         return sum(t.numel() * t.element_size() for t in (self.kpts, self.desc, self.enc))
-
-    def reserve(self, keys):
-        """slots for the images about to be inserted (distinct keys; a resident key keeps its slot and is overwritten), the least
-        recently used images evicted to make room"""
-        keys = list(keys)
-        if len(set(keys)) != len(keys):
-            raise ValueError("the images of one insertion must have distinct keys")
-        try:
-            slots, _ = self.table.assign(keys)
-        except ValueError as e:
-            raise GimHipError(f"keypoint bank: {e}") from e
-        self.table.unpin()
-        return slots
-
-    def slots(self, keys):
-        """slots of resident images, one per key (duplicates allowed); marks them most recently used.  An image that was never
-        inserted, or has been evicted since, raises: a pair must not read whatever lives in its old slot now."""
-        keys = list(keys)
-        gone = [k for k in dict.fromkeys(keys) if k not in self.table]
-        if gone:
-            raise GimHipError(f"keypoint bank: image {gone[0]!r} is not resident (never inserted, or evicted from the {self.capacity} slots)"
-                              + (f"; {len(gone) - 1} more" if len(gone) > 1 else ""))
-        out = []
-        for i in range(0, len(keys), self.capacity):   # SlotTable.assign takes at most `capacity` distinct keys at a time
-            out += self.table.assign(keys[i:i + self.capacity])[0]
-        self.table.unpin()
-        return out
 
     def slot_tensor(self, idx):
         """int32 device tensor of slot indices from a tensor or a sequence of ints (range-checked where that needs no read-back; the
@@ -94,11 +54,7 @@ class KeypointBank:
             if idx.dtype != torch.int32 or idx.device != self.device:
                 raise GimHipError(f"slot indices must be int32 on {self.device}, got {idx.dtype} on {idx.device}")
             return idx.reshape(-1).contiguous()
-        idx = [int(i) for i in idx]
-        bad = [i for i in idx if not 0 <= i < self.capacity]
-        if bad:
-            raise GimHipError(f"keypoint bank: slot {bad[0]} is outside [0, {self.capacity})")
-        return torch.tensor(idx, dtype=torch.int32, device=self.device)
+        return torch.tensor(self.check_slots(idx), dtype=torch.int32, device=self.device)
 
     # ---- device work --------------------------------------------------------------------------------------------------------------
     def put(self, key, keypoints, descriptors, image_size):

@@ -15,15 +15,7 @@ int16 and `matching_scores0` fp16.  The two datasets leave the device already in
 import torch
 
 from .._lib import GimHipError
-from ..hloc_formats import write_sparse_matches
-
-
-def pair_batches(pairs, batch_pairs):
-    """the pair list cut into consecutive batches of `batch_pairs` (the last one may be shorter; an empty list gives no batch)"""
-    if batch_pairs < 1:
-        raise ValueError("batch_pairs must be >= 1")
-    pairs = list(pairs)
-    return [pairs[i:i + batch_pairs] for i in range(0, len(pairs), batch_pairs)]
+from ..bank import pair_batches, sparse_pair_list  # noqa: F401  (pair_batches: re-exported)
 
 
 @torch.no_grad()
@@ -55,15 +47,7 @@ def match_pair_list(model, bank, pairs, batch_pairs=8, writer=None, names=None):
     """pairs: a sequence of (key0, key1) of images resident in `bank`.  Returns [(key0, key1, matches0 int16 [K], matching_scores0 fp16
     [K])] as numpy arrays, in the order of `pairs`; with `writer` every pair is also written as hloc stores it (group name from
     names[key] if `names` is given, else str(key))."""
-    out = []
-    name = (lambda k: names[k]) if names is not None else str
-    for batch in pair_batches(pairs, batch_pairs):
-        s0, s1 = bank.slots([p[0] for p in batch]), bank.slots([p[1] for p in batch])
+    def match_batch(s0, s1):
         pred = model.match_pairs(bank, s0, s1, hloc=True)
-        m = pred["matches0_i16"].cpu().numpy()
-        s = pred["matching_scores0_f16"].cpu().numpy()
-        for b, (k0, k1) in enumerate(batch):
-            if writer is not None:
-                write_sparse_matches(writer, name(k0), name(k1), m[b], s[b])
-            out.append((k0, k1, m[b], s[b]))
-    return out
+        return zip(pred["matches0_i16"].cpu().numpy(), pred["matching_scores0_f16"].cpu().numpy())
+    return sparse_pair_list(bank, pairs, batch_pairs, match_batch, writer, names)

@@ -3,8 +3,8 @@ ONCE, however many pairs name it.
 
   FeatureBank        slabs of backbone maps ([slots, H/8, W/8, 256] and [slots, H/2, W/2, 128], one pair of slabs per image shape and
                      dtype) plus the bookkeeping: caller-supplied hashable image key -> slot, LRU eviction, slots of the batch in flight
-                     pinned, hit / miss / eviction counts.  The bookkeeping (`SlotTable`) is plain Python; torch is touched only when a
-                     slab is allocated.
+                     pinned, hit / miss / eviction counts.  The bookkeeping (`SlotTable`, gim_amd/bank.py) is plain Python; torch is
+                     touched only when a slab is allocated.
   CachedPairMatcher  a callable with the contract of `model(batch)` (gim_amd.zeb.run_scene(matcher=...), gim_amd.runner): finds the
                      batch's images that are not in the bank, extracts them in one `LoFTR.extract` call, scatters the maps into their
                      slots (gim_slot_copy) and matches the batch from the bank (`LoFTR.match_features` with slot indices).
@@ -12,86 +12,7 @@ ONCE, however many pairs name it.
 Memory: at 640x480 an image's maps are 60*80*256 + 240*320*128 = 11 059 200 elements -- 22.1 MB in the 16-bit modes, 44.2 MB in fp32;
 `capacity_images` slots of that per image shape are allocated when the first image of the shape arrives.
 """
-import collections
-
-
-class BankStats:
-    """hits / misses count image LOOK-UPS per distinct image of a batch (an image named twice in one batch is one look-up);
-    evictions count images dropped to make room; invalidations count whole-bank resets (the module's tag changed)"""
-
-    def __init__(self):
-        self.hits = self.misses = self.evictions = self.invalidations = 0
-
-    def as_dict(self):
-        return {"hits": self.hits, "misses": self.misses, "evictions": self.evictions, "invalidations": self.invalidations}
-
-    def __repr__(self):
-        return f"BankStats({self.as_dict()})"
-
-
-class SlotTable:
-    """key -> slot over a fixed number of slots, least recently used key evicted first, pinned slots never."""
-
-    def __init__(self, slots, stats=None):
-        if slots < 1:
-            raise ValueError("a slot table needs at least one slot")
-        self.slots = int(slots)
-        self.stats = stats if stats is not None else BankStats()
-        self._lru = collections.OrderedDict()   # key -> slot, least recently used first
-        self._free = list(range(self.slots - 1, -1, -1))
-        self._pinned = set()
-
-    def __len__(self):
-        return len(self._lru)
-
-    def __contains__(self, key):
-        return key in self._lru
-
-    def keys(self):
-        """keys, least recently used first"""
-        return list(self._lru)
-
-    def slot_of(self, key):
-        return self._lru.get(key)
-
-    def unpin(self):
-        self._pinned.clear()
-
-    def assign(self, keys):
-        """Slots for the images of ONE batch.  `keys`: the batch's image keys, duplicates allowed.  Returns (slots, missing): slots[i] is the
-        slot of keys[i] (equal keys share one slot); missing = [(key, slot)] of the distinct keys that were not resident, in first-use
-        order -- the caller fills those slots before it reads any.  Every slot of the batch stays pinned until the next assign() /
-        unpin(): making room for one image of the batch never evicts another.  ValueError when the batch needs more distinct images than
-        there are slots (nothing is changed then)."""
-        distinct = list(dict.fromkeys(keys))
-        if len(distinct) > self.slots:
-            raise ValueError(f"the batch names {len(distinct)} distinct images, the bank has {self.slots} slots per image shape")
-        self.unpin()
-        missing = []
-        for k in distinct:   # residents first: pinned before anything is evicted
-            if k in self._lru:
-                self._lru.move_to_end(k)
-                self._pinned.add(self._lru[k])
-                self.stats.hits += 1
-        for k in distinct:
-            if k in self._lru:
-                continue
-            self.stats.misses += 1
-            if self._free:
-                slot = self._free.pop()
-            else:
-                victim = next(kk for kk, s in self._lru.items() if s not in self._pinned)   # exists: distinct <= slots
-                slot = self._lru.pop(victim)
-                self.stats.evictions += 1
-            self._lru[k] = slot
-            self._pinned.add(slot)
-            missing.append((k, slot))
-        return [self._lru[k] for k in keys], missing
-
-    def clear(self):
-        self._lru.clear()
-        self._free = list(range(self.slots - 1, -1, -1))
-        self._pinned.clear()
+from ..bank import BankStats, SlotTable
 
 
 class FeatureBank:

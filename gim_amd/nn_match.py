@@ -28,8 +28,7 @@ import torch
 
 from . import ops
 from ._lib import GimHipError
-from .hloc_formats import write_sparse_matches
-from .loftr.bank import SlotTable
+from .bank import SlotBank, sparse_pair_list
 
 NO_DETECTOR = ("root_sift needs OpenCV's SIFT detector (cv2.SIFT_create) to find keypoints, and cv2 does not import here: {}. "
                "Install opencv-python, or call RootSiftMatcher.match_descriptors with descriptors of your own.")
@@ -44,64 +43,29 @@ def _cv2():
     return cv2
 
 
-class DescriptorBank:
+class DescriptorBank(SlotBank):
     """`capacity_images` slots of at most `max_rows` descriptors of width D on the device (csrc/nn_match.hip for the layout):
         desc [S, R, D] fp32 (RootSIFT-normalised at insertion when `rootsift`), kpts [S, R, 2] fp32, n [S] int32
-    plus caller-supplied hashable image key -> slot with LRU eviction (gim_amd/loftr/bank.py `SlotTable`, as the keypoint bank of
+    plus caller-supplied hashable image key -> slot with LRU eviction (gim_amd/bank.py `SlotBank`, as the keypoint bank of
     gim_lightglue).  `counts` is the host mirror of n: sizing a batch never reads the device."""
 
     def __init__(self, capacity_images, max_rows, D=128, rootsift=True, device="cuda"):
-        if capacity_images < 1 or max_rows < 1:
-            raise ValueError("a descriptor bank needs at least one slot and one row per image")
+        if max_rows < 1:
+            raise ValueError("a descriptor bank needs at least one row per image")
+        super().__init__(capacity_images, "descriptor bank")
         if D % 16 or not 16 <= D <= 256:
             raise GimHipError(f"descriptor bank: D={D} is not a multiple of 16 in [16, 256]")
-        self.capacity, self.max_rows, self.D, self.rootsift = int(capacity_images), int(max_rows), int(D), bool(rootsift)
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.max_rows, self.D, self.rootsift = int(max_rows), int(D), bool(rootsift)
+        self.device = self.resolve_device(device)
         S, R = self.capacity, self.max_rows
-        self.table = SlotTable(S)
         self.desc = torch.empty(S, R, self.D, dtype=torch.float32, device=self.device)
         self.kpts = torch.zeros(S, R, 2, dtype=torch.float32, device=self.device)
         self.n = torch.zeros(S, dtype=torch.int32, device=self.device)
         self.counts = np.zeros(S, dtype=np.int32)
 
-    # ---- bookkeeping (plain Python: no device work) -----------------------------------------------------------------------------
-    @property
-    def stats(self):
-        return self.table.stats
-
-    def __len__(self):
-        return len(self.table)
-
-    def __contains__(self, key):
-        return key in self.table
-
     @property
     def nbytes(self):
         return sum(t.numel() * t.element_size() for t in (self.desc, self.kpts, self.n))
-
-    def slots(self, keys):
-        """slots of resident images, one per key (duplicates allowed); marks them most recently used.  An image that was never
-        inserted, or has been evicted since, raises: a pair must not read whatever lives in its old slot now."""
-        keys = list(keys)
-        gone = [k for k in dict.fromkeys(keys) if k not in self.table]
-        if gone:
-            raise GimHipError(f"descriptor bank: image {gone[0]!r} is not resident (never inserted, or evicted from the {self.capacity} "
-                              "slots)" + (f"; {len(gone) - 1} more" if len(gone) > 1 else ""))
-        out = []
-        for i in range(0, len(keys), self.capacity):   # SlotTable.assign takes at most `capacity` distinct keys at a time
-            out += self.table.assign(keys[i:i + self.capacity])[0]
-        self.table.unpin()
-        return out
-
-    def check_slots(self, idx):
-        """a host sequence of slot indices, range-checked"""
-        idx = [int(i) for i in idx]
-        bad = [i for i in idx if not 0 <= i < self.capacity]
-        if bad:
-            raise GimHipError(f"descriptor bank: slot {bad[0]} is outside [0, {self.capacity})")
-        return idx
 
     # ---- device work --------------------------------------------------------------------------------------------------------------
     def put(self, key, kpts, desc):
@@ -114,8 +78,7 @@ class DescriptorBank:
             raise GimHipError(f"descriptor bank: image {key!r} has {n} descriptors, a slot holds max_rows={self.max_rows}")
         if tuple(kpts.shape) != (n, 2):
             raise GimHipError(f"descriptor bank: keypoints {tuple(kpts.shape)} for {n} descriptors of image {key!r}")
-        slot = self.table.assign([key])[0][0]
-        self.table.unpin()
+        slot = self.reserve([key])[0]
         ops.nn_bank_put(desc.to(self.device).float(), slot, self.desc, self.n, rootsift=self.rootsift)
         if n:
             self.kpts[slot, :n] = kpts.to(self.device).float()
@@ -227,19 +190,8 @@ def match_descriptor_pair_list(bank, pairs, batch_pairs=32, ratio=0.8, writer=No
     matching_scores0 fp16 [n0])] as numpy arrays -- hloc's datasets, which leave the device in that format, one copy per batch; with
     `writer` (h5py's group protocol) every pair is also written through hloc_formats.write_sparse_matches (group name from names[key] if
     `names` is given, else str(key))."""
-    if batch_pairs < 1:
-        raise ValueError("batch_pairs must be >= 1")
-    pairs = list(pairs)
-    name = (lambda k: names[k]) if names is not None else str
-    out = []
-    for i in range(0, len(pairs), batch_pairs):
-        batch = pairs[i:i + batch_pairs]
-        s0, s1 = bank.slots([p[0] for p in batch]), bank.slots([p[1] for p in batch])
+    def match_batch(s0, s1):
         r = ops.nn_match_pairs(bank.desc, bank.n, bank.counts, s0, s1, ratio=ratio, hloc=True)
         m, s = r.matches0_i16.cpu().numpy(), r.matching_scores0_f16.cpu().numpy()
-        for b, (k0, k1) in enumerate(batch):
-            lo, hi = int(r.row_off[b]), int(r.row_off[b + 1])
-            if writer is not None:
-                write_sparse_matches(writer, name(k0), name(k1), m[lo:hi], s[lo:hi])
-            out.append((k0, k1, m[lo:hi], s[lo:hi]))
-    return out
+        return [(m[lo:hi], s[lo:hi]) for lo, hi in zip(r.row_off[:-1].tolist(), r.row_off[1:].tolist())]
+    return sparse_pair_list(bank, pairs, batch_pairs, match_batch, writer, names)

@@ -148,7 +148,8 @@ def copy_segments(pairs):
 
 def slot_index(idx, slots, device):
     """slot indices for `slot_copy`: a host sequence / CPU tensor is range-checked against `slots` HERE and uploaded as int32; a device tensor
-    is handed through as int32 (the kernel skips what is out of range, nothing waits for it).  None stays None (identity)."""
+    is handed through as int32 (the kernel skips what is out of range, nothing waits for it).  None stays None (identity).
+    The banks check the slot lists of their callers with gim_amd.bank.SlotBank.check_slots."""
     if idx is None:
         return None
     if torch.is_tensor(idx) and idx.is_cuda:
