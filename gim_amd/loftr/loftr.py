@@ -50,17 +50,13 @@ import torch.nn as nn
 
 from .. import ops
 from ..switches import flag
-from .._lib import ACT_ELU1, ACT_LEAKY, ACT_NONE, ACT_RELU, GIM_F16, GimHipError
+from .._lib import ACT_ELU1, ACT_NONE, ACT_RELU, GIM_F16, GimHipError
+from .fine_head import FineHead, _half
 from ..packing import (PRECISION_DTYPE as _DT, PackedStem, cstore, is_half, pack_bneck, pack_bneck_ds, pack_bneck_tail, pack_conv, pack_conv_split, pack_fine_fused,
                        pack_stem7x7, pack_token_mlp, pack_token_emit, split_channels, torch_dtype)
 
 # gim_conv_args.split16: the weight operand is scaled by 2^12 before its hi / lo split (conv_igemm.hip), and hi = rn16 of it must stay finite
 SPLIT16_WSCALE, SPLIT16_LIMIT = 4096.0, 65504.0
-
-
-def _half(v):
-    """output extent of a stride-2 convolution with pad = k // 2 (k7 p3, k3 p1) over an extent of v"""
-    return (v - 1) // 2 + 1
 
 
 def split16_weight_overflow(packs):
@@ -215,7 +211,7 @@ def _precision_from(config):
     return resolve(config.get("precision"), "loftr", default="fp16")
 
 
-class LoFTR(nn.Module):
+class LoFTR(FineHead, nn.Module):
     def __init__(self, config):
         super().__init__()
         self.config = config
@@ -286,15 +282,13 @@ class LoFTR(nn.Module):
         # the 8 x 32 patches the fine windows of the matches can read and nowhere else (see _fine_tail_sparse; False: the dense maps, as extract() keeps them)
         self.fine_sparse = flag("fine_sparse", True, config)
         self.lateral_sparse = flag("lateral_sparse", True, config)   # ... and the 1/2-level lateral conv + upsample-add in front of them (_fine_tail_sparse)
-        self.lateral_one_list = flag("lateral_one_list", False, config)   # A/B: all three launches walk the +-4 list (measured slower)
         # ... and the 1/4-level part of the head in front of that lateral (layer2_outconv + upsample-add, layer2_outconv2) where the lateral's
         # listed patches stage it as upsample sources (_fine_tail_sparse; effective only where lateral_sparse is)
         self.quarter_sparse = flag("quarter_sparse", True, config)
         # ... as that many pair-range chains on parallel streams where the whole sparse head runs (quarter_sparse's path): each chain builds the
         # patch lists of its own pairs and walks them, the short last rounds of one chain's launches fill with the other's (_fine_tail_sparse)
         self.fine_chains = flag("fine_chains", 2, config)
-        self._lat_ok = {}   # _lateral_sparse_ok per shape
-        self._q_ok = {}     # _quarter_sparse_ok per shape
+        self._head_ok = {}   # answers of the sparse head's predicates per _head_key (fine_head.py), emptied by _invalidate()
         self._packed = None
         self._health = None          # fp16 range guard word of the forward in flight (count[1] of its coarse matching), see _coarse_stage
         self._health_sync_left = 3   # forwards that still wait for the fine kernel to read its health bit at once (fp16 mode)
@@ -328,6 +322,7 @@ class LoFTR(nn.Module):
         """weights / device / precision changed: packed weights, captured graphs AND the seen-shape counters go (a stale
         counter would send the next forward of a known shape straight into capture with nothing packed)"""
         self._packed = None
+        self._head_ok = {}
         self._health_sync_left = 3
         self._weights_gen = getattr(self, "_weights_gen", 0) + 1   # part of the tag of every LoFTRFeatures handle (see extract)
         if hasattr(self, "_graphs"):
@@ -545,19 +540,12 @@ class LoFTR(nn.Module):
             off += im.shape[0]
         return out
 
-    def _backbone(self, P, x, dt, fine_tail=True, lateral=True, quarter=True):
+    def _backbone(self, P, x, dt, head=0):
         """x: NHWC [B,H,W,cstore(3)] images in the compute dtype.  Returns (x3_out NHWC [B,h8,w8,256], feat_f NHWC [B,h2,w2,128])
-        in the compute dtype.  (resnet.py:230-235, 306-329)  fine_tail = False: the second tensor is the INPUT of the fine head's last
-        two layers instead ([B,h2,w2,196], see _fpn_fine_tail); lateral = False as well: the pair (x1, x2_out) that the 1/2-level lateral
-        conv makes that input of (see _fpn_fine); quarter = False on top of that: the FPN stops behind the trunk, the triple (x1, x2, x3_out)."""
+        in the compute dtype.  (resnet.py:230-235, 306-329)  head = 1..3: the last `head` stages of the fine head are left to the caller and
+        the second result is their `HeadInputs` (fine_head.py)."""
         x1, x2, x3_out = self._backbone_trunk(P, x, dt)
-        if not lateral:
-            assert not fine_tail
-            if not quarter:
-                return x3_out, (x1, x2, x3_out)
-            return x3_out, (x1, self._fpn_fine(P, x1, x2, x3_out, lateral=False))
-        x1_out = self._fpn_fine(P, x1, x2, x3_out)
-        return x3_out, (self._fpn_fine_tail(P, x1_out) if fine_tail else x1_out)
+        return x3_out, self._fpn_fine(P, x1, x2, x3_out, head)
 
     def _backbone_trunk(self, P, x, dt):
         """stem + layer1-3 + layer3_outconv (resnet.py:306-320): returns (x1, x2, x3_out) -- the coarse features x3_out are complete
@@ -606,10 +594,7 @@ class LoFTR(nn.Module):
                 x3_out = self._conv(x3, P["l3o"])
             return x1, x2, x3_out
         n = B // K
-        main = torch.cuda.current_stream()
-        sides = self._side_streams(x.device, K - 1)
         x3_out = torch.empty(B, _half(x2.shape[1]), _half(x2.shape[2]), P["l3o"].n_store, dtype=x2.dtype, device=x2.device)
-        keep = []   # tensors that cross streams stay referenced until the join (the caching allocator re-uses a freed block per stream)
 
         def chain(g):
             if whole:
@@ -620,15 +605,10 @@ class LoFTR(nn.Module):
                 xo = self._conv(x3, P["l3o"])
             if xo.data_ptr() != x3_out[sl].data_ptr():
                 ops.copy_segments([(xo.contiguous(), x3_out[sl])])
-            keep.append((x3, xo))
+            return x3, xo
 
-        for g in range(1, K):
-            sides[g - 1].wait_stream(main)
-            with torch.cuda.stream(sides[g - 1]):
-                chain(g)
-        chain(0)
-        for s_ in sides:
-            main.wait_stream(s_)
+        # tensors that cross streams stay referenced until the join (the caching allocator re-uses a freed block per stream)
+        keep = self._fork_join(x.device, K, chain)   # noqa: F841
         return x1, x2, x3_out
 
     def _side_streams(self, dev, n):
@@ -636,6 +616,24 @@ class LoFTR(nn.Module):
         if ss is None or len(ss) < n or ss[0].device != dev:
             ss = self._sides = [torch.cuda.Stream(device=dev) for _ in range(n)]
         return ss[:n]
+
+    def _fork_join(self, dev, K, chain):
+        """chain(g), g = 0 .. K - 1, as K unsynchronised chains of launches: chains 1 .. K - 1 first, each on a side stream that waits for the
+        current (main) stream, then chain 0 on main, which then waits for every side.  Returns the chains' results: what they allocated
+        must stay referenced until the join (the caching allocator re-uses a freed block per stream, without regard to the others)."""
+        if K == 1:
+            return [chain(0)]
+        main = torch.cuda.current_stream()
+        sides = self._side_streams(dev, K - 1)
+        out = [None] * K
+        for g in range(1, K):
+            sides[g - 1].wait_stream(main)
+            with torch.cuda.stream(sides[g - 1]):
+                out[g] = chain(g)
+        out[0] = chain(0)
+        for s_ in sides:
+            main.wait_stream(s_)
+        return out
 
     def _trunk12(self, P, x, dt, out=None):
         """stem + layer 1 + layer 2 of a batch (or image group) -> (x1, x2, conv1 output of layer 3's first block or None);
@@ -690,189 +688,6 @@ class LoFTR(nn.Module):
             x = self._conv(o, P[p + "c3"], ACT_RELU, res=idn)   # the unfused block stores the stream too
             o = None
         return x, o, x3_out
-
-    def _fpn_fine(self, P, x1, x2, x3_out, lateral=True):
-        """the FPN's top-down path to the 1/2 resolution (resnet.py:321-328): four convolutions that nothing of the coarse level (position
-        encoding, transformer, coarse matching) depends on.  Returns the lateral sum x1_out; `_fpn_fine_tail` makes the fine features of it.
-        lateral = False: stops in front of the 1/2-level lateral conv and returns x2_out (forward's sparse lateral, _fine_tail_sparse)."""
-        # lateral 1x1 conv + F.interpolate(scale_factor=2, bilinear, align_corners=True) of the coarser level + add (resnet.py:
-        # 321-327): the upsample-add runs in the conv's epilogue when the launch takes it, else as a second pass over the output
-        x2_out = self._conv(x2, P["l2o"], ups=x3_out)
-        x2_out = self._conv(self._conv(x2_out, P["l2o2a"], ACT_LEAKY), P["l2o2b"])
-        if not lateral:
-            return x2_out
-        return self._conv(x1, P["l1o"], ups=x2_out)
-
-    def _fine_halo(self, P, h2, w2):
-        """do the fine head's last two layers run on the 3x3 halo kernel at this 1/2-resolution size?  With `fine_sparse` on, every path of the
-        module (forward, extract, debug) sends them there wherever the map is whole 8 x 32 patches, whether the launch then walks a patch list
-        or all patches: one kernel, one K order, so forward() and extract() + match_features() stay bit-identical."""
-        return bool(self.fine_sparse and is_half(self._dt()) and self.use_lds_dma and ops.HALO and P["l1o2a"].halo is not None
-                    and P["l1o2b"].halo is not None and h2 % 8 == 0 and w2 % 32 == 0)
-
-    def _fpn_fine_tail(self, P, x1_out, tiles=None, n_tiles=None, out=None):
-        """layer1_outconv2 (resnet.py:329): the two 3x3 layers at 1/2 resolution whose output is the fine map.  tiles / n_tiles
-        (ops.fine_tile_list): only those 8 x 32 patches are computed (see _fine_tail_sparse); out = (mid, f): the two layers' output maps
-        (the pair-range chains of _fine_tail_sparse share them)."""
-        B, H, W, _ = x1_out.shape
-        if self._fine_halo(P, H, W):
-            # (no health word: these launches add no residual -- ops.conv_rows hands the word to residual / split launches only)
-            mid, f = out if out is not None else self._fine_tail_maps(P, x1_out)
-            ops.conv3x3_halo(x1_out, P["l1o2a"], mid, ACT_LEAKY, tiles=tiles, n_tiles=n_tiles)
-            ops.conv3x3_halo(mid, P["l1o2b"], f, ACT_NONE, tiles=tiles, n_tiles=n_tiles)
-            return f
-        assert tiles is None and out is None
-        return self._conv(self._conv(x1_out, P["l1o2a"], ACT_LEAKY), P["l1o2b"])
-
-    def _fine_head_maps(self, P, x1, x2):
-        """the six (uncleared) maps the sparse head writes between the trunk and the fused fine kernel: layer2_outconv + upsample-add,
-        layer2_outconv2's two layers (1/4 level), the lateral sum x1_out, layer1_outconv2's two layers (1/2 level)"""
-        new = lambda t, pk: torch.empty(*t.shape[:3], pk.n_store, dtype=x1.dtype, device=x1.device)   # noqa: E731
-        x1_out = new(x1, P["l1o"])
-        return (new(x2, P["l2o"]), new(x2, P["l2o2a"]), new(x2, P["l2o2b"]), x1_out) + self._fine_tail_maps(P, x1_out)
-
-    @staticmethod
-    def _fine_tail_maps(P, x1_out):
-        """the (uncleared) output maps of layer1_outconv2's two layers on the halo kernel"""
-        B, H, W, _ = x1_out.shape
-        return (torch.empty(B, H, W, P["l1o2a"].n_store, dtype=x1_out.dtype, device=x1_out.device),
-                torch.empty(B, H, W, P["l1o2b"].n_store, dtype=x1_out.dtype, device=x1_out.device))
-
-    def _fine_sparse_ok(self, P, xs):
-        """may this forward compute the fine map under the matched windows only?  (the conditions of _fine_tail_sparse)"""
-        if self.debug is not None or len(xs) != 1:   # debug dumps and the extract() handles hold complete maps
-            return False
-        B, H, W = xs[0].shape[:3]
-        h2, w2 = _half(H), _half(W)
-        h8, w8 = _half(_half(h2)), _half(_half(w2))
-        # the window stride the gather uses (4 h8 = h2), and no more patches than the one-workgroup list kernel flags
-        return self._fine_halo(P, h2, w2) and h2 == 4 * h8 and w2 == 4 * w8 and B * (h2 // 8) * (w2 // 32) <= ops.FINE_TILE_MAX_FLAGS
-
-    def _lateral_sparse_ok(self, P, xs):
-        """may this forward (one that `_fine_sparse_ok` accepts) also compute the lateral sum x1_out under the matched windows only?  The
-        launch must be one the patch-list entry takes, and one whose dense form fuses the upsample-add as well -- extract() runs that one,
-        and forward() must stay bit-identical to extract() + match_features() (ops.conv_ups_tiles_supported); x1 is [B,h2,w2,.], x2_out
-        [B,h2/2,w2/2,.]."""
-        if not self.lateral_sparse:
-            return False
-        B, H, W = xs[0].shape[:3]
-        pk = P["l1o"]
-        key = (B, H, W, pk.dtype, pk.cin_pad, pk.n_store, ops.FORCE_BIG_TILE, ops.UPS_FUSED)   # all the predicates look at
-        ok = self._lat_ok.get(key)
-        if ok is None:
-            h2, w2 = _half(H), _half(W)
-            ok = self._lat_ok[key] = ops.conv_ups_tiles_supported((B, h2, w2, pk.cin_pad), pk, (B, h2 // 2, w2 // 2, pk.n_store), dense_too=True)
-        return ok
-
-    def _quarter_sparse_ok(self, P, xs):
-        """may this forward (one that `_lateral_sparse_ok` accepts) also compute the 1/4-level part of the head -- layer2_outconv + upsample-add
-        of x3_out, then the two 3 x 3 layers of layer2_outconv2 -- on patch lists behind coarse matching?  Each of the three launches must be one
-        its list entry takes AND one whose dense form runs on the same 256 x 256 tile in the same K order: extract() and every fall-back run
-        the dense launches, and forward() must stay bit-identical to extract() + match_features().  x2 is [B,h4,w4,.], x3_out [B,h8,w8,.]."""
-        if not (self.quarter_sparse and self._lateral_sparse_ok(P, xs)):
-            return False
-        B, H, W = xs[0].shape[:3]
-        key = (B, H, W, P["l2o"].dtype, ops.FORCE_BIG_TILE, ops.UPS_FUSED, ops.HALO, ops.HALO_MIN_TILES)   # all the predicates look at
-        ok = self._q_ok.get(key)
-        if ok is None:
-            h2, w2 = _half(H), _half(W)
-            h4, w4 = _half(h2), _half(w2)
-            pk, pa, pb = P["l2o"], P["l2o2a"], P["l2o2b"]
-            ok = self._q_ok[key] = bool(
-                h2 == 2 * h4 and w2 == 2 * w4 and h4 % 2 == 0 and w4 % 2 == 0 and ops.fine_tile_lists4_fits(B // 2, h2, w2)
-                and pa.cin_pad == pk.n_store and pb.cin_pad == pa.n_store
-                and ops.conv_ups_tiles_supported((B, h4, w4, pk.cin_pad), pk, (B, h4 // 2, w4 // 2, pk.n_store), dense_too=True)
-                and ops.conv_tiles_supported((B, h4, w4, pa.cin_pad), pa, dense_too=True)
-                and ops.conv_tiles_supported((B, h4, w4, pb.cin_pad), pb, dense_too=True))
-        return ok
-
-    def _fine_tail_sparse(self, P, x1_out, cr, bs):
-        """`_fpn_fine_tail` on the 8 x 32 patches that the fine level can read, behind coarse matching.  The fine map has ONE consumer: the
-        gather of a 5 x 5 window per match and side at rows 4 cy - 2 .. 4 cy + 2 (fine_fused.hip / gim_fine_gather; zeros outside the image).
-        A window pixel of the second layer reads the first layer at +-1 more, so both launches walk one list: the patches that hold a pixel
-        of [4 cy - 3, 4 cy + 3] x [4 cx - 3, 4 cx + 3] for some match (gim_fine_tile_list, from the device-side match count -- no host sync,
-        same captured graph).  Every input of a listed first-layer pixel lies in x1_out, which is dense.  Pixels of other patches are never
-        written and never read: the buffers are NOT cleared (a replayed graph leaves the previous forward's values there).
-        x1_out = (x1, x2_out) (`_lateral_sparse_ok`): the lateral conv + upsample-add that makes x1_out runs here too, on a patch list.
-        x1_out = (x1, x2, x3_out) (`_quarter_sparse_ok`): so do the three 1/4-level launches that make x2_out, on lists of their own."""
-        if isinstance(x1_out, tuple) and len(x1_out) == 3:
-            x1, x2, x3_out = x1_out
-            _, H, W, _ = x1.shape
-            # x2_out has ONE consumer, the list-walking lateral below, which reads it where Epilogue::ups_accumulate stages upsample sources
-            # for the +-4 patches: S, weight-0 sources included (0 x NaN = NaN, and an unlisted pixel may hold anything).  x2_out is valid on S
-            # if layer2_outconv2's first layer is valid on S dilated by 1, and that if the 1/4-level lateral is valid on S dilated by 2: lists
-            # C, B, A of gim_fine_tile_lists4 (C <= B <= A), from the same one-workgroup launch.  The ring a listed patch reads outside its
-            # list reaches only outputs outside S and its dilations, which nothing consumed reads (DESIGN.md 7d).
-            K = min(int(self.fine_chains), bs) if (self.debug is None and self.fine_chains > 1 and self._fine_halo(P, H, W)) else 1
-            if K > 1:
-                return self._fine_tail_chains(P, x1, x2, x3_out, cr, bs, K)
-            tiles, n_tiles, tiles4, n_tiles4, tq, nq = ops.fine_tile_lists4(cr.b_ids, cr.i_ids, cr.j_ids, cr.count, bs, cr.args.w0c, cr.args.w1c, 4, H, W)
-            x2_out = ops.conv2d_ups_tiles(x2, P["l2o"], x3_out, tq[0], nq[0:1])
-            x2_out = ops.conv2d_tiles(x2_out, P["l2o2a"], tq[1], nq[1:2], ACT_LEAKY)
-            x2_out = ops.conv2d_tiles(x2_out, P["l2o2b"], tq[2], nq[2:3])
-            x1_out = ops.conv2d_ups_tiles(x1, P["l1o"], x2_out, tiles4, n_tiles4)
-            if self.lateral_one_list:
-                tiles, n_tiles = tiles4, n_tiles4
-            return self._fpn_fine_tail(P, x1_out, tiles, n_tiles)
-        if isinstance(x1_out, tuple):
-            x1, x2_out = x1_out
-            _, H, W, _ = x1.shape
-            # Two lists from one launch: the +-3 list above for the two 3 x 3 layers, and the patches of the reach one pixel wider, +-4, for
-            # the lateral -- every x1_out pixel a CONSUMED first-layer output (+-3) reads lies within +-4, hence in a patch of the second
-            # list.  A listed first-layer patch also reads a one-pixel ring that may lie in patches the lateral never wrote (stale or
-            # uninitialised values): those reach only first-layer outputs outside every +-3 box, which the second layer's consumed
-            # outputs (+-2) never read -- convolution outputs do not mix across pixels.  The alternative, ONE +-4 list for all three
-            # launches, rests on the same argument but grows the two 3 x 3 launches (the expensive ones: a patch row is added below
-            # every match on an odd coarse row, 4 cy + 4 = 8 k) and shrinks nothing; the second list costs one more compaction in the
-            # one-workgroup kernel (DESIGN.md 7d).
-            tiles, n_tiles, tiles4, n_tiles4 = ops.fine_tile_lists(cr.b_ids, cr.i_ids, cr.j_ids, cr.count, bs, cr.args.w0c, cr.args.w1c, 4, H, W)
-            x1_out = ops.conv2d_ups_tiles(x1, P["l1o"], x2_out, tiles4, n_tiles4)
-            if self.lateral_one_list:
-                tiles, n_tiles = tiles4, n_tiles4
-            return self._fpn_fine_tail(P, x1_out, tiles, n_tiles)
-        _, H, W, _ = x1_out.shape
-        tiles, n_tiles = ops.fine_tile_list(cr.b_ids, cr.i_ids, cr.j_ids, cr.count, bs, cr.args.w0c, cr.args.w1c, 4, H, W)
-        return self._fpn_fine_tail(P, x1_out, tiles, n_tiles)
-
-    def _fine_tail_chains(self, P, x1, x2, x3_out, cr, bs, K):
-        """the whole sparse head of `_fine_tail_sparse` (x1_out = (x1, x2, x3_out)) as K pair-range chains on parallel streams.  Chain g owns
-        the pairs [bs g / K, bs (g + 1) / K), i.e. the images b and bs + b of those pairs: its list launch marks the patches of its own
-        matches only (ops.fine_tile_lists4, b_range), then its six launches walk those lists.  A patch belongs to one image and no
-        convolution, lateral or upsample reads across images, so the chains share no data: they write disjoint patches of the same six
-        (uncleared) maps, every listed patch gets the bits the one-chain launches write, and the one-pixel ring argument of DESIGN.md 7d
-        holds per image.  The launches are persistent (one workgroup per CU walking a list whose length the host does not know): alone
-        on the chip each pays a whole last round, two chains fill each other's.  Fork behind coarse matching, join in front of the fused
-        fine kernel, inside the captured graph; same kernels, same arithmetic."""
-        H, W = x1.shape[1:3]
-        # allocated on the main stream in front of the fork, read by the main stream behind the join
-        qa, qb, qc, x1_out, mid, f = self._fine_head_maps(P, x1, x2)
-        main = torch.cuda.current_stream()
-        sides = self._side_streams(x1.device, K - 1)
-        keep = []   # the chains' patch lists and counts stay referenced until the join (the caching allocator re-uses a freed block per stream)
-
-        def chain(g):
-            lists = ops.fine_tile_lists4(cr.b_ids, cr.i_ids, cr.j_ids, cr.count, bs, cr.args.w0c, cr.args.w1c, 4, H, W,
-                                         b_range=(bs * g // K, bs * (g + 1) // K))
-            keep.append(lists)
-            tiles, n_tiles, tiles4, n_tiles4, tq, nq = lists
-            got = (ops.conv2d_ups_tiles(x2, P["l2o"], x3_out, tq[0], nq[0:1], y=qa),
-                   ops.conv2d_tiles(qa, P["l2o2a"], tq[1], nq[1:2], ACT_LEAKY, out=qb),
-                   ops.conv2d_tiles(qb, P["l2o2b"], tq[2], nq[2:3], out=qc),
-                   ops.conv2d_ups_tiles(x1, P["l1o"], qc, tiles4, n_tiles4, y=x1_out))
-            if not all(a is b for a, b in zip(got, (qa, qb, qc, x1_out))):   # a dense fall-back allocates its own map: _quarter_sparse_ok admitted all four
-                raise RuntimeError("fine_chains: a list launch of the sparse fine head fell back to its dense form")
-            if self.lateral_one_list:
-                tiles, n_tiles = tiles4, n_tiles4
-            self._fpn_fine_tail(P, x1_out, tiles, n_tiles, out=(mid, f))
-
-        for g in range(1, K):
-            sides[g - 1].wait_stream(main)
-            with torch.cuda.stream(sides[g - 1]):
-                chain(g)
-        chain(0)
-        for s_ in sides:
-            main.wait_stream(s_)
-        return f   # (`keep` dies past the join: see the lifetime note at T.init_state, _transformer_emit)
 
     class _TfBuffers:
         """Row buffers of one LocalFeatureTransformer run over R rows of width C.  The q / k / v rows, the message, the pre-LayerNorm
@@ -1065,7 +880,7 @@ class LoFTR(nn.Module):
                         off += (n0, n1)[sd]
         # Cross-stream lifetime: the chains below run on side streams and read these workspaces (and write the ones in T.keep).  No
         # record_stream() is needed because the owning tensors stay referenced by T (init_state, keep) until _coarse_stage returns, i.e.
-        # past the main.wait_stream() join at the end of this function -- the caching allocator cannot hand their blocks out before that
+        # past the join of `_fork_join` at the end of this function -- the caching allocator cannot hand their blocks out before that
         T.init_state = init_state
         self._posenc(T, rows)   # whatever the projection-only launches did not cover
         for (li, sides), blks in groups.items():
@@ -1143,17 +958,8 @@ class LoFTR(nn.Module):
             T.ws = T.keep[0]
             return
         m = n0 // K
-        main = torch.cuda.current_stream()
-        sides_ = self._side_streams(T.X32.device, K - 1)
-        keep = []   # per-chain workspaces stay referenced until the join
-        for g in range(1, K):
-            sides_[g - 1].wait_stream(main)
-            with torch.cuda.stream(sides_[g - 1]):
-                keep.append(run((slice(g * m * L, (g + 1) * m * L), slice(n0 * L + g * m * S, n0 * L + (g + 1) * m * S)), m, m, None))
-        keep.append(run((slice(0, m * L), slice(n0 * L, n0 * L + m * S)), m, m, None))
-        for s_ in sides_:
-            main.wait_stream(s_)
-        T.keep = keep   # (every side-stream workspace outlives the join above: see the lifetime note at T.init_state)
+        # per-chain workspaces stay referenced until the join (every side-stream workspace outlives it: see the lifetime note at T.init_state)
+        T.keep = self._fork_join(T.X32.device, K, lambda g: run((slice(g * m * L, (g + 1) * m * L), slice(n0 * L + g * m * S, n0 * L + (g + 1) * m * S)), m, m, None))
 
     @staticmethod
     def _posenc(T, rows, sides=(0, 1)):
@@ -1208,14 +1014,13 @@ class LoFTR(nn.Module):
             # (round 4: the fine head on a second stream beside the coarse level -- a graph with two branches, the head's persistent
             # workgroups filling the CUs the transformer's 600-tile launches leave idle -- measured SLOWER, 10.96 vs 10.70 ms per step:
             # the two branches fight over L2 and LDS instead of complementing each other; one stream it is)
-            if self._fine_sparse_ok(P, xs):
-                # the fine head stops in front of its last two layers; they run behind coarse matching, under the matched windows only
-                # (... and, where the launch allows, in front of the 1/2-level lateral conv: x1_out is then the pair (x1, x2_out))
-                # (... and, where those launches allow too, behind the trunk: the triple (x1, x2, x3_out))
-                c_all, x1_out = self._extract_stage(P, xs[0], fine_tail=False, lateral=not self._lateral_sparse_ok(P, xs),
-                                                    quarter=not self._quarter_sparse_ok(P, xs))
+            depth = self._head_depth(P, xs)
+            if depth:
+                # the fine head stops in front of its last `depth` stages (fine_head.py); they run behind coarse matching, under the
+                # matched windows only
+                c_all, head = self._extract_stage(P, xs[0], head=depth)
                 st = self._match_stage(P, c_all[:bs], c_all[bs:], None, None, c_all, bs, xs[0].shape[1], scale0, scale1, mask0, mask1, count)
-                f_all = self._fine_tail_sparse(P, x1_out, st["cr"], bs)
+                f_all = self._fine_tail_sparse(P, head, st["cr"], bs)
                 st["f0"], st["f1"] = f_all[:bs], f_all[bs:]
                 return st
             c_all, f_all = self._extract_stage(P, xs[0])
@@ -1233,12 +1038,11 @@ class LoFTR(nn.Module):
         split = ops.FP32_SPLIT if self._split16 is None else self._split16
         return word if (self.precision == "fp16" or (self.precision == "fp32" and split)) else None
 
-    def _extract_stage(self, P, x, fine_tail=True, lateral=True, quarter=True):
+    def _extract_stage(self, P, x, head=0):
         """the per-image half: NHWC images [B,H,W,cstore(3)] -> (coarse map [B,H/8,W/8,256], fine map [B,H/2,W/2,128]) in the compute dtype.
         No image's maps depend on another image of the batch (eval-mode BatchNorm is folded into the weights).
-        fine_tail = False (forward's sparse fine tail): the fine head's last two layers are left to the caller, see _backbone;
-        lateral = False: the 1/2-level lateral conv too; quarter = False: and the 1/4-level part of the head."""
-        return self._backbone(P, x, self._dt(), fine_tail, lateral, quarter)
+        head = 1..3 (forward's sparse fine head): that many stages of the fine head are left to the caller, see _backbone."""
+        return self._backbone(P, x, self._dt(), head)
 
     def _match_stage(self, P, c0, c1, f0, f1, c_all, bs, H0, scale0, scale1, mask0, mask1, count):
         """the per-pair half: coarse maps c0 / c1 [bs,h,w,256] and fine maps f0 / f1 of the bs pairs -> position encoding, coarse
@@ -1283,7 +1087,7 @@ class LoFTR(nn.Module):
 
     def _graph_key(self, color0, color1, scale0, mask0):
         return (tuple(color0.shape), tuple(color1.shape), scale0 is not None, mask0 is not None, self.precision, bool(self.fp32_split),
-                bool(self.fine_sparse), bool(self.lateral_sparse), bool(self.quarter_sparse), bool(self.lateral_one_list), int(self.fine_chains), self.coarse_sim, self._img_dt(), self._split(), self._stem_k(), str(color0.device))
+                bool(self.fine_sparse), bool(self.lateral_sparse), bool(self.quarter_sparse), int(self.fine_chains), self.coarse_sim, self._img_dt(), self._split(), self._stem_k(), str(color0.device))
 
     def _stage_graphed(self, key, fill, warm, stage, bs, dev, scale0, scale1, mask0, mask1):
         """HIP-graph replay of a shape-static stage (one graph per `key`: input shapes / precision): forward's `_coarse_stage` (~140 kernel

@@ -461,14 +461,19 @@ def conv2d_tiles(x, pk, tiles, n_tiles, act=ACT_NONE, out=None):
 FINE_TILE_MAX_FLAGS = lib.gim_fine_tile_list_max_flags()
 
 
+def _match_list_cap(b_ids, i_ids, j_ids, count, *more):
+    """what the patch-list launches ask of the match lists (int64, contiguous, on the device like `count` and `more`); returns their capacity"""
+    _req_cuda(b_ids, i_ids, j_ids, count, *more)
+    assert b_ids.dtype == i_ids.dtype == j_ids.dtype == torch.int64 and count.dtype == torch.int32
+    assert b_ids.is_contiguous() and i_ids.is_contiguous() and j_ids.is_contiguous()
+    return min(b_ids.numel(), i_ids.numel(), j_ids.numel())
+
+
 def fine_tile_list(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W, tiles=None, n_tiles=None):
     """(tiles int32 [2 bs ceil(H/8) ceil(W/32)], n_tiles int32 [1]): the ascending list of 8 x 32 patches of the 1/2-resolution maps
     [2 bs, H, W, .] that the fine windows of the first min(count[0], capacity) matches reach through one 3 x 3 convolution
     (gim_fine_tile_list; one launch, the count is read on the device)"""
-    _req_cuda(b_ids, i_ids, j_ids, count, tiles, n_tiles)
-    assert b_ids.dtype == i_ids.dtype == j_ids.dtype == torch.int64 and count.dtype == torch.int32
-    assert b_ids.is_contiguous() and i_ids.is_contiguous() and j_ids.is_contiguous()
-    cap = min(b_ids.numel(), i_ids.numel(), j_ids.numel())
+    cap = _match_list_cap(b_ids, i_ids, j_ids, count, tiles, n_tiles)
     total = 2 * bs * ((H + 7) // 8) * ((W + 31) // 32)
     if tiles is None:
         tiles = torch.empty(total, dtype=torch.int32, device=b_ids.device)
@@ -483,10 +488,7 @@ def fine_tile_list(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W, tiles
 def fine_tile_lists(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W):
     """`fine_tile_list` and, from the same launch, the list of the reach grown by one pixel (+-4 instead of +-3 around stride * cell): the
     patches whose lateral sum the last-but-one 3 x 3 layer reads.  Returns (tiles, n_tiles, tiles4, n_tiles4)  (gim_fine_tile_lists)"""
-    _req_cuda(b_ids, i_ids, j_ids, count)
-    assert b_ids.dtype == i_ids.dtype == j_ids.dtype == torch.int64 and count.dtype == torch.int32
-    assert b_ids.is_contiguous() and i_ids.is_contiguous() and j_ids.is_contiguous()
-    cap = min(b_ids.numel(), i_ids.numel(), j_ids.numel())
+    cap = _match_list_cap(b_ids, i_ids, j_ids, count)
     total = 2 * bs * ((H + 7) // 8) * ((W + 31) // 32)
     tiles = torch.empty(2, total, dtype=torch.int32, device=b_ids.device)
     n = torch.empty(2, dtype=torch.int32, device=b_ids.device)
@@ -501,11 +503,8 @@ def fine_tile_lists4(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W, b_r
     n_tiles4, tilesq [3, total/4] = lists A (dilated by 2), B (by 1), C (S itself), n_tilesq [3])  (gim_fine_tile_lists4; H % 16 == 0,
     W % 64 == 0).  b_range = (b_lo, b_hi): only the matches of those pairs mark patches (gim_fine_tile_lists4_range; indices and buffer
     sizes stay those of the whole batch)."""
-    _req_cuda(b_ids, i_ids, j_ids, count)
-    assert b_ids.dtype == i_ids.dtype == j_ids.dtype == torch.int64 and count.dtype == torch.int32
-    assert b_ids.is_contiguous() and i_ids.is_contiguous() and j_ids.is_contiguous()
     assert H % 16 == 0 and W % 64 == 0, (H, W)
-    cap = min(b_ids.numel(), i_ids.numel(), j_ids.numel())
+    cap = _match_list_cap(b_ids, i_ids, j_ids, count)
     total = 2 * bs * (H // 8) * (W // 32)
     totq = 2 * bs * (H // 16) * (W // 64)
     tiles = torch.empty(2 * total + 3 * totq, dtype=torch.int32, device=b_ids.device)

@@ -13,8 +13,7 @@ Switches of gim_loftr (`LoFTR.__init__` has each with its comment): stem_fp16, s
 fine_dev_count, token_emit, bneck_fused, bneck_tail, bneck_ds, bneck_tail_ds, depth_groups, l3_chains, trunk_chains, tf_chains, fp32_split,
 kv_fused, q_local, kv_init, pos_fused, fine_sparse (the FPN's last two layers only under the matched fine windows), lateral_sparse (the
 1/2-level lateral conv + upsample-add in front of them too), quarter_sparse (and the 1/4-level lateral + 3 x 3 layers in front of that, where
-the lateral's listed patches read them), fine_chains (that whole sparse head as pair-range chains on parallel streams), lateral_one_list
-(A/B: one +-4 patch list for all three launches), graph, graph_cache;
+the lateral's listed patches read them), fine_chains (that whole sparse head as pair-range chains on parallel streams), graph, graph_cache;
 of gim_amd.ops: conv_halo, conv_halo_min_tiles, force_big_tile, fp32_split_all, ups_fused.
 
 Environment variables the package reads -- all of them, the C library reads none (round 6: the last two getenv() calls left csrc/):

@@ -1,4 +1,4 @@
-"""The sparse fine head of gim_loftr as two pair-range chains on parallel streams (gim_amd/loftr/loftr.py: `fine_chains`, _fine_tail_chains).
+"""The sparse fine head of gim_loftr as two pair-range chains on parallel streams (gim_amd/loftr/fine_head.py: `fine_chains`, _fine_tail_sparse).
 
 forward() with fine_chains = 2 against forward() with fine_chains = 1 (the launch sequence it had before), same weights, one process, fp16:
 every output tensor torch.equal -- eager, graph capture, and three replays on changing inputs.  Shapes: bs = 2 at 64 x 128 and bs = 3
