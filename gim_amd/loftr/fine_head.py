@@ -69,7 +69,7 @@ class FineHead:
 
     def _fpn_fine_tail(self, P, x1_out, tiles=None, n_tiles=None, out=None):
         """layer1_outconv2 (resnet.py:329): the two 3x3 layers at 1/2 resolution whose output is the fine map.  tiles / n_tiles
-        (ops.fine_tile_list): only those 8 x 32 patches are computed (see _fine_tail_sparse); out = (mid, f): the two layers' output maps
+        (ops.fine_tile_lists): only those 8 x 32 patches are computed (see _fine_tail_sparse); out = (mid, f): the two layers' output maps
         (the pair-range chains of _fine_tail_sparse share them)."""
         B, H, W, _ = x1_out.shape
         if self._fine_halo(P, H, W):
@@ -150,8 +150,8 @@ class FineHead:
     def _fine_tail_sparse(self, P, head, cr, bs):
         """The last `head.depth` stages of the head on the 8 x 32 patches that the fine level can read, behind coarse matching and in the same
         captured graph.  The fine map has ONE consumer: the gather of a 5 x 5 window per match and side at rows 4 cy - 2 .. 4 cy + 2
-        (fine_fused.hip / gim_fine_gather; zeros outside the image).  One one-workgroup launch builds the patch lists of the depth from the
-        device-side match count (no host sync); the launches then walk them.  Pixels of other patches are never written and never read:
+        (fine_fused.hip / gim_fine_gather; zeros outside the image).  One one-workgroup launch (ops.fine_tile_lists) builds the patch lists of
+        the depth from the device-side match count (no host sync); the launches then walk them.  Pixels of other patches are never written and never read:
         the maps are NOT cleared (a replayed graph leaves the previous forward's values there).
 
         depth 1 (gim_fine_tile_list).  A window pixel of layer1_outconv2's second layer reads the first layer at +-1 more, so both launches
@@ -182,23 +182,21 @@ class FineHead:
         K = min(int(self.fine_chains), bs) if (depth == 3 and self.debug is None and self.fine_chains > 1 and self._fine_halo(P, H, W)) else 1
         # allocated on the main stream in front of the fork, read by the main stream behind the join
         maps = self._fine_head_maps(P, head)
-        build = (ops.fine_tile_list, ops.fine_tile_lists, ops.fine_tile_lists4)[depth - 1]
 
         def chain(g):
             pairs = {"b_range": (bs * g // K, bs * (g + 1) // K)} if K > 1 else {}
-            lists = build(cr.b_ids, cr.i_ids, cr.j_ids, cr.count, bs, cr.args.w0c, cr.args.w1c, 4, H, W, **pairs)
-            tiles, n_tiles, tiles4, n_tiles4, tq, nq = lists + (None,) * (6 - len(lists))
+            lists = ops.fine_tile_lists(cr.b_ids, cr.i_ids, cr.j_ids, cr.count, bs, cr.args.w0c, cr.args.w1c, 4, H, W, depth=depth, **pairs)
             # (first depth that runs it, launch): t is what the launch in front returned, y the map to write
-            table = ((3, lambda t, y: ops.conv2d_ups_tiles(head.x2, P["l2o"], head.x3_out, tq[0], nq[0:1], y=y)),
-                     (3, lambda t, y: ops.conv2d_tiles(t, P["l2o2a"], tq[1], nq[1:2], ACT_LEAKY, out=y)),
-                     (3, lambda t, y: ops.conv2d_tiles(t, P["l2o2b"], tq[2], nq[2:3], out=y)),
-                     (2, lambda t, y: ops.conv2d_ups_tiles(head.x1, P["l1o"], t, tiles4, n_tiles4, y=y)))
+            table = ((3, lambda t, y: ops.conv2d_ups_tiles(head.x2, P["l2o"], head.x3_out, lists.tilesq[0], lists.n_tilesq[0:1], y=y)),
+                     (3, lambda t, y: ops.conv2d_tiles(t, P["l2o2a"], lists.tilesq[1], lists.n_tilesq[1:2], ACT_LEAKY, out=y)),
+                     (3, lambda t, y: ops.conv2d_tiles(t, P["l2o2b"], lists.tilesq[2], lists.n_tilesq[2:3], out=y)),
+                     (2, lambda t, y: ops.conv2d_ups_tiles(head.x1, P["l1o"], t, lists.tiles4, lists.n_tiles4, y=y)))
             t = head.x2_out if depth == 2 else head.x1_out
             for (_, launch), y in zip([row for row in table if depth >= row[0]], maps):
                 t = launch(t, y)
                 if K > 1 and t is not y:   # a dense fall-back allocates its own map: _quarter_sparse_ok admitted all four
                     raise RuntimeError("fine_chains: a list launch of the sparse fine head fell back to its dense form")
-            self._fpn_fine_tail(P, t, tiles, n_tiles, out=maps[-2:])
+            self._fpn_fine_tail(P, t, lists.tiles, lists.n_tiles, out=maps[-2:])
             return lists
 
         # the chains' patch lists and counts stay referenced until the join (the caching allocator re-uses a freed block per stream)

@@ -5,6 +5,7 @@ import collections
 import ctypes
 import math
 import os
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -212,80 +213,54 @@ def nhwc_to_nchw(src, C):
 
 
 # ---- conv / linear --------------------------------------------------------------------------------
-def conv_rows(x, pk, geom, y, act=ACT_NONE, res=None, res_mod=0, lds_dma=True, act_cols=0, ups=None, health=None, split16=None):
-    """Generic launch.  x: 2-D row view [rows_in, ldx]; geom = (B, H, W, Ho, Wo); y: 2-D row view.  ups: half-resolution NHWC
-    tensor whose bilinear x2 upsampling is added in the epilogue, or a callable that performs that addition as a separate pass when
-    the launch cannot take it (returns True when it was fused).  split16: fp32 operands as split products (None: the module's default, below)."""
-    _req_cuda(x, y, res)
-    B, H, W, Ho, Wo = geom
-    a = _lib.ConvArgs()
-    a.x, a.w, a.ktab = x.data_ptr(), pk.w.data_ptr(), pk.ktab.data_ptr()
-    a.bias = pk.bias.data_ptr() if pk.bias is not None else None
-    a.res = res.data_ptr() if res is not None else None
-    a.y = y.data_ptr()
-    es = elem_size(pk.dtype)
-    assert x.dtype == torch_dtype(pk.dtype), (x.dtype, pk.dtype)
-    a.x_bytes = ((B * H * W - 1) * x.stride(0) + pk.cin_pad) * es
-    a.B, a.H, a.W, a.Ho, a.Wo = B, H, W, Ho, Wo
-    a.stride, a.pad = pk.stride, pk.pad
-    a.ldx, a.ldy = x.stride(0), y.stride(0)
-    a.ldres = res.stride(0) if res is not None else 0
-    a.N, a.npad, a.kpad = pk.n_store, pk.npad, pk.kpad
-    a.act, a.res_mod, a.act_cols = act, res_mod, act_cols
-    a.dtype, a.out_dtype = pk.dtype, gim_dtype(y)
-    a.res_dtype = gim_dtype(res) if res is not None else GIM_F32
-    a.use_lds_dma = (3 if FORCE_BIG_TILE else 1) if lds_dma else 0
-    a.split16 = 1 if ((FP32_SPLIT if split16 is None else split16) and pk.dtype == GIM_F32 and lds_dma) else 0
-    # residual launches: the fp16 range guard (ORs 4); split launches: an operand beyond the fp16 range of the hi / lo split (ORs 8)
-    a.health = _health(health).value if (health is not None and (res is not None or a.split16)) else None
-    assert y.shape[0] >= B * Ho * Wo and y.shape[1] >= pk.n_store
-    if ups is not None:
-        a.ups, a.ups_h, a.ups_w, a.ups_ld = ups.data_ptr(), ups.shape[1], ups.shape[2], ups.shape[3]
-        if not (UPS_FUSED and ups.dtype in HALF and ups.dtype == y.dtype and lib.gim_conv_ups_supported(ctypes.byref(a))):
-            a.ups = None
-    fused_ups = ups is not None and a.ups is not None
-    with _Timed(lambda: f"{pk.cin}->{pk.cout} k{pk.kh}s{pk.stride} M={B * Ho * Wo}" + (" +ups" if fused_ups else ""),
-                lambda: 2.0 * B * Ho * Wo * pk.cout * pk.cin * pk.kh * pk.kw, conv=True):  # algorithmic flops: real channels, no padding
-        check(lib.gim_conv2d_bn_act(ctypes.byref(a), _stream()), "gim_conv2d_bn_act")
-    return fused_ups
-
-
 FORCE_BIG_TILE = flag("force_big_tile", False)   # tests: the 256 x 256 tile on every eligible launch, whatever its size (gim_conv_args.use_lds_dma = 3)
 # fp32 operands multiplied as IEEE-fp16 hi / lo pairs on the 16-bit MFMA (gim_conv_args.split16: three products per 16 K instead of eight fp32 MFMAs, 2^-22 per
 # product): the default of the launches that pass no `split16` -- gim_loftr's fp32 mode passes its own per launch (LoFTR.fp32_split)
 FP32_SPLIT = flag("fp32_split_all", False)
 UPS_FUSED = flag("ups_fused", True)   # FPN: bilinear x2 + add inside the lateral 1x1 conv's epilogue (False: a second pass over the output)
-
-
-def conv2d(x, pk, act=ACT_NONE, res=None, out_dtype=None, lds_dma=True, ups=None, health=None, split16=None):
-    """x [B,H,W,cin_pad] NHWC -> new [B,Ho,Wo,n_store].  ups: [B,Ho/2,Wo/2,n_store] -> y += bilinear_x2(ups) (align_corners=True):
-    in the conv's epilogue when the launch supports it, otherwise as a second pass (gim_upsample2x_add)."""
-    B, H, W, cs = x.shape
-    assert cs == pk.cin_pad, (cs, pk)
-    d = getattr(pk, "dil", 1)       # dilated taps (packing.pack_conv(dilation=)): effective extent (k - 1) d + 1
-    Ho = (H + 2 * pk.pad - (pk.kh - 1) * d - 1) // pk.stride + 1
-    Wo = (W + 2 * pk.pad - (pk.kw - 1) * d - 1) // pk.stride + 1
-    y = torch.empty(B, Ho, Wo, pk.n_store, dtype=out_dtype or x.dtype, device=x.device)
-    r = res.view(-1, res.shape[-1]) if res is not None else None
-    geom = (B, H, W, Ho, Wo)
-    if pk.kh == 1 and pk.kw == 1 and pk.stride == 1 and pk.pad == 0:
-        geom = (1, 1, B * H * W, 1, B * H * W)  # pixel index == row index: the kernel skips the coordinate decode
-    if HALO and pk.halo is not None and res is None and lds_dma and x.dtype in HALF and y.dtype == x.dtype \
-            and x.is_contiguous() and _halo_pays(pk, B, H, W):
-        conv3x3_halo(x, pk, y, act)
-        return y
-    if ups is not None:
-        assert ups.shape == (B, Ho // 2, Wo // 2, pk.n_store) and res is None and ups.is_contiguous()
-        if not conv_rows(x.view(-1, cs), pk, geom, y.view(-1, pk.n_store), act, r, 0, lds_dma, ups=ups, health=health, split16=split16):
-            upsample2x_add(ups, y)
-        return y
-    conv_rows(x.view(-1, cs), pk, geom, y.view(-1, pk.n_store), act, r, 0, lds_dma, health=health, split16=split16)
-    return y
-
-
 # 3x3 halo kernel (conv_igemm.hip: conv3x3_halo_kernel); module attributes, tests flip them (switches: conv_halo, conv_halo_min_tiles)
 HALO = flag("conv_halo", True)
 HALO_MIN_TILES = flag("conv_halo_min_tiles", 2000)   # round 3 sweep: below ~2000 tiles (the 1/4-resolution layers) the generic kernel is 5-8 % faster
+
+
+def _conv_args(pk, geom, ldx, ldy, *, x=None, y=None, act=ACT_NONE, res=None, res_mod=0, act_cols=0, lds_dma=True, ups=None, split16=False,
+               health=None, halo=False):
+    """The gim_conv_args of every launch and predicate of this file (the one place that fills the struct).  geom = (B, H, W, Ho, Wo) as the
+    launch states it, ldx / ldy: the row strides of input and output.  x / y: the tensors, or None -- the predicates need no pointer, the
+    output is then of the pack's dtype.  res: row view of the residual; ups: the half-resolution NHWC operand of the fused upsample-add, or its
+    shape; health: see `_health`, passed on to residual and split launches only.  halo: the halo kernel's form -- w / ktab / kpad / npad /
+    bias of `pk.halo`, res_mod = cin_pad, use_lds_dma = 2."""
+    B, H, W, Ho, Wo = geom
+    w, ktab, bias, npad, kpad = pk.w, pk.ktab, pk.bias, pk.npad, pk.kpad
+    if halo:
+        w, ktab, nslab, bias = pk.halo
+        npad, kpad, res_mod = w.shape[0], nslab * 64, pk.cin_pad
+    a = _lib.ConvArgs()
+    if x is not None:
+        assert x.dtype == torch_dtype(pk.dtype), (x.dtype, pk.dtype)
+        a.x, a.y = x.data_ptr(), y.data_ptr()
+    a.w, a.ktab = w.data_ptr(), ktab.data_ptr()
+    a.bias = bias.data_ptr() if bias is not None else None
+    a.res = res.data_ptr() if res is not None else None
+    a.x_bytes = ((B * H * W - 1) * ldx + pk.cin_pad) * (2 if halo else elem_size(pk.dtype))
+    a.B, a.H, a.W, a.Ho, a.Wo = B, H, W, Ho, Wo
+    a.stride, a.pad = (1, 1) if halo else (pk.stride, pk.pad)
+    a.ldx, a.ldy = ldx, ldy
+    a.ldres = res.stride(0) if res is not None else 0
+    a.N, a.npad, a.kpad = pk.n_store, npad, kpad
+    a.act, a.res_mod, a.act_cols = act, res_mod, act_cols
+    a.dtype, a.out_dtype = pk.dtype, gim_dtype(y) if y is not None else pk.dtype
+    a.res_dtype = gim_dtype(res) if res is not None else GIM_F32
+    a.use_lds_dma = 2 if halo else (3 if FORCE_BIG_TILE else 1) if lds_dma else 0
+    a.split16 = 1 if (split16 and pk.dtype == GIM_F32 and lds_dma) else 0
+    # residual launches: the fp16 range guard (ORs 4); split launches: an operand beyond the fp16 range of the hi / lo split (ORs 8)
+    a.health = _health(health).value if (health is not None and (res is not None or a.split16)) else None
+    if ups is not None:
+        if torch.is_tensor(ups):
+            assert y is None or ups.dtype == y.dtype   # (what the second pass, `upsample2x_add`, asks as well)
+            a.ups = ups.data_ptr()
+        a.ups_h, a.ups_w, a.ups_ld = tuple(getattr(ups, "shape", ups))[1:4]
+    return a
 
 
 def _halo_pays(pk, B, H, W):
@@ -303,78 +278,118 @@ def _halo_pays(pk, B, H, W):
     return B * (H // 8) * (W // 32) * (npad // bn) >= HALO_MIN_TILES
 
 
+def _dense_route(pk, a, xs=None, contiguous=True, tile=False):
+    """Where does the dense launch of `pk` go?  a: its generic struct (`_conv_args`: operand kinds, residual, lds_dma and, with an upsample
+    operand, ups_h / ups_w / ups_ld are read from it); xs: the (B, H, W) of the input map, None for a launch over rows (`conv_rows`,
+    `linear`), which never leaves the generic entry; contiguous: is x?
+      "halo"   `conv3x3_halo` (`conv2d` only)
+      "ups"    the persistent kernel with the upsample-add in its epilogue (gim_conv_ups_supported)
+      "big"    the persistent kernel on the 256 x 256 tile (gim_conv2d_big_tile) -- told from "other" only where `tile` asks for it: one more
+               question to the library, whose answer no launch needs
+      "other"  any other kernel of gim_conv2d_bn_act
+    A launch that cannot fuse its upsample operand goes without it: `a.ups` is cleared here, so that `a` is the launch as it runs, and the
+    caller adds the operand in a second pass.  `conv2d` / `conv_rows` dispatch on the answer, and the `dense_too` halves of
+    `conv_tiles_supported` / `conv_ups_tiles_supported` ask it with a struct built from shapes: they assume a contiguous 16-bit x, an output
+    of x's dtype, no residual and lds_dma, which is what gim_loftr's fine head hands its dense launches wherever it asks (`LoFTR._conv`;
+    fine_head.py `_fine_halo`, in front of every such question, wants a 16-bit module with lds_dma)."""
+    if (xs is not None and HALO and pk.halo is not None and not a.res and a.use_lds_dma in (1, 3) and a.dtype in (GIM_BF16, GIM_F16)
+            and a.out_dtype == a.dtype and contiguous and _halo_pays(pk, *xs)):
+        return "halo"
+    if a.ups_h and UPS_FUSED and lib.gim_conv_ups_supported(ctypes.byref(a)):
+        return "ups"
+    a.ups = None
+    return "big" if tile and lib.gim_conv2d_big_tile(ctypes.byref(a)) else "other"
+
+
+def _conv_timed(pk, M, tag="", n_tiles=None):
+    """`_Timed` of a conv launch (PROFILE): label = the layer's shape + tag; algorithmic flops (real channels, no padding) of M output pixels
+    or, over a patch list, of the computed patches x 256 pixels -- the live measurement alone reads that count back"""
+    return _Timed(lambda: f"{pk.cin}->{pk.cout} k{pk.kh}s{pk.stride} M={M}{tag}",
+                  lambda: 2.0 * (M if n_tiles is None else int(n_tiles[0].item()) * 256) * pk.cout * pk.cin * pk.kh * pk.kw, conv=True)
+
+
+def _conv_dense(a, pk, route):
+    """gim_conv2d_bn_act of the generic struct `a`; returns whether the upsample-add went along (`_dense_route` said "ups")"""
+    with _conv_timed(pk, a.B * a.Ho * a.Wo, " +ups" if route == "ups" else ""):
+        check(lib.gim_conv2d_bn_act(ctypes.byref(a), _stream()), "gim_conv2d_bn_act")
+    return route == "ups"
+
+
+def conv_rows(x, pk, geom, y, act=ACT_NONE, res=None, res_mod=0, lds_dma=True, act_cols=0, ups=None, health=None, split16=None):
+    """Generic launch.  x: 2-D row view [rows_in, ldx]; geom = (B, H, W, Ho, Wo); y: 2-D row view.  ups: half-resolution NHWC tensor whose
+    bilinear x2 upsampling is added in the epilogue when the launch can take it; returns whether it was (False: the caller adds it in a
+    separate pass).  split16: fp32 operands as split products (None: the module's default, FP32_SPLIT)."""
+    _req_cuda(x, y, res)
+    B, H, W, Ho, Wo = geom
+    assert y.shape[0] >= B * Ho * Wo and y.shape[1] >= pk.n_store
+    a = _conv_args(pk, geom, x.stride(0), y.stride(0), x=x, y=y, act=act, res=res, res_mod=res_mod, act_cols=act_cols, lds_dma=lds_dma, ups=ups,
+                   split16=FP32_SPLIT if split16 is None else split16, health=health)
+    return _conv_dense(a, pk, _dense_route(pk, a))
+
+
+def conv2d(x, pk, act=ACT_NONE, res=None, out_dtype=None, lds_dma=True, ups=None, health=None, split16=None):
+    """x [B,H,W,cin_pad] NHWC -> new [B,Ho,Wo,n_store].  ups: [B,Ho/2,Wo/2,n_store] -> y += bilinear_x2(ups) (align_corners=True):
+    in the conv's epilogue when the launch supports it, otherwise as a second pass (gim_upsample2x_add).  `_dense_route` picks the kernel."""
+    B, H, W, cs = x.shape
+    assert cs == pk.cin_pad, (cs, pk)
+    d = getattr(pk, "dil", 1)       # dilated taps (packing.pack_conv(dilation=)): effective extent (k - 1) d + 1
+    Ho = (H + 2 * pk.pad - (pk.kh - 1) * d - 1) // pk.stride + 1
+    Wo = (W + 2 * pk.pad - (pk.kw - 1) * d - 1) // pk.stride + 1
+    y = torch.empty(B, Ho, Wo, pk.n_store, dtype=out_dtype or x.dtype, device=x.device)
+    r = res.view(-1, res.shape[-1]) if res is not None else None
+    _req_cuda(x, y, res)
+    geom = (B, H, W, Ho, Wo)
+    if pk.kh == 1 and pk.kw == 1 and pk.stride == 1 and pk.pad == 0:
+        geom = (1, 1, B * H * W, 1, B * H * W)  # pixel index == row index: the kernel skips the coordinate decode
+    a = _conv_args(pk, geom, x.view(-1, cs).stride(0), pk.n_store, x=x, y=y, act=act, res=r, lds_dma=lds_dma, ups=ups,
+                   split16=FP32_SPLIT if split16 is None else split16, health=health)
+    route = _dense_route(pk, a, (B, H, W), x.is_contiguous())
+    if route == "halo":
+        conv3x3_halo(x, pk, y, act)
+        return y
+    if ups is not None:
+        assert ups.shape == (B, Ho // 2, Wo // 2, pk.n_store) and res is None and ups.is_contiguous()
+    if not _conv_dense(a, pk, route) and ups is not None:
+        upsample2x_add(ups, y)
+    return y
+
+
+def _tile_list(tiles, n_tiles):
+    """a patch list as the list-walking launches take it (int32 device tensors; the count stays on the device) -> its three C arguments"""
+    assert tiles.dtype == n_tiles.dtype == torch.int32 and tiles.is_contiguous() and n_tiles.numel() >= 1
+    return _p(tiles), _p(n_tiles), tiles.numel()
+
+
 def conv3x3_halo(x, pk, y, act=ACT_NONE, tiles=None, n_tiles=None):
     """x [B,H,W,cin_pad] bf16 -> y [B,H,W,n_store] bf16 through the halo-tile kernel (3x3, stride 1, pad 1, no residual).
-    tiles / n_tiles (int32 device tensors, `fine_tile_list`): only the 8 x 32 patches tiles[:n_tiles[0]] are computed, the count stays on
+    tiles / n_tiles (int32 device tensors, `fine_tile_lists`): only the 8 x 32 patches tiles[:n_tiles[0]] are computed, the count stays on
     the device; every other pixel of y keeps what it held (gim_conv3x3_halo_tiles)."""
     _req_cuda(x, y, tiles, n_tiles)
     assert x.is_contiguous() and y.is_contiguous(), "conv3x3_halo addresses pixels as (b*H + y)*W + x rows of width cin_pad"
     B, H, W, cs = x.shape
-    w, tab, nslab, bias = pk.halo
-    a = _lib.ConvArgs()
-    a.x, a.w, a.ktab = x.data_ptr(), w.data_ptr(), tab.data_ptr()
-    a.bias = bias.data_ptr() if bias is not None else None
-    a.res, a.y = None, y.data_ptr()
-    a.x_bytes = ((B * H * W - 1) * cs + pk.cin_pad) * 2
-    a.B, a.H, a.W, a.Ho, a.Wo = B, H, W, H, W
-    a.stride, a.pad = 1, 1
-    a.ldx, a.ldy, a.ldres = cs, y.shape[-1], 0
-    a.N, a.npad, a.kpad = pk.n_store, w.shape[0], nslab * 64
-    a.act, a.res_mod, a.act_cols = act, pk.cin_pad, 0
-    a.dtype = a.out_dtype = gim_dtype(x)
-    a.res_dtype = GIM_F32
-    a.use_lds_dma = 2
-    if tiles is not None:
-        assert tiles.dtype == n_tiles.dtype == torch.int32 and tiles.is_contiguous() and n_tiles.numel() >= 1
-        assert y.shape[:3] == x.shape[:3]
-    # sparse: the live measurement alone reads the count back -- computed patches x per-patch flops
-    with _Timed(lambda: f"{pk.cin}->{pk.cout} k3s1 M={B * H * W} halo" + ("" if tiles is None else " sparse"),
-                lambda: 2.0 * (B * H * W if tiles is None else int(n_tiles[0].item()) * 256) * pk.cout * pk.cin * 9, conv=True):
+    a = _conv_args(pk, (B, H, W, H, W), cs, y.shape[-1], x=x, y=y, act=act, halo=True)
+    assert tiles is None or y.shape[:3] == x.shape[:3]
+    with _conv_timed(pk, B * H * W, " halo" + ("" if tiles is None else " sparse"), n_tiles):
         if tiles is None:
             check(lib.gim_conv2d_bn_act(ctypes.byref(a), _stream()), "gim_conv2d_bn_act(halo)")
         else:
-            check(lib.gim_conv3x3_halo_tiles(ctypes.byref(a), _p(tiles), _p(n_tiles), tiles.numel(), _stream()), "gim_conv3x3_halo_tiles")
-
-
-def _ups_tiles_args(x, pk, ups, y):
-    """gim_conv_args of the lateral 1x1 conv + upsample-add, stated flat, as gim_conv2d_ups_tiles takes it.  x / ups / y: tensors, or
-    their shapes (the predicate needs no pointer)."""
-    xs, us = tuple(getattr(x, "shape", x)), tuple(getattr(ups, "shape", ups))
-    B, H, W, cs = xs
-    rows = B * H * W
-    a = _lib.ConvArgs()
-    if torch.is_tensor(x):
-        a.x, a.ups, a.y = x.data_ptr(), ups.data_ptr(), y.data_ptr()
-    a.w, a.ktab = pk.w.data_ptr(), pk.ktab.data_ptr()
-    a.bias = pk.bias.data_ptr() if pk.bias is not None else None
-    a.res = None
-    a.x_bytes = ((rows - 1) * cs + pk.cin_pad) * elem_size(pk.dtype)
-    a.B, a.H, a.W, a.Ho, a.Wo = 1, 1, rows, 1, rows
-    a.stride, a.pad = pk.stride, pk.pad
-    a.ldx, a.ldy, a.ldres = cs, pk.n_store, 0
-    a.N, a.npad, a.kpad = pk.n_store, pk.npad, pk.kpad
-    a.act, a.res_mod, a.act_cols = ACT_NONE, 0, 0
-    a.dtype = a.out_dtype = pk.dtype
-    a.res_dtype = GIM_F32
-    a.use_lds_dma = 3 if FORCE_BIG_TILE else 1
-    a.ups_h, a.ups_w, a.ups_ld = us[1], us[2], us[3]
-    return a
+            check(lib.gim_conv3x3_halo_tiles(ctypes.byref(a), *_tile_list(tiles, n_tiles), _stream()), "gim_conv3x3_halo_tiles")
 
 
 def conv_ups_tiles_supported(x, pk, ups, act=ACT_NONE, res=None, dense_too=False):
     """does `conv2d_ups_tiles` take this lateral launch?  x [B,H,W,cin_pad] / ups [B,H/2,W/2,n_store]: tensors or shapes
     (gim_conv_ups_tiles_supported: a bare 16-bit 1x1 conv onto a map of whole 8 x 32 patches).  dense_too: ... and would `conv2d` fuse the
-    upsample-add into the dense launch of the same shape as well (gim_conv_ups_supported: enough tiles for the 256 x 256 tile)?  Only then
-    are the two bit-identical: the two-pass path rounds the conv output before the add."""
+    upsample-add into the dense launch of the same shape as well (`_dense_route`, with what it assumes of a launch stated by its shapes)?
+    Only then are the two bit-identical: the two-pass path rounds the conv output before the add."""
     xs, us = tuple(getattr(x, "shape", x)), tuple(getattr(ups, "shape", ups))
     if not (UPS_FUSED and pk.kh == 1 and pk.kw == 1 and pk.stride == 1 and pk.pad == 0 and xs[3] == pk.cin_pad):
         return False
     if us != (xs[0], xs[1] // 2, xs[2] // 2, pk.n_store) or xs[1] % 2 or xs[2] % 2:
         return False
-    a = _ups_tiles_args(xs, pk, us, None)
-    a.act = act
+    rows = xs[0] * xs[1] * xs[2]
+    a = _conv_args(pk, (1, 1, rows, 1, rows), xs[3], pk.n_store, act=act, ups=us)
     a.res = 1 if res is not None else None   # (the predicate looks at whether there is one)
-    return bool(lib.gim_conv_ups_tiles_supported(ctypes.byref(a)) and (not dense_too or lib.gim_conv_ups_supported(ctypes.byref(a))))
+    return bool(lib.gim_conv_ups_tiles_supported(ctypes.byref(a)) and (not dense_too or _dense_route(pk, a, xs[:3]) == "ups"))
 
 
 def conv2d_ups_tiles(x, pk, ups, tiles, n_tiles, y=None):
@@ -385,76 +400,45 @@ def conv2d_ups_tiles(x, pk, ups, tiles, n_tiles, y=None):
     _req_cuda(x, ups, tiles, n_tiles, y)
     if not (x.is_contiguous() and ups.is_contiguous() and x.dtype in HALF and ups.dtype == x.dtype and conv_ups_tiles_supported(x, pk, ups)):
         return conv2d(x, pk, ups=ups)
-    B, H, W, _ = x.shape
+    B, H, W, cs = x.shape
     if y is None:
         y = torch.empty(B, H, W, pk.n_store, dtype=x.dtype, device=x.device)
     assert y.shape == (B, H, W, pk.n_store) and y.is_contiguous() and y.dtype == x.dtype
-    assert tiles.dtype == n_tiles.dtype == torch.int32 and tiles.is_contiguous() and n_tiles.numel() >= 1
-    a = _ups_tiles_args(x, pk, ups, y)
-    # sparse: the live measurement alone reads the count back -- computed patches x per-patch flops
-    with _Timed(lambda: f"{pk.cin}->{pk.cout} k1s1 M={B * H * W} +ups sparse",
-                lambda: 2.0 * int(n_tiles[0].item()) * 256 * pk.cout * pk.cin, conv=True):
-        check(lib.gim_conv2d_ups_tiles(ctypes.byref(a), _p(tiles), _p(n_tiles), tiles.numel(), _stream()), "gim_conv2d_ups_tiles")
+    rows = B * H * W
+    a = _conv_args(pk, (1, 1, rows, 1, rows), cs, pk.n_store, x=x, y=y, ups=ups)
+    with _conv_timed(pk, rows, " +ups sparse", n_tiles):
+        check(lib.gim_conv2d_ups_tiles(ctypes.byref(a), *_tile_list(tiles, n_tiles), _stream()), "gim_conv2d_ups_tiles")
     return y
-
-
-def _conv_tiles_args(x, pk, y, act):
-    """gim_conv_args of a plain 3 x 3 / stride 1 / pad 1 convolution as gim_conv2d_tiles (and the dense gim_conv2d_bn_act launch of
-    `conv2d`) takes it.  x / y: tensors, or x's shape alone (the predicates need no pointer)."""
-    B, H, W, cs = tuple(getattr(x, "shape", x))
-    a = _lib.ConvArgs()
-    if torch.is_tensor(x):
-        a.x, a.y = x.data_ptr(), y.data_ptr()
-    a.w, a.ktab = pk.w.data_ptr(), pk.ktab.data_ptr()
-    a.bias = pk.bias.data_ptr() if pk.bias is not None else None
-    a.res = None
-    a.x_bytes = ((B * H * W - 1) * cs + pk.cin_pad) * elem_size(pk.dtype)
-    a.B, a.H, a.W, a.Ho, a.Wo = B, H, W, H, W
-    a.stride, a.pad = pk.stride, pk.pad
-    a.ldx, a.ldy, a.ldres = cs, pk.n_store, 0
-    a.N, a.npad, a.kpad = pk.n_store, pk.npad, pk.kpad
-    a.act, a.res_mod, a.act_cols = act, 0, 0
-    a.dtype = a.out_dtype = pk.dtype
-    a.res_dtype = GIM_F32
-    a.use_lds_dma = 3 if FORCE_BIG_TILE else 1
-    return a
 
 
 def conv_tiles_supported(x, pk, dense_too=False):
     """does `conv2d_tiles` take this launch?  x [B,H,W,cin_pad]: a tensor or its shape (gim_conv2d_tiles_supported: a 16-bit 3 x 3 /
     stride 1 / pad 1 conv without residual onto a map of whole 8 x 32 patches, 256-channel tile columns).  dense_too: ... and does `conv2d`
-    run the dense launch of the same shape on the same 256 x 256 tile (gim_conv2d_big_tile; not the halo kernel, whose K order differs)?
-    Only then are the two bit-identical."""
+    run the dense launch of the same shape on the same 256 x 256 tile (`_dense_route`, with what it assumes of a launch stated by its shape;
+    not the halo kernel, whose K order differs)?  Only then are the two bit-identical."""
     xs = tuple(getattr(x, "shape", x))
     if not (pk.kh == 3 and pk.kw == 3 and pk.stride == 1 and pk.pad == 1 and getattr(pk, "dil", 1) == 1 and xs[3] == pk.cin_pad
             and pk.dtype in (GIM_BF16, GIM_F16)):
         return False
-    a = _conv_tiles_args(xs, pk, None, ACT_NONE)
-    if not lib.gim_conv2d_tiles_supported(ctypes.byref(a)):
-        return False
-    if dense_too and ((HALO and pk.halo is not None and _halo_pays(pk, xs[0], xs[1], xs[2])) or not lib.gim_conv2d_big_tile(ctypes.byref(a))):
-        return False
-    return True
+    a = _conv_args(pk, xs[:3] + xs[1:3], xs[3], pk.n_store)
+    return bool(lib.gim_conv2d_tiles_supported(ctypes.byref(a)) and (not dense_too or _dense_route(pk, a, xs[:3], tile=True) == "big"))
 
 
 def conv2d_tiles(x, pk, tiles, n_tiles, act=ACT_NONE, out=None):
     """`conv2d(x, pk, act)` for a 3 x 3 / stride 1 / pad 1 layer on the 8 x 32 patches tiles[:n_tiles[0]] of out [B,H,W,n_store] only
-    (int32 device tensors, `fine_tile_lists4`; the count stays on the device): listed patches get the bits the dense launch writes on the
+    (int32 device tensors, `fine_tile_lists`; the count stays on the device): listed patches get the bits the dense launch writes on the
     256 x 256 tile, every other pixel of `out` keeps what it held (gim_conv2d_tiles).  A launch the entry does not take
     (`conv_tiles_supported`) runs dense."""
     _req_cuda(x, tiles, n_tiles, out)
     if not (x.is_contiguous() and x.dtype in HALF and conv_tiles_supported(x, pk)):
         return conv2d(x, pk, act)
-    B, H, W, _ = x.shape
+    B, H, W, cs = x.shape
     if out is None:
         out = torch.empty(B, H, W, pk.n_store, dtype=x.dtype, device=x.device)
     assert out.shape == (B, H, W, pk.n_store) and out.is_contiguous() and out.dtype == x.dtype
-    assert tiles.dtype == n_tiles.dtype == torch.int32 and tiles.is_contiguous() and n_tiles.numel() >= 1
-    a = _conv_tiles_args(x, pk, out, act)
-    # sparse: the live measurement alone reads the count back -- computed patches x per-patch flops
-    with _Timed(lambda: f"{pk.cin}->{pk.cout} k3s1 M={B * H * W} sparse",
-                lambda: 2.0 * int(n_tiles[0].item()) * 256 * pk.cout * pk.cin * 9, conv=True):
-        check(lib.gim_conv2d_tiles(ctypes.byref(a), _p(tiles), _p(n_tiles), tiles.numel(), _stream()), "gim_conv2d_tiles")
+    a = _conv_args(pk, (B, H, W, H, W), cs, pk.n_store, x=x, y=out, act=act)
+    with _conv_timed(pk, B * H * W, " sparse", n_tiles):
+        check(lib.gim_conv2d_tiles(ctypes.byref(a), *_tile_list(tiles, n_tiles), _stream()), "gim_conv2d_tiles")
     return out
 
 
@@ -469,55 +453,52 @@ def _match_list_cap(b_ids, i_ids, j_ids, count, *more):
     return min(b_ids.numel(), i_ids.numel(), j_ids.numel())
 
 
-def fine_tile_list(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W, tiles=None, n_tiles=None):
-    """(tiles int32 [2 bs ceil(H/8) ceil(W/32)], n_tiles int32 [1]): the ascending list of 8 x 32 patches of the 1/2-resolution maps
-    [2 bs, H, W, .] that the fine windows of the first min(count[0], capacity) matches reach through one 3 x 3 convolution
-    (gim_fine_tile_list; one launch, the count is read on the device)"""
+class TileLists(NamedTuple):
+    """what `fine_tile_lists` returns: each list with its device-side count; the fields its depth does not build are None"""
+    tiles: torch.Tensor                        # half level, reach +-3: the two 3 x 3 layers of layer1_outconv2
+    n_tiles: torch.Tensor
+    tiles4: Optional[torch.Tensor] = None      # depth >= 2: half level, reach +-4: the lateral in front of them
+    n_tiles4: Optional[torch.Tensor] = None
+    tilesq: Optional[torch.Tensor] = None      # depth 3: [3, total / 4] quarter-level lists A, B, C
+    n_tilesq: Optional[torch.Tensor] = None
+
+
+def fine_tile_lists(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W, depth=1, b_range=None, tiles=None, n_tiles=None):
+    """The patch lists of the sparse fine head's last `depth` stages, from ONE one-workgroup launch that reads the match count on the device:
+    ascending lists of 8 x 32 patches that the fine windows of the first min(count[0], capacity) matches reach.
+      depth 1  (gim_fine_tile_list)   tiles int32 [2 bs ceil(H/8) ceil(W/32)], n_tiles int32 [1]: the patches of the 1/2-resolution maps
+               [2 bs, H, W, .] reached through one 3 x 3 convolution (+-3 around stride * cell).  tiles / n_tiles: the caller's buffers.
+      depth 2  (gim_fine_tile_lists)  ... and tiles4 / n_tiles4, the list of the reach grown by one pixel (+-4): the patches whose lateral
+               sum the last-but-one 3 x 3 layer reads.
+      depth 3  (gim_fine_tile_lists4; H % 16 == 0, W % 64 == 0)  ... and tilesq [3, total/4] / n_tilesq [3], three lists of the
+               1/4-resolution maps [2 bs, H/2, W/2] in front of the lateral that walks tiles4: every upsample source that launch stages (S)
+               dilated by 2 (list A), by 1 (B), and S itself (C).  b_range = (b_lo, b_hi): only the matches of those pairs mark patches
+               (gim_fine_tile_lists4_range; indices and buffer sizes stay those of the whole batch)."""
+    if b_range is not None and depth < 3:
+        raise ValueError("fine_tile_lists: a pair range needs depth 3 (gim_fine_tile_lists4_range)")
+    assert depth in (1, 2, 3) and (depth == 1 or (tiles is None and n_tiles is None)), "caller-supplied buffers are a depth-1 feature"
     cap = _match_list_cap(b_ids, i_ids, j_ids, count, tiles, n_tiles)
+    head = (_p(b_ids), _p(i_ids), _p(j_ids), _p(count), cap, bs, w0c, w1c, stride, H, W)
+    new = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=b_ids.device)   # noqa: E731
     total = 2 * bs * ((H + 7) // 8) * ((W + 31) // 32)
-    if tiles is None:
-        tiles = torch.empty(total, dtype=torch.int32, device=b_ids.device)
-    if n_tiles is None:
-        n_tiles = torch.empty(1, dtype=torch.int32, device=b_ids.device)
-    assert tiles.dtype == n_tiles.dtype == torch.int32 and tiles.is_contiguous()
-    check(lib.gim_fine_tile_list(_p(b_ids), _p(i_ids), _p(j_ids), _p(count), cap, bs, w0c, w1c, stride, H, W, _p(tiles), _p(n_tiles),
-                                 tiles.numel(), _stream()), "gim_fine_tile_list")
-    return tiles, n_tiles
-
-
-def fine_tile_lists(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W):
-    """`fine_tile_list` and, from the same launch, the list of the reach grown by one pixel (+-4 instead of +-3 around stride * cell): the
-    patches whose lateral sum the last-but-one 3 x 3 layer reads.  Returns (tiles, n_tiles, tiles4, n_tiles4)  (gim_fine_tile_lists)"""
-    cap = _match_list_cap(b_ids, i_ids, j_ids, count)
-    total = 2 * bs * ((H + 7) // 8) * ((W + 31) // 32)
-    tiles = torch.empty(2, total, dtype=torch.int32, device=b_ids.device)
-    n = torch.empty(2, dtype=torch.int32, device=b_ids.device)
-    check(lib.gim_fine_tile_lists(_p(b_ids), _p(i_ids), _p(j_ids), _p(count), cap, bs, w0c, w1c, stride, H, W, _p(tiles[0]), _p(n[0:1]),
-                                  _p(tiles[1]), _p(n[1:2]), total, _stream()), "gim_fine_tile_lists")
-    return tiles[0], n[0:1], tiles[1], n[1:2]
-
-
-def fine_tile_lists4(b_ids, i_ids, j_ids, count, bs, w0c, w1c, stride, H, W, b_range=None):
-    """`fine_tile_lists` and, from the same launch, the three patch lists of the 1/4-resolution maps [2 bs, H/2, W/2] in front of the
-    lateral that walks tiles4: every upsample source that launch stages (S), S dilated by 1 and by 2.  Returns (tiles, n_tiles, tiles4,
-    n_tiles4, tilesq [3, total/4] = lists A (dilated by 2), B (by 1), C (S itself), n_tilesq [3])  (gim_fine_tile_lists4; H % 16 == 0,
-    W % 64 == 0).  b_range = (b_lo, b_hi): only the matches of those pairs mark patches (gim_fine_tile_lists4_range; indices and buffer
-    sizes stay those of the whole batch)."""
-    assert H % 16 == 0 and W % 64 == 0, (H, W)
-    cap = _match_list_cap(b_ids, i_ids, j_ids, count)
-    total = 2 * bs * (H // 8) * (W // 32)
-    totq = 2 * bs * (H // 16) * (W // 64)
-    tiles = torch.empty(2 * total + 3 * totq, dtype=torch.int32, device=b_ids.device)
-    n = torch.empty(5, dtype=torch.int32, device=b_ids.device)
-    tq = tiles[2 * total:].view(3, totq)
-    if b_range is None:
-        check(lib.gim_fine_tile_lists4(_p(b_ids), _p(i_ids), _p(j_ids), _p(count), cap, bs, w0c, w1c, stride, H, W, _p(tiles[:total]), _p(n[0:1]),
-                                       _p(tiles[total:2 * total]), _p(n[1:2]), total, _p(tq), _p(n[2:5]), totq, _stream()), "gim_fine_tile_lists4")
+    if depth == 1:
+        tiles = new(total) if tiles is None else tiles
+        n_tiles = new(1) if n_tiles is None else n_tiles
+        check(lib.gim_fine_tile_list(*head, *_tile_list(tiles, n_tiles), _stream()), "gim_fine_tile_list")
+        return TileLists(tiles, n_tiles)
+    assert depth == 2 or (H % 16 == 0 and W % 64 == 0), (H, W)
+    totq = total // 4
+    t, n = new(2 * total + (3 * totq if depth == 3 else 0)), new(5 if depth == 3 else 2)
+    lists = TileLists(t[:total], n[0:1], t[total:2 * total], n[1:2], *((t[2 * total:].view(3, totq), n[2:5]) if depth == 3 else ()))
+    half = (_p(lists.tiles), _p(lists.n_tiles), _p(lists.tiles4), _p(lists.n_tiles4), total)
+    if depth == 2:
+        check(lib.gim_fine_tile_lists(*head, *half, _stream()), "gim_fine_tile_lists")
+    elif b_range is None:
+        check(lib.gim_fine_tile_lists4(*head, *half, _p(lists.tilesq), _p(lists.n_tilesq), totq, _stream()), "gim_fine_tile_lists4")
     else:
-        check(lib.gim_fine_tile_lists4_range(_p(b_ids), _p(i_ids), _p(j_ids), _p(count), cap, bs, w0c, w1c, stride, H, W, _p(tiles[:total]),
-                                             _p(n[0:1]), _p(tiles[total:2 * total]), _p(n[1:2]), total, _p(tq), _p(n[2:5]), totq,
-                                             int(b_range[0]), int(b_range[1]), _stream()), "gim_fine_tile_lists4_range")
-    return tiles[:total], n[0:1], tiles[total:2 * total], n[1:2], tq, n[2:5]
+        check(lib.gim_fine_tile_lists4_range(*head, *half, _p(lists.tilesq), _p(lists.n_tilesq), totq, int(b_range[0]), int(b_range[1]), _stream()),
+              "gim_fine_tile_lists4_range")
+    return lists
 
 
 def fine_tile_lists4_fits(bs, H, W):

@@ -59,3 +59,47 @@ def test_fine_chains_switch():
     k1 = m._graph_key(a, a, None, None)
     m.fine_chains = 2
     assert m._graph_key(a, a, None, None) != k1     # a captured graph keeps its chains: another value is another graph
+
+
+def test_one_patch_list_call_per_depth(monkeypatch):
+    """ops.fine_tile_lists without a GPU (the library replaced by a stand-in that notes the entry and its arguments): the C entry of each
+    depth, the buffer sizes, the fields a depth does not build, and the refusal of a pair range below depth 3"""
+    import pytest
+    import torch
+    from gim_amd import ops
+    calls = []
+
+    class Lib:
+        def __getattr__(self, name):
+            return lambda *a: calls.append((name, a)) or 0
+    monkeypatch.setattr(ops, "lib", Lib())
+    monkeypatch.setattr(ops, "_stream", lambda: None)
+    monkeypatch.setattr(ops, "_req_cuda", lambda *ts: None)
+    ids, cnt = torch.zeros(3, 5, dtype=torch.int64), torch.zeros(4, dtype=torch.int32)
+    bs = 2
+    one = ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, 8, 8, 4, 36, 72)            # no whole patches: ceil(36 / 8) x ceil(72 / 32)
+    assert one.tiles.numel() == 2 * bs * 5 * 3 and one.n_tiles.numel() == 1 and one[2:] == (None,) * 4
+    own = ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, 8, 8, 4, 32, 64, tiles=one.tiles, n_tiles=one.n_tiles)
+    assert own.tiles is one.tiles and own.n_tiles is one.n_tiles and calls[-1][1][-2] == one.tiles.numel()
+    two = ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, 8, 8, 4, 32, 64, depth=2)
+    assert two.tiles.numel() == two.tiles4.numel() == 2 * bs * 4 * 2 and two.n_tiles4.numel() == 1 and two[4:] == (None, None)
+    three = ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, 8, 8, 4, 32, 64, depth=3)
+    ranged = ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, 8, 8, 4, 32, 64, depth=3, b_range=(1, 2))
+    for t in (three, ranged):
+        assert t.tiles.numel() == t.tiles4.numel() == 16 * bs and tuple(t.tilesq.shape) == (3, 4 * bs) and t.n_tilesq.numel() == 3
+        assert t.tiles4.data_ptr() == t.tiles.data_ptr() + 4 * 16 * bs and t.tilesq.data_ptr() == t.tiles.data_ptr() + 8 * 16 * bs   # one buffer
+    assert [c[0] for c in calls] == ["gim_fine_tile_list", "gim_fine_tile_list", "gim_fine_tile_lists", "gim_fine_tile_lists4",
+                                     "gim_fine_tile_lists4_range"]
+    assert calls[-1][1][-3:-1] == (1, 2) and calls[-1][1][4] == 5                           # b_lo, b_hi in front of the stream; the capacity
+    assert [len(c[1]) for c in calls] == [len(_lib_args(c[0])) for c in calls]
+    for depth in (1, 2):
+        with pytest.raises(ValueError, match="pair range"):
+            ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, 8, 8, 4, 32, 64, depth=depth, b_range=(0, 1))
+    with pytest.raises(AssertionError):
+        ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, 8, 8, 4, 24, 64, depth=3)       # the quarter map is not whole patches
+    assert len(calls) == 5
+
+
+def _lib_args(name):
+    from gim_amd import _lib
+    return _lib.PROTOTYPES[name][1]

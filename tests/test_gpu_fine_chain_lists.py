@@ -1,4 +1,4 @@
-"""The pair range of the fine head's patch-list kernel (gim_fine_tile_lists4_range, ops.fine_tile_lists4(b_range=...)): what the two
+"""The pair range of the fine head's patch-list kernel (gim_fine_tile_lists4_range, ops.fine_tile_lists(depth=3, b_range=...)): what the two
 pair-range chains of gim_loftr's sparse fine head (loftr.py: `fine_chains`) build their lists with.
 
 Synthetic match lists (fixed seed) on bs = 2 and 3 pairs, half-level map 32 x 64 (4 x 2 patches per image), quarter-level map 16 x 32.  For
@@ -117,11 +117,11 @@ def test_the_wrapper_takes_the_range_and_the_entry_refuses_a_bad_one():
     ids = torch.from_numpy(np.ascontiguousarray(m)).to(DEV)
     cnt = torch.tensor([m.shape[1], 0, 0, 0], dtype=torch.int32, device=DEV)
     ref, nref = _lists(ids, cnt, bs, (1, 2))
-    t3, n3, t4, n4, tq, nq = ops.fine_tile_lists4(ids[0], ids[1], ids[2], cnt, bs, WC, WC, 4, H, W, b_range=(1, 2))
+    t3, n3, t4, n4, tq, nq = ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, WC, WC, 4, H, W, depth=3, b_range=(1, 2))
     torch.cuda.synchronize()
     got = [t3[:int(n3)], t4[:int(n4)]] + [tq[k, :int(nq[k])] for k in range(3)]
     for k in range(5):
         assert np.array_equal(got[k].cpu().numpy(), ref[k]), NAMES[k]
     for bad in ((-1, 1), (1, 3), (2, 1)):
         with pytest.raises(Exception, match="pair range"):
-            ops.fine_tile_lists4(ids[0], ids[1], ids[2], cnt, bs, WC, WC, 4, H, W, b_range=bad)
+            ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, WC, WC, 4, H, W, depth=3, b_range=bad)

@@ -54,7 +54,7 @@ def test_tile_list_matches_the_rule(count):
     total = 2 * bs * (H // 8) * (W // 32)
     tiles = torch.full((total,), -7, dtype=torch.int32, device=DEV)
     n = torch.full((1,), -7, dtype=torch.int32, device=DEV)
-    ops.fine_tile_list(ids[0], ids[1], ids[2], cnt, bs, w0c, w1c, 4, H, W, tiles=tiles, n_tiles=n)
+    ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, w0c, w1c, 4, H, W, tiles=tiles, n_tiles=n)
     torch.cuda.synchronize()
     ref = _ref_tiles(*(np.array([m[k] for m in MATCHES[:count]], dtype=np.int64) for k in range(3)), bs, w0c, w1c, H, W)
     got_n = int(n.item())
@@ -69,7 +69,7 @@ def test_tile_list_count_beyond_capacity_is_clamped():
     bs, H, W = 2, 64, 96
     ids = torch.tensor(MATCHES[:4], dtype=torch.int64).T.contiguous().to(DEV)   # capacity 4
     cnt = torch.tensor([1000, 0], dtype=torch.int32, device=DEV)
-    tiles, n = ops.fine_tile_list(ids[0], ids[1], ids[2], cnt, bs, 24, 24, 4, H, W)
+    tiles, n = ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, 24, 24, 4, H, W)[:2]
     ref = _ref_tiles(*(np.array([m[k] for m in MATCHES[:4]], dtype=np.int64) for k in range(3)), bs, 24, 24, H, W)
     assert int(n.item()) == len(ref) and np.array_equal(tiles[:len(ref)].cpu().numpy(), ref)
 

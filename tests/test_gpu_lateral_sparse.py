@@ -52,8 +52,8 @@ def test_both_lists_match_the_rule(count):
     ids[:, :len(MATCHES)] = torch.tensor(MATCHES, dtype=torch.int64).T
     ids = ids.to(DEV)
     cnt = torch.tensor([count, 0, 0, 0], dtype=torch.int32, device=DEV)
-    t3, n3, t4, n4 = ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, w0c, w1c, 4, H, W)
-    old_t, old_n = ops.fine_tile_list(ids[0], ids[1], ids[2], cnt, bs, w0c, w1c, 4, H, W)
+    t3, n3, t4, n4 = ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, w0c, w1c, 4, H, W, depth=2)[:4]
+    old_t, old_n = ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, w0c, w1c, 4, H, W)[:2]
     torch.cuda.synchronize()
     m = [np.array([r[k] for r in MATCHES[:count]], dtype=np.int64) for k in range(3)]
     ref3, ref4 = _ref_tiles(*m, bs, w0c, w1c, H, W, 3), _ref_tiles(*m, bs, w0c, w1c, H, W, 4)

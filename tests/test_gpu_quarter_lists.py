@@ -1,4 +1,4 @@
-"""The quarter-level patch lists of gim_loftr's sparse fine head (gim_fine_tile_lists4, ops.fine_tile_lists4) and the chain they feed.
+"""The quarter-level patch lists of gim_loftr's sparse fine head (gim_fine_tile_lists4, ops.fine_tile_lists(depth=3)) and the chain they feed.
 
 The 1/2-level lateral that walks the +-4 list reads its upsample operand x2_out where Epilogue::ups_accumulate (conv_igemm.hip, lambda
 `issue`) stages it: per 32-pixel pass (row Y, first column X0) of a listed patch, source rows y0 = (int)(sy Y), y0 + (y0 < h - 1) and
@@ -99,8 +99,8 @@ def test_quarter_lists_match_the_staging_model(size, which):
     ids = ids.to(DEV)
     cnt = torch.tensor([len(matches), 0, 0, 0], dtype=torch.int32, device=DEV)
     assert ops.fine_tile_lists4_fits(bs, H, W)
-    t3, n3, t4, n4, tq, nq = ops.fine_tile_lists4(ids[0], ids[1], ids[2], cnt, bs, wc, wc, 4, H, W)
-    o3, on3, o4, on4 = ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, wc, wc, 4, H, W)
+    t3, n3, t4, n4, tq, nq = ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, wc, wc, 4, H, W, depth=3)
+    o3, on3, o4, on4 = ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, wc, wc, 4, H, W, depth=2)[:4]
     torch.cuda.synchronize()
     m = [np.array([r[k] for r in matches], dtype=np.int64) for k in range(3)]
     ref3, ref4 = _ref_tiles(*m, bs, wc, wc, H, W, 3), _ref_tiles(*m, bs, wc, wc, H, W, 4)
@@ -158,7 +158,7 @@ def test_poison_chain(tdt, monkeypatch):
     matches = [(0, cell(0, 0), cell(hc - 1, wc - 1)), (0, cell(1, 7), cell(9, 24)), (0, cell(8, 17), cell(5, 9))]
     ids = torch.tensor(matches, dtype=torch.int64).T.contiguous().to(DEV)
     cnt = torch.tensor([len(matches), 0, 0], dtype=torch.int32, device=DEV)
-    t3, n3, t4, n4, tq, nq = ops.fine_tile_lists4(ids[0], ids[1], ids[2], cnt, bs, wc, wc, 4, H, W)
+    t3, n3, t4, n4, tq, nq = ops.fine_tile_lists(ids[0], ids[1], ids[2], cnt, bs, wc, wc, 4, H, W, depth=3)
     nan = lambda *s: torch.full(s, float("nan"), dtype=tdt, device=DEV)
     a_out, b_out, c_out, x1_out = nan(2 * bs, h, w, 256), nan(2 * bs, h, w, 256), nan(2 * bs, h, w, P["l2o2b"].n_store), nan(2 * bs, H, W, P["l1o"].n_store)
     ops.conv2d_ups_tiles(x2, P["l2o"], x3_out, tq[0], nq[0:1], y=a_out)
