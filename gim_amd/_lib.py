@@ -217,6 +217,10 @@ PROTOTYPES = {
     # RegressionMatcher.sample for a batch of pairs, no host read (added within ABI revision 115)
     "gim_balanced_sample_pairs_ws_bytes": (c_int64, [c_int] * 3),
     "gim_balanced_sample_pairs": (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_float, c_int, c_void_p]),
+    # homography RANSAC step and perspective warp of gim_amd/demo.py (added within ABI revision 115)
+    "gim_homography_step": (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_int, ctypes.c_double] + [c_void_p] * 4),
+    "gim_homography_mask": (c_int, [c_void_p] * 4 + [c_int, ctypes.c_double, c_void_p, c_void_p]),
+    "gim_warp_perspective": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p] * 2 + [c_int] * 2 + [c_void_p]),
 }
 
 

@@ -14,6 +14,12 @@ Mirrors the reference entry point step by step (reference file:line):
                                             module's dict; gim_lightglue: detector x2 + matcher + per-pair gather)
   * robust fitting       demo.py:514-517  cv2.findFundamentalMat(USAC_MAGSAC, 1.0 px, 0.999999, 10000) stays on the host (north_star);
                                             without OpenCV: seven-point RANSAC of gim_amd/pose.py with the same parameters
+  * `compute_geom`       demo.py:180-227  the fundamental matrix of the step above and cv2.findHomography(mkpts1, mkpts0, ...) as
+                                            pose.find_homography (four-point solve and scoring fused on the device)
+  * `warp_pair`          demo.py:230-266  wrap_images(..., "Homography"): image 0 beside cv2.warpPerspective(image 1, H, size of image
+                                            0) as ops.warp_perspective; `--out DIR` writes DIR/<name0>_<name1>_<model>_warp.png
+Out of scope: the matplotlib figure and its titles (the PNG is the two images side by side, nothing drawn on them),
+cv2.stereoRectifyUncalibrated (`H1`, `H2`, the "Fundamental" flavour of wrap_images) and the match-line drawing (`_match.png`).
 Returns / prints `{mkpts0_f, mkpts1_f, mconf, m_bids}` in pixels of the ORIGINAL images (kpts * scale, demo.py:499-500 and
 the `scale0/scale1` the other models get through their own adapters).
 """
@@ -170,7 +176,8 @@ def match_pair(model_name, model, detector, path0, path1, device="cuda", resize_
         gim_lightglue_inference(detector, model, d)
         kpts0, kpts1, b_ids, mconf = d["mkpts0_f"], d["mkpts1_f"], d["m_bids"], d["mconf"]
     out = {"mkpts0_f": kpts0, "mkpts1_f": kpts1, "m_bids": b_ids, "mconf": mconf,
-           "hw0_i": image0.shape[2:], "hw1_i": image1.shape[2:], "scale0": scale0, "scale1": scale1}
+           "hw0_i": image0.shape[2:], "hw1_i": image1.shape[2:], "scale0": scale0, "scale1": scale1,
+           "color0": image0, "color1": image1}
     # robust fitting on the host (demo.py:514-517): OpenCV's USAC_MAGSAC when cv2 imports, else plain seven-point RANSAC with the
     # same threshold / confidence / iteration bound (gim_amd/pose.py; `backend` says which one produced the mask)
     if len(kpts0) >= 8:
@@ -179,14 +186,59 @@ def match_pair(model_name, model, detector, path0, path1, device="cuda", resize_
         out["ransac_backend"] = pose.backend()
         if out["ransac_backend"] == "cv2":
             import cv2
-            _, mask = cv2.findFundamentalMat(p0, p1, cv2.USAC_MAGSAC, ransacReprojThreshold=1.0, confidence=0.999999, maxIters=10000)
+            out["F"], mask = cv2.findFundamentalMat(p0, p1, cv2.USAC_MAGSAC, ransacReprojThreshold=1.0, confidence=0.999999, maxIters=10000)
             out["inliers"] = mask.ravel() > 0 if mask is not None else np.zeros(len(p0), dtype=bool)
         else:
             # the seven-point candidates are scored on the model's device (pose.DeviceScorer), the solver stays on the host
-            _, mask = pose.find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000,
-                                                device=kpts0.device if kpts0.is_cuda else None)
+            out["F"], mask = pose.find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000,
+                                                       device=kpts0.device if kpts0.is_cuda else None)
             out["inliers"] = mask
     return out
+
+
+def compute_geom(out, device=None):
+    """demo.py:180-227 on the dict of `match_pair` -> {"Fundamental": F [3,3] | None, "Homography": H [3,3] | None}, or {} for
+    fewer than 8 matches (the reference's 2 x DEFAULT_MIN_NUM_MATCHES).  "Fundamental" is the model the robust-fitting step of
+    `match_pair` found (`out["F"]`: pose.find_fundamental_mat's on the numpy backend, cv2's when cv2 filtered; computed here with
+    pose.find_fundamental_mat when the dict has none).  "Homography" maps image 1 onto image 0, the reference's argument order and
+    parameters: pose.find_homography(mkpts1, mkpts0, 1.0, 0.999999, 10000, device=device) -- on `device` the four-point solve and the
+    scoring are one launch per RANSAC step, device=None is the host path."""
+    from . import pose
+    p0 = np.asarray(out["mkpts0_f"].detach().float().cpu().numpy() if torch.is_tensor(out["mkpts0_f"]) else out["mkpts0_f"], dtype=np.float64)
+    p1 = np.asarray(out["mkpts1_f"].detach().float().cpu().numpy() if torch.is_tensor(out["mkpts1_f"]) else out["mkpts1_f"], dtype=np.float64)
+    if len(p0) < 8:
+        return {}
+    F = out["F"] if "F" in out else pose.find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, device=device)[0]
+    H, _ = pose.find_homography(p1, p0, 1.0, 0.999999, 10000, device=device)
+    return {"Fundamental": None if F is None else np.asarray(F, dtype=np.float64), "Homography": H}
+
+
+def _as_u8_chw(image, device):
+    """uint8 [H,W,3] / [H,W] array (`read_image`) or float tensor [3,H,W] / [1,3,H,W] in [0,1] (`preprocess`) -> uint8 [C,H,W] tensor"""
+    if torch.is_tensor(image):
+        t = image[0] if image.dim() == 4 else image
+        if t.dtype != torch.uint8:
+            t = (t.float() * 255.0).round().clamp(0, 255).to(torch.uint8)
+    else:
+        a = np.asarray(image)
+        t = torch.from_numpy(np.ascontiguousarray(a[None] if a.ndim == 2 else a.transpose(2, 0, 1)))
+    return t.contiguous().to(device) if device is not None else t.contiguous()
+
+
+def warp_pair(image0, image1, H, device="cuda", warp=None):
+    """wrap_images(image0, image1, geom, "Homography") of demo.py:230-266 without the figure -> uint8 [H0, W0 + W0, 3]: image 0
+    beside cv2.warpPerspective(image 1, H, size of image 0), which is ops.warp_perspective on `device` (exact bilinear weights, zero
+    border; include/gim_hip.h states the difference from cv2's fixed-point weights).  Images: uint8 arrays of `read_image` or float
+    tensors of `preprocess`.  warp: another implementation of ops.warp_perspective(image uint8 [C,H,W], H, out_hw) -- a test's oracle
+    on a box without a GPU; there is no silent host path."""
+    from . import ops
+    i0 = _as_u8_chw(image0, None)
+    i1 = _as_u8_chw(image1, device if warp is None else None)
+    w1 = (ops.warp_perspective if warp is None else warp)(i1, H, tuple(i0.shape[-2:]))
+    w1 = torch.as_tensor(w1).cpu()
+    pair = torch.cat([i0.cpu().expand(w1.shape[0], -1, -1) if i0.shape[0] == 1 else i0.cpu(), w1], dim=2)
+    pair = pair.expand(3, -1, -1) if pair.shape[0] == 1 else pair
+    return np.ascontiguousarray(pair.permute(1, 2, 0).numpy())
 
 
 def main(argv=None):
@@ -198,6 +250,7 @@ def main(argv=None):
     ap.add_argument("--precision", choices=["bf16", "fp32"], default=None)
     ap.add_argument("--resize-max", type=int, default=None)
     ap.add_argument("--dinov2-weights", default=None, help="gim_roma: the DINOv2 ViT-L/14 file the reference downloads")
+    ap.add_argument("--out", default=None, help="directory for <name0>_<name1>_<model>_warp.png (image 0 beside image 1 warped by the homography)")
     args = ap.parse_args(argv)
     weights = args.weights
     if weights is None and args.model in CKPT and os.path.exists(join("weights", CKPT[args.model])):
@@ -211,6 +264,18 @@ def main(argv=None):
     for k in range(min(n, 5)):
         a, b = out["mkpts0_f"][k].tolist(), out["mkpts1_f"][k].tolist()
         print(f"  ({a[0]:8.2f}, {a[1]:8.2f}) <-> ({b[0]:8.2f}, {b[1]:8.2f})  conf {float(out['mconf'][k]):.4f}")
+    if args.out is not None:     # demo.py:537-540
+        kp = out["mkpts0_f"]
+        out["geom"] = compute_geom(out, device=kp.device if kp.is_cuda else None)
+        if out["geom"].get("Homography") is None:
+            print("  no homography (fewer than 8 matches, or no sample with 4 inliers): no _warp.png")
+        else:
+            from PIL import Image
+            os.makedirs(args.out, exist_ok=True)
+            name0, name1 = (os.path.splitext(os.path.basename(p))[0] for p in (args.image0, args.image1))
+            path = join(args.out, f"{name0}_{name1}_{args.model}_warp.png")
+            Image.fromarray(warp_pair(out["color0"], out["color1"], out["geom"]["Homography"], device=out["color1"].device)).save(path)
+            print(f"  wrote {path}")
     return out
 
 

@@ -1594,6 +1594,81 @@ def ransac_mask(models, x0, x1, thr2, offsets=None):
     return mask.view(torch.bool)
 
 
+# ---- homography RANSAC step and perspective warp (gim_amd/pose.py, gim_amd/demo.py) ---------------------------------------
+def homography_step(src, dst, idx, thr2, offsets=None):
+    """Four-point homographies dst ~ H src of the samples `idx`, solved and scored in one launch (gim_homography_step; fp64, the
+    arithmetic and validity rules of pose.homography_4pt / pose.transfer_error).  One pair: src / dst fp64 [P,2], idx int32 [K,4]
+    -> (models fp64 [K,3,3] with h33 = 1, valid bool [K], counts int32 [K]).  B pairs: offsets int32 [B+1] over the concatenated
+    points, idx [B,K,4] relative to each pair's offset -> [B,K,3,3], [B,K], [B,K].  A rejected sample: zero model, valid 0, count 0."""
+    _req_cuda(src, dst, idx, offsets)
+    single = offsets is None
+    if idx.dtype != torch.int32 or idx.dim() != (2 if single else 3) or idx.shape[-1] != 4 or not idx.is_contiguous():
+        raise _lib.GimHipError(f"homography idx must be contiguous int32 {'[K,4]' if single else '[B,K,4]'}, got {idx.dtype} {tuple(idx.shape)}")
+    B, K = (1, idx.shape[0]) if single else idx.shape[:2]
+    offsets, P = _ransac_points(src, dst, offsets, B)
+    if idx.device != src.device:
+        raise _lib.GimHipError("homography idx and points are on different devices")
+    lead = tuple(idx.shape[:-1])
+    models = torch.zeros(*lead, 3, 3, dtype=torch.float64, device=src.device)
+    valid = torch.zeros(lead, dtype=torch.uint8, device=src.device)
+    counts = torch.zeros(lead, dtype=torch.int32, device=src.device)
+    if B * K and P:               # without points every index is outside its pair: nothing is valid
+        check(lib.gim_homography_step(_p(src), _p(dst), _p(offsets), B, _p(idx), K, float(thr2), _p(models), _p(valid), _p(counts),
+                                      _stream()), "gim_homography_step")
+    return models, valid.view(torch.bool), counts
+
+
+def homography_mask(model, src, dst, thr2, offsets=None):
+    """Inlier mask of one homography per pair (gim_homography_mask): model fp64 [3,3] (one pair) or [B,3,3] with offsets int32 [B+1]
+    -> bool [Ptot], transfer_error(model of the point's pair) <= thr2."""
+    _req_cuda(model, src, dst, offsets)
+    single = offsets is None
+    if model.dtype != torch.float64 or model.shape != ((3, 3) if single else (model.shape[0], 3, 3)) or not model.is_contiguous():
+        raise _lib.GimHipError(f"homography_mask model must be contiguous fp64 {'[3,3]' if single else '[B,3,3]'}, got {model.dtype} {tuple(model.shape)}")
+    B = 1 if single else model.shape[0]
+    offsets, P = _ransac_points(src, dst, offsets, B)
+    if model.device != src.device:
+        raise _lib.GimHipError("homography model and points are on different devices")
+    mask = torch.empty(P, dtype=torch.uint8, device=src.device)
+    if P and B:
+        check(lib.gim_homography_mask(_p(model), _p(src), _p(dst), _p(offsets), B, float(thr2), _p(mask), _stream()), "gim_homography_mask")
+    return mask.view(torch.bool)
+
+
+def warp_perspective(image, H, out_hw):
+    """cv2.warpPerspective(image, H, (out_w, out_h)) with exact bilinear weights and a zero border (gim_warp_perspective).
+    image: uint8 or fp32 [B,C,H,W] or [C,H,W] on the device, contiguous, C <= 4; H: 3x3 or [B,3,3] tensor or array (any device or
+    the host; it is read on the host), mapping image pixels to output pixels; out_hw = (out_h, out_w).  -> the image's dtype,
+    [B,C,out_h,out_w] or [C,out_h,out_w].  A singular H or one with an entry that is not finite raises before any launch."""
+    _req_cuda(image)
+    if image.dtype not in (torch.uint8, torch.float32) or image.dim() not in (3, 4) or not image.is_contiguous():
+        raise _lib.GimHipError(f"warp_perspective image must be contiguous uint8 / fp32 [B,C,H,W] or [C,H,W], got {image.dtype} {tuple(image.shape)}")
+    img = image if image.dim() == 4 else image[None]
+    B, C, Hs, Ws = img.shape
+    if not 1 <= C <= 4 or Hs < 1 or Ws < 1:
+        raise _lib.GimHipError(f"warp_perspective takes 1 to 4 channels of a non-empty image, got {tuple(img.shape)}")
+    Hn = np.array(H.detach().cpu().numpy() if isinstance(H, torch.Tensor) else H, dtype=np.float64)
+    if Hn.shape == (3, 3):
+        Hn = np.broadcast_to(Hn, (B, 3, 3))
+    if Hn.shape != (B, 3, 3):
+        raise _lib.GimHipError(f"warp_perspective H must be [3,3] or [B = {B},3,3], got {tuple(Hn.shape)}")
+    if not np.isfinite(Hn).all():
+        raise _lib.GimHipError("warp_perspective: H has an entry that is not finite")
+    det = (Hn[:, 0, 0] * (Hn[:, 1, 1] * Hn[:, 2, 2] - Hn[:, 1, 2] * Hn[:, 2, 1]) - Hn[:, 0, 1] * (Hn[:, 1, 0] * Hn[:, 2, 2] - Hn[:, 1, 2] * Hn[:, 2, 0]) +
+           Hn[:, 0, 2] * (Hn[:, 1, 0] * Hn[:, 2, 1] - Hn[:, 1, 1] * Hn[:, 2, 0]))     # by cofactors: exact zero for a repeated or zero row
+    if not (np.isfinite(det).all() and (det != 0.0).all()):
+        raise _lib.GimHipError(f"warp_perspective: singular H (det = {det.tolist()})")
+    Hd, Wd = int(out_hw[0]), int(out_hw[1])
+    if Hd < 0 or Wd < 0:
+        raise _lib.GimHipError(f"warp_perspective: out_hw = {tuple(out_hw)}")
+    out = torch.empty(B, C, Hd, Wd, dtype=img.dtype, device=img.device)
+    if out.numel():
+        d_H = torch.from_numpy(np.ascontiguousarray(Hn)).to(img.device)
+        check(lib.gim_warp_perspective(_p(img), 0 if img.dtype == torch.uint8 else 1, B, C, Hs, Ws, _p(d_H), _p(out), Hd, Wd, _stream()),
+              "gim_warp_perspective")
+    return out if image.dim() == 4 else out[0]
+
+
 # ---- gim_semseg ------------------------------------------------------------------------------------------------
 PPM_SCALES = (1, 2, 3, 6)
 PPM_BINS = 50            # 1 + 4 + 9 + 36 pooled vectors per image, bins of scale s from offset PPM_OFFSETS[s]

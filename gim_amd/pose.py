@@ -20,6 +20,9 @@ What is restated (OpenCV 4.x, modules/calib3d/src/five-point.cpp and ptsetreg.cp
     points in front of both cameras (depth < distanceThresh) wins; its count is returned.
   * seven-point fundamental matrix inside the same RANSAC loop for the demo (plain RANSAC with the Sampson distance in pixels --
     OpenCV's USAC_MAGSAC scoring is NOT restated; the inlier mask is RANSAC's, which is what the demo prints and draws).
+  * four-point homography inside the same loop for the demo's warp (demo.py:180-227 cv2.findHomography; fundam.cpp): forward transfer
+    error, re-fit on the inliers by normalised DLT, no Levenberg-Marquardt polish.  This solver also runs on the device, fused with
+    the scoring (`find_homography(device=)`, csrc/homography.hip): a step uploads sample indices only.
 
 Parity: UNPINNED against cv2 (no OpenCV here to record vectors from; sampling is random in both).  tests/test_pose_cpu.py pins
 the solvers on exact synthetic geometry (every ground-truth E / F is among the candidates to 1e-9, recovered poses within 1e-6
@@ -190,11 +193,12 @@ def sampson_error(M, x0, x1):
     return num / np.maximum(den, 1e-300)
 
 
-def _count_inliers(Ms, valid, x0, x1, thr2, chunk=128):
+def _count_inliers(Ms, valid, x0, x1, thr2, chunk=128, error=None):
     """inlier counts of the models Ms [K, 3, 3] over all points, in chunks whose temporaries stay cache-resident"""
+    error = sampson_error if error is None else error
     out = np.zeros(Ms.shape[0], dtype=np.int64)
     for c0 in range(0, Ms.shape[0], chunk):
-        out[c0:c0 + chunk] = (sampson_error(Ms[c0:c0 + chunk], x0, x1) <= thr2).sum(1)
+        out[c0:c0 + chunk] = (error(Ms[c0:c0 + chunk], x0, x1) <= thr2).sum(1)
     return np.where(valid, out, 0)
 
 
@@ -229,10 +233,12 @@ class DeviceScorer:
             return self._ops.ransac_mask(self._up(M, np.float64), self.x0, self.x1, self.thr2, offsets=self.offsets).cpu().numpy()
 
 
-def _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch=250):
+def _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch=250, solve_idx=None):
     """The sampling / solving / bookkeeping half of RANSACPointSetRegistrator::run as a generator: every step yields its candidate
     models (Ms [nb * k, 3, 3], valid [nb * k]) and is sent their inlier counts [nb * k]; the generator's return value is the best
-    model [3, 3] or None.  Who counts (the host, a device, one launch for many pairs in lockstep) is the driver's business."""
+    model [3, 3] or None.  Who counts (the host, a device, one launch for many pairs in lockstep) is the driver's business.
+    solve_idx: a hook that receives the step's sample indices idx [nb, m] and returns (Ms [nb, k, 3, 3], valid [nb, k]) in place of
+    solver(s0[idx], s1[idx]) -- a solver that lives where the points already are (`DeviceHomography`)."""
     lconf = np.log(max(1.0 - conf, 1e-300))
     best_n, best_M = 0, None
     niters, done = int(max_iters), 0
@@ -241,7 +247,7 @@ def _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch=250):
         # m distinct indices per sample: the m smallest of P random keys
         idx = np.argsort(rng.random((nb, P)), axis=1)[:, :m] if P <= 4096 else \
             np.stack([rng.choice(P, m, replace=False) for _ in range(nb)])
-        Ms, valid = solver(s0[idx], s1[idx])
+        Ms, valid = solver(s0[idx], s1[idx]) if solve_idx is None else solve_idx(idx)
         k = Ms.shape[1]
         Ms = Ms.reshape(-1, 3, 3)
         per = (yield Ms, valid.reshape(-1)).reshape(nb, k)
@@ -262,28 +268,31 @@ def _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch=250):
     return best_M
 
 
-def _ransac(x0, x1, solver, m, thr, conf, max_iters, rng, s0=None, s1=None, batch=250, scorer=None):
+def _ransac(x0, x1, solver, m, thr, conf, max_iters, rng, s0=None, s1=None, batch=250, scorer=None, solve_idx=None, error=None):
     """RANSACPointSetRegistrator::run with `solver` on samples of m points; the error is evaluated on (x0, x1), the solver sees
     (s0, s1) when given (normalised copies of the same points).  `scorer`: None counts inliers and takes the final mask on the host
     (`_count_inliers`, `sampson_error`); otherwise an object with counts(Ms [K,3,3], valid [K]) -> int64 [K] and
-    mask(M [3,3]) -> bool [P] over the same points and threshold (`DeviceScorer`).  -> (model [3,3] or None, mask [P] bool)"""
+    mask(M [3,3]) -> bool [P] over the same points and threshold (`DeviceScorer`).  solve_idx: the hook of `_ransac_steps`.
+    error: the host error in place of `sampson_error`, error(Ms [..., 3, 3], x0, x1) -> [..., P] (`transfer_error`).
+    -> (model [3,3] or None, mask [P] bool)"""
     P = x0.shape[0]
     if P < m:
         return None, np.zeros(P, dtype=bool)
     s0 = x0 if s0 is None else s0
     s1 = x1 if s1 is None else s1
     thr2 = float(thr) ** 2
-    steps = _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch)
+    steps = _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch, solve_idx)
+    error = sampson_error if error is None else error
     try:
         Ms, valid = next(steps)
         while True:
-            counts = _count_inliers(Ms, valid, x0, x1, thr2) if scorer is None else scorer.counts(Ms, valid)
+            counts = _count_inliers(Ms, valid, x0, x1, thr2, error=error) if scorer is None else scorer.counts(Ms, valid)
             Ms, valid = steps.send(counts)
     except StopIteration as stop:
         best_M = stop.value
     if best_M is None:
         return None, np.zeros(P, dtype=bool)
-    return best_M, (sampson_error(best_M, x0, x1) <= thr2) if scorer is None else scorer.mask(best_M)
+    return best_M, (error(best_M, x0, x1) <= thr2) if scorer is None else scorer.mask(best_M)
 
 
 def find_essential_mat(x0, x1, threshold, prob=0.999, max_iters=1000, seed=0, device=None):
@@ -372,6 +381,204 @@ def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, 
 
     scorer = DeviceScorer(p0, p1, float(threshold) ** 2, device) if device is not None else None
     return _ransac(p0, p1, solver, 7, threshold, prob, max_iters, np.random.default_rng(seed), s0=q0, s1=q1, scorer=scorer)
+
+
+# ---- homography: four-point minimal solver, transfer error, DLT re-fit, RANSAC (demo.py:180-227 cv2.findHomography) ------------
+H4_PIVOT_EPS = 1e-12     # smallest pivot of the normalised 8 x 8 system
+H4_AREA_EPS = 1e-9       # smallest doubled triangle area in normalised coordinates
+_H4_TRI = ((0, 1, 2), (1, 2, 3), (0, 2, 3), (0, 1, 3))   # the triples of HomographyEstimatorCallback::checkSubset
+
+
+def _h4_normalise(p):
+    """[N, 4, 2] -> (q [N, 4, 2] with zero mean and mean distance sqrt(2), centre [N, 2], scale [N], ok [N]); q = (p - c) * s"""
+    c = (((p[:, 0] + p[:, 1]) + p[:, 2]) + p[:, 3]) * 0.25
+    q = p - c[:, None]
+    d = np.sqrt(q[..., 0] * q[..., 0] + q[..., 1] * q[..., 1])
+    md = (((d[:, 0] + d[:, 1]) + d[:, 2]) + d[:, 3]) * 0.25
+    ok = np.isfinite(md) & (md > 0.0)
+    s = np.sqrt(2.0) / np.where(ok, md, 1.0)
+    return q * s[:, None, None], c, s, ok
+
+
+def _h4_area2(q, i, j, k):
+    return (q[:, j, 0] - q[:, i, 0]) * (q[:, k, 1] - q[:, i, 1]) - (q[:, j, 1] - q[:, i, 1]) * (q[:, k, 0] - q[:, i, 0])
+
+
+def homography_4pt(x_src, x_dst, detail=False):
+    """Homographies through 4 correspondences, x_dst ~ H x_src.  x_src, x_dst: [N, 4, 2] -> (H [N, 1, 3, 3], valid [N, 1]).
+    The arithmetic and the validity rules of gim_homography_step (include/gim_hip.h; csrc/homography_solve.h is the same code for
+    the device), batched over the samples: each side shifted to zero mean and scaled to mean distance sqrt(2); the 8 x 9 augmented
+    system of the eight equations with h33 = 1 reduced by Gaussian elimination with partial pivoting; H de-normalised and scaled to
+    h33 = 1.  valid = 0 (and a zero model) when the four points of a side coincide, three points of a side are collinear (doubled
+    area below 1e-9 in normalised coordinates -- a repeated point is such a triple), the orientation test of
+    HomographyEstimatorCallback::checkSubset (fundam.cpp) fails, a pivot is below 1e-12, or the result is not finite.
+    detail=True adds a dict: min_area [N] (smallest |doubled area| over both sides), min_pivot [N] (smallest pivot reached),
+    orient_ok [N], and the normalisations (qs, qd, cs, cd, ss, sd) -- what a test needs to see how far a sample is from a rule."""
+    x_src = np.asarray(x_src, dtype=np.float64)
+    x_dst = np.asarray(x_dst, dtype=np.float64)
+    n = x_src.shape[0]
+    with np.errstate(all="ignore"):
+        qs, cs, ss, ok_s = _h4_normalise(x_src)
+        qd, cd, sd, ok_d = _h4_normalise(x_dst)
+        valid = ok_s & ok_d
+        min_area = np.full(n, np.inf)
+        negative = np.zeros(n, dtype=np.int64)
+        for i, j, k in _H4_TRI:
+            a_s, a_d = _h4_area2(qs, i, j, k), _h4_area2(qd, i, j, k)
+            min_area = np.fmin(min_area, np.fmin(np.abs(a_s), np.abs(a_d)))
+            valid &= (np.abs(a_s) >= H4_AREA_EPS) & (np.abs(a_d) >= H4_AREA_EPS)
+            negative += (a_s < 0.0) != (a_d < 0.0)
+        orient_ok = (negative == 0) | (negative == 4)
+        valid &= orient_ok
+        x, y, u, v = qs[..., 0], qs[..., 1], qd[..., 0], qd[..., 1]                    # [N, 4]
+        o, z = np.ones_like(x), np.zeros_like(x)
+        A = np.empty((n, 8, 9))
+        A[:, 0::2] = np.stack([x, y, o, z, z, z, -u * x, -u * y, u], -1)
+        A[:, 1::2] = np.stack([z, z, z, x, y, o, -v * x, -v * y, v], -1)
+        rows = np.arange(n)
+        min_pivot = np.full(n, np.inf)
+        for k in range(8):
+            col = np.abs(A[:, k:, k])
+            piv = np.where(np.isnan(col).any(1), 0, col.argmax(1)) + k            # argmax: the first row of the largest magnitude
+            best = col[rows, piv - k]
+            min_pivot = np.fmin(min_pivot, np.where(valid, best, np.inf))
+            valid &= best >= H4_PIVOT_EPS
+            tmp = A[rows, k].copy()
+            A[rows, k] = A[rows, piv]
+            A[rows, piv] = tmp
+            dk = np.where(valid, A[:, k, k], 1.0)
+            f = A[:, k + 1:, k] / dk[:, None]
+            A[:, k + 1:, k + 1:] -= f[:, :, None] * A[:, None, k, k + 1:]
+        h = np.ones((n, 9))
+        for k in range(7, -1, -1):
+            acc = A[:, k, 8].copy()
+            for c in range(k + 1, 8):
+                acc -= A[:, k, c] * h[:, c]
+            h[:, k] = acc / np.where(valid, A[:, k, k], 1.0)
+        h = h.reshape(n, 3, 3)
+        # H = Td^-1 Hn Ts, Ts = [ss 0 -ss cs.x; 0 ss -ss cs.y; 0 0 1], Td^-1 = [1/sd 0 cd.x; 0 1/sd cd.y; 0 0 1]
+        g = np.empty((n, 3, 3))
+        g[:, :, 0] = h[:, :, 0] * ss[:, None]
+        g[:, :, 1] = h[:, :, 1] * ss[:, None]
+        g[:, :, 2] = h[:, :, 2] - ss[:, None] * (h[:, :, 0] * cs[:, None, 0] + h[:, :, 1] * cs[:, None, 1])
+        isd = 1.0 / sd
+        H = np.empty((n, 3, 3))
+        H[:, 0] = g[:, 0] * isd[:, None] + cd[:, None, 0] * g[:, 2]
+        H[:, 1] = g[:, 1] * isd[:, None] + cd[:, None, 1] * g[:, 2]
+        H[:, 2] = g[:, 2]
+        H = H / H[:, 2:, 2:]
+        valid &= np.isfinite(H).all((1, 2))
+        H[:, 2, 2] = 1.0
+    H = np.where(valid[:, None, None], H, 0.0)[:, None]
+    if detail:
+        return H, valid[:, None], dict(min_area=min_area, min_pivot=min_pivot, orient_ok=orient_ok, qs=qs, qd=qd, cs=cs, cd=cd, ss=ss, sd=sd)
+    return H, valid[:, None]
+
+
+def transfer_error(H, src, dst):
+    """|dst - proj(H src)|^2 for models H [..., 3, 3] and points [P, 2] -> [..., P]: the forward transfer error of
+    HomographyEstimatorCallback::computeError (fp64, IEEE division).  inf where w = h31 x + h32 y + h33 is 0 or the error is not
+    finite, so that such a point fails every `<= thr2`."""
+    H = np.asarray(H, dtype=np.float64)
+    ht = np.concatenate([src, np.ones((src.shape[0], 1))], 1).T                     # [3, P]
+    q = H @ ht                                                                      # [..., 3, P]
+    w = q[..., 2, :]
+    with np.errstate(all="ignore"):
+        e = (dst[:, 0] - q[..., 0, :] / w) ** 2 + (dst[:, 1] - q[..., 1, :] / w) ** 2
+    return np.where((w != 0.0) & np.isfinite(e), e, np.inf)
+
+
+def homography_dlt(src, dst):
+    """Normalised DLT over n >= 4 correspondences, dst ~ H src: Hartley scaling of both sides, the right singular vector of the
+    smallest singular value of the 2n x 9 system, de-normalised and scaled to h33 = 1.  Runs on the host, once per call (the re-fit
+    on the final inliers).  -> H [3, 3], or None for fewer than 4 points or a degenerate set."""
+    src = np.asarray(src, dtype=np.float64).reshape(-1, 2)
+    dst = np.asarray(dst, dtype=np.float64).reshape(-1, 2)
+    if src.shape[0] < 4:
+        return None
+
+    def norm_T(p):
+        c = p.mean(0)
+        md = np.sqrt(((p - c) ** 2).sum(1)).mean()
+        s = np.sqrt(2.0) / md if md > 0 else 0.0
+        return np.array([[s, 0, -s * c[0]], [0, s, -s * c[1]], [0, 0, 1.0]])
+
+    Ts, Td = norm_T(src), norm_T(dst)
+    if Ts[0, 0] == 0.0 or Td[0, 0] == 0.0 or not (np.isfinite(Ts).all() and np.isfinite(Td).all()):
+        return None
+    a = src * Ts[0, 0] + Ts[:2, 2]
+    b = dst * Td[0, 0] + Td[:2, 2]
+    x, y, u, v = a[:, 0], a[:, 1], b[:, 0], b[:, 1]
+    o, z = np.ones_like(x), np.zeros_like(x)
+    A = np.concatenate([np.stack([x, y, o, z, z, z, -u * x, -u * y, -u], 1), np.stack([z, z, z, x, y, o, -v * x, -v * y, -v], 1)])
+    _, _, vt = np.linalg.svd(A)
+    H = np.linalg.inv(Td) @ vt[-1].reshape(3, 3) @ Ts
+    with np.errstate(all="ignore"):
+        H = H / H[2, 2]
+    return H if np.isfinite(H).all() else None
+
+
+class DeviceHomography:
+    """A whole homography RANSAC step on the GPU (csrc/homography.hip through ops.homography_step / ops.homography_mask): the points
+    go to the device once; a step uploads only its sample indices and reads back models, flags and counts of ONE launch.  `solve`
+    is the `solve_idx` hook of `_ransac_steps`, `counts` / `mask` the scorer interface of `_ransac` (the counts are those of the
+    launch that made the models)."""
+
+    def __init__(self, src, dst, thr2, device):
+        import torch
+        from . import ops
+        self._torch, self._ops = torch, ops
+        self.device = torch.device(device)
+        self.thr2 = float(thr2)
+        self._counts = None
+        with torch.cuda.device(self.device):
+            self.src = torch.from_numpy(np.ascontiguousarray(src, dtype=np.float64)).to(self.device)
+            self.dst = torch.from_numpy(np.ascontiguousarray(dst, dtype=np.float64)).to(self.device)
+
+    def solve(self, idx):
+        with self._torch.cuda.device(self.device):
+            d_idx = self._torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(self.device)
+            models, valid, counts = self._ops.homography_step(self.src, self.dst, d_idx, self.thr2)
+            self._counts = counts.cpu().numpy().astype(np.int64)
+            return models.cpu().numpy()[:, None], valid.cpu().numpy()[:, None]
+
+    def counts(self, Ms, valid):
+        return self._counts
+
+    def mask(self, M):
+        with self._torch.cuda.device(self.device):
+            d_M = self._torch.from_numpy(np.ascontiguousarray(M, dtype=np.float64)).to(self.device)
+            return self._ops.homography_mask(d_M, self.src, self.dst, self.thr2).cpu().numpy()
+
+
+def find_homography(src, dst, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None):
+    """cv2.findHomography(src, dst, RANSAC, threshold, maxIters=max_iters, confidence=prob) restated: dst ~ H src
+    -> (H [3, 3] with h33 = 1 | None, mask [P] bool).  Plain RANSAC over four-point samples with the forward transfer error in
+    pixels; sampling and the shrinking iteration bound are `_ransac_steps`'.  Host path: `homography_4pt` and `transfer_error`.
+    device: the same indices are drawn on the host and uploaded; models, flags and counts come from one gim_homography_step per
+    step (`DeviceHomography`; the device rounds differently, so its trajectory need not be the host's).  Then, as
+    RANSACPointSetRegistrator::run + findHomography do, the model is re-fitted on the inliers of the best sample (`homography_dlt`)
+    and the mask taken once more with the re-fitted model; the re-fit is kept only if it does not lose inliers.  OpenCV's final
+    Levenberg-Marquardt polish of the re-fit (HomographyRefineCallback) is NOT built, and neither is USAC_MAGSAC's scoring (the
+    reference's demo asks for it; the mask here is RANSAC's)."""
+    src = np.ascontiguousarray(src, dtype=np.float64).reshape(-1, 2)
+    dst = np.ascontiguousarray(dst, dtype=np.float64).reshape(-1, 2)
+    P = src.shape[0]
+    if P < 4:
+        return None, np.zeros(P, dtype=bool)
+    thr2 = float(threshold) ** 2
+    dev = DeviceHomography(src, dst, thr2, device) if device is not None else None
+    H, mask = _ransac(src, dst, homography_4pt, 4, threshold, prob, max_iters, np.random.default_rng(seed), scorer=dev,
+                      solve_idx=None if dev is None else dev.solve, error=transfer_error)
+    if H is None:
+        return None, mask
+    mask = np.asarray(mask, dtype=bool)
+    H2 = homography_dlt(src[mask], dst[mask])
+    if H2 is not None:
+        mask2 = (transfer_error(H2, src, dst) <= thr2) if dev is None else np.asarray(dev.mask(H2), dtype=bool)
+        if mask2.sum() >= mask.sum():
+            H, mask = H2, mask2
+    return H, mask
 
 
 def decompose_essential(E):

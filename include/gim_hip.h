@@ -932,6 +932,63 @@ int64_t gim_balanced_sample_pairs_ws_bytes(int B, int n, int num);
 int gim_balanced_sample_pairs(const float* matches, const float* certainty, const uint32_t* seeds, float* sparse, float* mconf,
                               int32_t* count, void* ws, int B, int n, int num, float thresh, int kde_half, gim_stream_t stream);
 
+/* ======================================================================================================
+ * Homography RANSAC step and perspective warp: the last two steps of the reference's demo (added within ABI revision 115: no
+ * existing structure or prototype changed with it).  The reference calls cv2.findHomography(mkpts1, mkpts0, ...) and
+ * cv2.warpPerspective(img1, H, size of img0) (demo.py:180-227, 230-266).  Sampling, the iteration bound and the final re-fit
+ * stay on the host (gim_amd/pose.py); the minimal solve, the sample checks and the scoring are one launch per step.
+ * ====================================================================================================== */
+
+/* K four-point hypotheses per pair, solved AND scored in ONE launch, B pairs.  All pointers are DEVICE memory.  src, dst fp64
+ * [Ptot][2] (16-byte aligned), the points of the pairs concatenated; offsets int32 [B + 1], non-decreasing: pair b owns the points
+ * offsets[b] .. offsets[b + 1] (trusted, as in gim_ransac_score: the caller checks them); idx int32 [B][K][4]: the sample's four
+ * point indices RELATIVE to the pair's offset.  fp64 throughout, no fast-math.  The model is dst ~ H src:
+ *   * each side's four points are shifted to zero mean and scaled to mean distance sqrt(2);
+ *   * the eight equations (x, y, 1, 0, 0, 0, -u x, -u y | u), (0, 0, 0, x, y, 1, -v x, -v y | v) of the normalised correspondences
+ *     (x, y) -> (u, v), point-major, are solved for h11 .. h32 with h33 = 1 by Gaussian elimination with partial pivoting on the
+ *     8 x 9 augmented system (the first row of the largest magnitude wins a tie);
+ *   * H is de-normalised (T_dst^-1 H T_src) and scaled so that h33 = 1 (HomographyEstimatorCallback::runKernel of OpenCV 4.x,
+ *     modules/calib3d/src/fundam.cpp, also normalises, de-normalises and scales to h33 = 1; it scales each axis by its mean absolute
+ *     deviation and takes the smallest eigenvector of the 9 x 9 normal matrix, this takes Hartley's scaling and the direct solve: no
+ *     eigen-decomposition, the same model on exact data).
+ * valid[b][k] = 0, counts[b][k] = 0 and an all-zero model are written when
+ *   * an index is outside [0, the pair's point count) or the sample repeats an index;
+ *   * the four points of a side coincide (no scale);
+ *   * any three of the four points of either side are collinear: the doubled area of the triangle, in normalised coordinates,
+ *     is below 1e-9 in magnitude (the haveCollinearPoints rule of fundam.cpp, stated on areas);
+ *   * the sample fails the orientation test of HomographyEstimatorCallback::checkSubset (fundam.cpp): over the triples (0,1,2),
+ *     (1,2,3), (0,2,3), (0,1,3) the sign of the oriented area on the src side differs from the dst side for some but not all four
+ *     (none differing, or all four: a reflection, pass -- as OpenCV decides it);
+ *   * a pivot of the normalised system is below 1e-12 in magnitude;
+ *   * the de-normalised model has an entry that is not finite after the division by h33.
+ * Otherwise valid = 1, models fp64 [B][K][3][3] row-major holds H, and counts int32 [B][K] the number of the pair's points with
+ *   err = |dst - proj(H src)|^2 <= thr2     (HomographyEstimatorCallback::computeError: the forward transfer error; IEEE division),
+ * where a point with w = h31 x + h32 y + h33 == 0 or an error that is not finite is an outlier.  models, valid and counts are FULLY
+ * written (no memset by the caller; no atomics: one workgroup owns one hypothesis).  B == 0 or K == 0 returns without touching
+ * anything.  B <= 65535. */
+int gim_homography_step(const double* src, const double* dst, const int32_t* offsets, int B, const int32_t* idx, int K, double thr2,
+                        double* models, uint8_t* valid, int32_t* counts, gim_stream_t stream);
+/* The inlier mask of ONE model per pair with the same error: models fp64 [B][3][3]; mask uint8 [Ptot], 1 where err <= thr2 (an
+ * all-zero model has w == 0 everywhere: no inlier); every point of [offsets[0], offsets[B]) is written.  B == 0 returns without
+ * touching anything. */
+int gim_homography_mask(const double* models, const double* src, const double* dst, const int32_t* offsets, int B, double thr2,
+                        uint8_t* mask, gim_stream_t stream);
+
+/* Perspective warp, cv2.warpPerspective(src, H, (Wd, Hd)) with INTER_LINEAR and BORDER_CONSTANT 0.  src / dst: DEVICE memory,
+ * channels-first contiguous [B][C][Hs][Ws] / [B][C][Hd][Wd] of uint8 (dtype 0) or fp32 (dtype 1; pixel kinds of this call alone,
+ * not the GIM_F32 / GIM_BF16 / GIM_F16 tags; another value is refused), 1 <= C <= 4; Hmat fp64 [B][3][3]
+ * DEVICE memory, row-major: H maps src pixels to dst pixels.  The destination pixel (x, y), integer pixel centres, reads
+ *   (u, v) = proj(H^-1 (x, y, 1))   in fp64, H^-1 taken as the adjugate of H (the projection does not see the factor 1 / det),
+ *   dst = sum over the four neighbours (x0 + i, y0 + j), x0 = floor(u), y0 = floor(v), of weight_ij * src, a neighbour outside the
+ *   source contributing 0; the weights (1 - ax | ax)(1 - ay | ay) are formed in fp64, rounded once to fp32, and blended in fp32
+ *   (four products, three additions).  The result is a continuous function of (u, v).  w == 0 or a coordinate that is not finite: 0.
+ * uint8 stores rint (to nearest even) of the fp32 value, saturated.  cv2 interpolates with 5-bit fixed-point weights (INTER_BITS); this
+ * is the exact-weight operator and is compared against its own formula, not against cv2's bytes.  The caller rejects a singular
+ * H (det == 0) or one with an entry that is not finite before the call (ops.warp_perspective, on the host); the kernel does not
+ * check again: such an H gives an image without meaning, never an access outside src or dst.  B == 0 or an empty destination returns without touching anything. */
+int gim_warp_perspective(const void* src, int dtype, int B, int C, int Hs, int Ws, const double* Hmat, void* dst, int Hd, int Wd,
+                         gim_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
