@@ -23,6 +23,9 @@ What is restated (OpenCV 4.x, modules/calib3d/src/five-point.cpp and ptsetreg.cp
   * four-point homography inside the same loop for the demo's warp (demo.py:180-227 cv2.findHomography; fundam.cpp): forward transfer
     error, re-fit on the inliers by normalised DLT, no Levenberg-Marquardt polish.  This solver also runs on the device, fused with
     the scoring (`find_homography(device=)`, csrc/homography.hip): a step uploads sample indices only.
+  * the seven-point solver by elimination and a closed-form cubic (`seven_point_ge`), the arithmetic of the device step that solves
+    and scores in one launch (`find_fundamental_mat(solve="device")`, `find_fundamental_mat_batch`, `verify_pairs`;
+    csrc/fundamental.hip).  `seven_point` and the default path are unchanged.
 
 Parity: UNPINNED against cv2 (no OpenCV here to record vectors from; sampling is random in both).  tests/test_pose_cpu.py pins
 the solvers on exact synthetic geometry (every ground-truth E / F is among the candidates to 1e-9, recovered poses within 1e-6
@@ -180,6 +183,150 @@ def seven_point(x0, x1):
     return F, real
 
 
+F7_SCALE_EPS = 1e-12    # smallest mean distance of a side's seven points from their centre
+F7_RANK_EPS = 1e-12     # smallest seventh pivot of the 7 x 9 elimination, relative to the first
+F7_CUBIC_EPS = 1e-12    # smallest max |c| of the cubic: below it every matrix a F1 + (1 - a) F2 is singular, the cubic is noise
+F7_LEAD_EPS = 1e-14     # smallest |c3| relative to max |c| (seven_point's rule)
+F7_DISC_EPS = 1e-9      # |discriminant| / scale below which one real root and three cannot be told apart
+
+
+def _f7_normalise(p):
+    """[N, 7, 2] -> (q with zero mean and mean distance sqrt(2), centre [N, 2], scale [N], ok [N]); q = (p - c) * s"""
+    c = ((((((p[:, 0] + p[:, 1]) + p[:, 2]) + p[:, 3]) + p[:, 4]) + p[:, 5]) + p[:, 6]) / 7.0
+    q = p - c[:, None]
+    d = np.sqrt(q[..., 0] * q[..., 0] + q[..., 1] * q[..., 1])
+    md = ((((((d[:, 0] + d[:, 1]) + d[:, 2]) + d[:, 3]) + d[:, 4]) + d[:, 5]) + d[:, 6]) / 7.0
+    ok = np.isfinite(md) & (md >= F7_SCALE_EPS)
+    s = np.sqrt(2.0) / np.where(ok, md, 1.0)
+    return q * s[:, None, None], c, s, ok
+
+
+def _f7_det3(m):
+    return (m[..., 0] * (m[..., 4] * m[..., 8] - m[..., 5] * m[..., 7]) - m[..., 1] * (m[..., 3] * m[..., 8] - m[..., 5] * m[..., 6]) +
+            m[..., 2] * (m[..., 3] * m[..., 7] - m[..., 4] * m[..., 6]))
+
+
+def seven_point_ge(x0, x1, detail=False):
+    """Fundamental matrices through 7 correspondences by elimination.  x0, x1: [N, 7, 2] in any units (x1^T F x0 = 0)
+    -> (F [N, 3, 3, 3] of unit Frobenius norm, valid [N, 3]), the models ordered by their root a ascending, an unused slot zero.
+    The arithmetic and the validity rules of gim_fundamental_step (include/gim_hip.h; csrc/fundamental_solve.h is the same code for
+    the device), batched over the samples: each side shifted to zero mean and scaled to mean distance sqrt(2) per sample; the 7 x 9
+    rows of `_epipolar_rows` reduced by Gauss-Jordan elimination with full pivoting; the two free columns give F1, F2; the cubic
+    det(a F1 + (1 - a) F2) interpolated at a = 0, 1, -1, 2 as in `seven_point`, solved in closed form (Cardano for one real root, the
+    trigonometric form for three) and polished by two Newton steps; F = T1^T (a F1 + (1 - a) F2) T0.  All three slots are invalid
+    when the seven points of a side coincide (mean distance below 1e-12), the seventh pivot is below 1e-12 times the first (collinear
+    points, a planar scene), max |c| is below 1e-12 (every matrix of the pencil is singular -- three matches that share a point on
+    one side do that -- and the cubic is rounding noise), or |c3| <= 1e-14 max |c|; a slot is invalid when its model's norm is zero
+    or not finite.
+    detail=True adds a dict: ok_scale, ok_rank, ok_cubic, ok_lead [N] (the four rules, each True where an earlier rule already
+    failed), pivot_ratio [N] (seventh pivot / first), cubic_scale [N] (max |c|), lead_ratio [N] (|c3| / max |c|), disc_rel [N]
+    (discriminant / its scale, > 0: one root), roots [N, 3] -- what a test needs to see how far a sample is from a rule."""
+    x0 = np.asarray(x0, dtype=np.float64)
+    x1 = np.asarray(x1, dtype=np.float64)
+    n = x0.shape[0]
+    rows = np.arange(n)
+    with np.errstate(all="ignore"):
+        q0, c0, s0, ok0 = _f7_normalise(x0)
+        q1, c1, s1, ok1 = _f7_normalise(x1)
+        ok_scale = ok0 & ok1
+        A = _epipolar_rows(q0, q1)                                              # [N, 7, 9]
+        alive = ok_scale.copy()
+        rowof = np.full((n, 9), -1, dtype=np.int64)
+        first = last = np.zeros(n)
+        for k in range(7):
+            sub = np.abs(A[:, k:, :]).reshape(n, -1)
+            j = np.where(np.isnan(sub).any(1), 0, sub.argmax(1))                # argmax: the lowest row, then the lowest column
+            best = sub[rows, j]
+            pr, pc = j // 9 + k, j % 9
+            if k == 0:
+                first = best
+            alive &= np.isfinite(best) & (best > 0.0)
+            if k == 6:
+                last = best
+                alive &= best >= F7_RANK_EPS * first
+            tmp = A[rows, k].copy()
+            A[rows, k] = A[rows, pr]
+            A[rows, pr] = tmp
+            A[:, k] = A[:, k] / np.where(alive, A[rows, k, pc], 1.0)[:, None]
+            f = A[rows, :, pc]                                                  # [N, 7] (a copy: fancy indexing)
+            f[:, k] = 0.0
+            A -= f[:, :, None] * A[:, None, k, :]
+            rowof[rows, pc] = k
+        ok_rank = alive | ~ok_scale
+        free = np.argsort(rowof >= 0, axis=1, kind="stable")[:, :2]             # the two free columns, ascending
+        f1 = np.where(alive, free[:, 0], 7)
+        f2 = np.where(alive, free[:, 1], 8)
+        r = np.where(rowof >= 0, rowof, 0)
+        F1 = -A[rows[:, None], r, f1[:, None]]
+        F2 = -A[rows[:, None], r, f2[:, None]]
+        F1[rows, f1], F1[rows, f2], F2[rows, f2], F2[rows, f1] = 1.0, 0.0, 1.0, 0.0
+        d0, d1, dm, d2 = _f7_det3(F2), _f7_det3(F1), _f7_det3(2.0 * F2 - F1), _f7_det3(2.0 * F1 - F2)
+        k0 = d0
+        k2 = (d1 + dm) * 0.5 - k0
+        sum13 = (d1 - dm) * 0.5
+        sum143 = ((d2 - k0) - 4.0 * k2) * 0.5
+        k3 = (sum143 - sum13) / 3.0
+        k1 = sum13 - k3
+        cmax = np.fmax(np.fmax(np.abs(k0), np.abs(k1)), np.fmax(np.abs(k2), np.abs(k3)))
+        ok_cubic = cmax >= F7_CUBIC_EPS
+        ok_lead = np.abs(k3) > F7_LEAD_EPS * (cmax + 1e-300)
+        alive &= ok_cubic & ok_lead
+        ld = np.where(alive, k3, 1.0)
+        b2, b1, b0 = k2 / ld, k1 / ld, k0 / ld
+        sh = b2 / 3.0
+        p = b1 - b2 * sh
+        q = (2.0 * sh * sh - b1) * sh + b0
+        hq, tp = 0.5 * q, p / 3.0
+        D = hq * hq + tp * tp * tp
+        one = D > 0.0
+        alive &= one | (D <= 0.0)
+        # one real root: Cardano, no cancellation under the cube root
+        sD = np.sqrt(np.where(one, D, 0.0))
+        u = np.where(hq >= 0.0, -np.cbrt(hq + sD), np.cbrt(sD - hq))
+        v = np.where(u != 0.0, -tp / np.where(u != 0.0, u, 1.0), 0.0)
+        a1 = (u + v) - sh
+        # three real roots: trigonometric form
+        m = np.sqrt(np.where(one, 0.0, -tp))
+        w = np.clip(-hq / np.where(m > 0.0, m * m * m, 1.0), -1.0, 1.0)
+        th = np.arccos(w) / 3.0
+        tw = 2.0943951023931954923
+        a3 = np.stack([2.0 * m * np.cos(th), 2.0 * m * np.cos(th - tw), 2.0 * m * np.cos(th - 2.0 * tw)], 1)
+        a3 = np.where((m > 0.0)[:, None], a3, 0.0) - sh[:, None]
+        a = np.where(one[:, None], np.stack([a1, np.zeros(n), np.zeros(n)], 1), a3)
+        for _ in range(2):                                                       # Newton on a^3 + b2 a^2 + b1 a + b0
+            fa = ((a + b2[:, None]) * a + b1[:, None]) * a + b0[:, None]
+            ga = (3.0 * a + 2.0 * b2[:, None]) * a + b1[:, None]
+            da = fa / ga
+            a = np.where(np.isfinite(da), a - da, a)
+        a = np.where(one[:, None], a, np.sort(a, axis=1))
+        slot = alive[:, None] & (~one[:, None] | (np.arange(3) == 0))
+        a = np.where(slot, a, 0.0)
+        N = a[:, :, None] * F1[:, None] + (1.0 - a)[:, :, None] * F2[:, None]     # [N, 3, 9]
+        N = N.reshape(n, 3, 3, 3)
+        G = np.empty_like(N)
+        G[..., 0] = N[..., 0] * s0[:, None, None]
+        G[..., 1] = N[..., 1] * s0[:, None, None]
+        G[..., 2] = N[..., 2] - s0[:, None, None] * (N[..., 0] * c0[:, None, None, 0] + N[..., 1] * c0[:, None, None, 1])
+        P = np.empty_like(G)
+        P[:, :, 0] = s1[:, None, None] * G[:, :, 0]
+        P[:, :, 1] = s1[:, None, None] * G[:, :, 1]
+        P[:, :, 2] = G[:, :, 2] - s1[:, None, None] * (c1[:, None, None, 0] * G[:, :, 0] + c1[:, None, None, 1] * G[:, :, 1])
+        Pf = P.reshape(n, 3, 9)
+        n2 = np.zeros((n, 3))
+        for i in range(9):
+            n2 = n2 + Pf[..., i] * Pf[..., i]
+        nrm = np.sqrt(n2)
+        valid = slot & np.isfinite(nrm) & (nrm > 0.0)
+        F = np.where(valid[..., None, None], P / np.where(valid, nrm, 1.0)[..., None, None], 0.0)
+    if detail:
+        with np.errstate(all="ignore"):
+            before = ok_scale & ok_rank
+            info = dict(ok_scale=ok_scale, ok_rank=ok_rank, ok_cubic=ok_cubic | ~before, ok_lead=ok_lead | ~(before & ok_cubic),
+                        pivot_ratio=last / first, cubic_scale=cmax, lead_ratio=np.abs(k3) / (cmax + 1e-300), disc_rel=D / (hq * hq + np.abs(tp * tp * tp)), roots=a)
+        return F, valid, info
+    return F, valid
+
+
 def sampson_error(M, x0, x1):
     """(x1^T M x0)^2 / (|M x0|_xy^2 + |M^T x1|_xy^2) for models M [..., 3, 3] and points [P, 2] -> [..., P]
     (EMEstimatorCallback::computeError / FMEstimatorCallback::computeError)"""
@@ -238,7 +385,9 @@ def _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch=250, solve_i
     models (Ms [nb * k, 3, 3], valid [nb * k]) and is sent their inlier counts [nb * k]; the generator's return value is the best
     model [3, 3] or None.  Who counts (the host, a device, one launch for many pairs in lockstep) is the driver's business.
     solve_idx: a hook that receives the step's sample indices idx [nb, m] and returns (Ms [nb, k, 3, 3], valid [nb, k]) in place of
-    solver(s0[idx], s1[idx]) -- a solver that lives where the points already are (`DeviceHomography`)."""
+    solver(s0[idx], s1[idx]) -- a solver that lives where the points already are (`DeviceHomography`, `DeviceFundamental`).  The
+    arrays it returns are read only after the counts have been sent, so a lockstep driver may hand out empty ones and fill them in
+    place from one launch for many pairs (`find_fundamental_mat_batch`)."""
     lconf = np.log(max(1.0 - conf, 1e-300))
     best_n, best_M = 0, None
     niters, done = int(max_iters), 0
@@ -355,14 +504,66 @@ def find_essential_mat_batch(pairs, threshold, prob=0.999, max_iters=1000, seed=
             for b in range(B)]
 
 
-def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None):
+class DeviceFundamental:
+    """A whole fundamental-matrix RANSAC step on the GPU (csrc/fundamental.hip through ops.fundamental_step; the mask through
+    ops.ransac_mask, the same Sampson error): the points go to the device once; a step uploads only its sample indices and reads back
+    the up to three models per sample, their flags and counts of ONE launch.  `solve` is the `solve_idx` hook of `_ransac_steps`,
+    `counts` / `mask` the scorer interface of `_ransac` (the counts are those of the launch that made the models).
+    One pair: x0, x1 [P, 2], idx [K, 7].  Several pairs in lockstep: their points concatenated and `offsets` [B + 1]; `solve` then
+    takes idx [B, K, 7] relative to each pair (an index of -1 marks padding) and `mask` one model per pair [B, 3, 3] -> bool [Ptot]."""
+
+    def __init__(self, x0, x1, thr2, device, offsets=None):
+        import torch
+        from . import ops
+        self._torch, self._ops = torch, ops
+        self.device = torch.device(device)
+        self.thr2 = float(thr2)
+        self._counts = None
+        with torch.cuda.device(self.device):
+            self.x0 = torch.from_numpy(np.ascontiguousarray(x0, dtype=np.float64)).to(self.device)
+            self.x1 = torch.from_numpy(np.ascontiguousarray(x1, dtype=np.float64)).to(self.device)
+            self.offsets = None if offsets is None else torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int32)).to(self.device)
+
+    def solve(self, idx):
+        with self._torch.cuda.device(self.device):
+            d_idx = self._torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(self.device)
+            models, valid, counts = self._ops.fundamental_step(self.x0, self.x1, d_idx, self.thr2, offsets=self.offsets)
+            self._counts = counts.cpu().numpy().astype(np.int64)
+            return models.cpu().numpy(), valid.cpu().numpy()
+
+    def counts(self, Ms, valid):
+        return self._counts.reshape(-1) if self.offsets is None else self._counts
+
+    def mask(self, M):
+        with self._torch.cuda.device(self.device):
+            d_M = self._torch.from_numpy(np.ascontiguousarray(M, dtype=np.float64)).to(self.device)
+            return self._ops.ransac_mask(d_M, self.x0, self.x1, self.thr2, offsets=self.offsets).cpu().numpy()
+
+
+def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, solve="host"):
     """Plain RANSAC over seven-point samples with the Sampson distance in pixels (the demo's geometry filter, demo.py:514-517;
-    the reference's USAC_MAGSAC scoring is not restated).  The solver works on Hartley-normalised points, the candidates are
-    mapped back to pixel units for scoring (on `device` when given, as in find_essential_mat).  -> (F [3,3] | None, mask [P])"""
+    the reference's USAC_MAGSAC scoring is not restated).  -> (F [3,3] | None, mask [P])
+    solve="host": `seven_point` (SVD null space, eigenvalues) on points Hartley-normalised once per call, the candidates mapped back
+    to pixel units for scoring (on `device` when given, as in find_essential_mat: same trajectory as the host run).
+    solve="device" (needs `device`): the same indices are drawn on the host and uploaded; models, flags and counts come from one
+    gim_fundamental_step per step (`DeviceFundamental`: elimination, a closed-form cubic, normalisation per sample; it rounds
+    differently from `seven_point`, so its trajectory need not be the host's), the mask from gim_ransac_mask.
+    solve="ge" (host only): the same RANSAC over `seven_point_ge`, the numpy restatement of the device solver -- its CPU oracle."""
+    if solve not in ("host", "device", "ge"):
+        raise ValueError(f"solve={solve!r}: host, device or ge")
+    if solve == "device" and device is None:
+        raise ValueError("solve='device' needs a device")
+    if solve == "ge" and device is not None:
+        raise ValueError("solve='ge' runs on the host: device must be None")
     p0 = np.ascontiguousarray(p0, dtype=np.float64)
     p1 = np.ascontiguousarray(p1, dtype=np.float64)
     if p0.shape[0] < 7:
         return None, np.zeros(p0.shape[0], dtype=bool)
+    if solve == "ge":
+        return _ransac(p0, p1, seven_point_ge, 7, threshold, prob, max_iters, np.random.default_rng(seed))
+    if solve == "device":
+        dev = DeviceFundamental(p0, p1, float(threshold) ** 2, device)
+        return _ransac(p0, p1, None, 7, threshold, prob, max_iters, np.random.default_rng(seed), scorer=dev, solve_idx=dev.solve)
 
     def norm_T(p):
         c = p.mean(0)
@@ -381,6 +582,83 @@ def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, 
 
     scorer = DeviceScorer(p0, p1, float(threshold) ** 2, device) if device is not None else None
     return _ransac(p0, p1, solver, 7, threshold, prob, max_iters, np.random.default_rng(seed), s0=q0, s1=q1, scorer=scorer)
+
+
+class _DeferredSolve:
+    """The `solve_idx` hook of one pair of a lockstep run: it keeps the step's indices and hands out empty arrays, which the driver
+    fills in place from the launch that serves every pair before it sends the counts."""
+
+    def __call__(self, idx):
+        self.idx = idx
+        self.models, self.valid = np.zeros((idx.shape[0], 3, 3, 3)), np.zeros((idx.shape[0], 3), dtype=bool)
+        return self.models, self.valid
+
+
+def find_fundamental_mat_batch(pairs, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, solve="device"):
+    """`find_fundamental_mat(p0, p1, threshold, prob, max_iters, seed, device, solve="device")` for every (p0, p1) of `pairs`, run in
+    lockstep as find_essential_mat_batch runs its pairs: a step draws the samples of every unfinished pair on the host and solves and
+    scores all of them in ONE gim_fundamental_step launch (ragged point sets through offsets; a finished pair and the padding of a
+    shorter step are index -1: invalid); one gim_ransac_mask call for all pairs ends the run.  Every pair has its own
+    default_rng(seed) and its own shrinking iteration bound, so its result is that of the single call.
+    -> [(F [3,3] | None, mask [P_b] bool)] in the order of `pairs`."""
+    if solve != "device" or device is None:
+        raise ValueError("find_fundamental_mat_batch runs solve='device' on a device")
+    pairs = [(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 2), np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 2)) for a, b in pairs]
+    B = len(pairs)
+    if B == 0:
+        return []
+    offsets = np.concatenate([[0], np.cumsum([a.shape[0] for a, _ in pairs])]).astype(np.int64)
+    best = [None] * B
+    steps, hooks, pending = {}, {}, set()
+    for b, (a, c) in enumerate(pairs):
+        if a.shape[0] >= 7:
+            hooks[b] = _DeferredSolve()
+            steps[b] = _ransac_steps(a.shape[0], None, 7, prob, max_iters, np.random.default_rng(seed), a, c, solve_idx=hooks[b])
+
+    def advance(b, counts):
+        try:
+            next(steps[b]) if counts is None else steps[b].send(counts)
+            pending.add(b)
+        except StopIteration as stop:
+            best[b] = stop.value
+            pending.discard(b)
+
+    for b in steps:
+        advance(b, None)
+    dev = None
+    if pending:
+        dev = DeviceFundamental(np.concatenate([a for a, _ in pairs]), np.concatenate([b for _, b in pairs]), float(threshold) ** 2, device,
+                                offsets=offsets)
+    while pending:
+        K = max(hooks[b].idx.shape[0] for b in pending)
+        idx = np.full((B, K, 7), -1, dtype=np.int32)
+        for b in pending:
+            idx[b, :hooks[b].idx.shape[0]] = hooks[b].idx
+        models, valid = dev.solve(idx)
+        counts = dev.counts(models, valid)
+        for b in sorted(pending):
+            nb = hooks[b].idx.shape[0]
+            hooks[b].models[...], hooks[b].valid[...] = models[b, :nb], valid[b, :nb]
+            advance(b, counts[b, :nb].reshape(-1))
+    found = [b for b in range(B) if best[b] is not None]
+    masks = np.zeros(offsets[-1], dtype=bool)
+    if found:
+        models = np.zeros((B, 3, 3))
+        for b in found:
+            models[b] = best[b]
+        masks = dev.mask(models)
+    return [(best[b], masks[offsets[b]:offsets[b + 1]] if best[b] is not None else np.zeros(offsets[b + 1] - offsets[b], dtype=bool))
+            for b in range(B)]
+
+
+def verify_pairs(pairs_of_points, threshold=1.0, device=None, prob=0.999999, max_iters=10000, seed=0, batch=32):
+    """Two-view verification of a pair list (the matches of a LightGlue / root_sift / dense pair list, in pixels) without OpenCV:
+    `find_fundamental_mat_batch` over `batch` pairs per launch sequence -> [(F [3,3] | None, mask [P_b] bool)] in the list's order."""
+    pairs_of_points = list(pairs_of_points)
+    out = []
+    for i in range(0, len(pairs_of_points), int(batch)):
+        out += find_fundamental_mat_batch(pairs_of_points[i:i + int(batch)], threshold, prob, max_iters, seed, device)
+    return out
 
 
 # ---- homography: four-point minimal solver, transfer error, DLT re-fit, RANSAC (demo.py:180-227 cv2.findHomography) ------------

@@ -989,6 +989,47 @@ int gim_homography_mask(const double* models, const double* src, const double* d
 int gim_warp_perspective(const void* src, int dtype, int B, int C, int Hs, int Ws, const double* Hmat, void* dst, int Hd, int Wd,
                          gim_stream_t stream);
 
+/* ======================================================================================================
+ * Fundamental-matrix RANSAC step: the seven-point minimal solve and the scoring of its models in one launch (added within ABI
+ * revision 115: no existing structure or prototype changed with it).  The reference calls cv2.findFundamentalMat(mkpts0, mkpts1,
+ * ...) (demo.py:514-517).  Sampling and the iteration bound stay on the host (gim_amd/pose.py); the final mask is gim_ransac_mask,
+ * the same Sampson error.  The five-point solver (a 10 x 10 non-symmetric eigenproblem) stays on the host.
+ * ====================================================================================================== */
+
+/* K seven-point samples per pair, solved AND scored in ONE launch, B pairs; a sample gives up to three models.  All pointers are
+ * DEVICE memory.  x0, x1 fp64 [Ptot][2] (16-byte aligned), the points of the pairs concatenated; offsets int32 [B + 1],
+ * non-decreasing: pair b owns the points offsets[b] .. offsets[b + 1] (trusted, as in gim_ransac_score: the caller checks them); idx
+ * int32 [B][K][7]: the sample's seven point indices RELATIVE to the pair's offset.  fp64 throughout, no fast-math.  The model is
+ * x1^T F x0 = 0 (pose.seven_point_ge is this arithmetic in batched numpy, csrc/fundamental_solve.h the code):
+ *   * normalisation: each side's seven points are shifted to zero mean (sum in index order, divided by 7) and scaled to mean distance
+ *     sqrt(2); a side whose mean distance is below 1e-12 (seven coincident points) or not finite is invalid;
+ *   * null space: the 7 x 9 rows (u x, u y, u, v x, v y, v, x, y, 1) of the normalised correspondences (x, y) -> (u, v) (the column
+ *     order of pose._epipolar_rows) are reduced by Gauss-Jordan elimination with FULL pivoting: step k takes the largest |a| over the
+ *     rows k .. 6 and all columns (the lowest row, then the lowest column, wins a tie), swaps that row into place, divides it by the
+ *     pivot and eliminates the pivot column from the six other rows.  A zero pivot, or a seventh pivot below 1e-12 times the first,
+ *     is a rank-deficient sample (collinear points, a planar scene).  The two free columns f1 < f2 give the basis: F1 has 1 in
+ *     column f1, 0 in f2 and minus the reduced row's entry of column f1 in each pivot column; F2 likewise for f2;
+ *   * cubic: det(a F1 + (1 - a) F2) = c0 + c1 a + c2 a^2 + c3 a^3 is interpolated at a = 0, 1, -1, 2 (determinants by cofactors of
+ *     the first row).  A sample with max |c| < 1e-12 is invalid: every matrix of the pencil is singular (three matches that share a
+ *     point on one side do that) and the cubic is rounding noise, which pose.seven_point's relative rule does not see.  A sample
+ *     with |c3| <= 1e-14 (max |c| + 1e-300) is invalid (pose.seven_point's rule);
+ *   * roots: with b = c / c3 and a = t - b2 / 3 the depressed cubic is t^3 + p t + q; D = (q/2)^2 + (p/3)^3 > 0 gives one real root
+ *     by Cardano (u the cube root without cancellation, v = -p / (3 u)), D <= 0 three by the trigonometric form
+ *     t_k = 2 sqrt(-p/3) cos(acos(-(q/2) / sqrt(-p/3)^3) / 3 - 2 pi k / 3); every root gets two Newton steps on
+ *     a^3 + b2 a^2 + b1 a + b0 and the roots are ordered ascending into the slots 0, 1, 2.  A sample with |D| within 1e-9 of
+ *     (q/2)^2 + |p/3|^3 is ambiguous between one root and three; it is solved as D decides;
+ *   * output: each root gives T1^T (a F1 + (1 - a) F2) T0, scaled to unit Frobenius norm; a norm that is zero or not finite is
+ *     invalid.
+ * An index outside [0, the pair's point count) or a repeated index invalidates the whole sample and never becomes an address.
+ * models fp64 [B][K][3][3][3] row-major, valid uint8 [B][K][3] and counts int32 [B][K][3] are FULLY written (no memset by the caller;
+ * no atomics: one workgroup owns one sample): an invalid or unused slot holds a zero matrix, valid 0 and count 0; a valid one the
+ * number of the pair's points with
+ *   err = (x1^T F x0)^2 / max(|F x0|_xy^2 + |F^T x1|_xy^2, 1e-300) <= thr2     (the arithmetic and operation order of gim_ransac_score).
+ * B == 0 or K == 0 returns without touching anything.  Refused before a launch: a NULL pointer, x0 / x1 not 16-byte aligned, models
+ * not 8-byte or an int32 array not 4-byte aligned, B > 65535, B * K * 27 > INT32_MAX. */
+int gim_fundamental_step(const double* x0, const double* x1, const int32_t* offsets, int B, const int32_t* idx, int K, double thr2,
+                         double* models, uint8_t* valid, int32_t* counts, gim_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
