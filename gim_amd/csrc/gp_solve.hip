@@ -12,6 +12,13 @@
 //   gp_solve(K [B][n][ldk] fp32 (K_yy with sigma already on the diagonal), F [B][n][nrhs] fp32)
 //        -> Xt [B][nrhs][npad] fp32 = ((K)^-1 F)^T, zero padded to npad: the [N][K] "weight" layout the igemm takes
 //           for the final mu = K_xy X product.
+//
+// A failed factorisation is visible in the output.  The diagonal kernel records a pivot that is not positive (a matrix that is not
+// positive definite, or NaN / overflowed entries: a NaN pivot fails `d > 0` too) in info[b], puts 1.0 in its place and carries on, so
+// the launch sequence never depends on the data and nothing waits for the host.  The two kernels that write the result read info[b]:
+// where it is non-zero EVERY element of batch entry b is written as quiet NaN -- all of Xt[b] (the padding columns [n, npad) included)
+// from gim_gp_solve, all n x nrhs elements of mu[b] from gim_gp_posterior_f64 -- instead of the finite numbers the substituted pivots
+// lead to.  Entries whose factorisation succeeded are bit for bit what they are without the check, whatever their neighbours hold.
 #include "gim_common.h"
 
 namespace {
@@ -364,10 +371,11 @@ __global__ void __launch_bounds__(256) gemm_f64_kernel(const GemmArgs g) {
         }
 }
 
-// Xt[b][c][i] = (float) X[b][i][c], zero for i in [n, npad)
-__global__ void store_xt_kernel(const double* __restrict__ X, float* __restrict__ Xt, int n, int nrhs, int npad) {
+// Xt[b][c][i] = (float) X[b][i][c], zero for i in [n, npad); all of Xt[b] quiet NaN where the factorisation of entry b failed (info[b] != 0)
+__global__ void store_xt_kernel(const double* __restrict__ X, float* __restrict__ Xt, int n, int nrhs, int npad, const int* __restrict__ info) {
     __shared__ float tile[64][65];
     const int b = blockIdx.z, i0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
+    const bool failed = info[b] != 0;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     for (int r = ty; r < 64; r += 4) {
         const int i = i0 + r, c = c0 + tx;
@@ -376,7 +384,7 @@ __global__ void store_xt_kernel(const double* __restrict__ X, float* __restrict_
     __syncthreads();
     for (int r = ty; r < 64; r += 4) {
         const int c = c0 + r, i = i0 + tx;
-        if (c < nrhs && i < npad) Xt[((size_t)b * nrhs + c) * npad + i] = tile[tx][r];
+        if (c < nrhs && i < npad) Xt[((size_t)b * nrhs + c) * npad + i] = failed ? __builtin_nanf("") : tile[tx][r];
     }
 }
 
@@ -471,7 +479,7 @@ extern "C" int gim_gp_solve(const float* K, const float* F, float* Xt, void* ws,
         hipLaunchKernelGGL(to_f64_kernel, dim3((unsigned)(((size_t)n * nrhs + 255) / 256)), dim3(256), 0, s, F + (size_t)b * fs, R + b * fs, n, nrhs, nrhs, nrhs);
     }
     chol_solve(s, A, Lf, Tb, R, R2, info, B, n, nrhs);
-    hipLaunchKernelGGL(store_xt_kernel, dim3((npad + 63) / 64, (nrhs + 63) / 64, B), dim3(256), 0, s, R, Xt, n, nrhs, npad);
+    hipLaunchKernelGGL(store_xt_kernel, dim3((npad + 63) / 64, (nrhs + 63) / 64, B), dim3(256), 0, s, R, Xt, n, nrhs, npad, info);
     return gim_check_launch("gp_solve");
 }
 
@@ -504,11 +512,12 @@ __global__ void cos_finish_f64_kernel(double* __restrict__ k, const double* __re
     const double c = *p / (nx[(size_t)b * n + i] * ny[(size_t)b * n + j] + eps);
     *p = exp((c - 1.0) / T) + (i == j ? diag : 0.0);
 }
-__global__ void to_f32_rows_kernel(const double* __restrict__ src, float* __restrict__ dst, int rows, int cols, int ldd) {
+// one batch entry: dst[r][c] = (float) src[r][c]; quiet NaN throughout where its factorisation failed (*info != 0, the entry's own word)
+__global__ void to_f32_rows_kernel(const double* __restrict__ src, float* __restrict__ dst, int rows, int cols, int ldd, const int* __restrict__ info) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)rows * cols) return;
     const size_t r = idx / cols, c = idx - r * cols;
-    dst[r * ldd + c] = (float)src[idx];
+    dst[r * ldd + c] = *info != 0 ? __builtin_nanf("") : (float)src[idx];
 }
 }  // namespace
 
@@ -564,6 +573,6 @@ extern "C" int gim_gp_posterior_f64(const float* X, const float* Y, const float*
         launch_gemm(s, B, g);
     }
     for (int b = 0; b < B; ++b)
-        hipLaunchKernelGGL(to_f32_rows_kernel, dim3(gf), dim3(256), 0, s, R2 + b * fs, mu + (size_t)b * n * ld_mu, n, nrhs, ld_mu);
+        hipLaunchKernelGGL(to_f32_rows_kernel, dim3(gf), dim3(256), 0, s, R2 + b * fs, mu + (size_t)b * n * ld_mu, n, nrhs, ld_mu, info + b);
     return gim_check_launch("gp_posterior_f64");
 }

@@ -1190,7 +1190,10 @@ def cos_kernel_finish(k, nx, ny, B, n, m, T, eps, diag_add):
 
 
 def gp_solve(K, F, npad):
-    """K [B,n,ld] fp32 (SPD, sigma on the diagonal), F [B,n,nrhs] fp32 -> Xt [B,nrhs,npad] fp32 = (K^-1 F)^T, zero padded"""
+    """K [B,n,ld] fp32 (SPD, sigma on the diagonal), F [B,n,nrhs] fp32 -> Xt [B,nrhs,npad] fp32 = (K^-1 F)^T, zero padded.  B <= 16.
+    A batch entry whose Cholesky factorisation fails (a pivot that is not positive: K[b] not positive definite, or holding NaN / overflowed
+    values) comes back with EVERY element of Xt[b] quiet NaN, the padding columns included; the other entries are unaffected.  Nothing is
+    raised for it (the call does not wait for the device): test the result with isnan / isfinite."""
     _req_cuda(K, F)
     B, n, ld = K.shape
     nrhs = F.shape[2]
@@ -1203,7 +1206,9 @@ def gp_solve(K, F, npad):
 
 def gp_posterior_f64(X, Y, F, out, T=0.2, eps=1e-6, sigma=0.1):
     """GP posterior mean, every step in fp64 (the dense matchers' parity mode): X / Y [B,n,d] fp32 query / support rows (contiguous),
-    F [n,nrhs] fp32 -> out: fp32 row view [B*n, >= nrhs] receives K_xy (K_yy + sigma I)^-1 F, K = exp((cos - 1) / T)."""
+    F [n,nrhs] fp32 -> out: fp32 row view [B*n, >= nrhs] receives K_xy (K_yy + sigma I)^-1 F, K = exp((cos - 1) / T).  B <= 16.
+    A direction b whose K_yy + sigma I fails to factor (NaN or overflowed rows in Y[b]) has all n x nrhs elements of its block of `out`
+    written as quiet NaN; the other directions are unaffected and the columns of `out` beyond nrhs are never written."""
     _req_cuda(X, Y, F, out)
     B, n, d = X.shape
     nrhs = F.shape[1]

@@ -603,7 +603,10 @@ int gim_cos_kernel_finish(float* k, const float* nx, const float* ny, int B, int
                           float diag_add, gim_stream_t stream);
 /* (K_yy + sigma I)^-1 f of GP.forward -- dkm.py:352-359 -- as a blocked fp64 Cholesky solve (the reference inverts
  * with LU in fp32).  K [B][n][ldk] fp32 with sigma on the diagonal, F [B][n][nrhs] fp32;
- * Xt [B][nrhs][npad] fp32 = (K^-1 F)^T zero padded: the [N][K] operand layout of gim_conv2d_bn_act. */
+ * Xt [B][nrhs][npad] fp32 = (K^-1 F)^T zero padded: the [N][K] operand layout of gim_conv2d_bn_act.  B <= 16.
+ * A batch entry whose factorisation meets a pivot that is not positive (matrix not positive definite, NaN or overflowed entries) comes
+ * back as quiet NaN in EVERY element of Xt[b], padding included; the other entries are unaffected.  No status is returned for it: the
+ * call does not wait for the device. */
 int64_t gim_gp_solve_ws_bytes(int B, int n, int nrhs);
 int gim_gp_solve(const float* K, const float* F, float* Xt, void* ws, int B, int n, int ldk, int nrhs, int npad,
                  gim_stream_t stream);
@@ -611,7 +614,8 @@ int gim_gp_solve(const float* K, const float* F, float* Xt, void* ws, int B, int
  * Cholesky and both products on the fp64 MFMA.  X (queries) / Y (supports): [B][n][ldx] fp32, d features per row; F [n][nrhs] fp32
  * (shared by all B directions); mu [B][n][ld_mu] fp32 = K_xy (K_yy + sigma I)^-1 F with K = exp((cos - 1) / T), cos = x.y / (|x||y| + eps)
  * (dkm.py:135-144, 340-370; roma.py:94-136).  The system's condition number (~2e4) turns the 1e-7 rounding of fp32 kernel entries
- * into ~1e-4 of mu; this entry point removes that term from the engine's side. */
+ * into ~1e-4 of mu; this entry point removes that term from the engine's side.  B <= 16.  As with gim_gp_solve, a direction whose
+ * K_yy + sigma I fails to factor (NaN or overflowed support features) has every element of mu[b] (n x nrhs) written as quiet NaN. */
 int64_t gim_gp_posterior_f64_ws_bytes(int B, int n, int d, int nrhs);
 int gim_gp_posterior_f64(const float* X, const float* Y, const float* F, float* mu, void* ws, int B, int n, int d, int ldx,
                          int nrhs, int ld_mu, float T, float eps, float sigma, gim_stream_t stream);

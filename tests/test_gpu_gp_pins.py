@@ -24,6 +24,7 @@ import torch
 
 import dkm_oracle as DO
 import roma_oracle as RO
+from gp_cases import ref_posterior as _fp64_posterior
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -33,16 +34,6 @@ def _rel(got, ref):
     got, ref = got.detach().float().cpu(), ref.detach().float().cpu()
     assert got.shape == ref.shape, (got.shape, ref.shape)
     return ((got - ref).abs().max() / ref.abs().max().clamp_min(1e-6)).item()
-
-
-def _fp64_posterior(xr, yr, fr, sigma=0.1, T=0.2, eps=1e-6):
-    """mu = K_xy (K_yy + sigma I)^-1 f in fp64 from fp32 feature rows [n, d] (cos kernel of dkm.py:135-144)"""
-    x, y, f = xr.double(), yr.double(), fr.double()
-    def k(a, b):
-        c = a @ b.T / (a.norm(dim=-1)[:, None] * b.norm(dim=-1)[None] + eps)
-        return ((c - 1.0) / T).exp()
-    Kyy = k(y, y) + sigma * torch.eye(y.shape[0], dtype=torch.float64)
-    return k(x, y) @ torch.linalg.solve(Kyy, f)
 
 
 # ------------------------------------------------------------------------------------------------------ gim_dkm
