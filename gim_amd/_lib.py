@@ -223,6 +223,8 @@ PROTOTYPES = {
     "gim_warp_perspective": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p] * 2 + [c_int] * 2 + [c_void_p]),
     # fundamental-matrix RANSAC step: seven-point solve and scoring in one launch (added within ABI revision 115)
     "gim_fundamental_step": (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_int, ctypes.c_double] + [c_void_p] * 4),
+    # essential-matrix RANSAC step: five-point solve and scoring in one launch (added within ABI revision 115)
+    "gim_essential_step": (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_int, ctypes.c_double] + [c_void_p] * 4),
 }
 
 

@@ -3,7 +3,7 @@
 //
 // gim_amd/pose.py draws the samples; a step uploads only its sample indices [B][K][7] and reads back models, flags and counts.  The
 // points stay on the device, as for csrc/ransac_score.hip and csrc/homography.hip; the final mask is gim_ransac_mask (the same Sampson
-// error).  The five-point solver (a 10 x 10 non-symmetric eigenproblem) stays on the host.
+// error).  The five-point solver (a 10 x 10 non-symmetric eigenproblem) is csrc/essential.hip.
 //
 // Replaces (reference file:line): the minimal solve and the scoring inside cv2.findFundamentalMat(mkpts0, mkpts1, ...) of demo.py:514-517
 // (FMEstimatorCallback::runKernel / run7Point and ::computeError of OpenCV's modules/calib3d/src/fundam.cpp, the inlier count of

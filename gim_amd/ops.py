@@ -1647,6 +1647,31 @@ def fundamental_step(x0, x1, idx, thr2, offsets=None):
     return models, valid.view(torch.bool), counts
 
 
+def essential_step(x0, x1, idx, thr2, offsets=None):
+    """Five-point essential matrices x1^T E x0 = 0 of the samples `idx`, solved and scored in one launch (gim_essential_step; fp64,
+    the arithmetic and validity rules of pose.five_point_ge / pose.sampson_error).  One pair: x0 / x1 fp64 [P,2] in normalised
+    camera coordinates, idx int32 [K,5] -> (models fp64 [K,10,3,3] of unit Frobenius norm, valid bool [K,10], counts int32 [K,10]):
+    up to ten models per sample, in the order of their roots.  B pairs: offsets int32 [B+1] over the concatenated points, idx
+    [B,K,5] relative to each pair's offset -> [B,K,10,3,3], [B,K,10], [B,K,10].  A rejected sample or an unused slot: zero model,
+    valid 0, count 0."""
+    _req_cuda(x0, x1, idx, offsets)
+    single = offsets is None
+    if idx.dtype != torch.int32 or idx.dim() != (2 if single else 3) or idx.shape[-1] != 5 or not idx.is_contiguous():
+        raise _lib.GimHipError(f"essential idx must be contiguous int32 {'[K,5]' if single else '[B,K,5]'}, got {idx.dtype} {tuple(idx.shape)}")
+    B, K = (1, idx.shape[0]) if single else idx.shape[:2]
+    offsets, P = _ransac_points(x0, x1, offsets, B)
+    if idx.device != x0.device:
+        raise _lib.GimHipError("essential idx and points are on different devices")
+    lead = tuple(idx.shape[:-1])
+    models = torch.zeros(*lead, 10, 3, 3, dtype=torch.float64, device=x0.device)
+    valid = torch.zeros(*lead, 10, dtype=torch.uint8, device=x0.device)
+    counts = torch.zeros(*lead, 10, dtype=torch.int32, device=x0.device)
+    if B * K and P:               # without points every index is outside its pair: nothing is valid
+        check(lib.gim_essential_step(_p(x0), _p(x1), _p(offsets), B, _p(idx), K, float(thr2), _p(models), _p(valid), _p(counts),
+                                     _stream()), "gim_essential_step")
+    return models, valid.view(torch.bool), counts
+
+
 def homography_mask(model, src, dst, thr2, offsets=None):
     """Inlier mask of one homography per pair (gim_homography_mask): model fp64 [3,3] (one pair) or [B,3,3] with offsets int32 [B+1]
     -> bool [Ptot], transfer_error(model of the point's pair) <= thr2."""

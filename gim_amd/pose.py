@@ -26,13 +26,16 @@ What is restated (OpenCV 4.x, modules/calib3d/src/five-point.cpp and ptsetreg.cp
   * the seven-point solver by elimination and a closed-form cubic (`seven_point_ge`), the arithmetic of the device step that solves
     and scores in one launch (`find_fundamental_mat(solve="device")`, `find_fundamental_mat_batch`, `verify_pairs`;
     csrc/fundamental.hip).  `seven_point` and the default path are unchanged.
+  * the five-point solver by elimination and a real QR iteration (`five_point_ge`), the arithmetic of the device step that solves
+    and scores in one launch (`find_essential_mat(solve="device")`, `find_essential_mat_batch(solve="device")`; csrc/essential.hip).
+    `five_point` and the default path are unchanged.
 
 Parity: UNPINNED against cv2 (no OpenCV here to record vectors from; sampling is random in both).  tests/test_pose_cpu.py pins
 the solvers on exact synthetic geometry (every ground-truth E / F is among the candidates to 1e-9, recovered poses within 1e-6
 of the truth on noise-free data, sub-degree on noisy data with 50 % outliers) and compares with cv2 under `importorskip`.
 Batched numpy: 250 samples (2 500 candidate models) are solved and scored per step.  Scoring was most of a step, and it can run on
-the GPU (`device=` / `DeviceScorer`, csrc/ransac_score.hip; sampling, the solvers, the iteration bound and recover_pose stay here,
-and the result for a seed is the host's).  Measured on one MI355X box (tools/bench_pose.py, profiles/r12_pose_score.txt; 2 000
+the GPU (`device=` / `DeviceScorer`, csrc/ransac_score.hip; sampling, the iteration bound and recover_pose stay here, and so do
+the solvers unless `solve="device"` is asked for; the result for a seed is then the host's).  Measured on one MI355X box (tools/bench_pose.py, profiles/r12_pose_score.txt; 2 000
 matches, 50 % outliers): one scoring step 53.6 ms on the host against 0.23 ms on the device, estimate_pose 242 ms per pair on the
 host against 53 ms with `device=`.
 """
@@ -327,6 +330,346 @@ def seven_point_ge(x0, x1, detail=False):
     return F, valid
 
 
+E5_RANK_EPS = 1e-12     # smallest fifth pivot of the 5 x 9 elimination, relative to the first
+E5_PIVOT_EPS = 1e-12    # smallest pivot of the 10 x 10 cubic block, relative to the largest |entry| of the 10 x 20 matrix
+E5_W_EPS = 1e-14        # smallest |v[9]| relative to max |v| of a root's null vector (five_point's 1e-14)
+E5_QR_EPS = 2.220446049250313e-16   # the deflation tests of the QR iteration
+E5_QR_ITS = 30          # QR sweeps allowed per eigenvalue; exceptional shifts at sweeps 10 and 20
+_E5_T12 = _T12.reshape(4, 4, -1).argmax(-1)          # (linear a) * (linear b) -> index in _MONO2: gim_e5_t12
+_E5_T23 = _T23.reshape(len(_MONO2), 4, 20).argmax(-1)   # (_MONO2 m) * (linear b) -> index in _MONO: gim_e5_t23
+
+
+def _e5_acc11(P2, sg, Bs, ca, cb):
+    """P2 [N, 10] += sg * e[ca] * e[cb], the entries of E as linear polynomials (Bs [N, 4, 9]): gim_e5_acc11"""
+    for a in range(4):
+        for b in range(4):
+            P2[:, _E5_T12[a, b]] += sg * (Bs[:, a, ca] * Bs[:, b, cb])
+
+
+def _e5_acc21(row, sg, P2, Bs, c):
+    """row [N, 20] += sg * P2 [N, 10] * e[c]: gim_e5_acc21"""
+    for m in range(10):
+        for b in range(4):
+            row[:, _E5_T23[m, b]] += sg * (P2[:, m] * Bs[:, b, c])
+
+
+def _e5_eigenvalues(act):
+    """gim_e5_eigenvalues on one 10 x 10 matrix (nested lists of Python floats: IEEE doubles, no contraction), statement by
+    statement: Householder reduction to Hessenberg form (EISPACK orthes), the real double-shift QR iteration (EISPACK hqr,
+    eigenvalues only) -> (real roots ascending, smallest |discriminant| of a 2 x 2 block relative to its scale, most sweeps
+    spent on one eigenvalue, all sweeps, converged)"""
+    import math
+    a = [list(map(float, r)) for r in act]
+    ort = [0.0] * 10
+    roots, disc, its_max, sweeps = [], math.inf, 0, 0
+    try:
+        for m in range(1, 9):
+            scale = 0.0
+            for i in range(m, 10):
+                scale += abs(a[i][m - 1])
+            if scale == 0.0:
+                continue
+            h = 0.0
+            for i in range(9, m - 1, -1):
+                ort[i] = a[i][m - 1] / scale
+                h += ort[i] * ort[i]
+            g = -math.copysign(math.sqrt(h), ort[m])
+            h -= ort[m] * g
+            ort[m] -= g
+            for j in range(m, 10):
+                f = 0.0
+                for i in range(9, m - 1, -1):
+                    f += ort[i] * a[i][j]
+                f /= h
+                for i in range(m, 10):
+                    a[i][j] -= f * ort[i]
+            for i in range(10):
+                f = 0.0
+                for j in range(9, m - 1, -1):
+                    f += ort[j] * a[i][j]
+                f /= h
+                for j in range(m, 10):
+                    a[i][j] -= f * ort[j]
+            a[m][m - 1] = scale * g
+            for i in range(m + 1, 10):
+                a[i][m - 1] = 0.0
+        anorm = 0.0
+        for i in range(10):
+            for j in range(max(i - 1, 0), 10):
+                anorm += abs(a[i][j])
+        if not math.isfinite(anorm):
+            return [], disc, 0, 0, False
+        nn, its, t = 9, 0, 0.0
+        for _ in range(10 * (E5_QR_ITS + 1)):
+            if nn < 0:
+                break
+            l = nn
+            while l > 0:
+                s = abs(a[l - 1][l - 1]) + abs(a[l][l])
+                if s == 0.0:
+                    s = anorm
+                if abs(a[l][l - 1]) <= E5_QR_EPS * s:
+                    a[l][l - 1] = 0.0
+                    break
+                l -= 1
+            x = a[nn][nn]
+            if l == nn:
+                roots.append(x + t)
+                nn, its = nn - 1, 0
+                continue
+            y = a[nn - 1][nn - 1]
+            ww = a[nn][nn - 1] * a[nn - 1][nn]
+            if l == nn - 1:
+                p = 0.5 * (y - x)
+                q = p * p + ww
+                z = math.sqrt(abs(q))
+                x += t
+                den = p * p + abs(ww)
+                disc = min(disc, abs(q) / den if den > 0.0 else 0.0)
+                if q >= 0.0:
+                    z = p + math.copysign(z, p)
+                    roots.append(x + z)
+                    roots.append(x - ww / z if z != 0.0 else x + z)
+                nn, its = nn - 2, 0
+                continue
+            if its == E5_QR_ITS:
+                return sorted(roots), disc, its_max, sweeps, False
+            if its in (10, 20):
+                t += x
+                for i in range(nn + 1):
+                    a[i][i] -= x
+                s = abs(a[nn][nn - 1]) + abs(a[nn - 1][nn - 2])
+                y = x = 0.75 * s
+                ww = -0.4375 * s * s
+            its += 1
+            sweeps += 1
+            its_max = max(its_max, its)
+            p = q = r = z = 0.0
+            m = nn - 2
+            while m >= l:
+                z = a[m][m]
+                r = x - z
+                s = y - z
+                p = (r * s - ww) / a[m + 1][m] + a[m][m + 1]
+                q = a[m + 1][m + 1] - z - r - s
+                r = a[m + 2][m + 1]
+                s = abs(p) + abs(q) + abs(r)
+                p, q, r = p / s, q / s, r / s
+                if m == l:
+                    break
+                u = abs(a[m][m - 1]) * (abs(q) + abs(r))
+                v = abs(p) * (abs(a[m - 1][m - 1]) + abs(z) + abs(a[m + 1][m + 1]))
+                if u <= E5_QR_EPS * v:
+                    break
+                m -= 1
+            for i in range(m, nn - 1):
+                a[i + 2][i] = 0.0
+                if i != m:
+                    a[i + 2][i - 1] = 0.0
+            for k in range(m, nn):
+                if k != m:
+                    p = a[k][k - 1]
+                    q = a[k + 1][k - 1]
+                    r = a[k + 2][k - 1] if k + 1 != nn else 0.0
+                    x = abs(p) + abs(q) + abs(r)
+                    if x != 0.0:
+                        p, q, r = p / x, q / x, r / x
+                s = math.copysign(math.sqrt(p * p + q * q + r * r), p)
+                if s == 0.0 or not math.isfinite(s):
+                    continue
+                if k == m:
+                    if l != m:
+                        a[k][k - 1] = -a[k][k - 1]
+                else:
+                    a[k][k - 1] = -s * x
+                p += s
+                x, y, z = p / s, q / s, r / s
+                q /= p
+                r /= p
+                ak, ak1 = a[k], a[k + 1]
+                ak2 = a[k + 2] if k + 1 != nn else None
+                for j in range(k, nn + 1):
+                    p = ak[j] + q * ak1[j]
+                    if ak2 is not None:
+                        p += r * ak2[j]
+                        ak2[j] -= p * z
+                    ak1[j] -= p * y
+                    ak[j] -= p * x
+                for i in range(l, min(nn, k + 3) + 1):
+                    ai = a[i]
+                    p = x * ai[k] + y * ai[k + 1]
+                    if ak2 is not None:
+                        p += z * ai[k + 2]
+                        ai[k + 2] -= p * r
+                    ai[k + 1] -= p * q
+                    ai[k] -= p
+        return sorted(roots), disc, its_max, sweeps, nn < 0
+    except (ZeroDivisionError, ValueError, OverflowError):   # where C++ goes on with an infinity or a NaN: no further roots
+        return sorted(r for r in roots if math.isfinite(r)), disc, its_max, sweeps, False
+
+
+def five_point_ge(x0, x1, detail=False):
+    """Essential matrices through 5 correspondences by elimination and a real QR iteration.  x0, x1: [N, 5, 2] normalised image points
+    (x1^T E x0 = 0) -> (E [N, 10, 3, 3] of unit Frobenius norm, valid [N, 10]), the models ordered by their root x ascending, an
+    unused or refused slot zero.  The arithmetic and the validity rules of gim_essential_step (include/gim_hip.h;
+    csrc/essential_solve.h is the same code for the device), batched over the samples, with one exception: the eigenvalue
+    iteration has a data-dependent course and runs sample by sample on Python floats (`_e5_eigenvalues`).
+      1. the 5 x 9 rows of `_epipolar_rows`, Gauss-Jordan with full pivoting; the four free columns give X, Y, Z, W.  Refused: an
+         input that is not finite, a fifth pivot below 1e-12 times the first (a repeated correspondence, coincident points);
+      2. the ten cubic constraints of `five_point` over `_MONO`, accumulated term by term in the order of the header;
+      3. Gauss-Jordan with partial pivoting on the cubic block -> [I | B].  Refused: a pivot below 1e-12 times the largest |entry|;
+      4. the action matrix of `five_point`; Hessenberg form by Householder reflections, eigenvalues by the real double-shift QR
+         iteration: at most 30 sweeps per eigenvalue, exceptional shifts at sweeps 10 and 20, a 2 x 2 block with a negative
+         discriminant is a complex pair (no models), no convergence leaves the slots not yet found invalid;
+      5. per real root the null vector v of Act - x I by Gauss-Jordan with full pivoting, (x, y, z) = v[6..8] / v[9], refused when
+         |v[9]| <= 1e-14 max |v|; E = x X + y Y + z Z + W over its norm, refused when that is zero or not finite.
+    detail=True adds a dict: ok_input, ok_rank, ok_pivot [N] (the three sample rules, each True where an earlier rule already
+    failed), rank_ratio [N] (fifth pivot / first), pivot_ratio [N] (smallest pivot of step 3 / largest |entry|), disc_rel [N]
+    (smallest |discriminant| of a 2 x 2 block relative to its scale; inf without such a block), gap_rel [N] (smallest gap between
+    two real roots relative to 1 + |x|; inf with fewer than two), w_ratio [N] (smallest |v[9]| / max |v| over the roots; inf
+    without a root), qr_its [N] (most sweeps spent on one eigenvalue), qr_sweeps [N] (all sweeps), qr_ok [N] (the iteration
+    converged), nroots [N], roots [N, 10] (NaN in an unused slot) -- what a test needs to see how far a sample is from a rule."""
+    x0 = np.asarray(x0, dtype=np.float64)
+    x1 = np.asarray(x1, dtype=np.float64)
+    n = x0.shape[0]
+    rows = np.arange(n)
+    with np.errstate(all="ignore"):
+        ok_input = np.isfinite(x0).all((1, 2)) & np.isfinite(x1).all((1, 2))
+        A = _epipolar_rows(x0, x1)                                              # [N, 5, 9]
+        alive = ok_input.copy()
+        rowof = np.full((n, 9), -1, dtype=np.int64)
+        first = last = np.zeros(n)
+        for k in range(5):
+            sub = np.abs(A[:, k:, :]).reshape(n, -1)
+            j = np.where(np.isnan(sub).any(1), 0, sub.argmax(1))                # argmax: the lowest row, then the lowest column
+            best = sub[rows, j]
+            pr, pc = j // 9 + k, j % 9
+            if k == 0:
+                first = best
+            alive &= np.isfinite(best) & (best > 0.0)
+            if k == 4:
+                last = best
+                alive &= best >= E5_RANK_EPS * first
+            tmp = A[rows, k].copy()
+            A[rows, k] = A[rows, pr]
+            A[rows, pr] = tmp
+            A[:, k] = A[:, k] / np.where(alive, A[rows, k, pc], 1.0)[:, None]
+            f = A[rows, :, pc]
+            f[:, k] = 0.0
+            A -= f[:, :, None] * A[:, None, k, :]
+            rowof[rows, pc] = k
+        ok_rank = alive | ~ok_input
+        free = np.argsort(rowof >= 0, axis=1, kind="stable")[:, :4]             # the four free columns, ascending
+        r = np.where(rowof >= 0, rowof, 0)
+        Bs = np.empty((n, 4, 9))
+        for k in range(4):
+            fk = free[:, k]
+            Bs[:, k] = np.where(rowof >= 0, -A[rows[:, None], r, fk[:, None]], 0.0)
+            Bs[rows, k, fk] = 1.0
+        Bs = np.where(alive[:, None, None], Bs, 0.0)
+        # the constraints
+        EEt = np.zeros((6, n, 10))
+        sym = lambda i, j: 3 * min(i, j) - (min(i, j) * (min(i, j) - 1)) // 2 + abs(j - i)   # noqa: E731
+        for i in range(3):
+            for j in range(i, 3):
+                for k in range(3):
+                    _e5_acc11(EEt[sym(i, j)], 1.0, Bs, 3 * i + k, 3 * j + k)
+        tr = (EEt[0] + EEt[3]) + EEt[5]
+        M = np.zeros((n, 10, 20))
+        for sg, (c1, c2, c3, c4), c in ((1.0, (4, 8, 5, 7), 0), (-1.0, (3, 8, 5, 6), 1), (1.0, (3, 7, 4, 6), 2)):
+            tmp = np.zeros((n, 10))
+            _e5_acc11(tmp, 1.0, Bs, c1, c2)
+            _e5_acc11(tmp, -1.0, Bs, c3, c4)
+            _e5_acc21(M[:, 0], sg, tmp, Bs, c)
+        for i in range(3):
+            for j in range(3):
+                row = M[:, 1 + 3 * i + j]
+                for k in range(3):
+                    _e5_acc21(row, 1.0, EEt[sym(i, k)], Bs, 3 * k + j)
+                row *= 2.0
+                _e5_acc21(row, -1.0, tr, Bs, 3 * i + j)
+        # [I | B]
+        mmax = np.abs(M).reshape(n, -1).max(1)
+        alive &= np.isfinite(M).all((1, 2)) & (mmax > 0.0)
+        minpiv = np.full(n, np.inf)
+        for k in range(10):
+            col = np.abs(M[:, k:, k])
+            pr = np.where(np.isnan(col).any(1), 0, col.argmax(1)) + k
+            best = col[rows, pr - k]
+            minpiv = np.fmin(minpiv, np.where(alive, best, np.inf))
+            alive &= np.isfinite(best) & (best >= E5_PIVOT_EPS * mmax)
+            tmp = M[rows, k, k:].copy()
+            M[rows, k, k:] = M[rows, pr, k:]
+            M[rows, pr, k:] = tmp
+            M[:, k, k:] = M[:, k, k:] / np.where(alive, M[:, k, k], 1.0)[:, None]
+            f = M[:, :, k].copy()
+            f[:, k] = 0.0
+            M[:, :, k:] -= f[:, :, None] * M[:, None, k, k:]
+        ok_pivot = alive | ~(ok_input & ok_rank)
+        Act = np.zeros((n, 10, 10))
+        Act[:, :6] = -M[:, :6, 10:]
+        Act[:, 6, 0] = Act[:, 7, 1] = Act[:, 8, 2] = Act[:, 9, 6] = 1.0
+        Act = np.where(alive[:, None, None], Act, 0.0)
+        # the eigenvalues, sample by sample
+        lam = np.full((n, 10), np.nan)
+        nroots = np.zeros(n, dtype=np.int64)
+        disc_rel, gap_rel = np.full(n, np.inf), np.full(n, np.inf)
+        qr_its, qr_sweeps, qr_ok = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.ones(n, dtype=bool)
+        for s in np.flatnonzero(alive):
+            rts, disc_rel[s], qr_its[s], qr_sweeps[s], qr_ok[s] = _e5_eigenvalues(Act[s].tolist())
+            nroots[s] = len(rts)
+            lam[s, :len(rts)] = rts
+            if len(rts) > 1:
+                rt = np.array(rts)
+                gap_rel[s] = (np.diff(rt) / (1.0 + np.abs(rt[:-1]))).min()
+        slot = np.arange(10)[None] < nroots[:, None]
+        # one system per root
+        S = np.broadcast_to(Act[:, None], (n, 10, 10, 10)).copy()
+        d = np.arange(10)
+        S[:, :, d, d] -= np.where(slot, lam, 0.0)[..., None]
+        NS = n * 10
+        S = S.reshape(NS, 10, 10)
+        srow = np.arange(NS)
+        sl = slot.reshape(NS).copy()
+        rof = np.full((NS, 10), -1, dtype=np.int64)
+        for k in range(9):
+            sub = np.abs(S[:, k:, :]).reshape(NS, -1)
+            j = np.where(np.isnan(sub).any(1), 0, sub.argmax(1))
+            best = sub[srow, j]
+            pr, pc = j // 10 + k, j % 10
+            sl &= np.isfinite(best) & (best > 0.0)
+            tmp = S[srow, k].copy()
+            S[srow, k] = S[srow, pr]
+            S[srow, pr] = tmp
+            S[:, k] = S[:, k] / np.where(sl, S[srow, k, pc], 1.0)[:, None]
+            f = S[srow, :, pc]
+            f[:, k] = 0.0
+            S -= f[:, :, None] * S[:, None, k, :]
+            rof[srow, pc] = k
+        fc = 9 - np.argmax((rof < 0)[:, ::-1], axis=1)                          # the free column (the last one, as the header takes it)
+        v = -S[srow[:, None], np.where(rof >= 0, rof, 0), fc[:, None]]
+        v[srow, fc] = 1.0
+        vmax = np.abs(v).max(1)
+        sl &= np.isfinite(vmax) & (np.abs(v[:, 9]) > E5_W_EPS * vmax)
+        w9 = np.where(sl, v[:, 9], 1.0)
+        x, y, z = (v[:, 6] / w9).reshape(n, 10, 1), (v[:, 7] / w9).reshape(n, 10, 1), (v[:, 8] / w9).reshape(n, 10, 1)
+        Em = ((x * Bs[:, None, 0] + y * Bs[:, None, 1]) + z * Bs[:, None, 2]) + Bs[:, None, 3]   # [N, 10, 9]
+        n2 = np.zeros((n, 10))
+        for i in range(9):
+            n2 = n2 + Em[..., i] * Em[..., i]
+        nrm = np.sqrt(n2)
+        valid = sl.reshape(n, 10) & np.isfinite(nrm) & (nrm > 0.0)
+        E = np.where(valid[..., None], Em / np.where(valid, nrm, 1.0)[..., None], 0.0).reshape(n, 10, 3, 3)
+    if detail:
+        with np.errstate(all="ignore"):
+            wr = np.where(slot, (np.abs(v[:, 9]) / vmax).reshape(n, 10), np.inf)
+            info = dict(ok_input=ok_input, ok_rank=ok_rank, ok_pivot=ok_pivot, rank_ratio=last / first, pivot_ratio=minpiv / mmax,
+                        disc_rel=disc_rel, gap_rel=gap_rel, w_ratio=np.where(np.isnan(wr), 0.0, wr).min(1), qr_its=qr_its,
+                        qr_sweeps=qr_sweeps, qr_ok=qr_ok, nroots=nroots, roots=lam)
+        return E, valid, info
+    return E, valid
+
+
 def sampson_error(M, x0, x1):
     """(x1^T M x0)^2 / (|M x0|_xy^2 + |M^T x1|_xy^2) for models M [..., 3, 3] and points [P, 2] -> [..., P]
     (EMEstimatorCallback::computeError / FMEstimatorCallback::computeError)"""
@@ -444,22 +787,49 @@ def _ransac(x0, x1, solver, m, thr, conf, max_iters, rng, s0=None, s1=None, batc
     return best_M, (error(best_M, x0, x1) <= thr2) if scorer is None else scorer.mask(best_M)
 
 
-def find_essential_mat(x0, x1, threshold, prob=0.999, max_iters=1000, seed=0, device=None):
+def find_essential_mat(x0, x1, threshold, prob=0.999, max_iters=1000, seed=0, device=None, solve="host"):
     """cv2.findEssentialMat(x0, x1, eye(3), method=RANSAC, prob, threshold) on normalised points -> (E [3,3] | None, mask [P]).
-    device: score the candidates on that GPU (`DeviceScorer`); same trajectory, model and mask as the host run of the same seed."""
+    solve="host": `five_point` (SVD null space, a linear solve, LAPACK's eigenvectors); device: score the candidates on that GPU
+    (`DeviceScorer`); same trajectory, model and mask as the host run of the same seed.
+    solve="device" (needs `device`): the same indices are drawn on the host and uploaded; models, flags and counts come from one
+    gim_essential_step per step (`DeviceEssential`: elimination and a real QR iteration; it rounds differently from `five_point`,
+    so its trajectory need not be the host's), the mask from gim_ransac_mask.
+    solve="ge" (host only): the same RANSAC over `five_point_ge`, the numpy restatement of the device solver -- its CPU oracle."""
+    if solve not in ("host", "device", "ge"):
+        raise ValueError(f"solve={solve!r}: host, device or ge")
+    if solve == "device" and device is None:
+        raise ValueError("solve='device' needs a device")
+    if solve == "ge" and device is not None:
+        raise ValueError("solve='ge' runs on the host: device must be None")
     x0 = np.ascontiguousarray(x0, dtype=np.float64)
     x1 = np.ascontiguousarray(x1, dtype=np.float64)
+    if solve == "ge":
+        return _ransac(x0, x1, five_point_ge, 5, threshold, prob, max_iters, np.random.default_rng(seed))
+    if solve == "device":
+        if x0.shape[0] < 5:
+            return None, np.zeros(x0.shape[0], dtype=bool)
+        dev = DeviceEssential(x0, x1, float(threshold) ** 2, device)
+        return _ransac(x0, x1, None, 5, threshold, prob, max_iters, np.random.default_rng(seed), scorer=dev, solve_idx=dev.solve)
     scorer = DeviceScorer(x0, x1, float(threshold) ** 2, device) if device is not None and x0.shape[0] >= 5 else None
     return _ransac(x0, x1, five_point, 5, threshold, prob, max_iters, np.random.default_rng(seed), scorer=scorer)
 
 
-def find_essential_mat_batch(pairs, threshold, prob=0.999, max_iters=1000, seed=0, device=None, scorer=None):
+def find_essential_mat_batch(pairs, threshold, prob=0.999, max_iters=1000, seed=0, device=None, scorer=None, solve="host"):
     """`find_essential_mat(x0, x1, threshold, prob, max_iters, seed)` for every (x0, x1) of `pairs`, run in lockstep: a step solves
     the samples of every unfinished pair on the host and scores all of them in ONE launch (ragged point sets through offsets); every
     pair has its own default_rng(seed) and its own shrinking iteration bound, so its result is that of the single call.
     scorer: an object like DeviceScorer over the concatenated points (counts(models [B,K,3,3], valid [B,K]) -> [B,K],
     mask(models [B,3,3]) -> bool [Ptot]); default DeviceScorer on `device`; neither: the pairs run one by one on the host.
+    solve="device" (needs `device`, takes no `scorer`): the lockstep run of `find_fundamental_mat_batch` over five-point samples --
+    a step uploads the sample indices of every unfinished pair and solves and scores all of them in ONE gim_essential_step launch;
+    a pair's result is that of find_essential_mat(..., device=device, solve="device").
     -> [(E [3,3] | None, mask [P_b] bool)] in the order of `pairs`."""
+    if solve not in ("host", "device"):
+        raise ValueError(f"solve={solve!r}: host or device")
+    if solve == "device":
+        if device is None or scorer is not None:
+            raise ValueError("solve='device' needs a device and takes no scorer")
+        return _lockstep_device(pairs, 5, 10, DeviceEssential, threshold, prob, max_iters, seed, device)
     pairs = [(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 2), np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 2)) for a, b in pairs]
     if scorer is None and device is None:
         return [find_essential_mat(a, b, threshold, prob, max_iters, seed) for a, b in pairs]
@@ -512,6 +882,8 @@ class DeviceFundamental:
     One pair: x0, x1 [P, 2], idx [K, 7].  Several pairs in lockstep: their points concatenated and `offsets` [B + 1]; `solve` then
     takes idx [B, K, 7] relative to each pair (an index of -1 marks padding) and `mask` one model per pair [B, 3, 3] -> bool [Ptot]."""
 
+    _step = "fundamental_step"
+
     def __init__(self, x0, x1, thr2, device, offsets=None):
         import torch
         from . import ops
@@ -527,7 +899,7 @@ class DeviceFundamental:
     def solve(self, idx):
         with self._torch.cuda.device(self.device):
             d_idx = self._torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(self.device)
-            models, valid, counts = self._ops.fundamental_step(self.x0, self.x1, d_idx, self.thr2, offsets=self.offsets)
+            models, valid, counts = getattr(self._ops, self._step)(self.x0, self.x1, d_idx, self.thr2, offsets=self.offsets)
             self._counts = counts.cpu().numpy().astype(np.int64)
             return models.cpu().numpy(), valid.cpu().numpy()
 
@@ -538,6 +910,13 @@ class DeviceFundamental:
         with self._torch.cuda.device(self.device):
             d_M = self._torch.from_numpy(np.ascontiguousarray(M, dtype=np.float64)).to(self.device)
             return self._ops.ransac_mask(d_M, self.x0, self.x1, self.thr2, offsets=self.offsets).cpu().numpy()
+
+
+class DeviceEssential(DeviceFundamental):
+    """A whole essential-matrix RANSAC step on the GPU, the twin of `DeviceFundamental` (csrc/essential.hip through
+    ops.essential_step; the mask through ops.ransac_mask): points in normalised camera coordinates, idx [K, 5] or [B, K, 5], up to
+    ten models per sample; `counts` are those of the launch that made the models."""
+    _step = "essential_step"
 
 
 def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, solve="host"):
@@ -585,24 +964,23 @@ def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, 
 
 
 class _DeferredSolve:
-    """The `solve_idx` hook of one pair of a lockstep run: it keeps the step's indices and hands out empty arrays, which the driver
-    fills in place from the launch that serves every pair before it sends the counts."""
+    """The `solve_idx` hook of one pair of a lockstep run: it keeps the step's indices and hands out empty arrays (k models per
+    sample), which the driver fills in place from the launch that serves every pair before it sends the counts."""
+
+    def __init__(self, k=3):
+        self.k = k
 
     def __call__(self, idx):
         self.idx = idx
-        self.models, self.valid = np.zeros((idx.shape[0], 3, 3, 3)), np.zeros((idx.shape[0], 3), dtype=bool)
+        self.models, self.valid = np.zeros((idx.shape[0], self.k, 3, 3)), np.zeros((idx.shape[0], self.k), dtype=bool)
         return self.models, self.valid
 
 
-def find_fundamental_mat_batch(pairs, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, solve="device"):
-    """`find_fundamental_mat(p0, p1, threshold, prob, max_iters, seed, device, solve="device")` for every (p0, p1) of `pairs`, run in
-    lockstep as find_essential_mat_batch runs its pairs: a step draws the samples of every unfinished pair on the host and solves and
-    scores all of them in ONE gim_fundamental_step launch (ragged point sets through offsets; a finished pair and the padding of a
-    shorter step are index -1: invalid); one gim_ransac_mask call for all pairs ends the run.  Every pair has its own
-    default_rng(seed) and its own shrinking iteration bound, so its result is that of the single call.
-    -> [(F [3,3] | None, mask [P_b] bool)] in the order of `pairs`."""
-    if solve != "device" or device is None:
-        raise ValueError("find_fundamental_mat_batch runs solve='device' on a device")
+def _lockstep_device(pairs, m, k, step_cls, threshold, prob, max_iters, seed, device):
+    """The lockstep driver of find_fundamental_mat_batch and find_essential_mat_batch(solve="device"): samples of m points, k models
+    per sample, `step_cls` (DeviceFundamental, DeviceEssential) over the concatenated points.  A step draws the samples of every
+    unfinished pair on the host and solves and scores all of them in ONE launch (ragged point sets through offsets; a finished pair
+    and the padding of a shorter step are index -1: invalid); one gim_ransac_mask call for all pairs ends the run."""
     pairs = [(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 2), np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 2)) for a, b in pairs]
     B = len(pairs)
     if B == 0:
@@ -611,9 +989,9 @@ def find_fundamental_mat_batch(pairs, threshold=1.0, prob=0.999999, max_iters=10
     best = [None] * B
     steps, hooks, pending = {}, {}, set()
     for b, (a, c) in enumerate(pairs):
-        if a.shape[0] >= 7:
-            hooks[b] = _DeferredSolve()
-            steps[b] = _ransac_steps(a.shape[0], None, 7, prob, max_iters, np.random.default_rng(seed), a, c, solve_idx=hooks[b])
+        if a.shape[0] >= m:
+            hooks[b] = _DeferredSolve(k)
+            steps[b] = _ransac_steps(a.shape[0], None, m, prob, max_iters, np.random.default_rng(seed), a, c, solve_idx=hooks[b])
 
     def advance(b, counts):
         try:
@@ -627,11 +1005,11 @@ def find_fundamental_mat_batch(pairs, threshold=1.0, prob=0.999999, max_iters=10
         advance(b, None)
     dev = None
     if pending:
-        dev = DeviceFundamental(np.concatenate([a for a, _ in pairs]), np.concatenate([b for _, b in pairs]), float(threshold) ** 2, device,
-                                offsets=offsets)
+        dev = step_cls(np.concatenate([a for a, _ in pairs]), np.concatenate([b for _, b in pairs]), float(threshold) ** 2, device,
+                       offsets=offsets)
     while pending:
         K = max(hooks[b].idx.shape[0] for b in pending)
-        idx = np.full((B, K, 7), -1, dtype=np.int32)
+        idx = np.full((B, K, m), -1, dtype=np.int32)
         for b in pending:
             idx[b, :hooks[b].idx.shape[0]] = hooks[b].idx
         models, valid = dev.solve(idx)
@@ -649,6 +1027,18 @@ def find_fundamental_mat_batch(pairs, threshold=1.0, prob=0.999999, max_iters=10
         masks = dev.mask(models)
     return [(best[b], masks[offsets[b]:offsets[b + 1]] if best[b] is not None else np.zeros(offsets[b + 1] - offsets[b], dtype=bool))
             for b in range(B)]
+
+
+def find_fundamental_mat_batch(pairs, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, solve="device"):
+    """`find_fundamental_mat(p0, p1, threshold, prob, max_iters, seed, device, solve="device")` for every (p0, p1) of `pairs`, run in
+    lockstep as find_essential_mat_batch runs its pairs: a step draws the samples of every unfinished pair on the host and solves and
+    scores all of them in ONE gim_fundamental_step launch (ragged point sets through offsets; a finished pair and the padding of a
+    shorter step are index -1: invalid); one gim_ransac_mask call for all pairs ends the run.  Every pair has its own
+    default_rng(seed) and its own shrinking iteration bound, so its result is that of the single call.
+    -> [(F [3,3] | None, mask [P_b] bool)] in the order of `pairs`."""
+    if solve != "device" or device is None:
+        raise ValueError("find_fundamental_mat_batch runs solve='device' on a device")
+    return _lockstep_device(pairs, 7, 3, DeviceFundamental, threshold, prob, max_iters, seed, device)
 
 
 def verify_pairs(pairs_of_points, threshold=1.0, device=None, prob=0.999999, max_iters=10000, seed=0, batch=32):

@@ -9,7 +9,8 @@ Restates, without Lightning:
     working on dumps produced by this engine;
   * `tools/metrics.py:28-53,107-168` relative pose error and the RANSAC call -- RANSAC stays on the host as north_star
     prescribes: OpenCV when it imports (it does not in the build container), else gim_amd/pose.py (numpy five-point RANSAC +
-    recoverPose, the published algorithms behind the two cv2 calls).
+    recoverPose, the published algorithms behind the two cv2 calls; with `device=` the scoring, and with `solve="device"` also
+    the five-point solve, run on the GPU, one launch per RANSAC step).
 Pinned by `tests/test_zeb_cpu.py` against AUC values computed by the reference's own `analysis.py` on a
 sample of its shipped dumps (`oracle/make_golden_zeb.py`).
 """
@@ -130,17 +131,19 @@ def _normalise(kpts0, kpts1, K0, K1, thresh):
     return kpts0, kpts1, thresh / np.mean([K0[0, 0], K1[1, 1], K0[0, 0], K1[1, 1]])
 
 
-def estimate_pose(kpts0, kpts1, K0, K1, thresh=0.5, conf=0.99999, device=None):
+def estimate_pose(kpts0, kpts1, K0, K1, thresh=0.5, conf=0.99999, device=None, solve="host"):
     """tools/metrics.py:77-103 (findEssentialMat RANSAC + recoverPose).  OpenCV when it imports (the reference's own call),
     otherwise the numpy restatement of the same two OpenCV routines in gim_amd/pose.py (`GIM_POSE_BACKEND` forces one).
     device: on the numpy backend, score the RANSAC candidates on that GPU (pose.DeviceScorer; same result as the host run);
-    sampling, the five-point solver and recoverPose stay on the host.  OpenCV ignores it."""
+    sampling, the five-point solver and recoverPose stay on the host.  solve: the `solve` of pose.find_essential_mat on the numpy
+    backend -- "device" also solves the five-point samples on `device` (one gim_essential_step per RANSAC step; sampling and
+    recoverPose stay on the host), "ge" is its host oracle.  OpenCV ignores both."""
     from . import pose
     if len(kpts0) < 5:
         return None
     kpts0, kpts1, ransac_thr = _normalise(kpts0, kpts1, K0, K1, thresh)
     if pose.backend() == "numpy":
-        E, mask = pose.find_essential_mat(kpts0, kpts1, ransac_thr, prob=conf, device=device)
+        E, mask = pose.find_essential_mat(kpts0, kpts1, ransac_thr, prob=conf, device=device, solve=solve)
         if E is None:
             return None
         n, R, t, _ = pose.recover_pose(E, kpts0, kpts1, 1e9, mask=mask)
@@ -173,16 +176,19 @@ def _np(x):
     return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
 
 
-def device_estimator(device, thresh=0.5, conf=0.99999):
-    """`estimate=` hook of evaluate_batch / run_scene: estimate_pose with the RANSAC candidates scored on `device`"""
-    return lambda a, b, k0, k1: estimate_pose(a, b, k0, k1, thresh, conf, device=device)
+def device_estimator(device, thresh=0.5, conf=0.99999, solve="host"):
+    """`estimate=` hook of evaluate_batch / run_scene: estimate_pose with the RANSAC candidates scored on `device`
+    (solve="device": solved there too)"""
+    return lambda a, b, k0, k1: estimate_pose(a, b, k0, k1, thresh, conf, device=device, solve=solve)
 
 
-def device_batch_estimator(device, thresh=0.5, conf=0.99999):
+def device_batch_estimator(device, thresh=0.5, conf=0.99999, solve="host"):
     """`estimate_batch=` hook of evaluate_batch / run_scene: the pairs of a batch through pose.find_essential_mat_batch -- their
     RANSAC loops advance in lockstep and every step scores all pairs' candidates in one launch on `device`.  Needs one threshold
     for the batch, so pairs whose intrinsics give another normalised threshold (and every pair when OpenCV is the backend) go through
-    estimate_pose one by one.  pairs: [(kpts0, kpts1, K0, K1)] -> [(R, t, inliers) | None], equal to estimate_pose on each pair."""
+    estimate_pose one by one.  pairs: [(kpts0, kpts1, K0, K1)] -> [(R, t, inliers) | None], equal to estimate_pose on each pair.
+    solve="device": every step also solves all pairs' samples in that launch (pose.find_essential_mat_batch(solve="device")); the
+    results equal estimate_pose(..., device=device, solve="device") on each pair."""
     from . import pose
 
     def estimate_batch(pairs):
@@ -195,7 +201,7 @@ def device_batch_estimator(device, thresh=0.5, conf=0.99999):
                 a, b, thr = _normalise(a, b, k0, k1, thresh)
                 groups.setdefault(float(thr), []).append((i, a, b))
         for thr, members in groups.items():
-            found = pose.find_essential_mat_batch([(a, b) for _, a, b in members], thr, prob=conf, device=device)
+            found = pose.find_essential_mat_batch([(a, b) for _, a, b in members], thr, prob=conf, device=device, solve=solve)
             for (i, a, b), (E, mask) in zip(members, found):
                 if E is not None:
                     n, R, t, _ = pose.recover_pose(E, a, b, 1e9, mask=mask)

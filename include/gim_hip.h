@@ -997,7 +997,7 @@ int gim_warp_perspective(const void* src, int dtype, int B, int C, int Hs, int W
  * Fundamental-matrix RANSAC step: the seven-point minimal solve and the scoring of its models in one launch (added within ABI
  * revision 115: no existing structure or prototype changed with it).  The reference calls cv2.findFundamentalMat(mkpts0, mkpts1,
  * ...) (demo.py:514-517).  Sampling and the iteration bound stay on the host (gim_amd/pose.py); the final mask is gim_ransac_mask,
- * the same Sampson error.  The five-point solver (a 10 x 10 non-symmetric eigenproblem) stays on the host.
+ * the same Sampson error.  The five-point solver (a 10 x 10 non-symmetric eigenproblem) is gim_essential_step, below.
  * ====================================================================================================== */
 
 /* K seven-point samples per pair, solved AND scored in ONE launch, B pairs; a sample gives up to three models.  All pointers are
@@ -1033,6 +1033,52 @@ int gim_warp_perspective(const void* src, int dtype, int B, int C, int Hs, int W
  * not 8-byte or an int32 array not 4-byte aligned, B > 65535, B * K * 27 > INT32_MAX. */
 int gim_fundamental_step(const double* x0, const double* x1, const int32_t* offsets, int B, const int32_t* idx, int K, double thr2,
                          double* models, uint8_t* valid, int32_t* counts, gim_stream_t stream);
+
+/* ======================================================================================================
+ * Essential-matrix RANSAC step: the five-point minimal solve and the scoring of its models in one launch (added within ABI
+ * revision 115: no existing structure or prototype changed with it).  The reference calls cv2.findEssentialMat(kpts0, kpts1,
+ * np.eye(3), threshold, prob, method=cv2.RANSAC) (tools/metrics.py:88-89).  Sampling, the iteration bound and recoverPose stay on
+ * the host (gim_amd/pose.py); the final mask is gim_ransac_mask, the same Sampson error.
+ * ====================================================================================================== */
+
+/* K five-point samples per pair, solved AND scored in ONE launch, B pairs; a sample gives up to ten models.  All pointers are
+ * DEVICE memory.  x0, x1 fp64 [Ptot][2] (16-byte aligned), the points of the pairs concatenated, in normalised camera coordinates
+ * (they are used as they are: no Hartley normalisation, as in pose.five_point); offsets int32 [B + 1], non-decreasing: pair b owns
+ * the points offsets[b] .. offsets[b + 1] (trusted, as in gim_ransac_score: the caller checks them); idx int32 [B][K][5]: the sample's
+ * five point indices RELATIVE to the pair's offset.  fp64 throughout, real arithmetic only, no fast-math, every loop bounded.  The
+ * model is x1^T E x0 = 0 (pose.five_point_ge is this arithmetic in numpy, csrc/essential_solve.h the code):
+ *   1. null space: the 5 x 9 rows (u x, u y, u, v x, v y, v, x, y, 1) of the correspondences (x, y) -> (u, v) (the column order of
+ *      pose._epipolar_rows) are reduced by Gauss-Jordan elimination with FULL pivoting, as in gim_fundamental_step.  A coordinate
+ *      that is not finite, a zero pivot, or a fifth pivot below 1e-12 times the first (a repeated correspondence, coincident points)
+ *      refuses the sample.  The four free columns f0 < f1 < f2 < f3 give the basis X, Y, Z, W: 1 in its own free column, 0 in the
+ *      other free columns, minus the reduced row's entry of its free column in each pivot column;
+ *   2. constraints: det E = 0 and the nine entries of 2 E E^T E - tr(E E^T) E on E = x X + y Y + z Z + W, as coefficients over the
+ *      20 monomials of pose._MONO, rows in the order pose.five_point stacks them.  E E^T (six polynomials of degree 2) and the 2 x 2
+ *      minors are sums of products of two entries, each product accumulated over the 16 coefficient pairs in row-major order; a
+ *      row is the sum of its (degree 2) x (entry) products, each accumulated over the 40 coefficient pairs in row-major order;
+ *      a row of the second kind is doubled before tr(E E^T) e_ij is subtracted;
+ *   3. reduction: Gauss-Jordan with PARTIAL pivoting (the first row of the largest magnitude) on the 10 x 10 block of the cubic
+ *      monomials gives [I | B].  A pivot below 1e-12 times the largest |entry| of the 10 x 20 matrix, or an entry that is not
+ *      finite, refuses the sample;
+ *   4. eigenvalues: the 10 x 10 action matrix of multiplication by x on (x2, xy, xz, y2, yz, z2, x, y, z, 1) -- rows 0 .. 5 are
+ *      -B's, rows 6 .. 9 pick x2, xy, xz, x -- is brought to Hessenberg form by Householder reflections (EISPACK orthes) and its
+ *      eigenvalues found by the real Francis double-shift QR iteration (EISPACK hqr, eigenvalues only; deflation tests
+ *      |h| <= 2^-52 s): at most 30 sweeps per eigenvalue, exceptional shifts at sweeps 10 and 20.  A 2 x 2 block with a negative
+ *      discriminant is a complex pair and gives no model; if a sweep count runs out, the eigenvalues not yet found give none.  The
+ *      real eigenvalues, ascending, fill the slots 0, 1, ...;
+ *   5. models: per real eigenvalue x the null vector v of (action matrix - x I) by Gauss-Jordan elimination with full pivoting
+ *      (nine steps, the free column is 1); a zero pivot or |v[9]| <= 1e-14 max |v| refuses the slot (pose.five_point's rule);
+ *      (x, y, z) = v[6..8] / v[9]; E = ((x X + y Y) + z Z) + W over its Frobenius norm; a norm that is zero or not finite
+ *      refuses the slot.
+ * An index outside [0, the pair's point count) or a repeated index invalidates the whole sample and never becomes an address.
+ * models fp64 [B][K][10][3][3] row-major, valid uint8 [B][K][10] and counts int32 [B][K][10] are FULLY written (no memset by the
+ * caller; no atomics: one workgroup owns one sample): an invalid or unused slot holds a zero matrix, valid 0 and count 0; a valid
+ * one the number of the pair's points with
+ *   err = (x1^T E x0)^2 / max(|E x0|_xy^2 + |E^T x1|_xy^2, 1e-300) <= thr2     (the arithmetic and operation order of gim_ransac_score).
+ * B == 0 or K == 0 returns without touching anything.  Refused before a launch: a NULL pointer, x0 / x1 not 16-byte aligned, models
+ * not 8-byte or an int32 array not 4-byte aligned, B > 65535, B * K * 90 > INT32_MAX. */
+int gim_essential_step(const double* x0, const double* x1, const int32_t* offsets, int B, const int32_t* idx, int K, double thr2,
+                       double* models, uint8_t* valid, int32_t* counts, gim_stream_t stream);
 
 #ifdef __cplusplus
 }
