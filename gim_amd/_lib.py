@@ -225,6 +225,9 @@ PROTOTYPES = {
     "gim_fundamental_step": (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_int, ctypes.c_double] + [c_void_p] * 4),
     # essential-matrix RANSAC step: five-point solve and scoring in one launch (added within ABI revision 115)
     "gim_essential_step": (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_int, ctypes.c_double] + [c_void_p] * 4),
+    # RANSAC on the device: the sampler and the per-step reduction to record samples (added within ABI revision 115)
+    "gim_ransac_sample": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, ctypes.c_uint64, c_void_p, c_void_p]),
+    "gim_ransac_records": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 2),
 }
 
 

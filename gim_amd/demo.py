@@ -145,13 +145,19 @@ def build(model_name, weights=None, precision=None, device="cuda", dinov2_weight
 
 
 @torch.no_grad()
-def match_pair(model_name, model, detector, path0, path1, device="cuda", resize_max=None, num=5000, ransac_solve="host"):
+def match_pair(model_name, model, detector, path0, path1, device="cuda", resize_max=None, num=5000, ransac_solve="host",
+               ransac_sampler="host"):
     """demo.py:405-511 -> dict(mkpts0_f, mkpts1_f, mconf, m_bids, hw0_i, hw1_i); coordinates in pixels of the pre-processed images
     for the dense matchers and gim_loftr (as the reference leaves them), of the original images for gim_lightglue (:499-500).
     ransac_solve="device": the seven-point solve of the geometry filter runs on the matches' device too, fused with the scoring
-    (pose.find_fundamental_mat(solve="device"); `ransac_backend` is then "device"); "host" is the path described below."""
+    (pose.find_fundamental_mat(solve="device"); `ransac_backend` is then "device"); "host" is the path described below.
+    ransac_sampler: the `sampler` of pose.find_fundamental_mat on the numpy and device backends -- "host" (default_rng, the default),
+    "philox" (the counter-based draw, made on the host) or "device" (drawn and reduced on the GPU; needs ransac_solve="device").
+    OpenCV draws its own samples."""
     if ransac_solve not in ("host", "device"):
         raise ValueError(f"ransac_solve={ransac_solve!r}: host or device")
+    if ransac_sampler not in ("host", "philox", "device") or (ransac_sampler == "device" and ransac_solve != "device"):
+        raise ValueError(f"ransac_sampler={ransac_sampler!r}: host, philox or device, the last with ransac_solve='device'")
     image0, scale0 = preprocess(read_image(path0), resize_max=resize_max)
     image1, scale1 = preprocess(read_image(path1), resize_max=resize_max)
     image0, image1 = image0.to(device)[None], image1.to(device)[None]
@@ -191,7 +197,8 @@ def match_pair(model_name, model, detector, path0, path1, device="cuda", resize_
         if out["ransac_backend"] == "device":
             # solved and scored on the matches' device, one launch per RANSAC step (pose.DeviceFundamental)
             out["F"], out["inliers"] = pose.find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000,
-                                                                 device=kpts0.device if kpts0.is_cuda else None, solve="device")
+                                                                 device=kpts0.device if kpts0.is_cuda else None, solve="device",
+                                                                 sampler=ransac_sampler)
         elif out["ransac_backend"] == "cv2":
             import cv2
             out["F"], mask = cv2.findFundamentalMat(p0, p1, cv2.USAC_MAGSAC, ransacReprojThreshold=1.0, confidence=0.999999, maxIters=10000)
@@ -199,27 +206,28 @@ def match_pair(model_name, model, detector, path0, path1, device="cuda", resize_
         else:
             # the seven-point candidates are scored on the model's device (pose.DeviceScorer), the solver stays on the host
             out["F"], mask = pose.find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000,
-                                                       device=kpts0.device if kpts0.is_cuda else None)
+                                                       device=kpts0.device if kpts0.is_cuda else None, sampler=ransac_sampler)
             out["inliers"] = mask
     return out
 
 
-def compute_geom(out, device=None, ransac_solve="host"):
+def compute_geom(out, device=None, ransac_solve="host", ransac_sampler="host"):
     """demo.py:180-227 on the dict of `match_pair` -> {"Fundamental": F [3,3] | None, "Homography": H [3,3] | None}, or {} for
     fewer than 8 matches (the reference's 2 x DEFAULT_MIN_NUM_MATCHES).  "Fundamental" is the model the robust-fitting step of
     `match_pair` found (`out["F"]`: pose.find_fundamental_mat's on the numpy backend, cv2's when cv2 filtered; computed here with
     pose.find_fundamental_mat when the dict has none).  "Homography" maps image 1 onto image 0, the reference's argument order and
     parameters: pose.find_homography(mkpts1, mkpts0, 1.0, 0.999999, 10000, device=device) -- on `device` the four-point solve and the
     scoring are one launch per RANSAC step, device=None is the host path.  ransac_solve: the `solve` of pose.find_fundamental_mat
-    when the fundamental matrix is computed here ("device" needs `device`)."""
+    when the fundamental matrix is computed here ("device" needs `device`).  ransac_sampler: the `sampler` of both calls ("device"
+    needs `device`, and ransac_solve="device" when the fundamental matrix is computed here)."""
     from . import pose
     p0 = np.asarray(out["mkpts0_f"].detach().float().cpu().numpy() if torch.is_tensor(out["mkpts0_f"]) else out["mkpts0_f"], dtype=np.float64)
     p1 = np.asarray(out["mkpts1_f"].detach().float().cpu().numpy() if torch.is_tensor(out["mkpts1_f"]) else out["mkpts1_f"], dtype=np.float64)
     if len(p0) < 8:
         return {}
     F = out["F"] if "F" in out else pose.find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, device=device,
-                                                                   solve=ransac_solve)[0]
-    H, _ = pose.find_homography(p1, p0, 1.0, 0.999999, 10000, device=device)
+                                                                   solve=ransac_solve, sampler=ransac_sampler)[0]
+    H, _ = pose.find_homography(p1, p0, 1.0, 0.999999, 10000, device=device, sampler=ransac_sampler)
     return {"Fundamental": None if F is None else np.asarray(F, dtype=np.float64), "Homography": H}
 
 
@@ -263,14 +271,20 @@ def main(argv=None):
     ap.add_argument("--out", default=None, help="directory for <name0>_<name1>_<model>_warp.png (image 0 beside image 1 warped by the homography)")
     ap.add_argument("--ransac-solve", choices=["host", "device"], default="host",
                     help="device: the seven-point solve of the geometry filter on the GPU, fused with the scoring (default: the host's solver)")
+    ap.add_argument("--ransac-sampler", choices=["host", "philox", "device"], default="host",
+                    help="who draws the RANSAC samples: numpy's default_rng (default), the counter-based draw on the host, or the same "
+                         "draw on the GPU with every step reduced there (device: needs --ransac-solve device)")
     args = ap.parse_args(argv)
+    if args.ransac_sampler == "device" and args.ransac_solve != "device":
+        ap.error("--ransac-sampler device needs --ransac-solve device")
     weights = args.weights
     if weights is None and args.model in CKPT and os.path.exists(join("weights", CKPT[args.model])):
         weights = join("weights", CKPT[args.model])
     if weights is None and args.model in CKPT:
         print(f"gim_amd.demo: no checkpoint ({join('weights', CKPT[args.model])} not found): running on the modules' seeded init")
     model, detector = build(args.model, weights, args.precision, dinov2_weights=args.dinov2_weights)
-    out = match_pair(args.model, model, detector, args.image0, args.image1, resize_max=args.resize_max, ransac_solve=args.ransac_solve)
+    out = match_pair(args.model, model, detector, args.image0, args.image1, resize_max=args.resize_max, ransac_solve=args.ransac_solve,
+                     ransac_sampler=args.ransac_sampler)
     n = len(out["mconf"])
     print(f"{args.model}: {n} matches" + (f", {int(out['inliers'].sum())} inliers ({out['ransac_backend']} RANSAC)" if "inliers" in out else " (fewer than 8: no RANSAC)"))
     for k in range(min(n, 5)):
@@ -278,7 +292,8 @@ def main(argv=None):
         print(f"  ({a[0]:8.2f}, {a[1]:8.2f}) <-> ({b[0]:8.2f}, {b[1]:8.2f})  conf {float(out['mconf'][k]):.4f}")
     if args.out is not None:     # demo.py:537-540
         kp = out["mkpts0_f"]
-        out["geom"] = compute_geom(out, device=kp.device if kp.is_cuda else None, ransac_solve=args.ransac_solve)
+        out["geom"] = compute_geom(out, device=kp.device if kp.is_cuda else None, ransac_solve=args.ransac_solve,
+                                   ransac_sampler=args.ransac_sampler)
         if out["geom"].get("Homography") is None:
             print("  no homography (fewer than 8 matches, or no sample with 4 inliers): no _warp.png")
         else:

@@ -1672,6 +1672,63 @@ def essential_step(x0, x1, idx, thr2, offsets=None):
     return models, valid.view(torch.bool), counts
 
 
+def _on(device, a, dtype):
+    """a tensor argument as it is, anything else (an int, a list, an array) as a tensor of `dtype` on `device`"""
+    return a if isinstance(a, torch.Tensor) else torch.as_tensor(np.atleast_1d(np.asarray(a)).astype(dtype), device=device)
+
+
+def ransac_sample(offsets_or_P, first, count, K, m, seed):
+    """The sample indices of one RANSAC step of B pairs, drawn on the device in one launch (gim_ransac_sample; the arithmetic of
+    pose.device_samples: Philox4x32-10 words, Floyd's m distinct draws, m in (4, 5, 7)).  offsets_or_P: offsets int32 [B+1] over the
+    concatenated points, or one pair's point count P; first int64 [B]: the ordinal of each pair's first sample of this step; count
+    int32 [B]: the samples each pair uses (tensors on the device, or ints / sequences, which are uploaded); seed: 64 unsigned bits.
+    -> idx int32 [B,K,m] ([K,m] for a point count): slot s of pair b is sample number first[b] + s of the pair's run; slots at or
+    beyond count[b], and every slot of a pair with fewer than m points, hold -1."""
+    K, m, seed = int(K), int(m), int(seed)
+    if m not in (4, 5, 7):
+        raise _lib.GimHipError(f"ransac_sample m={m}: 4, 5 or 7")
+    if not 0 <= seed < 1 << 64 or K < 0:
+        raise _lib.GimHipError(f"ransac_sample seed={seed} K={K}: a seed of 64 unsigned bits, K >= 0")
+    tensors = [t for t in (offsets_or_P, first, count) if isinstance(t, torch.Tensor)]
+    device = tensors[0].device if tensors else torch.device("cuda", torch.cuda.current_device())
+    single = not isinstance(offsets_or_P, torch.Tensor) and np.ndim(offsets_or_P) == 0
+    if single and not 0 <= int(offsets_or_P) < 1 << 31:
+        raise _lib.GimHipError(f"ransac_sample P={offsets_or_P}: 0 <= P < 2^31")
+    offsets = _on(device, [0, int(offsets_or_P)] if single else offsets_or_P, np.int32)
+    first, count = _on(device, first, np.int64), _on(device, count, np.int32)
+    _req_cuda(offsets, first, count)
+    B = offsets.shape[0] - 1
+    for t, dt, n, name in ((offsets, torch.int32, B + 1, "offsets"), (first, torch.int64, B, "first"), (count, torch.int32, B, "count")):
+        if t.dtype != dt or t.dim() != 1 or t.shape[0] != n or not t.is_contiguous() or t.device != device or n < 0:
+            raise _lib.GimHipError(f"ransac_sample {name} must be contiguous {dt} [{n}] on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    idx = torch.empty(B, K, m, dtype=torch.int32, device=device)
+    if idx.numel():
+        with torch.cuda.device(device):
+            check(lib.gim_ransac_sample(_p(offsets), B, _p(first), _p(count), K, m, seed, _p(idx), _stream()), "gim_ransac_sample")
+    return idx[0] if single else idx
+
+
+def ransac_records(counts, nb, floor):
+    """The samples of a RANSAC step that set a new strict maximum of the inlier count, found on the device (gim_ransac_records; the
+    rule of pose.step_records).  counts int32 [B,K,k], k in (1, 3, 10): the counts of homography_step / fundamental_step /
+    essential_step; nb int32 [B]: the samples in use; floor int32 [B]: the count to beat (tensors on the device, or ints / sequences,
+    which are uploaded).  -> rec int32 [B, 1 + 3 K]: rec[b, 0] = n_rec, then the triples (s, j_s, c_s) in ascending s; the words
+    beyond the last triple are unspecified."""
+    _req_cuda(counts)
+    if counts.dtype != torch.int32 or counts.dim() != 3 or counts.shape[2] not in (1, 3, 10) or not counts.is_contiguous():
+        raise _lib.GimHipError(f"ransac_records counts must be contiguous int32 [B,K,k], k in (1, 3, 10), got {counts.dtype} {tuple(counts.shape)}")
+    B, K, k = counts.shape
+    nb, floor = _on(counts.device, nb, np.int32), _on(counts.device, floor, np.int32)
+    for t, name in ((nb, "nb"), (floor, "floor")):
+        if t.dtype != torch.int32 or t.shape != (B,) or not t.is_contiguous() or t.device != counts.device:
+            raise _lib.GimHipError(f"ransac_records {name} must be contiguous int32 [{B}] on the counts' device, got {t.dtype} {tuple(t.shape)}")
+    rec = torch.empty(B, 1 + 3 * K, dtype=torch.int32, device=counts.device)
+    if B:
+        with torch.cuda.device(counts.device):
+            check(lib.gim_ransac_records(_p(counts), _p(nb), _p(floor), B, K, k, _p(rec), _stream()), "gim_ransac_records")
+    return rec
+
+
 def homography_mask(model, src, dst, thr2, offsets=None):
     """Inlier mask of one homography per pair (gim_homography_mask): model fp64 [3,3] (one pair) or [B,3,3] with offsets int32 [B+1]
     -> bool [Ptot], transfer_error(model of the point's pair) <= thr2."""

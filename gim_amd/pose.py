@@ -29,6 +29,11 @@ What is restated (OpenCV 4.x, modules/calib3d/src/five-point.cpp and ptsetreg.cp
   * the five-point solver by elimination and a real QR iteration (`five_point_ge`), the arithmetic of the device step that solves
     and scores in one launch (`find_essential_mat(solve="device")`, `find_essential_mat_batch(solve="device")`; csrc/essential.hip).
     `five_point` and the default path are unchanged.
+  * `sampler=`: who draws the samples.  "host" (the default) is numpy's default_rng, as ever.  "philox" is a counter-based draw
+    (`device_samples`: Philox4x32-10 words, Floyd's m distinct indices) made on the host; "device" makes the same draw on the GPU
+    (csrc/ransac_sample.hip) and reduces every step there to the samples that set a new best count (csrc/ransac_records.hip,
+    `step_records`): nothing of a step is read back but those records and the 72 bytes of a newly best model.  Same seed, same
+    device: "device" and "philox" give the same model bytes and mask.  Neither walks the trajectory of "host".
 
 Parity: UNPINNED against cv2 (no OpenCV here to record vectors from; sampling is random in both).  tests/test_pose_cpu.py pins
 the solvers on exact synthetic geometry (every ground-truth E / F is among the candidates to 1e-9, recovered poses within 1e-6
@@ -723,22 +728,139 @@ class DeviceScorer:
             return self._ops.ransac_mask(self._up(M, np.float64), self.x0, self.x1, self.thr2, offsets=self.offsets).cpu().numpy()
 
 
-def _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch=250, solve_idx=None):
+# ---- counter-based sampling and the per-step reduction (csrc/ransac_sample.h, csrc/ransac_records.hip restated) -----------------
+SAMPLERS = ("host", "philox", "device")
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+_U32, _SH32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+RECORDS_FIRST_COPY = 32      # records per pair that the first device-to-host copy of a step carries
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11): counter [..., 4] and key [..., 2] of 32-bit words (broadcast against each
+    other) -> uint32 [..., 4].  uint64 products, the high and low halves taken by shift and mask."""
+    counter, key = np.asarray(counter, dtype=np.uint64), np.asarray(key, dtype=np.uint64)
+    c0, c1, c2, c3 = (counter[..., i] for i in range(4))
+    k0, k1 = key[..., 0], key[..., 1]
+    for _ in range(10):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2
+        c0, c1, c2, c3 = (p1 >> _SH32) ^ c1 ^ k0, p1 & _U32, (p0 >> _SH32) ^ c3 ^ k1, p0 & _U32
+        k0, k1 = (k0 + _PHILOX_W0) & _U32, (k1 + _PHILOX_W1) & _U32
+    return np.stack(np.broadcast_arrays(c0, c1, c2, c3), -1).astype(np.uint32)
+
+
+def _check_seed64(seed):
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed={seed}: the philox / device samplers take a seed of 64 unsigned bits")
+    return seed
+
+
+def device_samples(seed, first, n, P, m):
+    """The samples number first .. first + n - 1 of the run `seed` over P points, m in (4, 5, 7) indices each -> int32 [n, m]: what
+    gim_ransac_sample writes (csrc/ransac_sample.h), in numpy.  Sample number N (the 0-based ordinal over the whole run, modulo
+    2^64) depends on (seed, N, P, m) alone: r[0..7] = philox4x32((N & 0xffffffff, N >> 32, blk, 0), (seed & 0xffffffff, seed >> 32))
+    for blk = 0, 1; Floyd's algorithm with exactly m draws: j = P - m + i, t = (r[i] * (j + 1)) >> 32, out[i] = t unless t is
+    among out[:i], then j.  Distinct indices of [0, P); the set is uniform over the m-subsets up to the multiply-shift bias (a value
+    of [0, j] is off by at most (j + 1) / 2^32 relative: 5e-7 at P = 2 000); the order inside a sample is not uniform.
+    P < m: every index is -1."""
+    seed, n, P, m = _check_seed64(seed), int(n), int(P), int(m)
+    if m not in (4, 5, 7):
+        raise ValueError(f"m={m}: 4, 5 or 7")
+    if not 0 <= P < 1 << 31 or n < 0:
+        raise ValueError(f"P={P}, n={n}: 0 <= P < 2^31, n >= 0")
+    if P < m:
+        return np.full((n, m), -1, dtype=np.int32)
+    with np.errstate(over="ignore"):
+        N = np.uint64(int(first) & ((1 << 64) - 1)) + np.arange(n, dtype=np.uint64)          # wraps modulo 2^64
+    key = np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64)
+    ctr = np.zeros((n, 4), dtype=np.uint64)
+    ctr[:, 0], ctr[:, 1] = N & _U32, N >> _SH32
+    r = [philox4x32(ctr, key)]
+    if m > 4:
+        ctr[:, 2] = 1
+        r.append(philox4x32(ctr, key))
+    r = np.concatenate(r, 1).astype(np.uint64)
+    out = np.empty((n, m), dtype=np.int64)
+    for i in range(m):
+        j = P - m + i
+        t = ((r[:, i] * np.uint64(j + 1)) >> _SH32).astype(np.int64)
+        out[:, i] = np.where((out[:, :i] == t[:, None]).any(1), j, t)
+    return out.astype(np.int32)
+
+
+def step_records(counts, nb, floor):
+    """The samples of a step that set a new strict maximum -- what gim_ransac_records writes (csrc/ransac_records.hip), in numpy.
+    counts int [B, K, k], nb [B] (samples in use, clamped to [0, K]), floor [B] (the count to beat: max(best so far, m - 1)) ->
+    int32 [B, 1 + 3 K]: n_rec, then the triples (s, j_s, c_s) in ascending s with c_s = counts[b, s].max(), j_s = its argmax (the
+    lowest slot) and c_s > max(floor[b], c_0 .. c_{s-1}); zeros beyond the last triple (the device leaves those words unwritten)."""
+    counts = np.asarray(counts)
+    B, K, _ = counts.shape
+    out = np.zeros((B, 1 + 3 * K), dtype=np.int32)
+    for b in range(B):
+        n = min(max(int(nb[b]), 0), K)
+        c, j = counts[b, :n].max(1), counts[b, :n].argmax(1)
+        before = np.maximum.accumulate(np.concatenate([[int(floor[b])], c]))[:n]
+        s = np.flatnonzero(c > before)
+        out[b, 0] = len(s)
+        out[b, 1:1 + 3 * len(s)] = np.stack([s, j[s], c[s]], 1).reshape(-1)
+    return out
+
+
+class _RecordWalk:
+    """The bookkeeping of `_ransac_steps` for one pair, driven by a step's records instead of its counts: the same best count, the
+    same shrinking bound `niters` by the same formula, the same number of samples consumed.  `plan` says how many samples the next
+    step takes (0: the run is over) and what count a sample has to beat; `replay` takes the step's records [n_rec, 3] and returns
+    the (s, j) of the last one it accepted, or None.  A record is a sample above every earlier count of its step, so up to the
+    break point the records are exactly the samples the counts walk accepts; records beyond it (s > niters - done - 1) are ignored
+    as that walk never reaches them."""
+
+    def __init__(self, P, m, conf, max_iters, batch=250):
+        self.P, self.m, self.batch = int(P), int(m), int(batch)
+        self.lconf = np.log(max(1.0 - conf, 1e-300))
+        self.best_n, self.niters, self.done, self.nb = 0, int(max_iters), 0, 0
+
+    def plan(self):
+        self.nb = max(0, min(self.batch, self.niters - self.done))
+        return self.nb, max(self.best_n, self.m - 1)
+
+    def replay(self, records):
+        last = None
+        for s, j, c in records:
+            s, c = int(s), int(c)
+            if s >= self.nb or self.done + s >= self.niters:       # the walk broke at an earlier sample
+                break
+            self.best_n, last = c, (s, int(j))
+            den = 1.0 - (c / self.P) ** self.m
+            if den < 1e-12:
+                self.niters = min(self.niters, self.done + s + 1)
+            else:
+                self.niters = min(self.niters, max(self.done + s + 1, int(np.ceil(self.lconf / np.log(den)))))
+        self.done += self.nb
+        return last
+
+
+def _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch=250, solve_idx=None, draw=None):
     """The sampling / solving / bookkeeping half of RANSACPointSetRegistrator::run as a generator: every step yields its candidate
     models (Ms [nb * k, 3, 3], valid [nb * k]) and is sent their inlier counts [nb * k]; the generator's return value is the best
     model [3, 3] or None.  Who counts (the host, a device, one launch for many pairs in lockstep) is the driver's business.
     solve_idx: a hook that receives the step's sample indices idx [nb, m] and returns (Ms [nb, k, 3, 3], valid [nb, k]) in place of
     solver(s0[idx], s1[idx]) -- a solver that lives where the points already are (`DeviceHomography`, `DeviceFundamental`).  The
     arrays it returns are read only after the counts have been sent, so a lockstep driver may hand out empty ones and fill them in
-    place from one launch for many pairs (`find_fundamental_mat_batch`)."""
+    place from one launch for many pairs (`find_fundamental_mat_batch`).
+    draw: None draws from `rng` as ever; otherwise draw(first, nb) -> the samples number first .. first + nb - 1 of the run
+    (sampler="philox": `device_samples`) and `rng` is not used."""
     lconf = np.log(max(1.0 - conf, 1e-300))
     best_n, best_M = 0, None
     niters, done = int(max_iters), 0
     while done < niters:
         nb = min(batch, niters - done)
         # m distinct indices per sample: the m smallest of P random keys
-        idx = np.argsort(rng.random((nb, P)), axis=1)[:, :m] if P <= 4096 else \
-            np.stack([rng.choice(P, m, replace=False) for _ in range(nb)])
+        if draw is not None:
+            idx = draw(done, nb)
+        else:
+            idx = np.argsort(rng.random((nb, P)), axis=1)[:, :m] if P <= 4096 else \
+                np.stack([rng.choice(P, m, replace=False) for _ in range(nb)])
         Ms, valid = solver(s0[idx], s1[idx]) if solve_idx is None else solve_idx(idx)
         k = Ms.shape[1]
         Ms = Ms.reshape(-1, 3, 3)
@@ -760,12 +882,22 @@ def _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch=250, solve_i
     return best_M
 
 
-def _ransac(x0, x1, solver, m, thr, conf, max_iters, rng, s0=None, s1=None, batch=250, scorer=None, solve_idx=None, error=None):
+def _draw(sampler, seed, P, m):
+    """the `draw` hook of `_ransac_steps` for a `sampler`: None for "host" (default_rng), otherwise `device_samples` under `seed`"""
+    if sampler == "host":
+        return None
+    seed = _check_seed64(seed)
+    return lambda first, nb: device_samples(seed, first, nb, P, m)
+
+
+def _ransac(x0, x1, solver, m, thr, conf, max_iters, rng, s0=None, s1=None, batch=250, scorer=None, solve_idx=None, error=None,
+            draw=None):
     """RANSACPointSetRegistrator::run with `solver` on samples of m points; the error is evaluated on (x0, x1), the solver sees
     (s0, s1) when given (normalised copies of the same points).  `scorer`: None counts inliers and takes the final mask on the host
     (`_count_inliers`, `sampson_error`); otherwise an object with counts(Ms [K,3,3], valid [K]) -> int64 [K] and
     mask(M [3,3]) -> bool [P] over the same points and threshold (`DeviceScorer`).  solve_idx: the hook of `_ransac_steps`.
     error: the host error in place of `sampson_error`, error(Ms [..., 3, 3], x0, x1) -> [..., P] (`transfer_error`).
+    draw: the sampling hook of `_ransac_steps` (`_draw`).
     -> (model [3,3] or None, mask [P] bool)"""
     P = x0.shape[0]
     if P < m:
@@ -773,7 +905,7 @@ def _ransac(x0, x1, solver, m, thr, conf, max_iters, rng, s0=None, s1=None, batc
     s0 = x0 if s0 is None else s0
     s1 = x1 if s1 is None else s1
     thr2 = float(thr) ** 2
-    steps = _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch, solve_idx)
+    steps = _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch, solve_idx, draw)
     error = sampson_error if error is None else error
     try:
         Ms, valid = next(steps)
@@ -787,34 +919,41 @@ def _ransac(x0, x1, solver, m, thr, conf, max_iters, rng, s0=None, s1=None, batc
     return best_M, (error(best_M, x0, x1) <= thr2) if scorer is None else scorer.mask(best_M)
 
 
-def find_essential_mat(x0, x1, threshold, prob=0.999, max_iters=1000, seed=0, device=None, solve="host"):
+def find_essential_mat(x0, x1, threshold, prob=0.999, max_iters=1000, seed=0, device=None, solve="host", sampler="host"):
     """cv2.findEssentialMat(x0, x1, eye(3), method=RANSAC, prob, threshold) on normalised points -> (E [3,3] | None, mask [P]).
     solve="host": `five_point` (SVD null space, a linear solve, LAPACK's eigenvectors); device: score the candidates on that GPU
     (`DeviceScorer`); same trajectory, model and mask as the host run of the same seed.
     solve="device" (needs `device`): the same indices are drawn on the host and uploaded; models, flags and counts come from one
     gim_essential_step per step (`DeviceEssential`: elimination and a real QR iteration; it rounds differently from `five_point`,
     so its trajectory need not be the host's), the mask from gim_ransac_mask.
-    solve="ge" (host only): the same RANSAC over `five_point_ge`, the numpy restatement of the device solver -- its CPU oracle."""
+    solve="ge" (host only): the same RANSAC over `five_point_ge`, the numpy restatement of the device solver -- its CPU oracle.
+    sampler: "host" draws from default_rng(seed) (the default; every seeded result so far); "philox" draws `device_samples` on the
+    host, with any `solve` (with solve="ge" it is the CPU oracle of the next); "device" (needs `device` and solve="device") draws
+    on the GPU and reads back only each step's record samples (`_ransac_on_device`): same model bytes and mask as "philox" there."""
     if solve not in ("host", "device", "ge"):
         raise ValueError(f"solve={solve!r}: host, device or ge")
     if solve == "device" and device is None:
         raise ValueError("solve='device' needs a device")
     if solve == "ge" and device is not None:
         raise ValueError("solve='ge' runs on the host: device must be None")
+    _check_sampler(sampler, device, solve)
     x0 = np.ascontiguousarray(x0, dtype=np.float64)
     x1 = np.ascontiguousarray(x1, dtype=np.float64)
+    if sampler == "device":
+        return _ransac_on_device([(x0, x1)], DeviceEssential, threshold, prob, max_iters, seed, device)[0][0]
+    draw = _draw(sampler, seed, x0.shape[0], 5)
     if solve == "ge":
-        return _ransac(x0, x1, five_point_ge, 5, threshold, prob, max_iters, np.random.default_rng(seed))
+        return _ransac(x0, x1, five_point_ge, 5, threshold, prob, max_iters, np.random.default_rng(seed), draw=draw)
     if solve == "device":
         if x0.shape[0] < 5:
             return None, np.zeros(x0.shape[0], dtype=bool)
         dev = DeviceEssential(x0, x1, float(threshold) ** 2, device)
-        return _ransac(x0, x1, None, 5, threshold, prob, max_iters, np.random.default_rng(seed), scorer=dev, solve_idx=dev.solve)
+        return _ransac(x0, x1, None, 5, threshold, prob, max_iters, np.random.default_rng(seed), scorer=dev, solve_idx=dev.solve, draw=draw)
     scorer = DeviceScorer(x0, x1, float(threshold) ** 2, device) if device is not None and x0.shape[0] >= 5 else None
-    return _ransac(x0, x1, five_point, 5, threshold, prob, max_iters, np.random.default_rng(seed), scorer=scorer)
+    return _ransac(x0, x1, five_point, 5, threshold, prob, max_iters, np.random.default_rng(seed), scorer=scorer, draw=draw)
 
 
-def find_essential_mat_batch(pairs, threshold, prob=0.999, max_iters=1000, seed=0, device=None, scorer=None, solve="host"):
+def find_essential_mat_batch(pairs, threshold, prob=0.999, max_iters=1000, seed=0, device=None, scorer=None, solve="host", sampler="host"):
     """`find_essential_mat(x0, x1, threshold, prob, max_iters, seed)` for every (x0, x1) of `pairs`, run in lockstep: a step solves
     the samples of every unfinished pair on the host and scores all of them in ONE launch (ragged point sets through offsets); every
     pair has its own default_rng(seed) and its own shrinking iteration bound, so its result is that of the single call.
@@ -823,16 +962,20 @@ def find_essential_mat_batch(pairs, threshold, prob=0.999, max_iters=1000, seed=
     solve="device" (needs `device`, takes no `scorer`): the lockstep run of `find_fundamental_mat_batch` over five-point samples --
     a step uploads the sample indices of every unfinished pair and solves and scores all of them in ONE gim_essential_step launch;
     a pair's result is that of find_essential_mat(..., device=device, solve="device").
+    sampler: as in find_essential_mat, every pair's ordinals running from 0 under the shared seed ("device" needs solve="device").
     -> [(E [3,3] | None, mask [P_b] bool)] in the order of `pairs`."""
     if solve not in ("host", "device"):
         raise ValueError(f"solve={solve!r}: host or device")
+    _check_sampler(sampler, device, solve)
     if solve == "device":
         if device is None or scorer is not None:
             raise ValueError("solve='device' needs a device and takes no scorer")
-        return _lockstep_device(pairs, 5, 10, DeviceEssential, threshold, prob, max_iters, seed, device)
+        if sampler == "device":
+            return _ransac_on_device(pairs, DeviceEssential, threshold, prob, max_iters, seed, device)[0]
+        return _lockstep_device(pairs, 5, 10, DeviceEssential, threshold, prob, max_iters, seed, device, sampler)
     pairs = [(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 2), np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 2)) for a, b in pairs]
     if scorer is None and device is None:
-        return [find_essential_mat(a, b, threshold, prob, max_iters, seed) for a, b in pairs]
+        return [find_essential_mat(a, b, threshold, prob, max_iters, seed, sampler=sampler) for a, b in pairs]
     B = len(pairs)
     if B == 0:
         return []
@@ -844,7 +987,8 @@ def find_essential_mat_batch(pairs, threshold, prob=0.999, max_iters=1000, seed=
     steps, pending = {}, {}
     for b, (a, c) in enumerate(pairs):
         if a.shape[0] >= 5:
-            steps[b] = _ransac_steps(a.shape[0], five_point, 5, prob, max_iters, np.random.default_rng(seed), a, c)
+            steps[b] = _ransac_steps(a.shape[0], five_point, 5, prob, max_iters, np.random.default_rng(seed), a, c,
+                                     draw=_draw(sampler, seed, a.shape[0], 5))
 
     def advance(b, counts):
         try:
@@ -883,6 +1027,7 @@ class DeviceFundamental:
     takes idx [B, K, 7] relative to each pair (an index of -1 marks padding) and `mask` one model per pair [B, 3, 3] -> bool [Ptot]."""
 
     _step = "fundamental_step"
+    m, k = 7, 3              # points per sample, models per sample
 
     def __init__(self, x0, x1, thr2, device, offsets=None):
         import torch
@@ -906,6 +1051,12 @@ class DeviceFundamental:
     def counts(self, Ms, valid):
         return self._counts.reshape(-1) if self.offsets is None else self._counts
 
+    def step_on_device(self, idx):
+        """the step's launch alone, for `_ransac_on_device`: idx int32 [B, K, m] on the device -> (models [B, K, k, 3, 3], counts
+        int32 [B, K, k]) on the device; nothing is read back"""
+        models, _, counts = getattr(self._ops, self._step)(self.x0, self.x1, idx, self.thr2, offsets=self.offsets)
+        return models, counts
+
     def mask(self, M):
         with self._torch.cuda.device(self.device):
             d_M = self._torch.from_numpy(np.ascontiguousarray(M, dtype=np.float64)).to(self.device)
@@ -917,9 +1068,10 @@ class DeviceEssential(DeviceFundamental):
     ops.essential_step; the mask through ops.ransac_mask): points in normalised camera coordinates, idx [K, 5] or [B, K, 5], up to
     ten models per sample; `counts` are those of the launch that made the models."""
     _step = "essential_step"
+    m, k = 5, 10
 
 
-def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, solve="host"):
+def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, solve="host", sampler="host"):
     """Plain RANSAC over seven-point samples with the Sampson distance in pixels (the demo's geometry filter, demo.py:514-517;
     the reference's USAC_MAGSAC scoring is not restated).  -> (F [3,3] | None, mask [P])
     solve="host": `seven_point` (SVD null space, eigenvalues) on points Hartley-normalised once per call, the candidates mapped back
@@ -927,22 +1079,27 @@ def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, 
     solve="device" (needs `device`): the same indices are drawn on the host and uploaded; models, flags and counts come from one
     gim_fundamental_step per step (`DeviceFundamental`: elimination, a closed-form cubic, normalisation per sample; it rounds
     differently from `seven_point`, so its trajectory need not be the host's), the mask from gim_ransac_mask.
-    solve="ge" (host only): the same RANSAC over `seven_point_ge`, the numpy restatement of the device solver -- its CPU oracle."""
+    solve="ge" (host only): the same RANSAC over `seven_point_ge`, the numpy restatement of the device solver -- its CPU oracle.
+    sampler: "host", "philox" or "device", as in find_essential_mat ("device" needs `device` and solve="device")."""
     if solve not in ("host", "device", "ge"):
         raise ValueError(f"solve={solve!r}: host, device or ge")
     if solve == "device" and device is None:
         raise ValueError("solve='device' needs a device")
     if solve == "ge" and device is not None:
         raise ValueError("solve='ge' runs on the host: device must be None")
+    _check_sampler(sampler, device, solve)
     p0 = np.ascontiguousarray(p0, dtype=np.float64)
     p1 = np.ascontiguousarray(p1, dtype=np.float64)
+    if sampler == "device":
+        return _ransac_on_device([(p0, p1)], DeviceFundamental, threshold, prob, max_iters, seed, device)[0][0]
+    draw = _draw(sampler, seed, p0.shape[0], 7)
     if p0.shape[0] < 7:
         return None, np.zeros(p0.shape[0], dtype=bool)
     if solve == "ge":
-        return _ransac(p0, p1, seven_point_ge, 7, threshold, prob, max_iters, np.random.default_rng(seed))
+        return _ransac(p0, p1, seven_point_ge, 7, threshold, prob, max_iters, np.random.default_rng(seed), draw=draw)
     if solve == "device":
         dev = DeviceFundamental(p0, p1, float(threshold) ** 2, device)
-        return _ransac(p0, p1, None, 7, threshold, prob, max_iters, np.random.default_rng(seed), scorer=dev, solve_idx=dev.solve)
+        return _ransac(p0, p1, None, 7, threshold, prob, max_iters, np.random.default_rng(seed), scorer=dev, solve_idx=dev.solve, draw=draw)
 
     def norm_T(p):
         c = p.mean(0)
@@ -960,7 +1117,7 @@ def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, 
         return Fp / np.where(nrm > 0, nrm, 1.0)[..., None, None], v
 
     scorer = DeviceScorer(p0, p1, float(threshold) ** 2, device) if device is not None else None
-    return _ransac(p0, p1, solver, 7, threshold, prob, max_iters, np.random.default_rng(seed), s0=q0, s1=q1, scorer=scorer)
+    return _ransac(p0, p1, solver, 7, threshold, prob, max_iters, np.random.default_rng(seed), s0=q0, s1=q1, scorer=scorer, draw=draw)
 
 
 class _DeferredSolve:
@@ -976,7 +1133,7 @@ class _DeferredSolve:
         return self.models, self.valid
 
 
-def _lockstep_device(pairs, m, k, step_cls, threshold, prob, max_iters, seed, device):
+def _lockstep_device(pairs, m, k, step_cls, threshold, prob, max_iters, seed, device, sampler="host"):
     """The lockstep driver of find_fundamental_mat_batch and find_essential_mat_batch(solve="device"): samples of m points, k models
     per sample, `step_cls` (DeviceFundamental, DeviceEssential) over the concatenated points.  A step draws the samples of every
     unfinished pair on the host and solves and scores all of them in ONE launch (ragged point sets through offsets; a finished pair
@@ -991,7 +1148,8 @@ def _lockstep_device(pairs, m, k, step_cls, threshold, prob, max_iters, seed, de
     for b, (a, c) in enumerate(pairs):
         if a.shape[0] >= m:
             hooks[b] = _DeferredSolve(k)
-            steps[b] = _ransac_steps(a.shape[0], None, m, prob, max_iters, np.random.default_rng(seed), a, c, solve_idx=hooks[b])
+            steps[b] = _ransac_steps(a.shape[0], None, m, prob, max_iters, np.random.default_rng(seed), a, c, solve_idx=hooks[b],
+                                     draw=_draw(sampler, seed, a.shape[0], m))
 
     def advance(b, counts):
         try:
@@ -1029,25 +1187,99 @@ def _lockstep_device(pairs, m, k, step_cls, threshold, prob, max_iters, seed, de
             for b in range(B)]
 
 
-def find_fundamental_mat_batch(pairs, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, solve="device"):
+def _ransac_on_device(pairs, step_cls, threshold, prob, max_iters, seed, device, batch=250):
+    """sampler="device": the RANSAC runs of `pairs` in lockstep with sampling, solving, scoring and the reduction of every step on
+    the GPU.  A step is three launches of this library -- gim_ransac_sample, the step kernel of `step_cls` (DeviceHomography,
+    DeviceFundamental, DeviceEssential), gim_ransac_records -- fed by ONE upload of 4 B words (first as int64, count, floor) and
+    read by ONE copy of n_rec and the first RECORDS_FIRST_COPY triples of every pair (a second copy when some pair has more).  The
+    host replays the records (`_RecordWalk`: the rule and the bound of `_ransac_steps`) and reads the 72 bytes of a pair's model
+    only in a step that accepted a record of that pair; models, flags and counts are never read back in bulk.  A pair's ordinals run
+    from 0 under the shared seed: its result is that of the single call, and that of sampler="philox" on the same device.
+    Pairs with fewer than m points get (None, all-False) and, when no pair has more, nothing is launched.
+    -> ([(model [3,3] | None, mask [P_b] bool)], the step object or None -- `find_homography` takes its re-fit mask from it)"""
+    m, k = step_cls.m, step_cls.k
+    seed = _check_seed64(seed)
+    pairs = [(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 2), np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 2)) for a, b in pairs]
+    B = len(pairs)
+    offsets = np.concatenate([[0], np.cumsum([a.shape[0] for a, _ in pairs])]).astype(np.int64)
+    walks = {b: _RecordWalk(a.shape[0], m, prob, max_iters, batch) for b, (a, _) in enumerate(pairs) if a.shape[0] >= m}
+    best = [None] * B
+    none = [(None, np.zeros(offsets[b + 1] - offsets[b], dtype=bool)) for b in range(B)]
+    if not walks:
+        return none, None
+    import torch
+    from . import ops
+    dev = step_cls(np.concatenate([a for a, _ in pairs]), np.concatenate([b for _, b in pairs]), float(threshold) ** 2, device, offsets=offsets)
+    ctl = np.zeros(4 * B, dtype=np.int32)                       # [first as int64 | count | floor]: one upload per step
+    first, count, floor = ctl[:2 * B].view(np.int64), ctl[2 * B:3 * B], ctl[3 * B:]
+    head = 1 + 3 * RECORDS_FIRST_COPY
+    with torch.cuda.device(dev.device):
+        while True:
+            count[:] = 0
+            for b, w in walks.items():
+                first[b] = w.done
+                count[b], floor[b] = w.plan()
+            K = int(count.max())
+            if K == 0:
+                break
+            d_ctl = torch.from_numpy(ctl).to(dev.device)
+            d_count, d_floor = d_ctl[2 * B:3 * B], d_ctl[3 * B:]
+            idx = ops.ransac_sample(dev.offsets, d_ctl[:2 * B].view(torch.int64), d_count, K, m, seed)
+            models, counts = dev.step_on_device(idx)
+            rec = ops.ransac_records(counts.view(B, K, k), d_count, d_floor)
+            h = rec[:, :head].cpu().numpy()
+            if (h[:, 0] > RECORDS_FIRST_COPY).any():
+                h = np.concatenate([h, rec[:, head:].cpu().numpy()], 1)
+            models = models.view(B, K, k, 3, 3)
+            for b, w in walks.items():
+                if count[b]:
+                    hit = w.replay(h[b, 1:1 + 3 * h[b, 0]].reshape(-1, 3))
+                    if hit is not None:
+                        best[b] = models[b, hit[0], hit[1]].cpu().numpy()
+        found = [b for b in range(B) if best[b] is not None]
+        if not found:
+            return none, dev
+        M = np.zeros((B, 3, 3))
+        for b in found:
+            M[b] = best[b]
+        masks = np.asarray(dev.mask(M), dtype=bool)
+    return [(best[b], masks[offsets[b]:offsets[b + 1]]) if best[b] is not None else none[b] for b in range(B)], dev
+
+
+def _check_sampler(sampler, device, solve="device"):
+    """the `sampler=` rules shared by the entry points; raises before anything is launched"""
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler={sampler!r}: host, philox or device")
+    if sampler == "device" and (device is None or solve != "device"):
+        raise ValueError("sampler='device' draws and reduces on the GPU: it needs a device" + ("" if solve == "device" else " and solve='device'"))
+
+
+def find_fundamental_mat_batch(pairs, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, solve="device", sampler="host"):
     """`find_fundamental_mat(p0, p1, threshold, prob, max_iters, seed, device, solve="device")` for every (p0, p1) of `pairs`, run in
     lockstep as find_essential_mat_batch runs its pairs: a step draws the samples of every unfinished pair on the host and solves and
     scores all of them in ONE gim_fundamental_step launch (ragged point sets through offsets; a finished pair and the padding of a
     shorter step are index -1: invalid); one gim_ransac_mask call for all pairs ends the run.  Every pair has its own
     default_rng(seed) and its own shrinking iteration bound, so its result is that of the single call.
+    sampler: "philox" draws every pair's samples with `device_samples` on the host, "device" on the GPU, where each step is then
+    reduced to its record samples (`_ransac_on_device`); a pair's result is again that of the single call with that sampler.
     -> [(F [3,3] | None, mask [P_b] bool)] in the order of `pairs`."""
     if solve != "device" or device is None:
         raise ValueError("find_fundamental_mat_batch runs solve='device' on a device")
-    return _lockstep_device(pairs, 7, 3, DeviceFundamental, threshold, prob, max_iters, seed, device)
+    _check_sampler(sampler, device, solve)
+    if sampler == "device":
+        return _ransac_on_device(pairs, DeviceFundamental, threshold, prob, max_iters, seed, device)[0]
+    return _lockstep_device(pairs, 7, 3, DeviceFundamental, threshold, prob, max_iters, seed, device, sampler)
 
 
-def verify_pairs(pairs_of_points, threshold=1.0, device=None, prob=0.999999, max_iters=10000, seed=0, batch=32):
+def verify_pairs(pairs_of_points, threshold=1.0, device=None, prob=0.999999, max_iters=10000, seed=0, batch=32, sampler="host"):
     """Two-view verification of a pair list (the matches of a LightGlue / root_sift / dense pair list, in pixels) without OpenCV:
-    `find_fundamental_mat_batch` over `batch` pairs per launch sequence -> [(F [3,3] | None, mask [P_b] bool)] in the list's order."""
+    `find_fundamental_mat_batch` over `batch` pairs per launch sequence -> [(F [3,3] | None, mask [P_b] bool)] in the list's order.
+    sampler: that of find_fundamental_mat_batch."""
+    _check_sampler(sampler, device)
     pairs_of_points = list(pairs_of_points)
     out = []
     for i in range(0, len(pairs_of_points), int(batch)):
-        out += find_fundamental_mat_batch(pairs_of_points[i:i + int(batch)], threshold, prob, max_iters, seed, device)
+        out += find_fundamental_mat_batch(pairs_of_points[i:i + int(batch)], threshold, prob, max_iters, seed, device, sampler=sampler)
     return out
 
 
@@ -1190,9 +1422,11 @@ class DeviceHomography:
     """A whole homography RANSAC step on the GPU (csrc/homography.hip through ops.homography_step / ops.homography_mask): the points
     go to the device once; a step uploads only its sample indices and reads back models, flags and counts of ONE launch.  `solve`
     is the `solve_idx` hook of `_ransac_steps`, `counts` / `mask` the scorer interface of `_ransac` (the counts are those of the
-    launch that made the models)."""
+    launch that made the models).  offsets [B + 1] (several pairs, their points concatenated) serves `_ransac_on_device` alone:
+    `step_on_device` and `mask` (one model per pair [B, 3, 3]) honour it, `solve` is the single pair's."""
+    m, k = 4, 1
 
-    def __init__(self, src, dst, thr2, device):
+    def __init__(self, src, dst, thr2, device, offsets=None):
         import torch
         from . import ops
         self._torch, self._ops = torch, ops
@@ -1202,6 +1436,11 @@ class DeviceHomography:
         with torch.cuda.device(self.device):
             self.src = torch.from_numpy(np.ascontiguousarray(src, dtype=np.float64)).to(self.device)
             self.dst = torch.from_numpy(np.ascontiguousarray(dst, dtype=np.float64)).to(self.device)
+            self.offsets = None if offsets is None else torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int32)).to(self.device)
+
+    def step_on_device(self, idx):
+        models, _, counts = self._ops.homography_step(self.src, self.dst, idx, self.thr2, offsets=self.offsets)
+        return models, counts
 
     def solve(self, idx):
         with self._torch.cuda.device(self.device):
@@ -1216,10 +1455,10 @@ class DeviceHomography:
     def mask(self, M):
         with self._torch.cuda.device(self.device):
             d_M = self._torch.from_numpy(np.ascontiguousarray(M, dtype=np.float64)).to(self.device)
-            return self._ops.homography_mask(d_M, self.src, self.dst, self.thr2).cpu().numpy()
+            return self._ops.homography_mask(d_M, self.src, self.dst, self.thr2, offsets=self.offsets).cpu().numpy()
 
 
-def find_homography(src, dst, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None):
+def find_homography(src, dst, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, sampler="host"):
     """cv2.findHomography(src, dst, RANSAC, threshold, maxIters=max_iters, confidence=prob) restated: dst ~ H src
     -> (H [3, 3] with h33 = 1 | None, mask [P] bool).  Plain RANSAC over four-point samples with the forward transfer error in
     pixels; sampling and the shrinking iteration bound are `_ransac_steps`'.  Host path: `homography_4pt` and `transfer_error`.
@@ -1228,22 +1467,31 @@ def find_homography(src, dst, threshold=1.0, prob=0.999999, max_iters=10000, see
     RANSACPointSetRegistrator::run + findHomography do, the model is re-fitted on the inliers of the best sample (`homography_dlt`)
     and the mask taken once more with the re-fitted model; the re-fit is kept only if it does not lose inliers.  OpenCV's final
     Levenberg-Marquardt polish of the re-fit (HomographyRefineCallback) is NOT built, and neither is USAC_MAGSAC's scoring (the
-    reference's demo asks for it; the mask here is RANSAC's)."""
+    reference's demo asks for it; the mask here is RANSAC's).
+    sampler: "host", "philox" or "device", as in find_essential_mat ("device" needs `device`; the solve is the device's whenever
+    a device is given)."""
+    _check_sampler(sampler, device)
     src = np.ascontiguousarray(src, dtype=np.float64).reshape(-1, 2)
     dst = np.ascontiguousarray(dst, dtype=np.float64).reshape(-1, 2)
     P = src.shape[0]
+    draw = _draw(sampler, seed, P, 4)          # checks the seed of "philox" and "device" before P is looked at
     if P < 4:
         return None, np.zeros(P, dtype=bool)
     thr2 = float(threshold) ** 2
-    dev = DeviceHomography(src, dst, thr2, device) if device is not None else None
-    H, mask = _ransac(src, dst, homography_4pt, 4, threshold, prob, max_iters, np.random.default_rng(seed), scorer=dev,
-                      solve_idx=None if dev is None else dev.solve, error=transfer_error)
+    if sampler == "device":
+        found, dev = _ransac_on_device([(src, dst)], DeviceHomography, threshold, prob, max_iters, seed, device)
+        H, mask = found[0]
+    else:
+        dev = DeviceHomography(src, dst, thr2, device) if device is not None else None
+        H, mask = _ransac(src, dst, homography_4pt, 4, threshold, prob, max_iters, np.random.default_rng(seed), scorer=dev,
+                          solve_idx=None if dev is None else dev.solve, error=transfer_error, draw=draw)
     if H is None:
         return None, mask
     mask = np.asarray(mask, dtype=bool)
     H2 = homography_dlt(src[mask], dst[mask])
     if H2 is not None:
-        mask2 = (transfer_error(H2, src, dst) <= thr2) if dev is None else np.asarray(dev.mask(H2), dtype=bool)
+        mask2 = (transfer_error(H2, src, dst) <= thr2) if dev is None else \
+            np.asarray(dev.mask(H2 if dev.offsets is None else H2[None]), dtype=bool)
         if mask2.sum() >= mask.sum():
             H, mask = H2, mask2
     return H, mask

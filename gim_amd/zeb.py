@@ -131,19 +131,22 @@ def _normalise(kpts0, kpts1, K0, K1, thresh):
     return kpts0, kpts1, thresh / np.mean([K0[0, 0], K1[1, 1], K0[0, 0], K1[1, 1]])
 
 
-def estimate_pose(kpts0, kpts1, K0, K1, thresh=0.5, conf=0.99999, device=None, solve="host"):
+def estimate_pose(kpts0, kpts1, K0, K1, thresh=0.5, conf=0.99999, device=None, solve="host", sampler="host"):
     """tools/metrics.py:77-103 (findEssentialMat RANSAC + recoverPose).  OpenCV when it imports (the reference's own call),
     otherwise the numpy restatement of the same two OpenCV routines in gim_amd/pose.py (`GIM_POSE_BACKEND` forces one).
     device: on the numpy backend, score the RANSAC candidates on that GPU (pose.DeviceScorer; same result as the host run);
     sampling, the five-point solver and recoverPose stay on the host.  solve: the `solve` of pose.find_essential_mat on the numpy
     backend -- "device" also solves the five-point samples on `device` (one gim_essential_step per RANSAC step; sampling and
-    recoverPose stay on the host), "ge" is its host oracle.  OpenCV ignores both."""
+    recoverPose stay on the host), "ge" is its host oracle.  sampler: the `sampler` of pose.find_essential_mat -- "philox" draws
+    the counter-based samples on the host, "device" (needs `device` and solve="device") draws them on the GPU and reads back only
+    each step's record samples.  OpenCV ignores all three."""
     from . import pose
+    pose._check_sampler(sampler, device, solve)
     if len(kpts0) < 5:
         return None
     kpts0, kpts1, ransac_thr = _normalise(kpts0, kpts1, K0, K1, thresh)
     if pose.backend() == "numpy":
-        E, mask = pose.find_essential_mat(kpts0, kpts1, ransac_thr, prob=conf, device=device, solve=solve)
+        E, mask = pose.find_essential_mat(kpts0, kpts1, ransac_thr, prob=conf, device=device, solve=solve, sampler=sampler)
         if E is None:
             return None
         n, R, t, _ = pose.recover_pose(E, kpts0, kpts1, 1e9, mask=mask)
@@ -176,20 +179,24 @@ def _np(x):
     return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
 
 
-def device_estimator(device, thresh=0.5, conf=0.99999, solve="host"):
+def device_estimator(device, thresh=0.5, conf=0.99999, solve="host", sampler="host"):
     """`estimate=` hook of evaluate_batch / run_scene: estimate_pose with the RANSAC candidates scored on `device`
-    (solve="device": solved there too)"""
-    return lambda a, b, k0, k1: estimate_pose(a, b, k0, k1, thresh, conf, device=device, solve=solve)
+    (solve="device": solved there too; sampler: estimate_pose's)"""
+    from . import pose
+    pose._check_sampler(sampler, device, solve)
+    return lambda a, b, k0, k1: estimate_pose(a, b, k0, k1, thresh, conf, device=device, solve=solve, sampler=sampler)
 
 
-def device_batch_estimator(device, thresh=0.5, conf=0.99999, solve="host"):
+def device_batch_estimator(device, thresh=0.5, conf=0.99999, solve="host", sampler="host"):
     """`estimate_batch=` hook of evaluate_batch / run_scene: the pairs of a batch through pose.find_essential_mat_batch -- their
     RANSAC loops advance in lockstep and every step scores all pairs' candidates in one launch on `device`.  Needs one threshold
     for the batch, so pairs whose intrinsics give another normalised threshold (and every pair when OpenCV is the backend) go through
     estimate_pose one by one.  pairs: [(kpts0, kpts1, K0, K1)] -> [(R, t, inliers) | None], equal to estimate_pose on each pair.
     solve="device": every step also solves all pairs' samples in that launch (pose.find_essential_mat_batch(solve="device")); the
-    results equal estimate_pose(..., device=device, solve="device") on each pair."""
+    results equal estimate_pose(..., device=device, solve="device") on each pair.  sampler: that of
+    pose.find_essential_mat_batch and estimate_pose; the results equal estimate_pose's with the same sampler."""
     from . import pose
+    pose._check_sampler(sampler, device, solve)
 
     def estimate_batch(pairs):
         out = [None] * len(pairs)
@@ -201,7 +208,8 @@ def device_batch_estimator(device, thresh=0.5, conf=0.99999, solve="host"):
                 a, b, thr = _normalise(a, b, k0, k1, thresh)
                 groups.setdefault(float(thr), []).append((i, a, b))
         for thr, members in groups.items():
-            found = pose.find_essential_mat_batch([(a, b) for _, a, b in members], thr, prob=conf, device=device, solve=solve)
+            found = pose.find_essential_mat_batch([(a, b) for _, a, b in members], thr, prob=conf, device=device, solve=solve,
+                                                  sampler=sampler)
             for (i, a, b), (E, mask) in zip(members, found):
                 if E is not None:
                     n, R, t, _ = pose.recover_pose(E, a, b, 1e9, mask=mask)

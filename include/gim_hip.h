@@ -1080,6 +1080,44 @@ int gim_fundamental_step(const double* x0, const double* x1, const int32_t* offs
 int gim_essential_step(const double* x0, const double* x1, const int32_t* offsets, int B, const int32_t* idx, int K, double thr2,
                        double* models, uint8_t* valid, int32_t* counts, gim_stream_t stream);
 
+/* ======================================================================================================
+ * RANSAC on the device: the sampler and the reduction of a step to its record samples (added within ABI revision 115: no
+ * existing structure or prototype changed with it).  Together with one of the three step entry points above they make a RANSAC
+ * step three launches whose only host traffic is 3 B integers up and the records down; the reference draws its samples and keeps
+ * its best model inside OpenCV (RANSACPointSetRegistrator::run, cv::RNG), on the host.  Integer arithmetic only in both.
+ * ====================================================================================================== */
+
+/* The sample indices of one step of B pairs in ONE launch.  All pointers are DEVICE memory.  offsets int32 [B + 1], non-decreasing
+ * (trusted, as in gim_ransac_score): pair b has P_b = offsets[b + 1] - offsets[b] points; first int64 [B] (8-byte aligned): the
+ * ordinal of the pair's first sample of this step; count int32 [B]: the samples the pair uses this step; m in {4, 5, 7}.  Slot s
+ * of pair b holds sample number n = first[b] + s of the pair's run, a function of (seed, n, P_b, m) alone (csrc/ransac_sample.h is
+ * the code, pose.device_samples the numpy restatement):
+ *   words    Philox4x32-10, multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, key (seed & 0xffffffff,
+ *            seed >> 32), counter (n & 0xffffffff, n >> 32, blk, 0); r[0..7] = the four words of blk 0, then those of blk 1;
+ *   indices  Floyd's algorithm, exactly m draws, no retry: for i = 0 .. m-1: j = P_b - m + i, t = (r[i] * (j + 1)) >> 32;
+ *            idx[i] = t unless t occurs in idx[0 .. i-1], then idx[i] = j.  m distinct indices of [0, P_b); the set is uniform over
+ *            the m-subsets up to the multiply-shift bias, at most (j + 1) / 2^32 relative per draw; the order inside a sample is not
+ *            uniform.
+ * idx int32 [B][K][m] is FULLY written: slot s >= count[b], and every slot of a pair with P_b < m, holds -1 in all m places (the
+ * step entry points treat -1 as padding).  One lane per sample, plain per-lane stores, no atomics.  B == 0 or K == 0 returns
+ * without touching anything.  Refused before a launch: m outside {4, 5, 7}, a NULL pointer, first not 8-byte or an int32 array not
+ * 4-byte aligned, B > 65535, B * K * m > INT32_MAX. */
+int gim_ransac_sample(const int32_t* offsets, int B, const int64_t* first, const int32_t* count, int K, int m, uint64_t seed,
+                      int32_t* idx, gim_stream_t stream);
+
+/* The samples of a step that set a new strict maximum of the inlier count, per pair, in sample order: the only ones the RANSAC
+ * bookkeeping acts on.  All pointers are DEVICE memory.  counts int32 [B][K][k], k in {1, 3, 10}: the counts output of
+ * gim_homography_step / gim_fundamental_step / gim_essential_step; nb int32 [B]: the samples in use this step (clamped to [0, K]);
+ * floor_ int32 [B]: the count to beat, max(best so far, m - 1).  For s < nb[b]: c_s = the largest of the sample's k counts, j_s the
+ * lowest slot that holds it (numpy's argmax); s is a record iff c_s > max(floor_[b], c_0 .. c_{s-1}).
+ * rec int32 [B][1 + 3 K]: rec[b][0] = the number of records n_rec, then the triples (s, j_s, c_s) in ascending s; the words
+ * beyond the last triple are NOT written.  One workgroup per pair, prefix maximum and ordered compaction through wave shuffles and
+ * LDS, no atomics: the output does not depend on the launch shape.  (pose.step_records is the numpy restatement.)
+ * B == 0 returns without touching anything; K == 0 writes n_rec = 0.  Refused before a launch: k outside {1, 3, 10}, a NULL
+ * pointer, an array not 4-byte aligned, B > 65535, B * K * k or B * (1 + 3 K) > INT32_MAX. */
+int gim_ransac_records(const int32_t* counts, const int32_t* nb, const int32_t* floor_, int B, int K, int k, int32_t* rec,
+                       gim_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
