@@ -115,7 +115,11 @@ __global__ void grid_sample_kernel(const void* __restrict__ feat, const float* _
     // grid_sampler_unnormalize(align_corners=false): ((g + 1) * size - 1) / 2
     const float ix = ((gx + 1.f) * (float)w - 1.f) / 2.f, iy = ((gy + 1.f) * (float)h - 1.f) / 2.f;
     const float fx = floorf(ix), fy = floorf(iy);
-    const int x0 = (int)fx, y0 = (int)fy;
+    // Targets far outside the map (random weights) must not reach the int conversion: it saturates at INT_MAX, x0 + 1 wraps, and the
+    // compiler -- entitled to assume that it does not -- tests `xx < 0` as `x0 < -1` and `xx >= w` on the wrapped value: both pass and
+    // the tap is loaded 2^31 pixels away (a grid value of +1e9 on one axis, the other inside).  Every tap is out of range anyway
+    // (map sides <= 65536: gim_grid_sample)
+    const int x0 = (int)fminf(fmaxf(fx, -65536.f), 65536.f), y0 = (int)fminf(fmaxf(fy, -65536.f), 65536.f);
     const float wx1 = ix - fx, wx0 = (fx + 1.f) - ix, wy1 = iy - fy, wy0 = (fy + 1.f) - iy;
     const float wt[4] = {wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};
 #pragma unroll
@@ -841,6 +845,7 @@ extern "C" int GIM_FN(gim_grid_sample)(const void* feat, const float* grid_xy, v
     const int G = dtype == GIM_H16 ? 8 : 4;
     GIM_REQUIRE(feat && grid_xy && out && B > 0 && h > 0 && w > 0 && Ho > 0 && Wo > 0 && C > 0, "grid_sample: bad args");
     GIM_REQUIRE(C % G == 0 && ldf % G == 0 && ldo % G == 0, "grid_sample: C / strides must keep 16-byte groups (C=%d)", C);
+    GIM_REQUIRE(h <= 65536 && w <= 65536, "grid_sample: map %d x %d: sides up to 65536 (the kernel's clamp of far targets)", h, w);
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(nblocks((size_t)B * Ho * Wo * (C / G), 256));
     DISPATCH_BF(grid_sample_kernel, dtype == GIM_H16, grid, feat, grid_xy, out, B, h, w, Ho * Wo, C / G, ldf, ldo);

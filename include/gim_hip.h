@@ -575,7 +575,7 @@ int gim_resize_bilinear(const void* x, void* y, int B, int h, int w, int Ho, int
 int gim_resize_image(const float* x, void* y, int B, int C, int h, int w, int Ho, int Wo, int cpad, int b_off,
                      int out_dtype, gim_stream_t stream);
 /* F.grid_sample(bilinear, zeros padding, align_corners=False): feat [B,h,w,C] at grid [B,Ho,Wo,2] (x, y)
- * -- dkm.py:89. */
+ * -- dkm.py:89.  Any finite grid value is allowed (targets far outside the map give zeros); h, w <= 65536. */
 int gim_grid_sample(const void* feat, const float* grid_xy, void* out, int B, int h, int w, int Ho, int Wo, int C,
                     int ldf, int ldo, int dtype, gim_stream_t stream);
 /* disp_emb(flow - query_coords): 1x1 conv 2 -> E on the displacement field -- dkm.py:91-101. wgt [E][2]. */
