@@ -228,6 +228,8 @@ PROTOTYPES = {
     # RANSAC on the device: the sampler and the per-step reduction to record samples (added within ABI revision 115)
     "gim_ransac_sample": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, ctypes.c_uint64, c_void_p, c_void_p]),
     "gim_ransac_records": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 2),
+    # recoverPose on the device: decomposition of E, triangulation and cheirality counts in one launch (added within ABI revision 115)
+    "gim_recover_pose": (c_int, [c_void_p] * 4 + [c_int, c_void_p, ctypes.c_double] + [c_void_p] * 6),
 }
 
 

@@ -3,7 +3,7 @@
 //
 // gim_amd/pose.py draws the samples; a step uploads only its sample indices [B][K][5] and reads back models, flags and counts.  The
 // points stay on the device, as for csrc/ransac_score.hip, csrc/homography.hip and csrc/fundamental.hip; the final mask is
-// gim_ransac_mask (the same Sampson error).  recoverPose stays on the host.
+// gim_ransac_mask (the same Sampson error).  recoverPose is csrc/recover_pose.hip, on the same points.
 //
 // Replaces (reference file:line): the minimal solve and the scoring inside cv2.findEssentialMat(kpts0, kpts1, np.eye(3), threshold,
 // prob, method=cv2.RANSAC) of tools/metrics.py:88-89 (EMEstimatorCallback::runKernel and ::computeError of OpenCV's

@@ -1672,6 +1672,44 @@ def essential_step(x0, x1, idx, thr2, offsets=None):
     return models, valid.view(torch.bool), counts
 
 
+def recover_pose(E, x0, x1, mask=None, offsets=None, distance_thresh=1e9):
+    """cv2.recoverPose for one pair or a batch in one launch (gim_recover_pose; fp64, the arithmetic of pose.recover_pose_ge): E is
+    decomposed into its four (R, t) candidates, every match triangulated under each and tested for lying in front of both cameras
+    nearer than distance_thresh.  One pair: E fp64 [3,3], x0 / x1 fp64 [P,2] in normalised camera coordinates, mask bool / uint8 [P]
+    or None -> (n_good int32 [4] per candidate (R1,t), (R2,t), (R1,-t), (R2,-t); best int32 []: the first maximum; R fp64 [3,3]
+    and t fp64 [3] of the winner; mask_out bool [P]: good under the winner).  B pairs: E [B,3,3], offsets int32 [B+1] over the
+    concatenated points, mask [Ptot] -> [B,4], [B], [B,3,3], [B,3], [Ptot].  An E that is not finite or all zero: n_good 0,
+    best -1, zero R and t, mask_out False; a pair without points: n_good 0, best 0, the first candidate."""
+    _req_cuda(E, x0, x1, mask, offsets)
+    single = offsets is None
+    if E.dtype != torch.float64 or E.shape != ((3, 3) if single else (E.shape[0], 3, 3)) or not E.is_contiguous():
+        raise _lib.GimHipError(f"recover_pose E must be contiguous fp64 {'[3,3]' if single else '[B,3,3]'}, got {E.dtype} {tuple(E.shape)}")
+    B = 1 if single else E.shape[0]
+    offsets, P = _ransac_points(x0, x1, offsets, B)
+    if E.device != x0.device:
+        raise _lib.GimHipError("recover_pose E and points are on different devices")
+    if mask is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        if mask.dtype != torch.uint8 or mask.shape != (P,) or not mask.is_contiguous() or mask.device != x0.device:
+            raise _lib.GimHipError(f"recover_pose mask must be contiguous bool / uint8 [{P}] on the points' device")
+    dev = x0.device
+    R = torch.empty(B, 3, 3, dtype=torch.float64, device=dev)
+    t = torch.empty(B, 3, dtype=torch.float64, device=dev)
+    n_good = torch.empty(B, 4, dtype=torch.int32, device=dev)
+    best = torch.empty(B, dtype=torch.int32, device=dev)
+    mask_out = torch.empty(P, dtype=torch.uint8, device=dev)
+    if B:
+        # without points nothing reads x0, x1 or writes mask_out, but the entry point refuses a NULL pointer: 16 bytes stand in
+        pad = torch.empty(2, dtype=torch.float64, device=dev) if P == 0 else None
+        px0, px1, pm = (_p(pad),) * 3 if P == 0 else (_p(x0), _p(x1), _p(mask_out))
+        check(lib.gim_recover_pose(_p(E), px0, px1, _p(offsets), B, _p(mask) if mask is not None and P else None, float(distance_thresh),
+                                   _p(R), _p(t), _p(n_good), _p(best), pm, _stream()), "gim_recover_pose")
+    if single:
+        return n_good[0], best[0], R[0], t[0], mask_out.view(torch.bool)
+    return n_good, best, R, t, mask_out.view(torch.bool)
+
+
 def _on(device, a, dtype):
     """a tensor argument as it is, anything else (an int, a list, an array) as a tensor of `dtype` on `device`"""
     return a if isinstance(a, torch.Tensor) else torch.as_tensor(np.atleast_1d(np.asarray(a)).astype(dtype), device=device)

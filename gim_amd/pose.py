@@ -930,6 +930,12 @@ def find_essential_mat(x0, x1, threshold, prob=0.999, max_iters=1000, seed=0, de
     sampler: "host" draws from default_rng(seed) (the default; every seeded result so far); "philox" draws `device_samples` on the
     host, with any `solve` (with solve="ge" it is the CPU oracle of the next); "device" (needs `device` and solve="device") draws
     on the GPU and reads back only each step's record samples (`_ransac_on_device`): same model bytes and mask as "philox" there."""
+    return _find_essential(x0, x1, threshold, prob, max_iters, seed, device, solve, sampler)[:2]
+
+
+def _find_essential(x0, x1, threshold, prob, max_iters, seed, device, solve, sampler, step_kw=None):
+    """`find_essential_mat` -> (E | None, mask, the DeviceEssential of a solve="device" run that built one, else None);
+    step_kw: further keywords of DeviceEssential (recover=True: the pose comes down with the mask)"""
     if solve not in ("host", "device", "ge"):
         raise ValueError(f"solve={solve!r}: host, device or ge")
     if solve == "device" and device is None:
@@ -940,17 +946,82 @@ def find_essential_mat(x0, x1, threshold, prob=0.999, max_iters=1000, seed=0, de
     x0 = np.ascontiguousarray(x0, dtype=np.float64)
     x1 = np.ascontiguousarray(x1, dtype=np.float64)
     if sampler == "device":
-        return _ransac_on_device([(x0, x1)], DeviceEssential, threshold, prob, max_iters, seed, device)[0][0]
+        found, dev = _ransac_on_device([(x0, x1)], DeviceEssential, threshold, prob, max_iters, seed, device, step_kw=step_kw)
+        return found[0] + (dev,)
     draw = _draw(sampler, seed, x0.shape[0], 5)
     if solve == "ge":
-        return _ransac(x0, x1, five_point_ge, 5, threshold, prob, max_iters, np.random.default_rng(seed), draw=draw)
+        return _ransac(x0, x1, five_point_ge, 5, threshold, prob, max_iters, np.random.default_rng(seed), draw=draw) + (None,)
     if solve == "device":
         if x0.shape[0] < 5:
-            return None, np.zeros(x0.shape[0], dtype=bool)
-        dev = DeviceEssential(x0, x1, float(threshold) ** 2, device)
-        return _ransac(x0, x1, None, 5, threshold, prob, max_iters, np.random.default_rng(seed), scorer=dev, solve_idx=dev.solve, draw=draw)
+            return None, np.zeros(x0.shape[0], dtype=bool), None
+        dev = DeviceEssential(x0, x1, float(threshold) ** 2, device, **(step_kw or {}))
+        return _ransac(x0, x1, None, 5, threshold, prob, max_iters, np.random.default_rng(seed), scorer=dev, solve_idx=dev.solve,
+                       draw=draw) + (dev,)
     scorer = DeviceScorer(x0, x1, float(threshold) ** 2, device) if device is not None and x0.shape[0] >= 5 else None
-    return _ransac(x0, x1, five_point, 5, threshold, prob, max_iters, np.random.default_rng(seed), scorer=scorer, draw=draw)
+    return _ransac(x0, x1, five_point, 5, threshold, prob, max_iters, np.random.default_rng(seed), scorer=scorer, draw=draw) + (None,)
+
+
+RECOVERS = ("host", "device")
+
+
+def _check_recover(recover, device):
+    """the `recover=` rules shared by the entry points; raises before anything is launched"""
+    if recover not in RECOVERS:
+        raise ValueError(f"recover={recover!r}: host or device")
+    if recover == "device" and device is None:
+        raise ValueError("recover='device' runs gim_recover_pose: it needs a device")
+
+
+def find_essential_pose(x0, x1, threshold, prob=0.999, max_iters=1000, seed=0, device=None, solve="host", sampler="host",
+                        distance_thresh=1e9):
+    """`find_essential_mat` followed by recoverPose ON `device` (needs one) -> (E | None, mask, (n_good, R, t) | None): E and the
+    RANSAC mask are find_essential_mat's of the same arguments.  solve="device": gim_recover_pose runs on the points the RANSAC
+    left on the device, on gim_ransac_mask's output where it lies, and ONE copy brings the mask, R, t and the counts back
+    (`DeviceEssential(recover=True)`).  solve="host": E, the points and the mask are uploaded for the recover alone
+    (`recover_pose(device=)`).  Without a model nothing is launched for the recover."""
+    _check_recover("device", device)
+    E, mask, dev = _find_essential(x0, x1, threshold, prob, max_iters, seed, device, solve, sampler,
+                                   step_kw=dict(recover=True, distance_thresh=distance_thresh))
+    if E is None:
+        return None, mask, None
+    if dev is not None:
+        return E, mask, dev.pose_of(0)
+    return E, mask, recover_pose(E, x0, x1, distance_thresh, mask=mask, device=device)[:3]
+
+
+def find_essential_pose_batch(pairs, threshold, prob=0.999, max_iters=1000, seed=0, device=None, solve="host", sampler="host",
+                              distance_thresh=1e9):
+    """`find_essential_mat_batch` followed by recoverPose ON `device` for every pair with a model, in ONE gim_recover_pose launch ->
+    [(E | None, mask, (n_good, R, t) | None)]; a pair's result is find_essential_pose's.  solve="device": the launch runs on the
+    lockstep run's points and mask (one copy for the batch); solve="host": the pairs with a model are uploaded for it."""
+    _check_recover("device", device)
+    pairs = [(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 2), np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 2)) for a, b in pairs]
+    if solve == "device":
+        _check_sampler(sampler, device, solve)
+        kw = dict(recover=True, distance_thresh=distance_thresh)
+        if sampler == "device":
+            found, dev = _ransac_on_device(pairs, DeviceEssential, threshold, prob, max_iters, seed, device, step_kw=kw)
+        else:
+            found, dev = _lockstep_device(pairs, 5, 10, DeviceEssential, threshold, prob, max_iters, seed, device, sampler, step_kw=kw)
+        return [(E, mask, dev.pose_of(b) if E is not None else None) for b, (E, mask) in enumerate(found)]
+    found = find_essential_mat_batch(pairs, threshold, prob, max_iters, seed, device, solve=solve, sampler=sampler)
+    have = [b for b, (E, _) in enumerate(found) if E is not None]
+    out = [(E, mask, None) for E, mask in found]
+    if have:
+        import torch
+        from . import ops
+        offsets = np.concatenate([[0], np.cumsum([pairs[b][0].shape[0] for b in have])]).astype(np.int32)
+        with torch.cuda.device(torch.device(device)):
+            up = lambda a, dt: torch.from_numpy(np.array(a, dtype=dt, order="C")).to(device)   # noqa: E731  (a copy: `a` may be read-only)
+            n_good, best, R, t, _ = ops.recover_pose(up(np.stack([found[b][0] for b in have]), np.float64),
+                                                     up(np.concatenate([pairs[b][0] for b in have]), np.float64),
+                                                     up(np.concatenate([pairs[b][1] for b in have]), np.float64),
+                                                     mask=up(np.concatenate([found[b][1] for b in have]), np.uint8), offsets=up(offsets, np.int32),
+                                                     distance_thresh=distance_thresh)
+            n_good, best, R, t = n_good.cpu().numpy(), best.cpu().numpy(), R.cpu().numpy(), t.cpu().numpy()
+        for i, b in enumerate(have):
+            out[b] = found[b] + (((int(n_good[i, best[i]]) if best[i] >= 0 else 0), R[i], t[i]),)
+    return out
 
 
 def find_essential_mat_batch(pairs, threshold, prob=0.999, max_iters=1000, seed=0, device=None, scorer=None, solve="host", sampler="host"):
@@ -972,7 +1043,7 @@ def find_essential_mat_batch(pairs, threshold, prob=0.999, max_iters=1000, seed=
             raise ValueError("solve='device' needs a device and takes no scorer")
         if sampler == "device":
             return _ransac_on_device(pairs, DeviceEssential, threshold, prob, max_iters, seed, device)[0]
-        return _lockstep_device(pairs, 5, 10, DeviceEssential, threshold, prob, max_iters, seed, device, sampler)
+        return _lockstep_device(pairs, 5, 10, DeviceEssential, threshold, prob, max_iters, seed, device, sampler)[0]
     pairs = [(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 2), np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 2)) for a, b in pairs]
     if scorer is None and device is None:
         return [find_essential_mat(a, b, threshold, prob, max_iters, seed, sampler=sampler) for a, b in pairs]
@@ -1066,9 +1137,44 @@ class DeviceFundamental:
 class DeviceEssential(DeviceFundamental):
     """A whole essential-matrix RANSAC step on the GPU, the twin of `DeviceFundamental` (csrc/essential.hip through
     ops.essential_step; the mask through ops.ransac_mask): points in normalised camera coordinates, idx [K, 5] or [B, K, 5], up to
-    ten models per sample; `counts` are those of the launch that made the models."""
+    ten models per sample; `counts` are those of the launch that made the models.
+    recover=True: `mask` also runs recoverPose on the points held here (`recover`: gim_recover_pose takes gim_ransac_mask's output
+    where it lies) and brings the RANSAC mask, R, t, the four counts and the winner back in ONE copy; the poses are left in
+    `self.poses` = (n_good [B, 4], best [B], R [B, 3, 3], t [B, 3]) as numpy arrays (B = 1 for a single pair)."""
     _step = "essential_step"
     m, k = 5, 10
+
+    def __init__(self, x0, x1, thr2, device, offsets=None, recover=False, distance_thresh=1e9):
+        super().__init__(x0, x1, thr2, device, offsets)
+        self.recover_too, self.distance_thresh, self.poses = bool(recover), float(distance_thresh), None
+
+    def recover(self, models, masks=None):
+        """gim_recover_pose over the points and offsets held here: models fp64 [3,3] / [B,3,3] and masks bool / uint8 [Ptot] (or
+        None) on the device -> ops.recover_pose's tensors, on the device"""
+        return self._ops.recover_pose(models, self.x0, self.x1, mask=masks, offsets=self.offsets, distance_thresh=self.distance_thresh)
+
+    def mask(self, M):
+        if not self.recover_too:
+            return super().mask(M)
+        torch = self._torch
+        with torch.cuda.device(self.device):
+            d_M = torch.from_numpy(np.ascontiguousarray(M, dtype=np.float64)).to(self.device)
+            d_mask = self._ops.ransac_mask(d_M, self.x0, self.x1, self.thr2, offsets=self.offsets)
+            n_good, best, R, t, _ = self.recover(d_M, d_mask)
+            B = 1 if self.offsets is None else d_M.shape[0]
+            # one copy: [R | t] as bytes, [n_good | best] as bytes, the mask
+            down = torch.cat([torch.cat([R.reshape(B, 9), t.reshape(B, 3)], 1).reshape(-1).view(torch.uint8),
+                              torch.cat([n_good.reshape(B, 4), best.reshape(B, 1)], 1).reshape(-1).view(torch.uint8),
+                              d_mask.view(torch.uint8)]).cpu().numpy()
+        Rt = down[:96 * B].view(np.float64).reshape(B, 12)
+        nb = down[96 * B:116 * B].view(np.int32).reshape(B, 5)
+        self.poses = (nb[:, :4].copy(), nb[:, 4].copy(), Rt[:, :9].reshape(B, 3, 3).copy(), Rt[:, 9:].copy())
+        return down[116 * B:].view(bool).copy()
+
+    def pose_of(self, b=0):
+        """(n_good of the winner, R, t) of pair b after `mask`; an invalid model: (0, zero R, zero t)"""
+        n_good, best, R, t = self.poses
+        return (int(n_good[b, best[b]]) if best[b] >= 0 else 0), R[b], t[b]
 
 
 def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, solve="host", sampler="host"):
@@ -1133,15 +1239,16 @@ class _DeferredSolve:
         return self.models, self.valid
 
 
-def _lockstep_device(pairs, m, k, step_cls, threshold, prob, max_iters, seed, device, sampler="host"):
+def _lockstep_device(pairs, m, k, step_cls, threshold, prob, max_iters, seed, device, sampler="host", step_kw=None):
     """The lockstep driver of find_fundamental_mat_batch and find_essential_mat_batch(solve="device"): samples of m points, k models
     per sample, `step_cls` (DeviceFundamental, DeviceEssential) over the concatenated points.  A step draws the samples of every
     unfinished pair on the host and solves and scores all of them in ONE launch (ragged point sets through offsets; a finished pair
-    and the padding of a shorter step are index -1: invalid); one gim_ransac_mask call for all pairs ends the run."""
+    and the padding of a shorter step are index -1: invalid); one gim_ransac_mask call for all pairs ends the run.  step_kw: further keywords of `step_cls`.
+    -> ([(model | None, mask)], the step object or None)"""
     pairs = [(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 2), np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 2)) for a, b in pairs]
     B = len(pairs)
     if B == 0:
-        return []
+        return [], None
     offsets = np.concatenate([[0], np.cumsum([a.shape[0] for a, _ in pairs])]).astype(np.int64)
     best = [None] * B
     steps, hooks, pending = {}, {}, set()
@@ -1164,7 +1271,7 @@ def _lockstep_device(pairs, m, k, step_cls, threshold, prob, max_iters, seed, de
     dev = None
     if pending:
         dev = step_cls(np.concatenate([a for a, _ in pairs]), np.concatenate([b for _, b in pairs]), float(threshold) ** 2, device,
-                       offsets=offsets)
+                       offsets=offsets, **(step_kw or {}))
     while pending:
         K = max(hooks[b].idx.shape[0] for b in pending)
         idx = np.full((B, K, m), -1, dtype=np.int32)
@@ -1184,10 +1291,10 @@ def _lockstep_device(pairs, m, k, step_cls, threshold, prob, max_iters, seed, de
             models[b] = best[b]
         masks = dev.mask(models)
     return [(best[b], masks[offsets[b]:offsets[b + 1]] if best[b] is not None else np.zeros(offsets[b + 1] - offsets[b], dtype=bool))
-            for b in range(B)]
+            for b in range(B)], dev
 
 
-def _ransac_on_device(pairs, step_cls, threshold, prob, max_iters, seed, device, batch=250):
+def _ransac_on_device(pairs, step_cls, threshold, prob, max_iters, seed, device, batch=250, step_kw=None):
     """sampler="device": the RANSAC runs of `pairs` in lockstep with sampling, solving, scoring and the reduction of every step on
     the GPU.  A step is three launches of this library -- gim_ransac_sample, the step kernel of `step_cls` (DeviceHomography,
     DeviceFundamental, DeviceEssential), gim_ransac_records -- fed by ONE upload of 4 B words (first as int64, count, floor) and
@@ -1209,7 +1316,8 @@ def _ransac_on_device(pairs, step_cls, threshold, prob, max_iters, seed, device,
         return none, None
     import torch
     from . import ops
-    dev = step_cls(np.concatenate([a for a, _ in pairs]), np.concatenate([b for _, b in pairs]), float(threshold) ** 2, device, offsets=offsets)
+    dev = step_cls(np.concatenate([a for a, _ in pairs]), np.concatenate([b for _, b in pairs]), float(threshold) ** 2, device, offsets=offsets,
+                   **(step_kw or {}))
     ctl = np.zeros(4 * B, dtype=np.int32)                       # [first as int64 | count | floor]: one upload per step
     first, count, floor = ctl[:2 * B].view(np.int64), ctl[2 * B:3 * B], ctl[3 * B:]
     head = 1 + 3 * RECORDS_FIRST_COPY
@@ -1268,7 +1376,7 @@ def find_fundamental_mat_batch(pairs, threshold=1.0, prob=0.999999, max_iters=10
     _check_sampler(sampler, device, solve)
     if sampler == "device":
         return _ransac_on_device(pairs, DeviceFundamental, threshold, prob, max_iters, seed, device)[0]
-    return _lockstep_device(pairs, 7, 3, DeviceFundamental, threshold, prob, max_iters, seed, device, sampler)
+    return _lockstep_device(pairs, 7, 3, DeviceFundamental, threshold, prob, max_iters, seed, device, sampler)[0]
 
 
 def verify_pairs(pairs_of_points, threshold=1.0, device=None, prob=0.999999, max_iters=10000, seed=0, batch=32, sampler="host"):
@@ -1516,8 +1624,22 @@ def _triangulate(P0, P1, x0, x1):
     return vt[:, -1, :]
 
 
-def recover_pose(E, x0, x1, distance_thresh=1e9, mask=None):
-    """cv2.recoverPose(E, x0, x1, eye(3), distanceThresh, mask=mask) on normalised points -> (n_good, R, t, mask_out)"""
+def recover_pose(E, x0, x1, distance_thresh=1e9, mask=None, device=None):
+    """cv2.recoverPose(E, x0, x1, eye(3), distanceThresh, mask=mask) on normalised points -> (n_good, R, t, mask_out).
+    device: None runs here (LAPACK's SVDs); a device uploads E, the points and the mask and runs gim_recover_pose there
+    (ops.recover_pose: `recover_pose_ge`'s arithmetic, so R1 / R2 and the sign of t may be LAPACK's exchanged -- the same candidate
+    set); an invalid E gives (0, zero R, zero t, all-False)."""
+    if device is not None:
+        import torch
+        from . import ops
+        with torch.cuda.device(torch.device(device)):
+            up = lambda a, dt: torch.from_numpy(np.array(a, dtype=dt, order="C")).to(device)   # noqa: E731  (a copy: `a` may be read-only)
+            x0 = np.asarray(x0, dtype=np.float64).reshape(-1, 2)
+            m = None if mask is None else up(np.asarray(mask).ravel() > 0, np.uint8)
+            n, best, R, t, good = ops.recover_pose(up(E, np.float64), up(x0, np.float64), up(np.asarray(x1, dtype=np.float64).reshape(-1, 2), np.float64),
+                                                   mask=m, distance_thresh=distance_thresh)
+            k = int(best)
+            return (int(n[k]) if k >= 0 else 0), R.cpu().numpy(), t.cpu().numpy(), good.cpu().numpy()
     x0 = np.asarray(x0, dtype=np.float64)
     x1 = np.asarray(x1, dtype=np.float64)
     m_in = np.ones(x0.shape[0], dtype=bool) if mask is None else np.asarray(mask).ravel() > 0
@@ -1537,6 +1659,125 @@ def recover_pose(E, x0, x1, distance_thresh=1e9, mask=None):
     k = 0 if (n[0] >= n[1] and n[0] >= n[2] and n[0] >= n[3]) else 1 if (n[1] >= n[2] and n[1] >= n[3]) else 2 if n[2] >= n[3] else 3
     R, tt = cands[k]
     return n[k], R, tt, goods[k]
+
+
+# ---- recoverPose as the device computes it (csrc/recover_pose_solve.h) -----------------------------------------------------------
+RP_SWEEPS3 = 8           # cyclic Jacobi sweeps over E^T E
+RP_SWEEPS4 = 8           # cyclic Jacobi sweeps over A^T A of a point
+RP_W_TINY = 1e-300       # recover_pose's clamp of the homogeneous coordinate
+
+
+def _rp_jacobi(a, sweeps):
+    """gim_rp_jacobi3 / gim_rp_jacobi4 on a stack of symmetric matrices a [..., N, N] (only the upper triangle is read; it is changed
+    in place) -> (diagonal [..., N], eigenvectors as columns [..., N, N])"""
+    N = a.shape[-1]
+    v = np.broadcast_to(np.eye(N), a.shape).copy()
+    with np.errstate(all="ignore"):
+        for _ in range(sweeps):
+            for p in range(N):
+                for q in range(p + 1, N):
+                    apq = a[..., p, q].copy()
+                    go = apq != 0.0
+                    theta = (a[..., q, q] - a[..., p, p]) / (2.0 * np.where(go, apq, 1.0))
+                    t = np.where(theta < 0.0, -1.0, 1.0) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+                    t = np.where(go, t, 0.0)             # a skipped rotation is the identity: c = 1, s = tau = 0
+                    c = 1.0 / np.sqrt(t * t + 1.0)
+                    s = t * c
+                    tau = s / (1.0 + c)
+                    a[..., p, p] -= t * apq
+                    a[..., q, q] += t * apq
+                    a[..., p, q] = np.where(go, 0.0, apq)
+                    for r in range(N):
+                        if r in (p, q):
+                            continue
+                        ip, iq = ((r, p) if r < p else (p, r)), ((r, q) if r < q else (q, r))
+                        g, h = a[(..., *ip)].copy(), a[(..., *iq)].copy()
+                        a[(..., *ip)] = np.where(go, g - s * (h + tau * g), g)
+                        a[(..., *iq)] = np.where(go, h + s * (g - tau * h), h)
+                    g, h = v[..., p].copy(), v[..., q].copy()
+                    v[..., p] = np.where(go[..., None], g - s[..., None] * (h + tau[..., None] * g), g)
+                    v[..., q] = np.where(go[..., None], h + s[..., None] * (g - tau[..., None] * h), h)
+    return np.stack([a[..., i, i] for i in range(N)], -1), v
+
+
+def _rp_dot3(a, b):
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+def decompose_essential_ge(E):
+    """gim_rp_decompose in numpy -> the four candidates [(R, t)] in the order of `recover_pose`, or None for an E with an entry
+    that is not finite or all zero.  cv::decomposeEssentialMat with a fixed-sweep Jacobi SVD: det U = det V = +1 by construction."""
+    E = np.asarray(E, dtype=np.float64).reshape(3, 3)
+    big = np.abs(E).max() if np.isfinite(E).all() else 0.0
+    if not big > 0.0:
+        return None
+    e = E / big
+    a = np.array([[(e[0, i] * e[0, j] + e[1, i] * e[1, j]) + e[2, i] * e[2, j] for j in range(3)] for i in range(3)])
+    d, v = _rp_jacobi(a, RP_SWEEPS3)
+    for i, j in ((0, 1), (0, 2), (1, 2)):
+        if d[j] > d[i]:
+            d[[i, j]] = d[[j, i]]
+            v[:, [i, j]] = v[:, [j, i]]
+    v0, v1 = v[:, 0].copy(), v[:, 1].copy()
+    v0 = v0 / np.sqrt(_rp_dot3(v0, v0))
+    v1 = v1 - _rp_dot3(v0, v1) * v0
+    v1 = v1 / np.sqrt(_rp_dot3(v1, v1))
+    cross = lambda p, q: np.array([p[1] * q[2] - p[2] * q[1], p[2] * q[0] - p[0] * q[2], p[0] * q[1] - p[1] * q[0]])   # noqa: E731
+    v2 = cross(v0, v1)
+    u0 = np.array([_rp_dot3(e[i], v0) for i in range(3)])
+    u1 = np.array([_rp_dot3(e[i], v1) for i in range(3)])
+    u0 = u0 / np.sqrt(_rp_dot3(u0, u0))
+    u1 = u1 - _rp_dot3(u0, u1) * u0
+    n = np.sqrt(_rp_dot3(u1, u1))
+    if not n > 1e-150:                   # rank one
+        u1 = cross(u0, np.eye(3)[int(np.argmin(np.abs(u0)))])
+        n = np.sqrt(_rp_dot3(u1, u1))
+    u1 = u1 / n
+    u2 = cross(u0, u1)
+    R1 = np.array([[(u0[i] * v1[j] - u1[i] * v0[j]) + u2[i] * v2[j] for j in range(3)] for i in range(3)])
+    R2 = np.array([[(u1[i] * v0[j] - u0[i] * v1[j]) + u2[i] * v2[j] for j in range(3)] for i in range(3)])
+    return [(R1, u2), (R2, u2), (R1, -u2), (R2, -u2)]
+
+
+def recover_pose_ge(E, x0, x1, distance_thresh=1e9, mask=None, detail=False):
+    """`recover_pose` in the arithmetic of gim_recover_pose (include/gim_hip.h; csrc/recover_pose_solve.h is the code), vectorised
+    over the points -- the CPU oracle of ops.recover_pose: Jacobi iterations with fixed sweep counts in place of LAPACK's SVDs, a
+    point's null vector as the smallest eigenvector of A^T A.  -> (n_good, R, t, mask_out) as `recover_pose`; detail=True adds
+    (counts int [4], best): the good points of each candidate in the device's candidate order and the winner's index.  An invalid
+    E: (0, zero R, zero t, all-False) and best = -1."""
+    x0 = np.asarray(x0, dtype=np.float64).reshape(-1, 2)
+    x1 = np.asarray(x1, dtype=np.float64).reshape(-1, 2)
+    P = x0.shape[0]
+    m_in = np.ones(P, dtype=bool) if mask is None else np.asarray(mask).ravel() > 0
+    cands = decompose_essential_ge(E)
+    if cands is None:
+        out = (0, np.zeros((3, 3)), np.zeros(3), np.zeros(P, dtype=bool))
+        return out + (np.zeros(4, dtype=np.int64), -1) if detail else out
+    goods = []
+    x, y, u, w1 = x0[:, 0], x0[:, 1], x1[:, 0], x1[:, 1]
+    zero, one = np.zeros(P), np.ones(P)
+    for R, tt in cands:
+        c = np.concatenate([R.ravel(), tt])
+        A = np.stack([np.stack([-one, zero, x, zero], -1), np.stack([zero, -one, y, zero], -1),
+                      np.stack([u * c[6] - c[0], u * c[7] - c[1], u * c[8] - c[2], u * c[11] - c[9]], -1),
+                      np.stack([w1 * c[6] - c[3], w1 * c[7] - c[4], w1 * c[8] - c[5], w1 * c[11] - c[10]], -1)], 1)   # [P, 4, 4]
+        a = np.zeros((P, 4, 4))
+        for i in range(4):
+            for j in range(i, 4):
+                a[:, i, j] = ((A[:, 0, i] * A[:, 0, j] + A[:, 1, i] * A[:, 1, j]) + A[:, 2, i] * A[:, 2, j]) + A[:, 3, i] * A[:, 3, j]
+        d, v = _rp_jacobi(a, RP_SWEEPS4)
+        k = np.argmin(d, -1) if P else np.zeros(0, dtype=np.int64)         # the first smallest, as the device's strict <
+        Q = np.take_along_axis(v, k[:, None, None], 2)[:, :, 0]
+        with np.errstate(all="ignore"):
+            w = np.where(np.abs(Q[:, 3]) > RP_W_TINY, Q[:, 3], RP_W_TINY)
+            X = Q[:, :3] / w[:, None]
+            z0 = X[:, 2]
+            z1 = ((X[:, 0] * c[6] + X[:, 1] * c[7]) + X[:, 2] * c[8]) + c[11]
+            goods.append(m_in & (z0 > 0) & (z0 < distance_thresh) & (z1 > 0) & (z1 < distance_thresh))
+    n = np.array([int(g.sum()) for g in goods], dtype=np.int64)
+    k = 0 if (n[0] >= n[1] and n[0] >= n[2] and n[0] >= n[3]) else 1 if (n[1] >= n[2] and n[1] >= n[3]) else 2 if n[2] >= n[3] else 3
+    out = (int(n[k]), cands[k][0], cands[k][1].copy(), goods[k])
+    return out + (n, k) if detail else out
 
 
 def backend():

@@ -131,7 +131,16 @@ def _normalise(kpts0, kpts1, K0, K1, thresh):
     return kpts0, kpts1, thresh / np.mean([K0[0, 0], K1[1, 1], K0[0, 0], K1[1, 1]])
 
 
-def estimate_pose(kpts0, kpts1, K0, K1, thresh=0.5, conf=0.99999, device=None, solve="host", sampler="host"):
+def _check_recover(recover, device):
+    """the `recover=` rules of estimate_pose and the two hooks: "device" needs a device and the numpy backend; raises before any
+    launch"""
+    from . import pose
+    pose._check_recover(recover, device)
+    if recover == "device" and pose.backend() != "numpy":
+        raise ValueError("recover='device' belongs to the numpy backend (GIM_POSE_BACKEND=numpy): OpenCV recovers the pose itself")
+
+
+def estimate_pose(kpts0, kpts1, K0, K1, thresh=0.5, conf=0.99999, device=None, solve="host", sampler="host", recover="host"):
     """tools/metrics.py:77-103 (findEssentialMat RANSAC + recoverPose).  OpenCV when it imports (the reference's own call),
     otherwise the numpy restatement of the same two OpenCV routines in gim_amd/pose.py (`GIM_POSE_BACKEND` forces one).
     device: on the numpy backend, score the RANSAC candidates on that GPU (pose.DeviceScorer; same result as the host run);
@@ -139,12 +148,19 @@ def estimate_pose(kpts0, kpts1, K0, K1, thresh=0.5, conf=0.99999, device=None, s
     backend -- "device" also solves the five-point samples on `device` (one gim_essential_step per RANSAC step; sampling and
     recoverPose stay on the host), "ge" is its host oracle.  sampler: the `sampler` of pose.find_essential_mat -- "philox" draws
     the counter-based samples on the host, "device" (needs `device` and solve="device") draws them on the GPU and reads back only
-    each step's record samples.  OpenCV ignores all three."""
+    each step's record samples.  OpenCV ignores all three.  recover: "host" (the default) runs pose.recover_pose here; "device"
+    (needs `device` and the numpy backend, with any `solve` / `sampler` that takes the device) runs gim_recover_pose there
+    (pose.find_essential_pose): with solve="device" on the points and the mask the RANSAC left on the GPU, one copy bringing the
+    mask, R and t back.  The returned inliers are the RANSAC mask either way."""
     from . import pose
     pose._check_sampler(sampler, device, solve)
+    _check_recover(recover, device)
     if len(kpts0) < 5:
         return None
     kpts0, kpts1, ransac_thr = _normalise(kpts0, kpts1, K0, K1, thresh)
+    if recover == "device":
+        E, mask, found = pose.find_essential_pose(kpts0, kpts1, ransac_thr, prob=conf, device=device, solve=solve, sampler=sampler)
+        return (found[1], found[2], mask) if E is not None and found[0] > 0 else None
     if pose.backend() == "numpy":
         E, mask = pose.find_essential_mat(kpts0, kpts1, ransac_thr, prob=conf, device=device, solve=solve, sampler=sampler)
         if E is None:
@@ -179,24 +195,28 @@ def _np(x):
     return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
 
 
-def device_estimator(device, thresh=0.5, conf=0.99999, solve="host", sampler="host"):
+def device_estimator(device, thresh=0.5, conf=0.99999, solve="host", sampler="host", recover="host"):
     """`estimate=` hook of evaluate_batch / run_scene: estimate_pose with the RANSAC candidates scored on `device`
-    (solve="device": solved there too; sampler: estimate_pose's)"""
+    (solve="device": solved there too; sampler, recover: estimate_pose's)"""
     from . import pose
     pose._check_sampler(sampler, device, solve)
-    return lambda a, b, k0, k1: estimate_pose(a, b, k0, k1, thresh, conf, device=device, solve=solve, sampler=sampler)
+    _check_recover(recover, device)
+    return lambda a, b, k0, k1: estimate_pose(a, b, k0, k1, thresh, conf, device=device, solve=solve, sampler=sampler, recover=recover)
 
 
-def device_batch_estimator(device, thresh=0.5, conf=0.99999, solve="host", sampler="host"):
+def device_batch_estimator(device, thresh=0.5, conf=0.99999, solve="host", sampler="host", recover="host"):
     """`estimate_batch=` hook of evaluate_batch / run_scene: the pairs of a batch through pose.find_essential_mat_batch -- their
     RANSAC loops advance in lockstep and every step scores all pairs' candidates in one launch on `device`.  Needs one threshold
     for the batch, so pairs whose intrinsics give another normalised threshold (and every pair when OpenCV is the backend) go through
     estimate_pose one by one.  pairs: [(kpts0, kpts1, K0, K1)] -> [(R, t, inliers) | None], equal to estimate_pose on each pair.
     solve="device": every step also solves all pairs' samples in that launch (pose.find_essential_mat_batch(solve="device")); the
     results equal estimate_pose(..., device=device, solve="device") on each pair.  sampler: that of
-    pose.find_essential_mat_batch and estimate_pose; the results equal estimate_pose's with the same sampler."""
+    pose.find_essential_mat_batch and estimate_pose; the results equal estimate_pose's with the same sampler.
+    recover="device": the poses of a group come from ONE gim_recover_pose launch (pose.find_essential_pose_batch); the results
+    equal estimate_pose(..., recover="device") on each pair."""
     from . import pose
     pose._check_sampler(sampler, device, solve)
+    _check_recover(recover, device)
 
     def estimate_batch(pairs):
         out = [None] * len(pairs)
@@ -208,6 +228,12 @@ def device_batch_estimator(device, thresh=0.5, conf=0.99999, solve="host", sampl
                 a, b, thr = _normalise(a, b, k0, k1, thresh)
                 groups.setdefault(float(thr), []).append((i, a, b))
         for thr, members in groups.items():
+            if recover == "device":
+                found = pose.find_essential_pose_batch([(a, b) for _, a, b in members], thr, prob=conf, device=device, solve=solve,
+                                                       sampler=sampler)
+                for (i, _, _), (E, mask, p) in zip(members, found):
+                    out[i] = (p[1], p[2], mask) if E is not None and p[0] > 0 else None
+                continue
             found = pose.find_essential_mat_batch([(a, b) for _, a, b in members], thr, prob=conf, device=device, solve=solve,
                                                   sampler=sampler)
             for (i, a, b), (E, mask) in zip(members, found):

@@ -1037,8 +1037,9 @@ int gim_fundamental_step(const double* x0, const double* x1, const int32_t* offs
 /* ======================================================================================================
  * Essential-matrix RANSAC step: the five-point minimal solve and the scoring of its models in one launch (added within ABI
  * revision 115: no existing structure or prototype changed with it).  The reference calls cv2.findEssentialMat(kpts0, kpts1,
- * np.eye(3), threshold, prob, method=cv2.RANSAC) (tools/metrics.py:88-89).  Sampling, the iteration bound and recoverPose stay on
- * the host (gim_amd/pose.py); the final mask is gim_ransac_mask, the same Sampson error.
+ * np.eye(3), threshold, prob, method=cv2.RANSAC) (tools/metrics.py:88-89).  The iteration bound stays on the host
+ * (gim_amd/pose.py); sampling has gim_ransac_sample and recoverPose gim_recover_pose, below; the final mask is gim_ransac_mask, the
+ * same Sampson error.
  * ====================================================================================================== */
 
 /* K five-point samples per pair, solved AND scored in ONE launch, B pairs; a sample gives up to ten models.  All pointers are
@@ -1117,6 +1118,39 @@ int gim_ransac_sample(const int32_t* offsets, int B, const int64_t* first, const
  * pointer, an array not 4-byte aligned, B > 65535, B * K * k or B * (1 + 3 K) > INT32_MAX. */
 int gim_ransac_records(const int32_t* counts, const int32_t* nb, const int32_t* floor_, int B, int K, int k, int32_t* rec,
                        gim_stream_t stream);
+
+/* ======================================================================================================
+ * recoverPose on the device (added within ABI revision 115: no existing structure or prototype changed with it).  The reference
+ * calls cv2.recoverPose(E, kpts0, kpts1, np.eye(3), 1e9, mask=mask) on the host after its RANSAC (tools/metrics.py:96-101); here
+ * the points are those the step entry points above already hold and the input mask is gim_ransac_mask's output.
+ * ====================================================================================================== */
+
+/* cv::recoverPose for B pairs in ONE launch.  All pointers are DEVICE memory.  E fp64 [B][3][3] row-major (x1^T E x0 = 0); x0, x1
+ * fp64 [Ptot][2] (16-byte aligned) and offsets int32 [B + 1] as in gim_essential_step (trusted); mask_in uint8 [Ptot] or NULL: a
+ * point with a zero byte is good under no candidate.  fp64 throughout, real arithmetic only, no fast-math, every loop bounded
+ * (pose.recover_pose_ge is this arithmetic in numpy, csrc/recover_pose_solve.h the code):
+ *   1. decomposition: e = E / max |E_ij|; the eigenvectors of e^T e by cyclic Jacobi (8 sweeps over the planes (0,1), (0,2), (1,2),
+ *      Rutishauser's rotation, a zero off-diagonal entry is skipped), ordered by eigenvalue, largest first; v0 normalised, v1
+ *      orthogonalised against v0 and normalised, v2 = v0 x v1; u0 = e v0 / |e v0|, u1 = e v1 orthogonalised against u0 and
+ *      normalised (when it vanishes, a rank-one E: u0 x the axis of u0's smallest |entry|), u2 = u0 x u1: det U = det V = +1, the
+ *      signs cv::decomposeEssentialMat forces.  With W = [[0,1,0],[-1,0,0],[0,0,1]]: R1 = U W V^T, R2 = U W^T V^T, t = u2; the
+ *      candidates, in order: (R1, t), (R2, t), (R1, -t), (R2, -t).  The SVD is not unique: R1 and R2 may be exchanged and t negated
+ *      relative to LAPACK's, the SET of four candidates is the same;
+ *   2. per point and candidate: the 4 x 4 DLT matrix of cv::triangulatePoints with P0 = [I | 0], P1 = [R | t], rows
+ *      x P0[2] - P0[0], y P0[2] - P0[1], u P1[2] - P1[0], v P1[2] - P1[1]; its null vector Q: the eigenvector of the smallest
+ *      eigenvalue of A^T A by cyclic Jacobi (8 sweeps over the six planes in row-major order; the first smallest diagonal entry);
+ *      w = Q[3] where |Q[3]| > 1e-300, else 1e-300; X = Q[:3] / w; z0 = X[2]; z1 = (R[2] . X) + t[2];
+ *      good iff mask_in allows the point and 0 < z0 < distance_thresh and 0 < z1 < distance_thresh;
+ *   3. n_good int32 [B][4]: the good points per candidate (integer sums through wave shuffles and LDS, no atomics: the result does
+ *      not depend on the launch shape); best int32 [B]: the first maximum in candidate order; R fp64 [B][3][3], t fp64 [B][3]: the
+ *      winner's; mask_out uint8 [Ptot]: 1 where the point is good under the winner, else 0.
+ * Everything is FULLY written for every pair (no memset by the caller).  An E[b] with an entry that is not finite, or all zero:
+ * n_good = 0, best = -1, R = 0, t = 0, the pair's mask_out 0.  A pair without points: n_good = 0, best = 0, R and t of the first
+ * candidate.  B == 0 returns without touching anything.  Refused before a launch: a NULL pointer other than mask_in, x0 / x1 not
+ * 16-byte aligned, E / R / t not 8-byte or an int32 array not 4-byte aligned, B > 65535. */
+int gim_recover_pose(const double* E, const double* x0, const double* x1, const int32_t* offsets, int B, const uint8_t* mask_in,
+                     double distance_thresh, double* R, double* t, int32_t* n_good, int32_t* best, uint8_t* mask_out,
+                     gim_stream_t stream);
 
 #ifdef __cplusplus
 }
