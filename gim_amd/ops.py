@@ -2046,3 +2046,122 @@ def dense_emit_pairs(sparse, mconf, geom, rescale):
     check(lib.gim_dense_emit_pairs(_p(sparse), _p(mconf), _p(geom), _p(k0), _p(k1), _p(sc), _p(count), B, num, int(bool(rescale)), _stream()),
           "gim_dense_emit_pairs")
     return k0, k1, sc, count
+
+
+# ---- video pseudo-labels (gim_amd/video_labels.py; csrc/label_link.hip) -------------------------------------------------------------
+LABEL_MAX_KEY = 1 << 24        # csrc/label_key.h GIM_LABEL_MAX_KEY: the largest key range w * (h + 1)
+
+
+def _label_sizes(width, height, B):
+    """(width, height) per link as a host int32 [B,2]; raises before anything touches the device"""
+    wh = np.stack(np.broadcast_arrays(np.asarray(width, dtype=np.int64).reshape(-1), np.asarray(height, dtype=np.int64).reshape(-1)), 1)
+    if wh.shape[0] == 1 and B != 1:
+        wh = np.repeat(wh, B, 0)
+    if wh.shape[0] != B:
+        raise ValueError(f"label_link: {wh.shape[0]} (width, height) pairs for {B} links")
+    if B and (wh.min() < 1 or (wh[:, 0] * (wh[:, 1] + 1)).max() > LABEL_MAX_KEY):
+        raise ValueError(f"label_link: width and height must be >= 1 and width * (height + 1) <= 2^24, got {wh.tolist()}")
+    return np.ascontiguousarray(wh, dtype=np.int32)
+
+
+def label_link_max_keys(width, height):
+    """the table length a workspace needs for these frame sizes: the largest w * (h + 1) + 1"""
+    w, h = np.asarray(width, dtype=np.int64).reshape(-1), np.asarray(height, dtype=np.int64).reshape(-1)
+    wh = _label_sizes(w, h, max(w.size, h.size)).astype(np.int64)
+    return int((wh[:, 0] * (wh[:, 1] + 1)).max()) + 1 if len(wh) else 1
+
+
+def label_link_workspace(B, max_keys, device):
+    """a zeroed workspace for label_link calls of up to B links and max_keys slots; every call leaves it zeroed again"""
+    nbytes = lib.gim_label_link_ws_bytes(int(B), int(max_keys))
+    if nbytes < 0:
+        raise _lib.GimHipError(f"label_link_workspace B={B} max_keys={max_keys}")
+    return torch.zeros(nbytes // 4, dtype=torch.int32, device=device)
+
+
+def label_link(lab0, lab1, width, height, *, offsets0=None, offsets1=None, workspace=None, out=None, ij=None):
+    """walk.py:link on the device (gim_label_link: three launches, no host read).  lab0 fp32 [N,4] and lab1 fp32 [M,4]: labels
+    (x0, y0, x1, y1) of the frame pairs a->b and b->c; width, height: the size of the frames the labels are in.  Rows of lab0 and lab1
+    that share the rounded pixel round(x) + round(y) * width of frame b are joined, the last row of a pixel on either side, in
+    ascending lab0 row -> (out fp32 [N,4]: (lab0[i, 0:2], lab1[j, 2:4]) in the first count rows; ij int32 [N,2]; count int32 [B];
+    dropped int32 [B,2]: the rows of either side whose key is not finite or outside [0, width * (height + 1)], which are ignored).
+    B links at once: the labels concatenated, offsets0 / offsets1 int32 [B+1] (device tensors, or sequences, which are uploaded) and
+    width / height ints or one per link; link b's rows are out[offsets0[b] : offsets0[b] + count[b]], ij is relative to the link.
+    workspace: label_link_workspace(...) to reuse across calls (zero on entry, zero again afterwards); out / ij: buffers to write into
+    (rows beyond a link's count are not touched)."""
+    _req_cuda(lab0, lab1, workspace, out, ij)
+    for t, name in ((lab0, "lab0"), (lab1, "lab1")):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 4 or not t.is_contiguous() or t.device != lab0.device:
+            raise _lib.GimHipError(f"label_link {name} must be contiguous fp32 [n,4] on one device, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    if (offsets0 is None) != (offsets1 is None):
+        raise _lib.GimHipError("label_link takes both offsets or neither")
+    dev, N, M = lab0.device, lab0.shape[0], lab1.shape[0]
+    single = offsets0 is None
+    if not single:
+        offsets0, offsets1 = _on(dev, offsets0, np.int32), _on(dev, offsets1, np.int32)
+        for t, name in ((offsets0, "offsets0"), (offsets1, "offsets1")):
+            if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] < 1 or t.shape != offsets0.shape or not t.is_contiguous() or t.device != dev:
+                raise _lib.GimHipError(f"label_link {name} must be contiguous int32 [B+1] on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    B = 1 if single else offsets0.shape[0] - 1
+    if B > 65535:
+        raise _lib.GimHipError(f"label_link B={B}: at most 65535 links")
+    wh = _label_sizes(width, height, B)
+    need = int((wh[:, 0].astype(np.int64) * (wh[:, 1] + 1)).max()) + 1 if B else 1
+    if workspace is None:
+        workspace = label_link_workspace(B, need, dev)
+        max_keys = need
+    else:
+        if workspace.dtype != torch.int32 or workspace.dim() != 1 or not workspace.is_contiguous() or workspace.device != dev:
+            raise _lib.GimHipError(f"label_link workspace must be contiguous int32 [.] on {dev} (label_link_workspace)")
+        max_keys = min(workspace.shape[0] // (2 * B), LABEL_MAX_KEY + 1) if B else need
+        if max_keys < need:
+            raise _lib.GimHipError(f"label_link workspace has {workspace.shape[0]} words, {B} links of {need} keys need {2 * B * need}")
+    if out is None:
+        out = torch.empty(N, 4, dtype=torch.float32, device=dev)
+    if ij is None:
+        ij = torch.empty(N, 2, dtype=torch.int32, device=dev)
+    for t, dt, k, name in ((out, torch.float32, 4, "out"), (ij, torch.int32, 2, "ij")):
+        if t.dtype != dt or t.shape != (N, k) or not t.is_contiguous() or t.device != dev:
+            raise _lib.GimHipError(f"label_link {name} must be contiguous {dt} [{N},{k}] on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    dropped = torch.empty(B, 2, dtype=torch.int32, device=dev)
+    if B:
+        wh_dev = None if B == 1 else torch.from_numpy(wh).to(dev)
+        with torch.cuda.device(dev):
+            check(lib.gim_label_link(_p(lab0) if N else None, _p(offsets0), N, _p(lab1) if M else None, _p(offsets1), M,
+                                     wh.ctypes.data_as(ctypes.c_void_p), _p(wh_dev), B, max_keys, _p(workspace), _p(out) if N else None,
+                                     _p(ij) if N else None, _p(count), _p(dropped), _stream()), "gim_label_link")
+    return out, ij, count, dropped
+
+
+def label_pack(k0, k1, keep=None, moved_thr=0.0, affine=None, vratio=1.0, out=None):
+    """The tail of a labelling step in one launch (gim_label_pack; video_preprocessor.py:513-555).  k0, k1 fp32 [n,2]: the matched
+    keypoints of a pair; keep bool / uint8 [n] or None: the inlier mask; moved_thr > 0: rows with |dx| < moved_thr and |dy| < moved_thr
+    are dropped (static matches: watermarks); affine: 8 numbers (sx0, sy0, ox0, oy0, sx1, sy1, ox1, oy1) -> (x * s + o) * vratio in
+    fp64, rounded to fp32; without it the fp32 product x * vratio -> (out fp32 [n,4]: the kept rows (x0, y0, x1, y1) in input order in
+    the first count rows, count int32 [])."""
+    _req_cuda(k0, k1, keep, out)
+    for t, name in ((k0, "k0"), (k1, "k1")):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 2 or t.shape != k0.shape or not t.is_contiguous() or t.device != k0.device:
+            raise _lib.GimHipError(f"label_pack {name} must be contiguous fp32 [n,2] on one device, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    n, dev = k0.shape[0], k0.device
+    if keep is not None:
+        if keep.dtype == torch.bool:
+            keep = keep.view(torch.uint8)
+        if keep.dtype != torch.uint8 or keep.shape != (n,) or not keep.is_contiguous() or keep.device != dev:
+            raise _lib.GimHipError(f"label_pack keep must be contiguous bool / uint8 [{n}] on the points' device")
+    a = None
+    if affine is not None:
+        a = np.ascontiguousarray(affine, dtype=np.float64).reshape(-1)
+        if a.shape != (8,):
+            raise ValueError(f"label_pack affine: 8 numbers (sx0, sy0, ox0, oy0, sx1, sy1, ox1, oy1), got {a.shape[0]}")
+    if out is None:
+        out = torch.empty(n, 4, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.shape != (n, 4) or not out.is_contiguous() or out.device != dev:
+        raise _lib.GimHipError(f"label_pack out must be contiguous fp32 [{n},4] on the points' device")
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.gim_label_pack(_p(k0) if n else None, _p(k1) if n else None, _p(keep) if n else None, n, float(moved_thr),
+                                 a.ctypes.data_as(ctypes.c_void_p) if a is not None else None, float(vratio), _p(out) if n else None, _p(count),
+                                 _stream()), "gim_label_pack")
+    return out, count[0]

@@ -1152,6 +1152,56 @@ int gim_recover_pose(const double* E, const double* x0, const double* x1, const 
                      double distance_thresh, double* R, double* t, int32_t* n_good, int32_t* best, uint8_t* mask_out,
                      gim_stream_t stream);
 
+/* ======================================================================================================
+ * Video pseudo-labels (added within ABI revision 115: no existing structure or prototype changed with them).  A label is an fp32
+ * [n][4] array of matches (x0, y0, x1, y1) between two frames.  The reference links the labels of frames a->b and b->c into a->c
+ * through the pixels they share in b (datasets/walk/walk.py:29 create_table, :217-247 link, with Python dicts and sets on DataLoader
+ * workers) and writes a label at the end of a labelling step (video_preprocessor.py:513-555).  csrc/label_key.h is the arithmetic,
+ * gim_amd/video_labels.py (link_tables, label_pack_np) its numpy restatement.
+ * ====================================================================================================== */
+
+/* bytes of gim_label_link's workspace: two int32 tables of max_keys slots per link; -1 for a negative argument.  max_keys is the
+ * largest w * (h + 1) + 1 of the links it will serve. */
+int64_t gim_label_link_ws_bytes(int B, int max_keys);
+
+/* walk.py:link for B links in one launch sequence (three launches: build, compact, clear).
+ * DEVICE memory: lab0 fp32 [n0_total][4], lab1 fp32 [n1_total][4] (16-byte aligned): the links' labels, concatenated; off0, off1
+ * int32 [B + 1]: ascending row offsets of the links in the two slabs (clamped into them), or NULL when B == 1: the whole slab;
+ * wh_dev int32 [B][2]: (width, height) per link, or NULL when B == 1; ws: gim_label_link_ws_bytes(B, max_keys) bytes, ALL ZERO on
+ * entry and all zero again when the sequence has run (the last launch clears exactly the slots the first one wrote; nobody pays a
+ * memset of the key range).  HOST memory: wh int32 [B][2], the same values as wh_dev: they are checked before anything is launched.
+ *   key      of a point (x, y) of link b: rintf(x) + rintf(y) * (float)w in fp32, round half to even, no fused multiply-add
+ *            (create_table: np.round(x) + np.round(y) * w).  lab0's point is its columns 2, 3, lab1's its columns 0, 1 -- the pixels
+ *            of the middle frame.  A key is usable iff it is finite and in [0, w * (h + 1)]: this keeps the reference's aliasing (an
+ *            x that rounds to w shares the key of (0, y + 1)).  Rows without a usable key are ignored and counted in dropped[b][side]
+ *            -- the one difference from the reference, which would join them too;
+ *   tables   per link and side, over the key range: the LARGEST row index of the link that has the key, stored as index + 1
+ *            (integer atomicMax; dict(zip(keys, range(n))) keeps the last row of a key);
+ *   result   row i of the link's lab0 rows survives iff table0[key_i] == i + 1 and table1[key_i] > 0; its partner is
+ *            j = table1[key_i] - 1.  Survivors in ascending i -- np.unique(np.vstack((i, j)), axis=1) of walk.py:240, where distinct
+ *            keys have distinct i -- placed by a block scan with a carried offset, one workgroup per link, no atomics:
+ *            out fp32 [n0_total][4]: row off0[b] + rank = (lab0[i][0:2], lab1[j][2:4]), copied bit for bit; ij int32 [n0_total][2]:
+ *            (i, j) relative to the link's rows; count int32 [B]; dropped int32 [B][2].  Nothing is written beyond count[b] rows of
+ *            a link or outside its row range.
+ * B == 0 returns without touching anything.  Refused before a launch (GIM_ERR_INVALID): B < 0 or > 65535, a negative row count,
+ * a width or height < 1, a key range w * (h + 1) above 2^24 (keys are exact in fp32 up to there) or not below max_keys, B > 1
+ * without offsets or wh_dev, a NULL or misaligned pointer. */
+int gim_label_link(const float* lab0, const int32_t* off0, int n0_total, const float* lab1, const int32_t* off1, int n1_total,
+                   const int32_t* wh, const int32_t* wh_dev, int B, int max_keys, void* ws, float* out, int32_t* ij,
+                   int32_t* count, int32_t* dropped, gim_stream_t stream);
+
+/* The tail of a labelling step for one pair in ONE launch (one workgroup, the same ordered compaction).  DEVICE memory: k0, k1 fp32
+ * [n][2] (8-byte aligned): the matched keypoints; keep uint8 [n] or NULL; out fp32 [n][4] (16-byte aligned); count int32 [1].
+ * HOST memory: affine, 8 doubles (sx0, sy0, ox0, oy0, sx1, sy1, ox1, oy1), or NULL.
+ *   kept     iff (keep is NULL or keep[i] != 0) and (moved_thr <= 0 or not (|x0 - x1| < moved_thr and |y0 - y1| < moved_thr)), the
+ *            differences in fp32: video_preprocessor.py:516, the watermark test; a NaN row counts as moved;
+ *   row      with an affine: ((double)x * s + o) * vratio in fp64, three roundings, no fused multiply-add, then to fp32 (line 549);
+ *            without: the fp32 product x * (float)vratio (line 552);
+ *   out      the kept rows in input order, count[0] of them; nothing is written beyond.
+ * Refused before a launch: n < 0, a NULL pointer (other than keep and affine; k0, k1, out may be NULL when n == 0), misalignment. */
+int gim_label_pack(const float* k0, const float* k1, const uint8_t* keep, int n, float moved_thr, const double* affine,
+                   double vratio, float* out, int32_t* count, gim_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
