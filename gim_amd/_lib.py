@@ -230,6 +230,8 @@ PROTOTYPES = {
     "gim_ransac_records": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 2),
     # recoverPose on the device: decomposition of E, triangulation and cheirality counts in one launch (added within ABI revision 115)
     "gim_recover_pose": (c_int, [c_void_p] * 4 + [c_int, c_void_p, ctypes.c_double] + [c_void_p] * 6),
+    # least-squares refit of H / F on the inliers and its local-optimisation rounds in one launch (added within ABI revision 115)
+    "gim_model_refit": (c_int, [c_int] + [c_void_p] * 3 + [c_int] + [c_void_p] * 2 + [ctypes.c_double, c_int] + [c_void_p] * 5),
     # video pseudo-labels: link of two labels through shared pixel keys, the tail of a labelling step (added within ABI revision 115)
     "gim_label_link_ws_bytes": (c_int64, [c_int] * 2),
     "gim_label_link": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 2 + [c_int] + [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 6),

@@ -146,14 +146,16 @@ def build(model_name, weights=None, precision=None, device="cuda", dinov2_weight
 
 @torch.no_grad()
 def match_pair(model_name, model, detector, path0, path1, device="cuda", resize_max=None, num=5000, ransac_solve="host",
-               ransac_sampler="host"):
+               ransac_sampler="host", ransac_refine=0):
     """demo.py:405-511 -> dict(mkpts0_f, mkpts1_f, mconf, m_bids, hw0_i, hw1_i); coordinates in pixels of the pre-processed images
     for the dense matchers and gim_loftr (as the reference leaves them), of the original images for gim_lightglue (:499-500).
     ransac_solve="device": the seven-point solve of the geometry filter runs on the matches' device too, fused with the scoring
     (pose.find_fundamental_mat(solve="device"); `ransac_backend` is then "device"); "host" is the path described below.
     ransac_sampler: the `sampler` of pose.find_fundamental_mat on the numpy and device backends -- "host" (default_rng, the default),
     "philox" (the counter-based draw, made on the host) or "device" (drawn and reduced on the GPU; needs ransac_solve="device").
-    OpenCV draws its own samples."""
+    OpenCV draws its own samples.
+    ransac_refine: the `refine` of pose.find_fundamental_mat on the numpy and device backends -- 0 (the default) or up to 8 rounds
+    of eight-point refit on the inliers, the step OpenCV's USAC ends with."""
     if ransac_solve not in ("host", "device"):
         raise ValueError(f"ransac_solve={ransac_solve!r}: host or device")
     if ransac_sampler not in ("host", "philox", "device") or (ransac_sampler == "device" and ransac_solve != "device"):
@@ -198,7 +200,7 @@ def match_pair(model_name, model, detector, path0, path1, device="cuda", resize_
             # solved and scored on the matches' device, one launch per RANSAC step (pose.DeviceFundamental)
             out["F"], out["inliers"] = pose.find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000,
                                                                  device=kpts0.device if kpts0.is_cuda else None, solve="device",
-                                                                 sampler=ransac_sampler)
+                                                                 sampler=ransac_sampler, refine=ransac_refine)
         elif out["ransac_backend"] == "cv2":
             import cv2
             out["F"], mask = cv2.findFundamentalMat(p0, p1, cv2.USAC_MAGSAC, ransacReprojThreshold=1.0, confidence=0.999999, maxIters=10000)
@@ -206,12 +208,13 @@ def match_pair(model_name, model, detector, path0, path1, device="cuda", resize_
         else:
             # the seven-point candidates are scored on the model's device (pose.DeviceScorer), the solver stays on the host
             out["F"], mask = pose.find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000,
-                                                       device=kpts0.device if kpts0.is_cuda else None, sampler=ransac_sampler)
+                                                       device=kpts0.device if kpts0.is_cuda else None, sampler=ransac_sampler,
+                                                       refine=ransac_refine)
             out["inliers"] = mask
     return out
 
 
-def compute_geom(out, device=None, ransac_solve="host", ransac_sampler="host"):
+def compute_geom(out, device=None, ransac_solve="host", ransac_sampler="host", ransac_refine=0, homography_refit="host"):
     """demo.py:180-227 on the dict of `match_pair` -> {"Fundamental": F [3,3] | None, "Homography": H [3,3] | None}, or {} for
     fewer than 8 matches (the reference's 2 x DEFAULT_MIN_NUM_MATCHES).  "Fundamental" is the model the robust-fitting step of
     `match_pair` found (`out["F"]`: pose.find_fundamental_mat's on the numpy backend, cv2's when cv2 filtered; computed here with
@@ -219,15 +222,19 @@ def compute_geom(out, device=None, ransac_solve="host", ransac_sampler="host"):
     parameters: pose.find_homography(mkpts1, mkpts0, 1.0, 0.999999, 10000, device=device) -- on `device` the four-point solve and the
     scoring are one launch per RANSAC step, device=None is the host path.  ransac_solve: the `solve` of pose.find_fundamental_mat
     when the fundamental matrix is computed here ("device" needs `device`).  ransac_sampler: the `sampler` of both calls ("device"
-    needs `device`, and ransac_solve="device" when the fundamental matrix is computed here)."""
+    needs `device`, and ransac_solve="device" when the fundamental matrix is computed here).  ransac_refine: the `refine` of
+    pose.find_fundamental_mat when the fundamental matrix is computed here.  homography_refit: the `refit` of pose.find_homography
+    -- "host" (the default: `homography_dlt`) or "device" (one gim_model_refit launch; needs `device`), which `main` asks for
+    whenever the RANSAC already runs on the device, i.e. on a GPU with --ransac-sampler device."""
     from . import pose
     p0 = np.asarray(out["mkpts0_f"].detach().float().cpu().numpy() if torch.is_tensor(out["mkpts0_f"]) else out["mkpts0_f"], dtype=np.float64)
     p1 = np.asarray(out["mkpts1_f"].detach().float().cpu().numpy() if torch.is_tensor(out["mkpts1_f"]) else out["mkpts1_f"], dtype=np.float64)
     if len(p0) < 8:
         return {}
     F = out["F"] if "F" in out else pose.find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, device=device,
-                                                                   solve=ransac_solve, sampler=ransac_sampler)[0]
-    H, _ = pose.find_homography(p1, p0, 1.0, 0.999999, 10000, device=device, sampler=ransac_sampler)
+                                                                   solve=ransac_solve, sampler=ransac_sampler, refine=ransac_refine)[0]
+    H, _ = pose.find_homography(p1, p0, 1.0, 0.999999, 10000, device=device, sampler=ransac_sampler,
+                                refit=homography_refit)
     return {"Fundamental": None if F is None else np.asarray(F, dtype=np.float64), "Homography": H}
 
 
@@ -274,6 +281,8 @@ def main(argv=None):
     ap.add_argument("--ransac-sampler", choices=["host", "philox", "device"], default="host",
                     help="who draws the RANSAC samples: numpy's default_rng (default), the counter-based draw on the host, or the same "
                          "draw on the GPU with every step reduced there (device: needs --ransac-solve device)")
+    ap.add_argument("--ransac-refine", type=int, choices=range(0, 9), default=0, metavar="R",
+                    help="rounds of eight-point refit on the inliers after the fundamental-matrix RANSAC, 0 to 8 (default 0: none)")
     args = ap.parse_args(argv)
     if args.ransac_sampler == "device" and args.ransac_solve != "device":
         ap.error("--ransac-sampler device needs --ransac-solve device")
@@ -284,7 +293,7 @@ def main(argv=None):
         print(f"gim_amd.demo: no checkpoint ({join('weights', CKPT[args.model])} not found): running on the modules' seeded init")
     model, detector = build(args.model, weights, args.precision, dinov2_weights=args.dinov2_weights)
     out = match_pair(args.model, model, detector, args.image0, args.image1, resize_max=args.resize_max, ransac_solve=args.ransac_solve,
-                     ransac_sampler=args.ransac_sampler)
+                     ransac_sampler=args.ransac_sampler, ransac_refine=args.ransac_refine)
     n = len(out["mconf"])
     print(f"{args.model}: {n} matches" + (f", {int(out['inliers'].sum())} inliers ({out['ransac_backend']} RANSAC)" if "inliers" in out else " (fewer than 8: no RANSAC)"))
     for k in range(min(n, 5)):
@@ -293,7 +302,8 @@ def main(argv=None):
     if args.out is not None:     # demo.py:537-540
         kp = out["mkpts0_f"]
         out["geom"] = compute_geom(out, device=kp.device if kp.is_cuda else None, ransac_solve=args.ransac_solve,
-                                   ransac_sampler=args.ransac_sampler)
+                                   ransac_sampler=args.ransac_sampler, ransac_refine=args.ransac_refine,
+                                   homography_refit="device" if kp.is_cuda and args.ransac_sampler == "device" else "host")
         if out["geom"].get("Homography") is None:
             print("  no homography (fewer than 8 matches, or no sample with 4 inliers): no _warp.png")
         else:

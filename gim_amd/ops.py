@@ -1710,6 +1710,49 @@ def recover_pose(E, x0, x1, mask=None, offsets=None, distance_thresh=1e9):
     return n_good, best, R, t, mask_out.view(torch.bool)
 
 
+def model_refit(kind, a, b, models, thr2, mask=None, offsets=None, rounds=1):
+    """Least-squares refit of a model on its inliers and up to `rounds` rounds of refit / re-score, one launch for one pair or a
+    batch (gim_model_refit; fp64, the arithmetic of pose.refit_ge).  kind 0: homographies b ~ H a (normalised DLT, transfer error);
+    kind 1: fundamental matrices b^T F a = 0 (normalised eight-point, rank 2, Sampson error).  One pair: a / b fp64 [P,2], models
+    fp64 [3,3], mask bool / uint8 [P] or None (None: the model's own mask under thr2) -> (model fp64 [3,3]: the last accepted refit,
+    or the input when none was; mask bool [P] of that model; counts int32 [2]: inliers at the start and at the end; accepted int32
+    []: rounds accepted).  B pairs: models [B,3,3], offsets int32 [B+1] over the concatenated points, mask [Ptot] -> [B,3,3],
+    [Ptot], [B,2], [B].  A model that is all zero or not finite: its pair is skipped -- zero model, mask and counts, accepted -1."""
+    kind, rounds = int(kind), int(rounds)
+    if kind not in (0, 1):
+        raise _lib.GimHipError(f"model_refit kind={kind}: 0 (homography) or 1 (fundamental matrix)")
+    if not 1 <= rounds <= 8:
+        raise _lib.GimHipError(f"model_refit rounds={rounds}: 1 <= rounds <= 8")
+    _req_cuda(a, b, models, mask, offsets)
+    single = offsets is None
+    if models.dtype != torch.float64 or models.shape != ((3, 3) if single else (models.shape[0], 3, 3)) or not models.is_contiguous():
+        raise _lib.GimHipError(f"model_refit models must be contiguous fp64 {'[3,3]' if single else '[B,3,3]'}, got {models.dtype} {tuple(models.shape)}")
+    B = 1 if single else models.shape[0]
+    offsets, P = _ransac_points(a, b, offsets, B)
+    if models.device != a.device:
+        raise _lib.GimHipError("model_refit models and points are on different devices")
+    if mask is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        if mask.dtype != torch.uint8 or mask.shape != (P,) or not mask.is_contiguous() or mask.device != a.device:
+            raise _lib.GimHipError(f"model_refit mask must be contiguous bool / uint8 [{P}] on the points' device")
+    dev = a.device
+    out = torch.empty(B, 3, 3, dtype=torch.float64, device=dev)
+    counts = torch.empty(B, 2, dtype=torch.int32, device=dev)
+    accepted = torch.empty(B, dtype=torch.int32, device=dev)
+    mask_out = torch.empty(P, dtype=torch.uint8, device=dev)
+    if B:
+        # without points nothing reads a, b or writes mask_out, but the entry point refuses a NULL pointer: 16 bytes stand in
+        pad = torch.empty(2, dtype=torch.float64, device=dev) if P == 0 else None
+        pa, pb, pm = (_p(pad),) * 3 if P == 0 else (_p(a), _p(b), _p(mask_out))
+        with torch.cuda.device(dev):
+            check(lib.gim_model_refit(kind, pa, pb, _p(offsets), B, _p(models), _p(mask) if mask is not None and P else None, float(thr2),
+                                      rounds, _p(out), pm, _p(counts), _p(accepted), _stream()), "gim_model_refit")
+    if single:
+        return out[0], mask_out.view(torch.bool), counts[0], accepted[0]
+    return out, mask_out.view(torch.bool), counts, accepted
+
+
 def _on(device, a, dtype):
     """a tensor argument as it is, anything else (an int, a list, an array) as a tensor of `dtype` on `device`"""
     return a if isinstance(a, torch.Tensor) else torch.as_tensor(np.atleast_1d(np.asarray(a)).astype(dtype), device=device)

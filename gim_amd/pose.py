@@ -727,6 +727,10 @@ class DeviceScorer:
         with self._torch.cuda.device(self.device):
             return self._ops.ransac_mask(self._up(M, np.float64), self.x0, self.x1, self.thr2, offsets=self.offsets).cpu().numpy()
 
+    def refit(self, M, rounds=1):
+        """gim_model_refit (kind 1: fundamental matrices in pixels) over the points held here -> `_device_refit`'s arrays"""
+        return _device_refit(self._ops, self._torch, 1, self.x0, self.x1, self.offsets, self.thr2, M, rounds)
+
 
 # ---- counter-based sampling and the per-step reduction (csrc/ransac_sample.h, csrc/ransac_records.hip restated) -----------------
 SAMPLERS = ("host", "philox", "device")
@@ -1133,6 +1137,11 @@ class DeviceFundamental:
             d_M = self._torch.from_numpy(np.ascontiguousarray(M, dtype=np.float64)).to(self.device)
             return self._ops.ransac_mask(d_M, self.x0, self.x1, self.thr2, offsets=self.offsets).cpu().numpy()
 
+    def refit(self, M, rounds=1):
+        """gim_model_refit (kind 1) over the points and offsets held here, from the models' own masks: M [3,3] / [B,3,3] ->
+        `_device_refit`'s arrays (models [B,3,3], mask bool [Ptot], counts [B,2], accepted [B]) after ONE copy"""
+        return _device_refit(self._ops, self._torch, 1, self.x0, self.x1, self.offsets, self.thr2, M, rounds)
+
 
 class DeviceEssential(DeviceFundamental):
     """A whole essential-matrix RANSAC step on the GPU, the twin of `DeviceFundamental` (csrc/essential.hip through
@@ -1147,6 +1156,9 @@ class DeviceEssential(DeviceFundamental):
     def __init__(self, x0, x1, thr2, device, offsets=None, recover=False, distance_thresh=1e9):
         super().__init__(x0, x1, thr2, device, offsets)
         self.recover_too, self.distance_thresh, self.poses = bool(recover), float(distance_thresh), None
+
+    def refit(self, M, rounds=1):
+        raise TypeError("essential matrices are not refitted (cv2.findEssentialMat(RANSAC) does not either)")
 
     def recover(self, models, masks=None):
         """gim_recover_pose over the points and offsets held here: models fp64 [3,3] / [B,3,3] and masks bool / uint8 [Ptot] (or
@@ -1177,7 +1189,8 @@ class DeviceEssential(DeviceFundamental):
         return (int(n_good[b, best[b]]) if best[b] >= 0 else 0), R[b], t[b]
 
 
-def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, solve="host", sampler="host"):
+def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, solve="host", sampler="host",
+                         refine=0):
     """Plain RANSAC over seven-point samples with the Sampson distance in pixels (the demo's geometry filter, demo.py:514-517;
     the reference's USAC_MAGSAC scoring is not restated).  -> (F [3,3] | None, mask [P])
     solve="host": `seven_point` (SVD null space, eigenvalues) on points Hartley-normalised once per call, the candidates mapped back
@@ -1186,7 +1199,11 @@ def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, 
     gim_fundamental_step per step (`DeviceFundamental`: elimination, a closed-form cubic, normalisation per sample; it rounds
     differently from `seven_point`, so its trajectory need not be the host's), the mask from gim_ransac_mask.
     solve="ge" (host only): the same RANSAC over `seven_point_ge`, the numpy restatement of the device solver -- its CPU oracle.
-    sampler: "host", "philox" or "device", as in find_essential_mat ("device" needs `device` and solve="device")."""
+    sampler: "host", "philox" or "device", as in find_essential_mat ("device" needs `device` and solve="device").
+    refine: 0 returns the RANSAC's best seven-point model and its mask (the default; every seeded result so far).  R in 1 .. 8 then
+    runs up to R rounds of local optimisation on it, the step USAC ends with: the normalised eight-point fit on the current inliers,
+    a fresh mask, kept while the inlier count does not fall (`refit_ge`).  With a device it is ONE gim_model_refit launch on the
+    points already there (with sampler="device" it also replaces the gim_ransac_mask call), with device=None `refit_ge` itself."""
     if solve not in ("host", "device", "ge"):
         raise ValueError(f"solve={solve!r}: host, device or ge")
     if solve == "device" and device is None:
@@ -1194,18 +1211,32 @@ def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, 
     if solve == "ge" and device is not None:
         raise ValueError("solve='ge' runs on the host: device must be None")
     _check_sampler(sampler, device, solve)
+    refine = _check_refine(refine)
     p0 = np.ascontiguousarray(p0, dtype=np.float64)
     p1 = np.ascontiguousarray(p1, dtype=np.float64)
     if sampler == "device":
-        return _ransac_on_device([(p0, p1)], DeviceFundamental, threshold, prob, max_iters, seed, device)[0][0]
+        return _ransac_on_device([(p0, p1)], DeviceFundamental, threshold, prob, max_iters, seed, device,
+                                 finish=_refit_finish(refine) if refine else None)[0][0]
     draw = _draw(sampler, seed, p0.shape[0], 7)
     if p0.shape[0] < 7:
         return None, np.zeros(p0.shape[0], dtype=bool)
+
+    def refined(found, dev):
+        F, mask = found
+        if not refine or F is None:
+            return found
+        if dev is None:
+            F, mask, _, _ = refit_ge(1, p0, p1, F, float(threshold) ** 2, rounds=refine)
+            return F, mask
+        models, mask, _, _ = dev.refit(F, refine)
+        return models[0], mask
+
     if solve == "ge":
-        return _ransac(p0, p1, seven_point_ge, 7, threshold, prob, max_iters, np.random.default_rng(seed), draw=draw)
+        return refined(_ransac(p0, p1, seven_point_ge, 7, threshold, prob, max_iters, np.random.default_rng(seed), draw=draw), None)
     if solve == "device":
         dev = DeviceFundamental(p0, p1, float(threshold) ** 2, device)
-        return _ransac(p0, p1, None, 7, threshold, prob, max_iters, np.random.default_rng(seed), scorer=dev, solve_idx=dev.solve, draw=draw)
+        return refined(_ransac(p0, p1, None, 7, threshold, prob, max_iters, np.random.default_rng(seed), scorer=dev, solve_idx=dev.solve,
+                               draw=draw), dev)
 
     def norm_T(p):
         c = p.mean(0)
@@ -1223,7 +1254,8 @@ def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, 
         return Fp / np.where(nrm > 0, nrm, 1.0)[..., None, None], v
 
     scorer = DeviceScorer(p0, p1, float(threshold) ** 2, device) if device is not None else None
-    return _ransac(p0, p1, solver, 7, threshold, prob, max_iters, np.random.default_rng(seed), s0=q0, s1=q1, scorer=scorer, draw=draw)
+    return refined(_ransac(p0, p1, solver, 7, threshold, prob, max_iters, np.random.default_rng(seed), s0=q0, s1=q1, scorer=scorer,
+                           draw=draw), scorer)
 
 
 class _DeferredSolve:
@@ -1239,11 +1271,12 @@ class _DeferredSolve:
         return self.models, self.valid
 
 
-def _lockstep_device(pairs, m, k, step_cls, threshold, prob, max_iters, seed, device, sampler="host", step_kw=None):
+def _lockstep_device(pairs, m, k, step_cls, threshold, prob, max_iters, seed, device, sampler="host", step_kw=None, finish=None):
     """The lockstep driver of find_fundamental_mat_batch and find_essential_mat_batch(solve="device"): samples of m points, k models
     per sample, `step_cls` (DeviceFundamental, DeviceEssential) over the concatenated points.  A step draws the samples of every
     unfinished pair on the host and solves and scores all of them in ONE launch (ragged point sets through offsets; a finished pair
     and the padding of a shorter step are index -1: invalid); one gim_ransac_mask call for all pairs ends the run.  step_kw: further keywords of `step_cls`.
+    finish: None, or finish(dev, models [B,3,3]) -> (models [B,3,3], masks [Ptot]) in place of that last call (`_refit_finish`).
     -> ([(model | None, mask)], the step object or None)"""
     pairs = [(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 2), np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 2)) for a, b in pairs]
     B = len(pairs)
@@ -1289,12 +1322,17 @@ def _lockstep_device(pairs, m, k, step_cls, threshold, prob, max_iters, seed, de
         models = np.zeros((B, 3, 3))
         for b in found:
             models[b] = best[b]
-        masks = dev.mask(models)
+        if finish is None:
+            masks = dev.mask(models)
+        else:
+            models, masks = finish(dev, models)
+            for b in found:
+                best[b] = models[b]
     return [(best[b], masks[offsets[b]:offsets[b + 1]] if best[b] is not None else np.zeros(offsets[b + 1] - offsets[b], dtype=bool))
             for b in range(B)], dev
 
 
-def _ransac_on_device(pairs, step_cls, threshold, prob, max_iters, seed, device, batch=250, step_kw=None):
+def _ransac_on_device(pairs, step_cls, threshold, prob, max_iters, seed, device, batch=250, step_kw=None, finish=None):
     """sampler="device": the RANSAC runs of `pairs` in lockstep with sampling, solving, scoring and the reduction of every step on
     the GPU.  A step is three launches of this library -- gim_ransac_sample, the step kernel of `step_cls` (DeviceHomography,
     DeviceFundamental, DeviceEssential), gim_ransac_records -- fed by ONE upload of 4 B words (first as int64, count, floor) and
@@ -1303,6 +1341,7 @@ def _ransac_on_device(pairs, step_cls, threshold, prob, max_iters, seed, device,
     only in a step that accepted a record of that pair; models, flags and counts are never read back in bulk.  A pair's ordinals run
     from 0 under the shared seed: its result is that of the single call, and that of sampler="philox" on the same device.
     Pairs with fewer than m points get (None, all-False) and, when no pair has more, nothing is launched.
+    finish: None, or finish(dev, models [B,3,3]) -> (models [B,3,3], masks [Ptot]) in place of the run's last mask call.
     -> ([(model [3,3] | None, mask [P_b] bool)], the step object or None -- `find_homography` takes its re-fit mask from it)"""
     m, k = step_cls.m, step_cls.k
     seed = _check_seed64(seed)
@@ -1350,7 +1389,12 @@ def _ransac_on_device(pairs, step_cls, threshold, prob, max_iters, seed, device,
         M = np.zeros((B, 3, 3))
         for b in found:
             M[b] = best[b]
-        masks = np.asarray(dev.mask(M), dtype=bool)
+        if finish is None:
+            masks = np.asarray(dev.mask(M), dtype=bool)
+        else:
+            M, masks = finish(dev, M)
+            for b in found:
+                best[b] = M[b]
     return [(best[b], masks[offsets[b]:offsets[b + 1]]) if best[b] is not None else none[b] for b in range(B)], dev
 
 
@@ -1362,7 +1406,8 @@ def _check_sampler(sampler, device, solve="device"):
         raise ValueError("sampler='device' draws and reduces on the GPU: it needs a device" + ("" if solve == "device" else " and solve='device'"))
 
 
-def find_fundamental_mat_batch(pairs, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, solve="device", sampler="host"):
+def find_fundamental_mat_batch(pairs, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, solve="device", sampler="host",
+                               refine=0):
     """`find_fundamental_mat(p0, p1, threshold, prob, max_iters, seed, device, solve="device")` for every (p0, p1) of `pairs`, run in
     lockstep as find_essential_mat_batch runs its pairs: a step draws the samples of every unfinished pair on the host and solves and
     scores all of them in ONE gim_fundamental_step launch (ragged point sets through offsets; a finished pair and the padding of a
@@ -1370,24 +1415,30 @@ def find_fundamental_mat_batch(pairs, threshold=1.0, prob=0.999999, max_iters=10
     default_rng(seed) and its own shrinking iteration bound, so its result is that of the single call.
     sampler: "philox" draws every pair's samples with `device_samples` on the host, "device" on the GPU, where each step is then
     reduced to its record samples (`_ransac_on_device`); a pair's result is again that of the single call with that sampler.
+    refine: that of find_fundamental_mat; R > 0 replaces the run's gim_ransac_mask call with ONE gim_model_refit launch over all
+    pairs (a pair without a model is skipped there, and a batch without any model launches nothing).
     -> [(F [3,3] | None, mask [P_b] bool)] in the order of `pairs`."""
     if solve != "device" or device is None:
         raise ValueError("find_fundamental_mat_batch runs solve='device' on a device")
     _check_sampler(sampler, device, solve)
+    refine = _check_refine(refine)
+    finish = _refit_finish(refine) if refine else None
     if sampler == "device":
-        return _ransac_on_device(pairs, DeviceFundamental, threshold, prob, max_iters, seed, device)[0]
-    return _lockstep_device(pairs, 7, 3, DeviceFundamental, threshold, prob, max_iters, seed, device, sampler)[0]
+        return _ransac_on_device(pairs, DeviceFundamental, threshold, prob, max_iters, seed, device, finish=finish)[0]
+    return _lockstep_device(pairs, 7, 3, DeviceFundamental, threshold, prob, max_iters, seed, device, sampler, finish=finish)[0]
 
 
-def verify_pairs(pairs_of_points, threshold=1.0, device=None, prob=0.999999, max_iters=10000, seed=0, batch=32, sampler="host"):
+def verify_pairs(pairs_of_points, threshold=1.0, device=None, prob=0.999999, max_iters=10000, seed=0, batch=32, sampler="host", refine=0):
     """Two-view verification of a pair list (the matches of a LightGlue / root_sift / dense pair list, in pixels) without OpenCV:
     `find_fundamental_mat_batch` over `batch` pairs per launch sequence -> [(F [3,3] | None, mask [P_b] bool)] in the list's order.
-    sampler: that of find_fundamental_mat_batch."""
+    sampler, refine: those of find_fundamental_mat_batch."""
     _check_sampler(sampler, device)
+    refine = _check_refine(refine)
     pairs_of_points = list(pairs_of_points)
     out = []
     for i in range(0, len(pairs_of_points), int(batch)):
-        out += find_fundamental_mat_batch(pairs_of_points[i:i + int(batch)], threshold, prob, max_iters, seed, device, sampler=sampler)
+        out += find_fundamental_mat_batch(pairs_of_points[i:i + int(batch)], threshold, prob, max_iters, seed, device, sampler=sampler,
+                                          refine=refine)
     return out
 
 
@@ -1565,8 +1616,13 @@ class DeviceHomography:
             d_M = self._torch.from_numpy(np.ascontiguousarray(M, dtype=np.float64)).to(self.device)
             return self._ops.homography_mask(d_M, self.src, self.dst, self.thr2, offsets=self.offsets).cpu().numpy()
 
+    def refit(self, M, rounds=1):
+        """gim_model_refit (kind 0) over the points and offsets held here, from the models' own masks: M [3,3] / [B,3,3] ->
+        `_device_refit`'s arrays (models [B,3,3], mask bool [Ptot], counts [B,2], accepted [B]) after ONE copy"""
+        return _device_refit(self._ops, self._torch, 0, self.src, self.dst, self.offsets, self.thr2, M, rounds)
 
-def find_homography(src, dst, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, sampler="host"):
+
+def find_homography(src, dst, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, sampler="host", refit="host"):
     """cv2.findHomography(src, dst, RANSAC, threshold, maxIters=max_iters, confidence=prob) restated: dst ~ H src
     -> (H [3, 3] with h33 = 1 | None, mask [P] bool).  Plain RANSAC over four-point samples with the forward transfer error in
     pixels; sampling and the shrinking iteration bound are `_ransac_steps`'.  Host path: `homography_4pt` and `transfer_error`.
@@ -1577,8 +1633,19 @@ def find_homography(src, dst, threshold=1.0, prob=0.999999, max_iters=10000, see
     Levenberg-Marquardt polish of the re-fit (HomographyRefineCallback) is NOT built, and neither is USAC_MAGSAC's scoring (the
     reference's demo asks for it; the mask here is RANSAC's).
     sampler: "host", "philox" or "device", as in find_essential_mat ("device" needs `device`; the solve is the device's whenever
-    a device is given)."""
+    a device is given).
+    refit: "host" re-fits with `homography_dlt` (LAPACK's SVD of the 2n x 9 system) and takes the second mask where the first was
+    taken (the default; every seeded result so far).  "device" (needs `device`) replaces both with ONE gim_model_refit launch of one
+    round on the points the step object holds, and one copy of H, the mask and the counts; with sampler="device" that launch also
+    replaces the gim_homography_mask call that ends the RANSAC.  "ge" (device=None) is the same on the host through `refit_ge`,
+    the CPU oracle of "device"."""
     _check_sampler(sampler, device)
+    if refit not in REFITS:
+        raise ValueError(f"refit={refit!r}: host, device or ge")
+    if refit == "device" and device is None:
+        raise ValueError("refit='device' runs gim_model_refit: it needs a device")
+    if refit == "ge" and device is not None:
+        raise ValueError("refit='ge' runs on the host: device must be None")
     src = np.ascontiguousarray(src, dtype=np.float64).reshape(-1, 2)
     dst = np.ascontiguousarray(dst, dtype=np.float64).reshape(-1, 2)
     P = src.shape[0]
@@ -1587,8 +1654,11 @@ def find_homography(src, dst, threshold=1.0, prob=0.999999, max_iters=10000, see
         return None, np.zeros(P, dtype=bool)
     thr2 = float(threshold) ** 2
     if sampler == "device":
-        found, dev = _ransac_on_device([(src, dst)], DeviceHomography, threshold, prob, max_iters, seed, device)
+        found, dev = _ransac_on_device([(src, dst)], DeviceHomography, threshold, prob, max_iters, seed, device,
+                                       finish=_refit_finish(1) if refit == "device" else None)
         H, mask = found[0]
+        if refit == "device":
+            return H, np.asarray(mask, dtype=bool)
     else:
         dev = DeviceHomography(src, dst, thr2, device) if device is not None else None
         H, mask = _ransac(src, dst, homography_4pt, 4, threshold, prob, max_iters, np.random.default_rng(seed), scorer=dev,
@@ -1596,6 +1666,12 @@ def find_homography(src, dst, threshold=1.0, prob=0.999999, max_iters=10000, see
     if H is None:
         return None, mask
     mask = np.asarray(mask, dtype=bool)
+    if refit == "device":
+        models, mask, _, _ = dev.refit(H, 1)
+        return models[0], mask
+    if refit == "ge":
+        H, mask, _, _ = refit_ge(0, src, dst, H, thr2, rounds=1)
+        return H, mask
     H2 = homography_dlt(src[mask], dst[mask])
     if H2 is not None:
         mask2 = (transfer_error(H2, src, dst) <= thr2) if dev is None else \
@@ -1778,6 +1854,203 @@ def recover_pose_ge(E, x0, x1, distance_thresh=1e9, mask=None, detail=False):
     k = 0 if (n[0] >= n[1] and n[0] >= n[2] and n[0] >= n[3]) else 1 if (n[1] >= n[2] and n[1] >= n[3]) else 2 if n[2] >= n[3] else 3
     out = (int(n[k]), cands[k][0], cands[k][1].copy(), goods[k])
     return out + (n, k) if detail else out
+
+
+# ---- least-squares refit on the inliers as the device computes it (csrc/model_refit_solve.h) -------------------------------------
+MR_SWEEPS9 = 8           # cyclic Jacobi sweeps over the 9 x 9 normal matrix
+MR_LANES = 256           # the lanes whose partial sums fix the summation order
+MR_MIN_POINTS = (4, 8)   # inliers a refit needs: homography, fundamental matrix
+MR_MAX_ROUNDS = 8
+REFITS = ("host", "device", "ge")
+
+
+def _mr_block_sum(terms, inl):
+    """the kernel's sum of terms [P, K] over the inliers `inl` [P]: lane l adds its points l, l + 256, ... in ascending order, a wave's
+    64 lanes are combined by the tree x[l] += x[l + o], o = 32 .. 1, the four wave totals are added in wave order -> [K]"""
+    P, K = terms.shape
+    rows = max(1, -(-P // MR_LANES))
+    pad = np.zeros((rows * MR_LANES, K))
+    pad[:P] = np.where(inl[:, None], terms, 0.0)             # a point outside the mask is never read: its NaN stays out
+    pad = pad.reshape(rows, MR_LANES, K)
+    acc = np.zeros((MR_LANES, K))
+    for r in range(rows):
+        acc = acc + pad[r]
+    w = acc.reshape(4, 64, K)
+    for o in (32, 16, 8, 4, 2, 1):
+        w = w[:, :o] + w[:, o:2 * o]
+    return ((w[0, 0] + w[1, 0]) + w[2, 0]) + w[3, 0]
+
+
+def _mr_solve(kind, a, b, inl, sweeps=MR_SWEEPS9, detail=False):
+    """steps 2 to 6 of gim_model_refit on the points a, b [P, 2] whose `inl` [P] is set (at least one, all finite) -> the model
+    [3, 3] or None (a side without extent, a result that is not finite, a zero norm or h33 == 0).  detail=True: (model, off) with
+    off = the largest off-diagonal |entry| of the 9 x 9 matrix after the sweeps over its largest diagonal |entry|."""
+    n = int(inl.sum())
+    with np.errstate(all="ignore"):
+        s4 = _mr_block_sum(np.concatenate([a, b], 1), inl)
+        ca, cb = s4[:2] / n, s4[2:] / n
+        pa, pb = a - ca, b - cb
+        dist = np.stack([np.sqrt(pa[:, 0] * pa[:, 0] + pa[:, 1] * pa[:, 1]), np.sqrt(pb[:, 0] * pb[:, 0] + pb[:, 1] * pb[:, 1])], 1)
+        md = _mr_block_sum(dist, inl) / n
+        if not (md[0] > 0.0 and md[1] > 0.0 and np.isfinite(md).all()):
+            return (None, 0.0) if detail else None
+        sa, sb = np.sqrt(2.0) / md[0], np.sqrt(2.0) / md[1]
+        x, y, u, v = pa[:, 0] * sa, pa[:, 1] * sa, pb[:, 0] * sb, pb[:, 1] * sb
+        o, z = np.ones_like(x), np.zeros_like(x)
+        if kind == 0:
+            r1 = [x, y, o, z, z, z, -u * x, -u * y, -u]
+            r2 = [z, z, z, x, y, o, -v * x, -v * y, -v]
+            terms = np.stack([r1[i] * r1[j] + r2[i] * r2[j] for i in range(9) for j in range(i, 9)], 1)
+        else:
+            r = [u * x, u * y, u, v * x, v * y, v, x, y, o]
+            terms = np.stack([r[i] * r[j] for i in range(9) for j in range(i, 9)], 1)
+        A = np.zeros((9, 9))
+        A[np.triu_indices(9)] = _mr_block_sum(terms, inl)
+        d, vec = _rp_jacobi(A, sweeps)
+        off = np.abs(np.triu(A, 1)).max() / max(np.abs(d).max(), 1e-300)
+        f = vec[:, int(np.argmin(d))].reshape(3, 3).copy()                  # the first smallest, as the device's strict <
+        if kind == 1:
+            g = np.array([[(f[0, i] * f[0, j] + f[1, i] * f[1, j]) + f[2, i] * f[2, j] for j in range(3)] for i in range(3)])
+            d3, v3 = _rp_jacobi(g, RP_SWEEPS3)
+            for i, j in ((0, 1), (0, 2), (1, 2)):
+                if d3[j] > d3[i]:
+                    d3[[i, j]] = d3[[j, i]]
+                    v3[:, [i, j]] = v3[:, [j, i]]
+            v2 = v3[:, 2] / np.sqrt(_rp_dot3(v3[:, 2], v3[:, 2]))
+            for i in range(3):
+                f[i] = f[i] - _rp_dot3(f[i], v2) * v2
+        m = np.stack([f[:, 0] * sa, f[:, 1] * sa, f[:, 2] - sa * (f[:, 0] * ca[0] + f[:, 1] * ca[1])], 1)          # f Ta
+        if kind == 0:
+            out = np.stack([m[0] / sb + cb[0] * m[2], m[1] / sb + cb[1] * m[2], m[2]])                              # Tb^-1 (f Ta)
+            scale = out[2, 2]
+        else:
+            out = np.stack([sb * m[0], sb * m[1], m[2] - sb * (cb[0] * m[0] + cb[1] * m[1])])                       # Tb^T (f Ta)
+            ss = 0.0
+            for e in out.ravel():
+                ss = ss + e * e
+            scale = np.sqrt(ss)
+        if not (scale != 0.0 and np.isfinite(scale)):
+            return (None, off) if detail else None
+        out = out / scale
+    if not np.isfinite(out).all():
+        out = None
+    return (out, off) if detail else out
+
+
+def _mr_points(a, b, n_min):
+    a = np.asarray(a, dtype=np.float64).reshape(-1, 2)
+    b = np.asarray(b, dtype=np.float64).reshape(-1, 2)
+    if a.shape[0] < n_min or not (np.isfinite(a).all() and np.isfinite(b).all()):
+        return None
+    return a, b
+
+
+def homography_dlt_ge(src, dst):
+    """`homography_dlt` in the arithmetic of gim_model_refit (kind 0): the 9 x 9 normal matrix of the normalised system summed in
+    the kernel's order, the eigenvector of its smallest eigenvalue by cyclic Jacobi with MR_SWEEPS9 sweeps in place of LAPACK's SVD
+    -> H [3, 3] with h33 = 1, or None (fewer than 4 points, a coordinate that is not finite, a degenerate set)."""
+    pts = _mr_points(src, dst, 4)
+    return None if pts is None else _mr_solve(0, pts[0], pts[1], np.ones(pts[0].shape[0], dtype=bool))
+
+
+def eight_point_ge(x0, x1):
+    """The normalised eight-point algorithm (Hartley 1997; OpenCV's run8Point) in the arithmetic of gim_model_refit (kind 1):
+    x1^T F x0 = 0 over n >= 8 correspondences, F of rank 2 and unit Frobenius norm, or None."""
+    pts = _mr_points(x0, x1, 8)
+    return None if pts is None else _mr_solve(1, pts[0], pts[1], np.ones(pts[0].shape[0], dtype=bool))
+
+
+def refit_ge(kind, a, b, model, thr2, mask=None, rounds=1, detail=False):
+    """gim_model_refit for one pair in numpy (include/gim_hip.h is the contract, csrc/model_refit_solve.h the code) -- the CPU oracle
+    of ops.model_refit.  kind 0: b ~ H a under `transfer_error`; kind 1: b^T F a = 0 under `sampson_error`.  Starting from `model`
+    and `mask` (None: the model's own mask under thr2), up to `rounds` times: refit on the current inliers (`_mr_solve`), take the
+    candidate's mask, keep the candidate iff it has no fewer inliers; stop at the first candidate that cannot be made, is rejected or
+    reproduces the current mask.  -> (model [3, 3], mask bool [P], counts (start, final), accepted); a model that is all zero or not
+    finite: (zeros, all-False, (0, 0), -1).
+    detail=True adds a dict: `models` the models whose error was compared with thr2 (the start when mask is None, then every
+    candidate), `counts` their inlier counts, `margin` [P] = the smallest |error - thr2| / thr2 of each point under those models (a
+    point is decidable when it is at least 1e-6), `off` the Jacobi off-diagonal mass of every solve, `stop` why the loop ended."""
+    if kind not in (0, 1):
+        raise ValueError(f"kind={kind!r}: 0 (homography) or 1 (fundamental matrix)")
+    rounds = int(rounds)
+    if not 1 <= rounds <= MR_MAX_ROUNDS:
+        raise ValueError(f"rounds={rounds}: 1 <= rounds <= {MR_MAX_ROUNDS}")
+    a = np.asarray(a, dtype=np.float64).reshape(-1, 2)
+    b = np.asarray(b, dtype=np.float64).reshape(-1, 2)
+    P = a.shape[0]
+    model = np.asarray(model, dtype=np.float64).reshape(3, 3)
+    thr2 = float(thr2)
+    error = transfer_error if kind == 0 else sampson_error
+    info = dict(models=[], counts=[], margin=np.full(P, np.inf), off=[], stop="skipped")
+
+    def score(M):
+        with np.errstate(all="ignore"):
+            e = error(M, a, b)
+            info["margin"] = np.fmin(info["margin"], np.where(np.isfinite(e), np.abs(e - thr2) / max(thr2, 1e-300), np.inf))
+            m = e <= thr2
+        info["models"].append(M)
+        info["counts"].append(int(m.sum()))
+        return m
+
+    if not (np.isfinite(model).all() and (model != 0.0).any()):
+        out = (np.zeros((3, 3)), np.zeros(P, dtype=bool), (0, 0), -1)
+        return out + (info,) if detail else out
+    cur = model.copy()
+    cur_mask = score(cur) if mask is None else np.asarray(mask).ravel() != 0
+    n = n0 = int(cur_mask.sum())
+    accepted, info["stop"] = 0, "rounds"
+    for _ in range(rounds):
+        if n < MR_MIN_POINTS[kind]:
+            info["stop"] = "few"
+            break
+        if not (np.isfinite(a[cur_mask]).all() and np.isfinite(b[cur_mask]).all()):
+            info["stop"] = "nonfinite"
+            break
+        cand, off = _mr_solve(kind, a, b, cur_mask, detail=True)
+        info["off"].append(off)
+        if cand is None:
+            info["stop"] = "degenerate"
+            break
+        cand_mask = score(cand)
+        nc = int(cand_mask.sum())
+        if nc < n:
+            info["stop"] = "rejected"
+            break
+        fixed = np.array_equal(cand_mask, cur_mask)
+        cur, cur_mask, n, accepted = cand, cand_mask, nc, accepted + 1
+        if fixed:
+            info["stop"] = "fixed"
+            break
+    out = (cur, cur_mask, (n0, n), accepted)
+    return out + (info,) if detail else out
+
+
+def _check_refine(refine):
+    refine = int(refine)
+    if not 0 <= refine <= MR_MAX_ROUNDS:
+        raise ValueError(f"refine={refine}: 0 (none) or 1 .. {MR_MAX_ROUNDS} rounds")
+    return refine
+
+
+def _device_refit(ops, torch, kind, a, b, offsets, thr2, M, rounds):
+    """ops.model_refit on points the device holds, from the models' own masks; ONE copy brings models, counts, accepted and the
+    mask back -> numpy (models [B, 3, 3], mask bool [Ptot], counts [B, 2], accepted [B])"""
+    with torch.cuda.device(a.device):
+        d_M = torch.from_numpy(np.ascontiguousarray(M, dtype=np.float64)).to(a.device)
+        models, mask, counts, accepted = ops.model_refit(kind, a, b, d_M, thr2, offsets=offsets, rounds=rounds)
+        B = 1 if offsets is None else d_M.shape[0]
+        down = torch.cat([models.reshape(-1).view(torch.uint8), torch.cat([counts.reshape(B, 2), accepted.reshape(B, 1)], 1).reshape(-1).view(torch.uint8),
+                          mask.view(torch.uint8)]).cpu().numpy()
+    ca = down[72 * B:84 * B].view(np.int32).reshape(B, 3)
+    return down[:72 * B].view(np.float64).reshape(B, 3, 3).copy(), down[84 * B:].view(bool).copy(), ca[:, :2].copy(), ca[:, 2].copy()
+
+
+def _refit_finish(rounds):
+    """the `finish` hook of `_lockstep_device` / `_ransac_on_device`: the refit's models and masks in place of the RANSAC's"""
+    def finish(dev, M):
+        models, masks, _, _ = dev.refit(M, rounds)
+        return models, masks
+    return finish
 
 
 def backend():

@@ -239,12 +239,15 @@ def _keypoints(matcher_out):
     return k0, k1
 
 
-def label_pair(matcher_out, *, device, affine=None, vratio=1.0, threshold=0.5, confidence=0.999999, max_iters=100000, seed=0):
+def label_pair(matcher_out, *, device, affine=None, vratio=1.0, threshold=0.5, confidence=0.999999, max_iters=100000, seed=0,
+               refine=0):
     """The tail of a labelling step (video_preprocessor.py:513-555) for one frame pair -> label fp32 [n,4] on the device.
     matcher_out: a matcher's result dict (`mkpts0_f` / `mkpts1_f`, matched keypoints [n,2] in pixels) or a (k0, k1) pair.
       1. ops.label_pack with moved_thr = 1 drops static matches (watermarks, line 516);
       2. pose.find_fundamental_mat(solve="device", sampler="device") on the survivors: PLAIN RANSAC with the Sampson distance where
          the reference calls cv2.findFundamentalMat(USAC_MAGSAC, 0.5, 0.999999, 100000) -- MAGSAC's scoring is not restated;
+         refine = R in 1 .. 8 adds the step USAC ends with, up to R rounds of eight-point refit on the inliers in the launch that
+         takes the mask (pose.find_fundamental_mat's `refine`; 0, the default, keeps the minimal-sample model's mask);
       3. ops.label_pack with the inlier mask and the rescale: `affine` (sx0, sy0, ox0, oy0, sx1, sy1, ox1, oy1) and `vratio` of
          line 549, or `vratio` alone (line 552).
     Fewer than 7 survivors, or no model: an empty label, without the second launch."""
@@ -263,7 +266,7 @@ def label_pair(matcher_out, *, device, affine=None, vratio=1.0, threshold=0.5, c
         moved = moved[:n]
         pts = moved.cpu().numpy().astype(np.float64)
         F, mask = pose.find_fundamental_mat(pts[:, :2], pts[:, 2:], threshold=threshold, prob=confidence, max_iters=max_iters, seed=seed,
-                                            device=device, solve="device", sampler="device")
+                                            device=device, solve="device", sampler="device", refine=refine)
         if F is None or not mask.any():
             return empty
         m0, m1 = moved[:, :2].contiguous(), moved[:, 2:].contiguous()

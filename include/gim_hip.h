@@ -1153,6 +1153,51 @@ int gim_recover_pose(const double* E, const double* x0, const double* x1, const 
                      gim_stream_t stream);
 
 /* ======================================================================================================
+ * Least-squares refit of H and F on their inliers, and local optimisation (added within ABI revision 115: no existing structure or
+ * prototype changed with it).  The reference filters matches with cv2.findHomography(..., USAC_MAGSAC, ...) (demo.py:197-217) and
+ * cv2.findFundamentalMat(..., USAC_MAGSAC, ...) (demo.py:514-517, datasets/walk/walk.py:295); both end with a least-squares fit on
+ * the inliers (HomographyEstimatorCallback::runKernel, run8Point: A^T A and its eigenvectors).  Here the points are those the step
+ * entry points above already hold.  MAGSAC's scoring and findHomography's Levenberg-Marquardt polish are not built.
+ * ====================================================================================================== */
+
+/* Refit of one model per pair for B pairs in ONE launch, one workgroup of 256 lanes per pair.  All pointers are DEVICE memory.
+ * kind 0: homographies, b ~ H a (normalised DLT, the forward transfer error of gim_homography_mask); kind 1: fundamental matrices,
+ * b^T F a = 0 (normalised eight-point algorithm with rank 2 enforced, the Sampson error of gim_ransac_mask).  a, b fp64 [Ptot][2]
+ * (16-byte aligned) and offsets int32 [B + 1] as in gim_homography_step / gim_fundamental_step (trusted); models_in fp64 [B][3][3]
+ * row-major; mask_in uint8 [Ptot] (a non-zero byte: an inlier; it must not overlap mask_out) or NULL: the starting mask is
+ * models_in's own under thr2; 1 <= rounds <= 8.  fp64 throughout, real arithmetic only, no fast-math, no atomics, every loop
+ * bounded (pose.refit_ge is this arithmetic in numpy, csrc/model_refit_solve.h the code).  The current model starts as models_in[b],
+ * the current mask as the starting mask; up to `rounds` times:
+ *   1. fewer current inliers than 4 (kind 0) or 8 (kind 1), or an inlier coordinate that is not finite: stop;
+ *   2. Hartley's normalisation of both sides over the inliers: centre = sum / n, then scale = sqrt(2) / (sum of the distances to the
+ *      centre / n); a mean distance that is zero or not finite: stop;
+ *   3. the 45 upper-triangle entries of A^T A: kind 0 two rows per inlier, (x, y, 1, 0, 0, 0, -u x, -u y, -u) and (0, 0, 0, x, y,
+ *      1, -v x, -v y, -v); kind 1 one row, (u x, u y, u, v x, v y, v, x, y, 1), with (x, y) / (u, v) the normalised point of a / b.
+ *      Every sum over the inliers (here and in 2) has ONE order: lane l adds its points l, l + 256, ... ascending, the 64 lanes of a
+ *      wave are combined by the tree x[l] += x[l + o], o = 32, 16, .., 1, the four wave totals are added in wave order -- a pair's
+ *      result depends neither on B nor on its place in the batch;
+ *   4. the eigenvector of the smallest eigenvalue (the first smallest diagonal entry) by cyclic Jacobi, 8 sweeps over the 36 planes
+ *      in row-major order, Rutishauser's rotation, a zero off-diagonal entry skipped;
+ *   5. kind 1: f - (f v2) v2^T with v2 the unit eigenvector of the smallest eigenvalue of f^T f (the 3 x 3 Jacobi iteration of
+ *      gim_recover_pose): the smallest singular value set to zero;
+ *   6. de-normalised with T = [s, 0, -s cx; 0, s, -s cy; 0, 0, 1]: kind 0 Tb^-1 h Ta scaled to h33 = 1, kind 1 Tb^T f Ta scaled to
+ *      unit Frobenius norm; a result that is not finite, a zero norm or h33 == 0: stop;
+ *   7. the candidate's mask over every point of the pair, with the error and the comparison of gim_homography_mask (kind 0) or
+ *      gim_ransac_mask (kind 1), and its count.  The candidate replaces the current model and mask iff its count is not below the
+ *      current count; a rejected candidate stops the loop; a candidate whose mask equals the current mask byte for byte is accepted
+ *      and then stops the loop (a fixed point).
+ * models_out fp64 [B][3][3]: the last accepted candidate, or models_in[b] when none was; mask_out uint8 [Ptot]: the current mask
+ * at the end, 0 / 1; counts int32 [B][2]: the inliers of the starting mask and of mask_out; accepted int32 [B]: the candidates
+ * accepted.  Everything is FULLY written for every pair (no memset by the caller), nothing outside [offsets[0], offsets[B]) of
+ * mask_out.  A models_in[b] with an entry that is not finite, or all zero: the pair is skipped -- models_out = 0, its mask_out 0,
+ * counts 0, accepted = -1.  B == 0 returns without touching anything.  Refused before a launch: kind outside {0, 1}, rounds outside
+ * 1 .. 8, a NULL pointer other than mask_in, a / b not 16-byte aligned, models_in / models_out not 8-byte or an int32 array not
+ * 4-byte aligned, B > 65535. */
+int gim_model_refit(int kind, const double* a, const double* b, const int32_t* offsets, int B, const double* models_in,
+                    const uint8_t* mask_in, double thr2, int rounds, double* models_out, uint8_t* mask_out, int32_t* counts,
+                    int32_t* accepted, gim_stream_t stream);
+
+/* ======================================================================================================
  * Video pseudo-labels (added within ABI revision 115: no existing structure or prototype changed with them).  A label is an fp32
  * [n][4] array of matches (x0, y0, x1, y1) between two frames.  The reference links the labels of frames a->b and b->c into a->c
  * through the pixels they share in b (datasets/walk/walk.py:29 create_table, :217-247 link, with Python dicts and sets on DataLoader
