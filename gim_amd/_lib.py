@@ -236,6 +236,10 @@ PROTOTYPES = {
     "gim_label_link_ws_bytes": (c_int64, [c_int] * 2),
     "gim_label_link": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 2 + [c_int] + [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 6),
     "gim_label_pack": (c_int, [c_void_p] * 3 + [c_int, c_float, c_void_p, ctypes.c_double] + [c_void_p] * 3),
+    # frame preparation of the video labeller: crop, area resize, class mask and the matchers' inputs (added within ABI revision 115)
+    "gim_frame_prep_tile": (c_int, [c_int] * 4 + [c_void_p] * 2),
+    "gim_frame_prep": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] + [c_int] * 2 + [c_void_p] * 3 + [c_int] + [c_void_p] * 2 + [c_int]
+                       + [c_void_p] * 9),
 }
 
 

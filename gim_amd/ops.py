@@ -2208,3 +2208,77 @@ def label_pack(k0, k1, keep=None, moved_thr=0.0, affine=None, vratio=1.0, out=No
                                  a.ctypes.data_as(ctypes.c_void_p) if a is not None else None, float(vratio), _p(out) if n else None, _p(count),
                                  _stream()), "gim_label_pack")
     return out, count[0]
+
+
+# ---- frame preparation of the video labeller (gim_amd/frame_prep.py) -----------------------------------------------
+class FramePrepResult(NamedTuple):
+    buffers: dict                      # output name -> the flat ragged buffer of the batch (absent: no job asked for it)
+    kept: Optional[torch.Tensor]       # int32 [J]: the sum of every job's mask, or None
+    plan: object                       # frame_prep.Plan: the tables and every job's (offset, shape) per output
+
+    def get(self, job, name):
+        """the output `name` of job `job`, a view of the batch's buffer in its own shape"""
+        off, shape = self.plan.views[job][name]
+        n = int(np.prod(shape))
+        return self.buffers[name][off:off + n].view(shape)
+
+
+def frame_prep(frames, seg, exclude, jobs, kept=True, buffers=None, guard=0):
+    """J jobs of crop + area resize + class mask + the matchers' inputs in one launch (gim_frame_prep; the reference's
+    video_preprocessor.py:292-366, :406-493, :603-621).  frames uint8 [S,H,W,3] RGB; seg uint8 [S,Hs,Ws] class maps or None (no job
+    may ask for a mask then, and `kept` is not computed); exclude: a uint8 [256] device tensor (non-zero: excluded), or what
+    frame_prep.exclude_table takes; jobs: a sequence of (slot, box (x0, y0, x1, y1) | None, (wn, hn), flags) with frame_prep's OUT_*
+    flags.  -> FramePrepResult: ragged flat buffers per output, get(job, name) for a job's view, kept int32 [J].  Every output equals
+    frame_prep.frame_prep_np bit for bit.  An empty job list launches nothing.  buffers: {name: flat tensor} to write into instead of
+    fresh ones (at least plan.elems long each); guard: elements left untouched in front of and behind every job's output."""
+    from . import frame_prep as fp
+    _req_cuda(frames, seg)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise _lib.GimHipError(f"frame_prep frames must be contiguous uint8 [S,H,W,3], got {frames.dtype} {tuple(frames.shape)}")
+    dev = frames.device
+    S, H, W = frames.shape[:3]
+    if seg is not None and (seg.dtype != torch.uint8 or seg.dim() != 3 or seg.shape[0] != S or not seg.is_contiguous() or seg.device != dev):
+        raise _lib.GimHipError(f"frame_prep seg must be contiguous uint8 [{S},Hs,Ws] on {dev}, got {seg.dtype} {tuple(seg.shape)} on {seg.device}")
+    jobs = list(jobs)
+    for slot, _, _, flags in jobs:
+        if not 0 <= int(slot) < S:
+            raise _lib.GimHipError(f"frame_prep: slot {slot} is outside [0, {S})")
+        if seg is None and int(flags) & (fp.OUT_MASK | fp.OUT_MASK8 | fp.MASKED):
+            raise _lib.GimHipError("frame_prep: a job asks for a mask and there are no class maps")
+    try:
+        pl = fp.plan((H, W), jobs, guard=int(guard))
+    except ValueError as e:
+        raise _lib.GimHipError(str(e)) from e
+    J, n_work = pl.jobs.shape[0], pl.work.shape[0]
+    dtypes = (torch.uint8, torch.uint8, torch.uint8, torch.float32, torch.float32, torch.float32)
+    if buffers is None:
+        bufs = {name: torch.empty(n, dtype=dt, device=dev) for name, n, dt in zip(fp.OUTPUTS, pl.elems, dtypes) if n}
+    else:
+        bufs = {name: buffers[name] for name, n in zip(fp.OUTPUTS, pl.elems) if n}
+        for name, n, dt in zip(fp.OUTPUTS, pl.elems, dtypes):
+            t = bufs.get(name)
+            if t is not None and (t.dtype != dt or t.dim() != 1 or t.shape[0] < n or not t.is_contiguous() or t.device != dev):
+                raise _lib.GimHipError(f"frame_prep buffers[{name!r}] must be contiguous {dt} [>= {n}] on {dev}")
+    want_kept = bool(kept) and seg is not None
+    kept_t = torch.empty(J, dtype=torch.int32, device=dev) if want_kept else None
+    if J == 0:
+        return FramePrepResult(bufs, kept_t, pl)
+    if isinstance(exclude, torch.Tensor):
+        if exclude.dtype != torch.uint8 or exclude.shape != (256,) or not exclude.is_contiguous() or exclude.device != dev:
+            raise _lib.GimHipError(f"frame_prep exclude must be contiguous uint8 [256] on {dev}")
+        excl = exclude
+    else:
+        excl = torch.from_numpy(fp.exclude_table(exclude if exclude is not None else [])).to(dev)
+    # one upload: the job table and, behind it (J * 128 bytes: 16-byte aligned), the work table
+    host = np.concatenate([pl.jobs.reshape(-1), np.ascontiguousarray(pl.work).reshape(-1).view(np.int64)])
+    tab = torch.from_numpy(host).to(dev)
+    jobs_dev, work_dev = tab, tab[J * fp.JOB_WORDS:]
+    elems = np.asarray([bufs[name].shape[0] if name in bufs else 0 for name in fp.OUTPUTS], dtype=np.int64)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+    with torch.cuda.device(dev):
+        with _Timed("frame_prep", 0.0):
+            check(lib.gim_frame_prep(_p(frames), S, H, W, _p(seg), seg.shape[1] if seg is not None else 0,
+                                     seg.shape[2] if seg is not None else 0, _p(excl), vp(pl.jobs), _p(jobs_dev), J, vp(pl.work),
+                                     _p(work_dev), n_work, vp(elems), *(_p(bufs.get(name)) for name in fp.OUTPUTS), _p(kept_t),
+                                     _stream()), "gim_frame_prep")
+    return FramePrepResult(bufs, kept_t, pl)

@@ -50,3 +50,32 @@ def segment(rgb, size, device, segmentation_module):
     img = read_segmentation_image(rgb, size)
     out = segmentation_module.segment(img[None].to(device), tuple(img.shape[1:]))
     return out[0].cpu().numpy().astype(np.uint8)
+
+
+def resized_wh(width, height, size):
+    """read_deeplab_image's target (hloc/utils/__init__.py:19-31): the long side brought down to `size`, or the frame's own size"""
+    if max(width, height) <= size:
+        return width, height
+    if width > height:
+        return size, int(size * height / width)
+    return int(size * width / height), size
+
+
+@torch.no_grad()
+def segment_device(frames_u8, size, segmentation_module):
+    """`segment` without a host pass: frames_u8 uint8 [S, H, W, 3] (or [H, W, 3]) on the device -> uint8 [S, H', W'] class maps on the
+    device at the long-side-`size` resolution.  The input of the module is ops.frame_prep's `norm` output (gim_amd/frame_prep.py: the
+    written area-resize contract, then (x / 255 - mean) / std), one launch for all frames, then `segmentation_module.segment` per
+    frame.  Where the frame is not resized this is `segment`'s input bit for bit; where it is, `segment` resizes with OpenCV or
+    average pooling and the inputs differ as those resizes differ from the contract."""
+    from .. import frame_prep as fp
+    from .. import ops
+    if frames_u8.dim() == 3:
+        frames_u8 = frames_u8[None]
+    S, H, W = frames_u8.shape[:3]
+    wn, hn = resized_wh(W, H, size)
+    r = ops.frame_prep(frames_u8.contiguous(), None, None, [(s, None, (wn, hn), fp.OUT_NORM) for s in range(S)], kept=False)
+    out = torch.empty(S, hn, wn, dtype=torch.uint8, device=frames_u8.device)
+    for s in range(S):
+        out[s] = segmentation_module.segment(r.get(s, "norm")[None], (hn, wn))[0].to(torch.uint8)
+    return out

@@ -10,13 +10,21 @@ one documented difference: rows whose key is not finite or lies outside [0, widt
 reference would still join them.  Everything else -- which rows join, their partners, their order, the copied bits -- is the
 reference's (tests/label_link_oracle.py holds the dict / set formulation the tests compare against).
 
+`FrameBank`, `prepare_pair` and `label_pair_list` are the loop in front of that tail (video_preprocessor.py:255-566 without decoding):
+frames uploaded and segmented once, both sides of a pair prepared in one launch (gim_amd/frame_prep.py, csrc/frame_prep.hip), the
+matcher behind a `match(inputs)` callable, the reference's files.
+
 Not here: video decoding and frame selection, the pair-id selection of walk.py:115-128, the debug figure, MAGSAC scoring
-(`label_pair` runs plain RANSAC), and a lockstep `propagate` over many pairs (ops.label_link takes B links per call for it).
+(`label_pair` runs plain RANSAC), the SIFT detector (OpenCV's, where it imports), and a lockstep `propagate` over many pairs
+(ops.label_link takes B links per call for it).
 """
 import collections
 import os
 
 import numpy as np
+
+from ._lib import GimHipError  # noqa: F401
+from .bank import SlotBank
 
 LABEL_MAX_KEY = 1 << 24
 
@@ -273,3 +281,280 @@ def label_pair(matcher_out, *, device, affine=None, vratio=1.0, threshold=0.5, c
         keep = torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8)).to(device)
         out, count = ops.label_pack(m0, m1, keep=keep, affine=affine, vratio=vratio)
         return out[:int(count.item())]
+
+
+# ---- frames on the device, the inputs of a pair, the labelling loop ---------------------------------------------------------------------
+METHODS = ("GIM_DKM", "GIM_LOFTR", "GIM_GLUE", "SIFT")
+
+
+class FrameBank(SlotBank):
+    """The frames of a video by frame index: uint8 [S, H, W, 3] RGB and their class maps uint8 [S, Hs, Ws], uploaded and segmented
+    ONCE per frame however many pairs name it (the reference segments on first use and caches on disk, video_preprocessor.py:309-340).
+    LRU eviction over `capacity_frames` slots (gim_amd/bank.py); a pair that names an evicted frame raises before any launch.
+    device=None keeps numpy arrays: the host path of `prepare_pair` / `label_pair_list` (frame_prep_np), which needs no device.
+    module: a gim_amd.semseg SegmentationModule; `put` then segments the frame on the device at the long-side-`seg_size` resolution
+    (semseg.segment_device).  Without one, `put` takes the class map (`seg=`), at any resolution, one resolution per bank."""
+
+    def __init__(self, capacity_frames, device=None, module=None, seg_size=720):
+        super().__init__(capacity_frames, "frame bank")
+        if module is not None and device is None:
+            raise ValueError("frame bank: segmenting needs a device")
+        self.device = self.resolve_device(device) if device is not None else None
+        self.module, self.seg_size = module, int(seg_size)
+        self.frames = self.seg = None
+
+    def _slab(self, shape):
+        if self.device is None:
+            return np.zeros(shape, dtype=np.uint8)
+        import torch
+        return torch.zeros(shape, dtype=torch.uint8, device=self.device)
+
+    def put(self, idx, frame_u8, seg=None):
+        """frame idx: uint8 [H, W, 3] RGB (array or tensor), uploaded once; seg: its uint8 [Hs, Ws] class map, or None: segmented here
+        when the bank has a module, else every pixel counts as class 0.  Returns the slot."""
+        frame = frame_u8 if not isinstance(frame_u8, np.ndarray) else np.ascontiguousarray(frame_u8)
+        if tuple(frame.shape[2:]) != (3,) or len(frame.shape) != 3 or str(frame.dtype).split(".")[-1] != "uint8":
+            raise ValueError(f"frame bank: a frame is uint8 [H, W, 3], got {frame.dtype} {tuple(frame.shape)}")
+        H, W = int(frame.shape[0]), int(frame.shape[1])
+        if self.frames is None:
+            self.frames = self._slab((self.capacity, H, W, 3))
+        elif tuple(self.frames.shape[1:3]) != (H, W):
+            raise ValueError(f"frame bank: holds {tuple(self.frames.shape[1:3])} frames, got {(H, W)}")
+        if self.device is None:
+            frame_d = np.asarray(frame)
+            seg_d = None if seg is None else np.ascontiguousarray(seg, dtype=np.uint8)
+        else:
+            import torch
+            frame_d = (frame if isinstance(frame, torch.Tensor) else torch.from_numpy(frame)).to(self.device)
+            if seg is not None:
+                seg_d = (seg if isinstance(seg, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(seg, dtype=np.uint8))).to(self.device)
+            elif self.module is not None:
+                from . import semseg
+                with torch.cuda.device(self.device):
+                    seg_d = semseg.segment_device(frame_d, self.seg_size, self.module)[0]
+            else:
+                seg_d = None
+        if seg_d is None:
+            seg_d = self._slab((1, 1))
+        if len(seg_d.shape) != 2 or str(seg_d.dtype).split(".")[-1] != "uint8":
+            raise ValueError(f"frame bank: a class map is uint8 [Hs, Ws], got {seg_d.dtype} {tuple(seg_d.shape)}")
+        if self.seg is None:
+            self.seg = self._slab((self.capacity,) + tuple(seg_d.shape))
+        elif tuple(self.seg.shape[1:]) != tuple(seg_d.shape):
+            raise ValueError(f"frame bank: holds {tuple(self.seg.shape[1:])} class maps, got {tuple(seg_d.shape)}")
+        slot = self.reserve([int(idx)])[0]
+        self.frames[slot] = frame_d
+        self.seg[slot] = seg_d
+        return slot
+
+
+def pair_boxes(pts, frame_hw, resize_hw, df=8):
+    """video_preprocessor.py:296-303 / :321-328 for both sides of a cached label pts [n, 4]: per side the crop box (floor / ceil of
+    the label's extent), its size (w, h) and the target (w_new, h_new) = get_divisible_wh(get_resized_wh(w, h, resize_hw), df)
+    -> [(box (x0, y0, x1, y1), (w, h), (w_new, h_new))] * 2.  A box that is empty or leaves the frame raises ValueError."""
+    import math
+    from .frame_prep import get_divisible_wh, get_resized_wh
+    pts = np.asarray(pts).reshape(-1, 4)
+    if len(pts) == 0:
+        raise ValueError("pair_boxes: an empty label has no extent")
+    out = []
+    for c in (0, 2):
+        x0, x1 = math.floor(pts[:, c].min()), math.ceil(pts[:, c].max())
+        y0, y1 = math.floor(pts[:, c + 1].min()), math.ceil(pts[:, c + 1].max())
+        if not (0 <= x0 < x1 <= frame_hw[1] and 0 <= y0 < y1 <= frame_hw[0]):
+            raise ValueError(f"pair_boxes: the label's extent {(x0, y0, x1, y1)} is empty or leaves the {frame_hw[1]} x {frame_hw[0]} frame")
+        w, h = x1 - x0, y1 - y0
+        w_new, h_new = get_divisible_wh(*get_resized_wh(w, h, list(resize_hw)), df)
+        out.append(((x0, y0, x1, y1), (w, h), (w_new, h_new)))
+    return out
+
+
+def _method_flags(method):
+    from . import frame_prep as fp
+    if method not in METHODS:
+        raise ValueError(f"method={method!r}: one of {METHODS}")
+    return {"GIM_DKM": fp.OUT_RGB | fp.MASKED, "GIM_LOFTR": fp.OUT_RGB | fp.OUT_GRAY | fp.OUT_MASK8,
+            "GIM_GLUE": fp.OUT_GRAY | fp.MASKED, "SIFT": fp.OUT_U8 | fp.OUT_MASK}[method]
+
+
+def method_inputs(method, side0, side1, as_tensor):
+    """the dict the reference builds for `method` (video_preprocessor.py:406-493) from the two sides' frame_prep outputs
+    ({name: array or tensor}); as_tensor: array -> the caller's tensor type (identity on the device path)"""
+    t = as_tensor
+    if method == "GIM_DKM":
+        return {"image0": t(side0["rgb"])[None], "image1": t(side1["rgb"])[None]}
+    if method == "GIM_LOFTR":
+        return {"image0": t(side0["gray"])[None], "image1": t(side1["gray"])[None], "color0": t(side0["rgb"])[None],
+                "color1": t(side1["rgb"])[None], "mask0": t(side0["mask8"])[None], "mask1": t(side1["mask8"])[None]}
+    if method == "GIM_GLUE":
+        import torch
+        g0, g1 = t(side0["gray"])[None], t(side1["gray"])[None]
+        return {"gray0": g0, "gray1": g1, "size0": torch.tensor([[g0.shape[-1], g0.shape[-2]]]), "size1": torch.tensor([[g1.shape[-1], g1.shape[-2]]])}
+    return {"rgb0": side0["u8"], "rgb1": side1["u8"], "mask0": side0["mask"], "mask1": side1["mask"]}
+
+
+def prepare_pair(bank, idx0, idx1, method, exclude, resize=None):
+    """The matcher's inputs of the frame pair (idx0, idx1) of `bank` -> (inputs, affine, kept).
+    method: "GIM_DKM" (image0 / image1 fp32 [1,3,h,w], masked), "GIM_LOFTR" (image0 / image1 grey [1,1,h,w], color0 / color1
+    [1,3,h,w], both unmasked, mask0 / mask1 uint8 [1,h/8,w/8]), "GIM_GLUE" (gray0 / gray1 [1,1,h,w] masked, size0 / size1 [1,2] (w, h))
+    or "SIFT" (rgb0 / rgb1 uint8 [h,w,3], mask0 / mask1 uint8 [h,w], for a host detector).  exclude: the excluded class ids or a
+    256-byte table.  resize=None: the first pass, whole frames at their own size, affine None.  resize=(pts, (h, w)): the second pass
+    -- pts [n,4] the pair's cached label, both frames cropped to its extent and resized into the (h, w) box (`pair_boxes`), affine =
+    (wA / wA_new, hA / hA_new, xA0, yA0, wB / wB_new, hB / hB_new, xB0, yB0) as label_pair(affine=) takes it (line 549).
+    kept: the mask sums of both sides -- int32 [2] on the bank's device (one launch serves both sides), a numpy array on the host path.
+    A frame that is not resident raises GimHipError before any launch."""
+    from . import frame_prep as fp
+    flags = _method_flags(method)
+    s0, s1 = bank.slots([int(idx0), int(idx1)])
+    H, W = (int(v) for v in bank.frames.shape[1:3])
+    if resize is None:
+        jobs, affine = [(s0, None, (W, H), flags), (s1, None, (W, H), flags)], None
+    else:
+        pts, box_hw = resize
+        (b0, (w0, h0), n0), (b1, (w1, h1), n1) = pair_boxes(pts, (H, W), box_hw)
+        jobs = [(s0, b0, n0, flags), (s1, b1, n1, flags)]
+        affine = (w0 / n0[0], h0 / n0[1], b0[0], b0[1], w1 / n1[0], h1 / n1[1], b1[0], b1[1])
+    if bank.device is None:
+        import torch
+        sides = [fp.frame_prep_np(bank.frames[s], bank.seg[s], exclude, box, size, fl) for s, box, size, fl in jobs]
+        kept = np.array([sides[0]["kept"], sides[1]["kept"]], dtype=np.int32)
+        return method_inputs(method, sides[0], sides[1], torch.from_numpy), affine, kept
+    import torch
+    from . import ops
+    with torch.cuda.device(bank.device):
+        r = ops.frame_prep(bank.frames, bank.seg, exclude, jobs)
+    sides = [{name: r.get(j, name) for name in r.plan.views[j]} for j in (0, 1)]
+    return method_inputs(method, sides[0], sides[1], lambda a: a), affine, r.kept
+
+
+def label_pair_host(matcher_out, *, affine=None, vratio=1.0, threshold=0.5, confidence=0.999999, max_iters=100000, seed=0, refine=0):
+    """`label_pair` on the host, the CPU oracle of its control flow: label_pack_np for both packs, pose.find_fundamental_mat with the
+    host solver and sampler -> label fp32 [n,4] as a numpy array"""
+    from . import pose
+    k0, k1 = (np.asarray(t.detach().cpu() if hasattr(t, "detach") else t, dtype=np.float32).reshape(-1, 2) for t in _keypoints(matcher_out))
+    moved = label_pack_np(k0, k1, moved_thr=1.0)
+    empty = np.zeros((0, 4), dtype=np.float32)
+    if len(moved) < 7:
+        return empty
+    pts = moved.astype(np.float64)
+    F, mask = pose.find_fundamental_mat(pts[:, :2], pts[:, 2:], threshold=threshold, prob=confidence, max_iters=max_iters, seed=seed, refine=refine)
+    if F is None or not mask.any():
+        return empty
+    return label_pack_np(moved[:, :2], moved[:, 2:], keep=mask, affine=affine, vratio=vratio)
+
+
+def label_pair_list(match, bank, ids, method, out_dir, *, vratio, exclude, resize_cache=None, resize_hw=(900, 1600), refine=0, seed=0,
+                    **ransac):
+    """The labelling loop of video_preprocessor.py:255-566 without decoding: for every (idx0, idx1) of `ids`, in order,
+        prepare_pair -> match(inputs) -> label_pair -> out_dir/str(np.array([idx0, idx1])) + '.npy', nums.npy, idxs.npy
+    in the reference's layout (`LabelStore.from_dirs` reads it back).  match(inputs) returns a matcher's result dict (mkpts0_f /
+    mkpts1_f) or a (k0, k1) pair, or None for a pair it cannot match (fewer than 8 descriptors on a side, :371 / :378; no matches,
+    :501).  resize_cache=None is the first pass; a directory is the second (opt.resize): every pair is cropped to the extent of its
+    label in that directory and resized into the resize_hw = (h, w) box.  Skipped, as the reference skips them: a pair whose file
+    exists, a second-pass pair without a cached label (:287), kept == 0 on either side (:367), a match of None, no inliers (:522).
+    Host reads per pair: `kept` (8 bytes) and what label_pair reads.  With a host bank (FrameBank(device=None)) everything runs in
+    numpy (`label_pair_host`).  ransac: threshold / confidence / max_iters of label_pair.
+    -> {"written": [(idx0, idx1)], "skipped": {(idx0, idx1): reason}}"""
+    os.makedirs(out_dir, exist_ok=True)
+    nums_path, idxs_path = os.path.join(out_dir, "nums.npy"), os.path.join(out_dir, "idxs.npy")
+    nums = np.load(nums_path) if os.path.exists(nums_path) else np.array([])
+    idxs = np.load(idxs_path) if os.path.exists(idxs_path) else np.array([])
+    written, skipped = [], {}
+    for idx0, idx1 in ids:
+        idx0, idx1 = int(idx0), int(idx1)
+        current = np.array([idx0, idx1])
+        name = "{}.npy".format(str(current))
+        path = os.path.join(out_dir, name)
+        if os.path.exists(path):
+            skipped[(idx0, idx1)] = "exists"
+            continue
+        resize = None
+        if resize_cache is not None:
+            cache = os.path.join(resize_cache, name)
+            if not os.path.exists(cache):
+                skipped[(idx0, idx1)] = "no cached label"
+                continue
+            resize = (np.load(cache), resize_hw)
+        inputs, affine, kept = prepare_pair(bank, idx0, idx1, method, exclude, resize)
+        k = kept.tolist()                                          # the pair's one host read before the matcher
+        if k[0] == 0 or k[1] == 0:
+            skipped[(idx0, idx1)] = "kept == 0"
+            continue
+        out = match(inputs)
+        if out is None:
+            skipped[(idx0, idx1)] = "no match"
+            continue
+        if bank.device is None:
+            pts = label_pair_host(out, affine=affine, vratio=vratio, seed=seed, refine=refine, **ransac)
+        else:
+            pts = label_pair(out, device=bank.device, affine=affine, vratio=vratio, seed=seed, refine=refine, **ransac).cpu().numpy()
+        if len(pts) == 0:
+            skipped[(idx0, idx1)] = "no inliers"
+            continue
+        pts = pts.astype(np.float32)
+        nums = np.concatenate([nums, np.array([len(pts)])], axis=0) if len(nums) else np.array([len(pts)])
+        idxs = np.concatenate([idxs, current[None]], axis=0) if len(idxs) else current[None]
+        np.save(path, pts)
+        np.save(nums_path, nums)
+        np.save(idxs_path, idxs)
+        written.append((idx0, idx1))
+    return {"written": written, "skipped": skipped}
+
+
+# ---- thin adapters: match(inputs) over the existing modules ------------------------------------------------------------------------------
+def loftr_match(model):
+    """match(inputs) for "GIM_LOFTR" over a gim_amd.loftr.LoFTR module (video_preprocessor.py:460-472)"""
+    def match(inputs):
+        data = dict(inputs)
+        model(data)
+        return {"mkpts0_f": data["mkpts0_f"], "mkpts1_f": data["mkpts1_f"]}
+    return match
+
+
+def dense_match(model, num=5000):
+    """match(inputs) for "GIM_DKM" over a gim_amd.dkm.DKMv3 / gim_amd.roma.RoMa module: match, sample `num`, pixels (:424-436)"""
+    def match(inputs):
+        from . import ops
+        img0, img1 = inputs["image0"], inputs["image1"]
+        dense, certainty = model.match(img0, img1)
+        sparse, _ = model.sample(dense, certainty, num)
+        k0, k1 = ops.dense_to_pixels(sparse, img0.shape[-2:], img1.shape[-2:])
+        return {"mkpts0_f": k0, "mkpts1_f": k1}
+    return match
+
+
+def glue_match(detector, model):
+    """match(inputs) for "GIM_GLUE" over gim_amd.lightglue's SuperPoint and LightGlue modules (:486-511); None without a match"""
+    def match(inputs):
+        import torch
+        from .lightglue.pipeline import gim_lightglue_inference
+        one = torch.ones(1, 2)
+        data = {"image0": inputs["gray0"], "image1": inputs["gray1"], "scale0": one, "scale1": one,
+                "image_size0": inputs["size0"], "image_size1": inputs["size1"]}
+        gim_lightglue_inference(detector, model, data)
+        if data["mkpts0_f"].shape[0] == 0:
+            return None
+        return {"mkpts0_f": data["mkpts0_f"], "mkpts1_f": data["mkpts1_f"]}
+    return match
+
+
+def sift_match(device="cuda", ratio=0.8):
+    """match(inputs) for "SIFT": OpenCV's detector under the masks on the host (:370-381), nn_match.RootSiftMatcher on the device.
+    Raises GimHipError where cv2 does not import (the detector is not restated); None with fewer than 8 descriptors on a side."""
+    from .nn_match import RootSiftMatcher, _cv2
+    cv2 = _cv2()
+    matcher = RootSiftMatcher(ratio=ratio, device=device)
+
+    def match(inputs):
+        import torch
+        sides = []
+        for s in ("0", "1"):
+            rgb, mask = (np.ascontiguousarray(inputs[k + s].cpu().numpy() if hasattr(inputs[k + s], "cpu") else inputs[k + s]) for k in ("rgb", "mask"))
+            sift = cv2.SIFT_create(nfeatures=rgb.shape[0] * rgb.shape[1] // 64, contrastThreshold=1e-5)
+            kpts, desc = sift.detectAndCompute(cv2.cvtColor(rgb, cv2.COLOR_RGB2BGR), mask)
+            if desc is None or desc.shape[0] < 8:
+                return None
+            kpts = np.array([[kp.pt[0], kp.pt[1]] for kp in kpts], dtype=np.float32).reshape(-1, 2)
+            sides += [torch.from_numpy(kpts).to(device), torch.from_numpy(np.ascontiguousarray(desc, dtype=np.float32)).to(device)]
+        return matcher.match_descriptors(*sides)
+    return match

@@ -1247,6 +1247,54 @@ int gim_label_link(const float* lab0, const int32_t* off0, int n0_total, const f
 int gim_label_pack(const float* k0, const float* k1, const uint8_t* keep, int n, float moved_thr, const double* affine,
                    double vratio, float* out, int32_t* count, gim_stream_t stream);
 
+/* ======================================================================================================
+ * Frame preparation of the video labeller (added within ABI revision 115: no existing structure or prototype changed with it).
+ * The reference prepares both frames of a pair on the host with OpenCV: the crop to the box of the previous pass's labels and the
+ * INTER_AREA resize (video_preprocessor.py:292-304, :318-329), the class map resized to the frame, cropped and resized to the
+ * output with INTER_NEAREST (:342-354), the exclusion mask (:359-365), the per-method tensors (:406-493: gim_dkm's masked colour
+ * image, LoFTR's grey and colour images and its 1/8 mask, gim_lightglue's masked grey image) and the segmenter's input
+ * (:603-621 read_segmentation_image).  csrc/frame_prep_math.h is the arithmetic, gim_amd/frame_prep.py (frame_prep_np) its numpy
+ * restatement.  The contract below is NOT byte-equality with cv2.resize: OpenCV rounds 1 / (dst / src) in double before the floor of
+ * its nearest-neighbour index and has a separate integer-factor path for bytes.
+ * ====================================================================================================== */
+
+/* The output tile (tw x th pixels, at most 64 x 16) gim_frame_prep wants for a job that resizes a crop of wc x hc pixels to wn x hn:
+ * the largest one, halving th and then tw, whose source footprint fits the kernel's 40 KiB of LDS.  Refused: an extent < 1, an axis
+ * shrunk by more than 16. */
+int gim_frame_prep_tile(int wc, int hc, int wn, int hn, int* tw, int* th);
+
+/* J jobs in ONE launch, one workgroup of 256 lanes per work item (a tile of a job's output).
+ * DEVICE memory: frames uint8 [S][H][W][3] RGB (16-byte aligned); seg uint8 [S][Hs][Ws] class maps (NULL when no job needs a mask
+ * and kept is NULL); exclude uint8 [256] (16-byte aligned), non-zero: the class is excluded; jobs_dev int64 [J][16]; work_dev int32
+ * [n_work][4] (16-byte aligned): (job, tile x origin, tile y origin, 0); the output buffers, each NULL when no job asks for it.
+ * HOST memory: jobs and work, the same values: they are checked before anything is launched; out_elems int64 [6]: the elements of
+ * the six output buffers in the order of the flags.
+ *   job      words: slot, x0, y0, x1, y1 (the crop box, wc = x1 - x0, hc = y1 - y0), wn, hn (the output size), flags, the element
+ *            offsets of the job's u8, mask, mask8, rgb, gray and norm outputs in their buffers, tw, th (gim_frame_prep_tile).
+ *   flags    1 u8, 2 mask, 4 mask8, 8 rgb, 16 gray, 32 norm: the outputs the job writes; 64: rgb and gray are multiplied by the mask.
+ *   resize   per axis with source extent n and destination extent m, s = n / m in double: destination index d covers [a, b) with
+ *            a = d s, b = min((d + 1) s, n); source index k from floor(a) to ceil(b) - 1 has the weight
+ *            (float)((min(b, k + 1) - max(a, k)) / (b - a)), a double expression rounded once.  Per channel
+ *            t_y = sum_k wx_k * (float)src[y][k] and v = sum_y wy_y * t_y in fp32 from 0, k and y ascending, every product and sum
+ *            rounded separately (no fused multiply-add); the byte is rintf(v) clamped to [0, 255].  For s < 1 this is the coverage
+ *            rule INTER_AREA applies when it zooms, for an integer s the mean.
+ *   mask     1 where exclude[seg[slot][sy][sx]] == 0, else 0, with cx = x0 + min(j wc / wn, wc - 1), sx = min(cx Ws / W, Ws - 1)
+ *            in integers (floors), rows likewise: the reference's resize to the frame, crop and resize to the output.
+ *   outputs  u8 uint8 [hn][wn][3]: the resized crop; mask uint8 [hn][wn]; mask8 uint8 [hn / 8][wn / 8] = mask[8 i][8 j]
+ *            (cv2.resize(fx = fy = 1/8, INTER_NEAREST)); rgb fp32 [3][hn][wn] = (float)(u8 * m) / 255.f; gray fp32 [hn][wn] =
+ *            (float)(g * m) / 255.f with g = (4899 r + 9617 g + 1868 b + 8192) >> 14 on the resized bytes; m = mask under flag 64,
+ *            else 1; norm fp32 [3][hn][wn] = ((float)u8 / 255.f - mean) / std with the ImageNet constants, never masked;
+ *            kept int32 [J] or NULL: the sum of the job's mask (the reference skips a pair when it is 0) -- set to zero by a
+ *            memset on the stream, then integer sums over a wave and one integer atomic per wave.
+ * Nothing is written outside a job's ranges.  J == 0 or n_work == 0 returns without touching anything.  Refused before a launch
+ * (GIM_ERR_INVALID): a NULL or misaligned pointer, a slot outside [0, S), a box that is empty or leaves the frame, an output extent
+ * < 1, an axis shrunk by more than 16, unknown flags, mask8 with hn or wn no multiple of 8, a tile that does not fit, an output that
+ * is asked for without a buffer or leaves it, a mask without class maps, a work item outside its job or off the tile grid. */
+int gim_frame_prep(const uint8_t* frames, int S, int H, int W, const uint8_t* seg, int Hs, int Ws, const uint8_t* exclude,
+                   const int64_t* jobs, const int64_t* jobs_dev, int J, const int32_t* work, const int32_t* work_dev, int n_work,
+                   const int64_t* out_elems, uint8_t* out_u8, uint8_t* out_mask, uint8_t* out_mask8, float* out_rgb,
+                   float* out_gray, float* out_norm, int32_t* kept, gim_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
