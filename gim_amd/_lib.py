@@ -188,6 +188,11 @@ PROTOTYPES = {
     "gim_lg_bank_put": (c_int, [c_void_p] * 8 + [c_int] * 4 + [c_void_p]),
     "gim_lg_gather_pairs": (c_int, [c_void_p] * 7 + [c_int] * 7 + [c_void_p]),
     "gim_lg_emit_hloc": (c_int, [c_void_p] * 4 + [c_int] * 2 + [c_void_p]),
+    # ragged batches of gim_lightglue: per-sequence lengths in the padded row layout (added within ABI revision 115)
+    "gim_lg_transpose_varlen": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p]),
+    "gim_sdpa_varlen": (c_int, [c_void_p] * 6 + [c_int] * 12 + [c_void_p]),
+    "gim_lg_assign_ragged": (c_int, [ctypes.POINTER(LgAssignArgs), c_void_p, c_void_p, c_void_p]),
+    "gim_lg_gather_pairs_ragged": (c_int, [c_void_p] * 10 + [c_int] * 7 + [c_void_p]),
     # sparse lateral of gim_loftr's fine FPN head (added within ABI revision 115)
     "gim_conv_ups_tiles_supported": (c_int, [ctypes.POINTER(ConvArgs)]),
     "gim_conv2d_ups_tiles": (c_int, [ctypes.POINTER(ConvArgs), c_void_p, c_void_p, c_int, c_void_p]),

@@ -174,16 +174,20 @@ def pair_batches(pairs, batch_pairs):
     return [pairs[i:i + batch_pairs] for i in range(0, len(pairs), batch_pairs)]
 
 
-def sparse_pair_list(bank, pairs, batch_pairs, match_batch, writer=None, names=None):
+def sparse_pair_list(bank, pairs, batch_pairs, match_batch, writer=None, names=None, counts0=None):
     """pairs: a sequence of (key0, key1) of images resident in `bank`, matched as given, in the order given, `batch_pairs` per call of
     `match_batch(slots0, slots1)`, which returns one (matches0 int16, matching_scores0 fp16) pair of numpy arrays per pair of the batch
     (views of ONE host copy per array).  Returns [(key0, key1, matches0, matching_scores0)]; with `writer` (h5py's group protocol) every
-    pair is also written through hloc_formats.write_sparse_matches (group name from names[key] if `names` is given, else str(key))."""
+    pair is also written through hloc_formats.write_sparse_matches (group name from names[key] if `names` is given, else str(key)).
+    counts0(slots0) -> the keypoint counts of the batch's first images, for a matcher whose rows are padded to the bank's capacity: each
+    pair's arrays are cut to image 0's own count, the length hloc's datasets have."""
     name = (lambda k: names[k]) if names is not None else str
     out = []
     for batch in pair_batches(pairs, batch_pairs):
         s0, s1 = bank.slots([p[0] for p in batch]), bank.slots([p[1] for p in batch])
-        for (k0, k1), (m, s) in zip(batch, match_batch(s0, s1)):
+        n0 = counts0(s0) if counts0 is not None else [None] * len(batch)
+        for (k0, k1), (m, s), n in zip(batch, match_batch(s0, s1), n0):
+            m, s = m[:n], s[:n]
             if writer is not None:
                 write_sparse_matches(writer, name(k0), name(k1), m, s)
             out.append((k0, k1, m, s))

@@ -67,7 +67,12 @@ struct LgaGeom {
     const float* md1;  // [B][N][C]
     int B, M, N, C;
     float inv_sqrt_d;  // 1 / (d^(1/4))^2
+    const int32_t* len0;  // ragged batch (gim_lg_assign_ragged): pair b has rows [0, len0[b]) of its M, columns [0, len1[b]) of its N;
+    const int32_t* len1;  // NULL: every pair has M x N
 };
+
+// rows / columns pair b really has: the rest of its M x N block does not exist (never read into a statistic, never matched)
+__device__ __forceinline__ int lga_len(const int32_t* len, int b, int cap) { return len != nullptr ? min(max(len[b], 0), cap) : cap; }
 
 __device__ __forceinline__ float logsigmoid(float x) {  // ATen: min(x, 0) - log1p(exp(-|x|))
     return fminf(x, 0.f) - log1pf(expf(-fabsf(x)));
@@ -141,6 +146,8 @@ __global__ void __launch_bounds__(256) lga_stats_kernel(const LgaGeom g, const L
     const int b = blockIdx.y;
     const int mt = blockIdx.x / w.ntN, nt = blockIdx.x - mt * w.ntN;
     const int m0 = mt * BM, n0 = nt * BN;
+    const int Mb = lga_len(g.len0, b, g.M), Nb = lga_len(g.len1, b, g.N);
+    if (m0 >= Mb || n0 >= Nb) return;   // a tile wholly outside the pair: no partial is written, lga_combine does not read one
     sim_tile_to_lds(g, w.ktab, b, m0, n0, smem);
     const float* St = (const float*)smem;
     float* red = (float*)(smem + BM * TLD * 4);
@@ -149,7 +156,7 @@ __global__ void __launch_bounds__(256) lga_stats_kernel(const LgaGeom g, const L
         float mx = -INFINITY;
         for (int jj = 0; jj < 64; ++jj) {
             const int j = half * 64 + jj;
-            if (n0 + j < g.N) mx = fmaxf(mx, St[idx * TLD + j]);
+            if (n0 + j < Nb) mx = fmaxf(mx, St[idx * TLD + j]);
         }
         red[half * 128 + idx] = mx;
         __syncthreads();
@@ -157,40 +164,53 @@ __global__ void __launch_bounds__(256) lga_stats_kernel(const LgaGeom g, const L
         float z = 0.f;
         for (int jj = 0; jj < 64; ++jj) {
             const int j = half * 64 + jj;
-            if (n0 + j < g.N) z += __expf(St[idx * TLD + j] - m);
+            if (n0 + j < Nb) z += __expf(St[idx * TLD + j] - m);
         }
         red[256 + half * 128 + idx] = z;
         __syncthreads();
-        if (half == 0 && m0 + idx < g.M)
+        if (half == 0 && m0 + idx < Mb)
             w.rowpart[((size_t)b * w.ntN + nt) * g.M + m0 + idx] = make_float2(m, red[256 + idx] + red[384 + idx]);
         __syncthreads();
     }
     {   // columns
         float mx = -INFINITY;
         for (int r = half * 64; r < half * 64 + 64; ++r)
-            if (m0 + r < g.M) mx = fmaxf(mx, St[r * TLD + idx]);
+            if (m0 + r < Mb) mx = fmaxf(mx, St[r * TLD + idx]);
         red[half * 128 + idx] = mx;
         __syncthreads();
         const float m = fmaxf(red[idx], red[128 + idx]);
         float z = 0.f;
         for (int r = half * 64; r < half * 64 + 64; ++r)
-            if (m0 + r < g.M) z += __expf(St[r * TLD + idx] - m);
+            if (m0 + r < Mb) z += __expf(St[r * TLD + idx] - m);
         red[256 + half * 128 + idx] = z;
         __syncthreads();
-        if (half == 0 && n0 + idx < g.N)
+        if (half == 0 && n0 + idx < Nb)
             w.colpart[((size_t)b * w.ntM + mt) * g.N + n0 + idx] = make_float2(m, red[256 + idx] + red[384 + idx]);
     }
 }
 
 // stat = (max over tiles, log(sum_t z_t exp(m_t - max)))
-__global__ void lga_combine_kernel(const float2* __restrict__ part, float2* __restrict__ stat, int B, int len, int ntile) {
+// Ragged (len_self / len_other != NULL; `tile` = the other dimension's tile edge): entry x of pair n exists for x < len_self[n], and only
+// the tiles that reach into [0, len_other[n]) wrote a partial -- each of them with at least one real element, so the maximum is finite
+// and (-inf) - (-inf) is never formed.  Entries that do not exist, or have nothing on the other side, get (0, 0) and are never read.
+__global__ void lga_combine_kernel(const float2* __restrict__ part, float2* __restrict__ stat, int B, int len, int ntile,
+                                   const int32_t* __restrict__ len_self, const int32_t* __restrict__ len_other, int tile) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)B * len) return;
     const size_t n = idx / len, x = idx - n * len;
+    int nt = ntile;   // tiles that wrote a partial for this pair; `ntile` stays the stride of the partial array
+    if (len_self != nullptr) {
+        const int other = min(max(len_other[n], 0), ntile * tile);
+        nt = (other + tile - 1) / tile;
+        if ((int)x >= len_self[n] || nt == 0) {
+            stat[idx] = make_float2(0.f, 0.f);
+            return;
+        }
+    }
     float m = -INFINITY;
-    for (int t = 0; t < ntile; ++t) m = fmaxf(m, part[(n * ntile + t) * len + x].x);
+    for (int t = 0; t < nt; ++t) m = fmaxf(m, part[(n * ntile + t) * len + x].x);
     float z = 0.f;
-    for (int t = 0; t < ntile; ++t) {
+    for (int t = 0; t < nt; ++t) {
         const float2 p = part[(n * ntile + t) * len + x];
         z += p.y * expf(p.x - m);
     }
@@ -204,6 +224,8 @@ __global__ void __launch_bounds__(256) lga_best_kernel(const LgaGeom g, const Lg
     const int b = blockIdx.y;
     const int mt = blockIdx.x / w.ntN, nt = blockIdx.x - mt * w.ntN;
     const int m0 = mt * BM, n0 = nt * BN;
+    const int Mb = lga_len(g.len0, b, g.M), Nb = lga_len(g.len1, b, g.N);
+    if (m0 >= Mb || n0 >= Nb) return;   // wholly outside the pair (uniform over the workgroup, before the first barrier)
     sim_tile_to_lds(g, w.ktab, b, m0, n0, smem);
     float* St = (float*)smem;
     float* sc = (float*)(smem + BM * TLD * 4);
@@ -216,12 +238,12 @@ __global__ void __launch_bounds__(256) lga_best_kernel(const LgaGeom g, const Lg
     unsigned long long* red = (unsigned long long*)(sc + 768);  // [128] second-half partial best
     const int t = threadIdx.x, idx = t & 127, half = t >> 7;
     if (half == 0) {
-        const bool ok = m0 + idx < g.M;
+        const bool ok = m0 + idx < Mb;
         const float2 s = ok ? w.rowstat[(size_t)b * g.M + m0 + idx] : make_float2(0.f, 0.f);
         rmax[idx] = s.x; rlz[idx] = s.y;
         rls[idx] = ok ? w.ls0[(size_t)b * g.M + m0 + idx] : 0.f;
     } else {
-        const bool ok = n0 + idx < g.N;
+        const bool ok = n0 + idx < Nb;
         const float2 s = ok ? w.colstat[(size_t)b * g.N + n0 + idx] : make_float2(0.f, 0.f);
         cmax[idx] = s.x; clz[idx] = s.y;
         cls[idx] = ok ? w.ls1[(size_t)b * g.N + n0 + idx] : 0.f;
@@ -245,24 +267,24 @@ __global__ void __launch_bounds__(256) lga_best_kernel(const LgaGeom g, const Lg
     if (MODE == 1) {
         for (int e = t; e < BM * BN; e += 256) {
             const int i = e >> 7, j = e & 127;
-            if (m0 + i < g.M && n0 + j < g.N)
+            if (m0 + i < Mb && n0 + j < Nb)
                 out[((size_t)b * (g.M + 1) + m0 + i) * (size_t)(g.N + 1) + n0 + j] = St[i * TLD + j];
         }
         return;
     }
     {   // row best: thread (row idx, column half); ties -> lowest j
         unsigned long long best = 0ull;
-        if (m0 + idx < g.M) {
+        if (m0 + idx < Mb) {
             for (int jj = 0; jj < 64; ++jj) {
                 const int j = half * 64 + jj;
-                if (n0 + j >= g.N) break;
+                if (n0 + j >= Nb) break;
                 const unsigned long long key = ((unsigned long long)ord(St[idx * TLD + j]) << 32) | (unsigned)(~(unsigned)(n0 + j));
                 best = key > best ? key : best;
             }
         }
         if (half == 1) red[idx] = best;
         __syncthreads();
-        if (half == 0 && m0 + idx < g.M) {
+        if (half == 0 && m0 + idx < Mb) {
             const unsigned long long o = red[idx];
             best = o > best ? o : best;
             atomicMax(&w.best0[(size_t)b * g.M + m0 + idx], best);
@@ -271,16 +293,16 @@ __global__ void __launch_bounds__(256) lga_best_kernel(const LgaGeom g, const Lg
     }
     {   // column best: thread (column idx, row half); ties -> lowest i
         unsigned long long best = 0ull;
-        if (n0 + idx < g.N) {
+        if (n0 + idx < Nb) {
             for (int r = half * 64; r < half * 64 + 64; ++r) {
-                if (m0 + r >= g.M) break;
+                if (m0 + r >= Mb) break;
                 const unsigned long long key = ((unsigned long long)ord(St[r * TLD + idx]) << 32) | (unsigned)(~(unsigned)(m0 + r));
                 best = key > best ? key : best;
             }
         }
         if (half == 1) red[idx] = best;
         __syncthreads();
-        if (half == 0 && n0 + idx < g.N) {
+        if (half == 0 && n0 + idx < Nb) {
             const unsigned long long o = red[idx];
             best = o > best ? o : best;
             atomicMax(&w.best1[(size_t)b * g.N + n0 + idx], best);
@@ -305,11 +327,14 @@ struct LgaOut {
     int32_t* pos;        // [B][M] scratch: position of row i in its pair's match list
 };
 
-// one workgroup per pair
-__global__ void __launch_bounds__(1024) lga_filter_kernel(const LgaWs w, const LgaOut o, int M, int N, float th) {
+// one workgroup per pair; ragged (len0 / len1 != NULL): rows >= len0[b] get matches0 = -1, score 0 and no place in the list, columns
+// >= len1[b] likewise -- the list keeps torch.where order over the rows that exist
+__global__ void __launch_bounds__(1024) lga_filter_kernel(const LgaWs w, const LgaOut o, int M, int N, float th,
+                                                          const int32_t* __restrict__ len0, const int32_t* __restrict__ len1) {
     __shared__ int warp_tot[16];
     __shared__ int s_base;
     const int b = blockIdx.x, t = threadIdx.x;
+    const int Mb = lga_len(len0, b, M), Nb = lga_len(len1, b, N);
     const unsigned long long* b0 = w.best0 + (size_t)b * M;
     const unsigned long long* b1 = w.best1 + (size_t)b * N;
     // rows
@@ -318,10 +343,14 @@ __global__ void __launch_bounds__(1024) lga_filter_kernel(const LgaWs w, const L
     for (int i0 = 0; i0 < M; i0 += 1024) {
         const int i = i0 + t;
         bool valid = false;
-        if (i < M) {
+        if (i >= Mb && i < M) {
+            o.matches0[(size_t)b * M + i] = -1;
+            o.mscores0[(size_t)b * M + i] = 0.f;
+        }
+        if (i < Mb) {
             const unsigned long long k = b0[i];
             int j = (int)(~(unsigned)k);
-            if ((unsigned)j >= (unsigned)N) j = 0;  // only reachable with NaN scores
+            if ((unsigned)j >= (unsigned)Nb) j = 0;  // only reachable with NaN scores, or a pair without columns (best0 still 0)
             const int back = (int)(~(unsigned)b1[j]);
             const bool mutual = back == i;
             const float ms = mutual ? expf(unord((unsigned)(k >> 32))) : 0.f;
@@ -349,9 +378,14 @@ __global__ void __launch_bounds__(1024) lga_filter_kernel(const LgaWs w, const L
     if (t == 0) w.count[b] = s_base;
     // columns: mscores1 = mutual1 ? mscores0[m1] : 0 ; valid1 = mutual1 & valid0[m1]
     for (int j = t; j < N; j += 1024) {
+        if (j >= Nb) {
+            o.matches1[(size_t)b * N + j] = -1;
+            o.mscores1[(size_t)b * N + j] = 0.f;
+            continue;
+        }
         const unsigned long long k = b1[j];
         int i = (int)(~(unsigned)k);
-        if ((unsigned)i >= (unsigned)M) i = 0;
+        if ((unsigned)i >= (unsigned)Mb) i = 0;
         const unsigned long long k0 = b0[i];
         const bool mutual = (int)(~(unsigned)k0) == j;
         const float ms0 = mutual ? expf(unord((unsigned)(k0 >> 32))) : 0.f;  // mutual1 => mutual0 for row i
@@ -416,9 +450,10 @@ extern "C" int64_t gim_lg_assign_ws_bytes(int B, int M, int N, int C) {
     return (int64_t)carve(w, nullptr, B, M, N, C);
 }
 
-static int lga_run_stats(const gim_lg_assign_args* a, LgaWs& w, LgaGeom& g, hipStream_t s) {
+static int lga_run_stats(const gim_lg_assign_args* a, const int32_t* len0, const int32_t* len1, LgaWs& w, LgaGeom& g, hipStream_t s) {
     carve(w, (char*)a->ws, a->B, a->M, a->N, a->C);
     g.md0 = a->md0; g.md1 = a->md1; g.B = a->B; g.M = a->M; g.N = a->N; g.C = a->C;
+    g.len0 = len0; g.len1 = len1;
     g.inv_sqrt_d = 1.0f / sqrtf((float)a->C);
     static GimPerDevice attr_set;
     if (attr_set.needed()) {
@@ -434,25 +469,32 @@ static int lga_run_stats(const gim_lg_assign_args* a, LgaWs& w, LgaGeom& g, hipS
     hipLaunchKernelGGL(lga_prep_kernel, dim3((a->B * a->N + 3) / 4), dim3(256), 0, s, a->desc1, a->match_w, a->match_b, w.ls1, w.lsn1, w.best1, a->B * a->N, a->ld_desc);
     const dim3 grid(w.ntM * w.ntN, a->B);
     hipLaunchKernelGGL(lga_stats_kernel, grid, dim3(256), TILE_SMEM, s, g, w);
-    hipLaunchKernelGGL(lga_combine_kernel, dim3((unsigned)(((size_t)a->B * a->M + 255) / 256)), dim3(256), 0, s, w.rowpart, w.rowstat, a->B, a->M, w.ntN);
-    hipLaunchKernelGGL(lga_combine_kernel, dim3((unsigned)(((size_t)a->B * a->N + 255) / 256)), dim3(256), 0, s, w.colpart, w.colstat, a->B, a->N, w.ntM);
+    hipLaunchKernelGGL(lga_combine_kernel, dim3((unsigned)(((size_t)a->B * a->M + 255) / 256)), dim3(256), 0, s, w.rowpart, w.rowstat, a->B, a->M, w.ntN, len0, len1, BN);
+    hipLaunchKernelGGL(lga_combine_kernel, dim3((unsigned)(((size_t)a->B * a->N + 255) / 256)), dim3(256), 0, s, w.colpart, w.colstat, a->B, a->N, w.ntM, len1, len0, BM);
     return GIM_OK;
 }
 
-extern "C" int gim_lg_assign(const gim_lg_assign_args* a, gim_stream_t stream) {
+static int lga_assign(const gim_lg_assign_args* a, const int32_t* len0, const int32_t* len1, gim_stream_t stream) {
     if (int rc = check_args(a)) return rc;
     GIM_REQUIRE(a->matches0 && a->matches1 && a->mscores0 && a->mscores1 && a->pos && a->count, "lg_assign: null output");
     hipStream_t s = (hipStream_t)stream;
     LgaWs w;
     LgaGeom g;
-    lga_run_stats(a, w, g, s);
+    lga_run_stats(a, len0, len1, w, g, s);
     const dim3 grid(w.ntM * w.ntN, a->B);
     hipLaunchKernelGGL(lga_best_kernel<0>, grid, dim3(256), TILE_SMEM, s, g, w, (float*)nullptr);
     LgaOut o;
     o.matches0 = a->matches0; o.matches1 = a->matches1; o.mscores0 = a->mscores0; o.mscores1 = a->mscores1; o.pos = a->pos;
-    hipLaunchKernelGGL(lga_filter_kernel, dim3(a->B), dim3(1024), 0, s, w, o, a->M, a->N, a->threshold);
+    hipLaunchKernelGGL(lga_filter_kernel, dim3(a->B), dim3(1024), 0, s, w, o, a->M, a->N, a->threshold, len0, len1);
     if (hipMemcpyAsync(a->count, w.count, (size_t)a->B * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return gim_check_launch("lg_assign count copy");
     return gim_check_launch("lg_assign");
+}
+
+extern "C" int gim_lg_assign(const gim_lg_assign_args* a, gim_stream_t stream) { return lga_assign(a, nullptr, nullptr, stream); }
+
+extern "C" int gim_lg_assign_ragged(const gim_lg_assign_args* a, const int32_t* len0, const int32_t* len1, gim_stream_t stream) {
+    GIM_REQUIRE(len0 && len1, "lg_assign_ragged: NULL length table");
+    return lga_assign(a, len0, len1, stream);
 }
 
 extern "C" int gim_lg_emit_matches(const int64_t* matches0, const float* mscores0, const int32_t* pos, const int32_t* count,
@@ -475,7 +517,7 @@ extern "C" int gim_lg_log_assignment(const gim_lg_assign_args* a, float* out, gi
     hipStream_t s = (hipStream_t)stream;
     LgaWs w;
     LgaGeom g;
-    lga_run_stats(a, w, g, s);
+    lga_run_stats(a, nullptr, nullptr, w, g, s);
     const dim3 grid(w.ntM * w.ntN, a->B);
     hipLaunchKernelGGL(lga_best_kernel<1>, grid, dim3(256), TILE_SMEM, s, g, w, out);
     const int mx = a->M > a->N ? a->M : a->N;

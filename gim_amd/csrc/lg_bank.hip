@@ -66,7 +66,9 @@ template <bool ST16>
 __global__ void __launch_bounds__(256) lg_gather_pairs_kernel(const void* __restrict__ bank_desc, const float* __restrict__ bank_enc,
                                                               const int32_t* __restrict__ idx0, const int32_t* __restrict__ idx1,
                                                               float* __restrict__ x32, void* __restrict__ cat, float* __restrict__ enc,
-                                                              int B, int K, int n_slots, int cat_kind, int ld_x32, int ld_cat) {
+                                                              int B, int K, int n_slots, int cat_kind, int ld_x32, int ld_cat,
+                                                              const int32_t* __restrict__ counts, int32_t* __restrict__ len0,
+                                                              int32_t* __restrict__ len1) {
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t half = (size_t)B * K;
     if (idx >= 2 * half * 32) return;
@@ -76,7 +78,12 @@ __global__ void __launch_bounds__(256) lg_gather_pairs_kernel(const void* __rest
     const size_t rr = side1 ? r - half : r;
     const int b = (int)(rr / K), k = (int)(rr % K);
     const int slot = side1 ? idx1[b] : idx0[b];
-    const bool ok = (unsigned)slot < (unsigned)n_slots;
+    bool ok = (unsigned)slot < (unsigned)n_slots;
+    if (counts != nullptr) {   // ragged bank: the image has counts[slot] keypoints; what the slab holds behind them is never read
+        const int n = ok ? min(max(counts[slot], 0), K) : 0;
+        if (k == 0 && c == 0) (side1 ? len1 : len0)[b] = n;
+        ok = ok && k < n;
+    }
     const size_t sr = (size_t)(ok ? slot : 0) * K + k;
     float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
     if (ok) {
@@ -147,10 +154,9 @@ extern "C" int gim_lg_bank_put(const float* kpts, const float* desc, const float
     return gim_check_launch("lg_bank_put");
 }
 
-extern "C" int gim_lg_gather_pairs(const void* bank_desc, const float* bank_enc, const int32_t* idx0, const int32_t* idx1, float* x32,
-                                   void* cat, float* enc, int B, int K, int n_slots, int storage, int dtype, int ld_x32, int ld_cat,
-                                   gim_stream_t stream) {
-    GIM_TAG_ANY(dtype, gim_lg_gather_pairs);   // the compute dtype; one object serves every kind, nothing to route
+static int lg_gather(const void* bank_desc, const float* bank_enc, const int32_t* idx0, const int32_t* idx1, const int32_t* counts,
+                     float* x32, void* cat, float* enc, int32_t* len0, int32_t* len1, int B, int K, int n_slots, int storage, int dtype,
+                     int ld_x32, int ld_cat, gim_stream_t stream) {
     GIM_REQUIRE(B >= 0 && K > 0 && n_slots > 0, "lg_gather_pairs: B=%d K=%d n_slots=%d", B, K, n_slots);
     GIM_REQUIRE(storage_ok(storage), "lg_gather_pairs: storage dtype tag %d (GIM_F32 or GIM_F16)", storage);
     if (B == 0) return GIM_OK;
@@ -166,11 +172,28 @@ extern "C" int gim_lg_gather_pairs(const void* bank_desc, const float* bank_enc,
     const int kind = dtype == GIM_F32 ? 0 : dtype;
     if (storage == GIM_F16)
         hipLaunchKernelGGL(lg_gather_pairs_kernel<true>, dim3(nblocks(t, 256)), dim3(256), 0, (hipStream_t)stream, bank_desc, bank_enc, idx0,
-                           idx1, x32, cat, enc, B, K, n_slots, kind, ld_x32, ld_cat);
+                           idx1, x32, cat, enc, B, K, n_slots, kind, ld_x32, ld_cat, counts, len0, len1);
     else
         hipLaunchKernelGGL(lg_gather_pairs_kernel<false>, dim3(nblocks(t, 256)), dim3(256), 0, (hipStream_t)stream, bank_desc, bank_enc, idx0,
-                           idx1, x32, cat, enc, B, K, n_slots, kind, ld_x32, ld_cat);
+                           idx1, x32, cat, enc, B, K, n_slots, kind, ld_x32, ld_cat, counts, len0, len1);
     return gim_check_launch("lg_gather_pairs");
+}
+
+extern "C" int gim_lg_gather_pairs(const void* bank_desc, const float* bank_enc, const int32_t* idx0, const int32_t* idx1, float* x32,
+                                   void* cat, float* enc, int B, int K, int n_slots, int storage, int dtype, int ld_x32, int ld_cat,
+                                   gim_stream_t stream) {
+    GIM_TAG_ANY(dtype, gim_lg_gather_pairs);   // the compute dtype; one object serves every kind, nothing to route
+    return lg_gather(bank_desc, bank_enc, idx0, idx1, nullptr, x32, cat, enc, nullptr, nullptr, B, K, n_slots, storage, dtype, ld_x32,
+                     ld_cat, stream);
+}
+
+extern "C" int gim_lg_gather_pairs_ragged(const void* bank_desc, const float* bank_enc, const int32_t* idx0, const int32_t* idx1,
+                                          const int32_t* counts, float* x32, void* cat, float* enc, int32_t* len0, int32_t* len1, int B,
+                                          int K, int n_slots, int storage, int dtype, int ld_x32, int ld_cat, gim_stream_t stream) {
+    GIM_TAG_ANY(dtype, gim_lg_gather_pairs_ragged);
+    GIM_REQUIRE(B == 0 || (counts && len0 && len1), "lg_gather_pairs_ragged: NULL count / length table");
+    return lg_gather(bank_desc, bank_enc, idx0, idx1, counts, x32, cat, enc, len0, len1, B, K, n_slots, storage, dtype, ld_x32, ld_cat,
+                     stream);
 }
 
 extern "C" int gim_lg_emit_hloc(const int64_t* matches0, const float* mscores0, int16_t* matches0_i16, void* mscores0_f16, int B, int K,

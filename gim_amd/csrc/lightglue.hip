@@ -56,14 +56,17 @@ __global__ void lg_rotary_kernel(void* __restrict__ x, const float* __restrict__
 }
 
 // src rows [nb*S][ld] (columns [0, C)) -> dst [nb][C][Sp], dst[s][c][key] = src[s*S + key][c], zeros for key >= S
+// len != NULL (ragged batch): sequence s holds len[s] <= S keys, zeros from there on -- rows [len[s], S) of src are never read
 template <bool BF16>
-__global__ void lg_transpose_kernel(const void* __restrict__ src, void* __restrict__ dst, int S, int Sp, int C, int ld) {
+__global__ void lg_transpose_kernel(const void* __restrict__ src, void* __restrict__ dst, const int32_t* __restrict__ len, int S, int Sp,
+                                    int C, int ld) {
     __shared__ float tile[64][65];
     const int s = blockIdx.z, k0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int Sv = len != nullptr ? min(max(len[s], 0), S) : S;
     for (int i = ty; i < 64; i += 4) {
         const int key = k0 + i, c = c0 + tx;
-        tile[i][tx] = (key < S && c < C) ? ElemIO<BF16>::ld(src, ((size_t)s * S + key) * ld + c) : 0.f;
+        tile[i][tx] = (key < Sv && c < C) ? ElemIO<BF16>::ld(src, ((size_t)s * S + key) * ld + c) : 0.f;
     }
     __syncthreads();
     for (int i = ty; i < 64; i += 4) {
@@ -131,6 +134,8 @@ struct SdpaArgs {
     void* out;       // rows [nb*L][ldo]
     int nb, H, L, S, Sp, ldq, ldk, ldo, kv_shift;
     float scale_log2e;  // d^-0.5 * log2(e)
+    const int32_t* len_q;  // VARLEN only: queries of sequence s = rows [0, len_q[s]) of its L
+    const int32_t* len_k;  // VARLEN only: keys of sequence kvseq = rows [0, len_k[kvseq]) of its S
 };
 
 // raw v_exp_f32 (exp2f() wraps it in a 6-instruction denormal-range fix-up; arguments here are <= 0 and a
@@ -138,8 +143,14 @@ struct SdpaArgs {
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 // D = head dimension (64: LightGlue, DINOv2 ViT-L; 128: RoMa's match decoder)
-template <bool BF16, bool OUT_BF16, int D>
-__global__ void __launch_bounds__(256, 2) sdpa_kernel(const SdpaArgs a) {
+// VARLEN (gim_sdpa_varlen, a ragged batch in the padded row layout): L and S are the row strides of a sequence, its own sizes Lq / Sk
+// come from the length tables.  A sequence walks exactly the tiles gim_sdpa walks at L = Lq, S = Sk, so its valid rows are that call's
+// bit for bit; query rows [Lq, L) are stored as zeros (the stream behind stays finite and independent of what the padding held).
+// Occupancy: two workgroups per CU, except fp32 operands at D = 128 -- their tiles take 128 KiB of the CU's 160 KiB of LDS, so one
+// workgroup per CU is all that ever ran, and telling the compiler so gives it the 512 registers that hold the fp32 tile set (at 256
+// it spilled about 70 of them to scratch).
+template <bool BF16, bool OUT_BF16, int D, bool VARLEN>
+__global__ void __launch_bounds__(256, (!BF16 && D == 128) ? 1 : 2) sdpa_kernel(const SdpaArgs a) {
     constexpr int ES = BF16 ? 2 : 4;
     constexpr int KROW = D * ES;                   // bytes of one K tile row (one key, D channels)
     constexpr int VROW = 64 * ES;                  // bytes of one V^T tile row (one channel, 64 keys)
@@ -154,10 +165,31 @@ __global__ void __launch_bounds__(256, 2) sdpa_kernel(const SdpaArgs a) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, lh = lane >> 5;
     const int seq = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * 128 + wave * 32;
     const int kvseq = (seq + a.kv_shift) % a.nb;
+    int Lq = a.L, Sk = a.S;
+    if constexpr (VARLEN) {
+        Lq = min(max(a.len_q[seq], 0), a.L);
+        Sk = min(max(a.len_k[kvseq], 0), a.S);
+    }
+    // lane holds query l31, d = db*32 + (r/4)*8 + lh*4 + r%4
+    auto store_zero_row = [&](int q) {
+        const size_t orow = (size_t)(seq * (size_t)a.L + q) * a.ldo + h * D;
+#pragma unroll
+        for (int d = 0; d < NDB; ++d)
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) ElemIO<OUT_BF16>::st4(a.out, orow + d * 32 + rg * 8 + lh * 4, make_float4(0.f, 0.f, 0.f, 0.f));
+    };
+    if constexpr (VARLEN) {
+        // no query of this workgroup exists, or there is no key to attend to (m_run would stay -inf: exp2(-inf + inf) = NaN):
+        // zeros, and out before the first barrier (the condition is uniform over the workgroup)
+        if ((int)blockIdx.x * 128 >= Lq || Sk == 0) {
+            if (q0 + l31 < a.L) store_zero_row(q0 + l31);
+            return;
+        }
+    }
     // 16-byte-slot swizzles of the tiles (conflict-free fragment reads): 128-byte rows pair up over the bank cycle
     auto kswz = [](int row) { return KROW == 128 ? ((row >> 1) & 7) : (row & 15); };
     // ---- Q fragments (B operand of S^T = K Q^T), held for the whole kernel --------------------------------
-    const int qrow = min(q0 + l31, a.L - 1);
+    const int qrow = min(q0 + l31, Lq - 1);
     const char* qp = (const char*)a.q + ((size_t)(seq * (size_t)a.L + qrow) * a.ldq + h * D) * ES;
     bf16x8_t qb[BF16 ? D / 16 : 1];
     f32x4_t qf[BF16 ? 1 : D / 8];
@@ -179,17 +211,20 @@ __global__ void __launch_bounds__(256, 2) sdpa_kernel(const SdpaArgs a) {
     // ---- staging: thread t moves 16-byte chunks c = t + 256 p of the K tile (row = c / KSLOT) and of the V^T tile ----
     const char* kbase = (const char*)a.k + ((size_t)kvseq * a.S * a.ldk + h * D) * ES;
     const char* vbase = (const char*)a.vt + ((size_t)(kvseq * (size_t)a.H + h) * D * a.Sp) * ES;
-    uint4 rk[NPK], rv[NPV];
+    // plain 4 x 32-bit vectors: arrays of HIP's uint4 (a struct around a union) were not promoted to registers in the fp32 variants
+    // and cost 80 B of scratch
+    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+    u32x4_t rk[NPK], rv[NPV];
     auto fetch = [&](int key0) {
 #pragma unroll
         for (int p = 0; p < NPK; ++p) {
             const int c = t + 256 * p, row = c / KSLOT, slot = c % KSLOT, key = key0 + row;
-            rk[p] = key < a.S ? *(const uint4*)(kbase + (size_t)key * a.ldk * ES + slot * 16) : make_uint4(0, 0, 0, 0);
+            rk[p] = key < Sk ? *(const u32x4_t*)(kbase + (size_t)key * a.ldk * ES + slot * 16) : u32x4_t{0, 0, 0, 0};
         }
 #pragma unroll
         for (int p = 0; p < NPV; ++p) {
             const int c = t + 256 * p, row = c / VSLOT, slot = c % VSLOT;
-            rv[p] = *(const uint4*)(vbase + ((size_t)row * a.Sp + key0) * ES + slot * 16);
+            rv[p] = *(const u32x4_t*)(vbase + ((size_t)row * a.Sp + key0) * ES + slot * 16);
         }
     };
     auto stash = [&](int buf) {
@@ -198,7 +233,7 @@ __global__ void __launch_bounds__(256, 2) sdpa_kernel(const SdpaArgs a) {
 #pragma unroll
         for (int p = 0; p < NPK; ++p) {
             const int c = t + 256 * p, row = c / KSLOT, slot = c % KSLOT;
-            *(uint4*)(sK + row * KROW + ((slot ^ kswz(row)) << 4)) = rk[p];
+            *(u32x4_t*)(sK + row * KROW + ((slot ^ kswz(row)) << 4)) = rk[p];
         }
 #pragma unroll
         for (int p = 0; p < NPV; ++p) {
@@ -208,7 +243,7 @@ __global__ void __launch_bounds__(256, 2) sdpa_kernel(const SdpaArgs a) {
                 *(uint2*)(sV + row * VROW + (((2 * slot) ^ sw) << 3)) = make_uint2(rv[p].x, rv[p].y);
                 *(uint2*)(sV + row * VROW + (((2 * slot + 1) ^ sw) << 3)) = make_uint2(rv[p].z, rv[p].w);
             } else {
-                *(uint4*)(sV + row * VROW + ((slot ^ (row & 15)) << 4)) = rv[p];
+                *(u32x4_t*)(sV + row * VROW + ((slot ^ (row & 15)) << 4)) = rv[p];
             }
         }
     };
@@ -242,13 +277,13 @@ __global__ void __launch_bounds__(256, 2) sdpa_kernel(const SdpaArgs a) {
     // online softmax of tile kt (scores in accS) and O^T += V^T P^T with the V^T tile in buffer `buf`
     auto softmax_pv = [&](int buf, int key0, f32x16_t (&accS)[2]) {
         const char* sV = sV0 + buf * VBYTES;
-        if (key0 + 64 > a.S) {
+        if (key0 + 64 > Sk) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = key0 + kb * 32 + (r >> 2) * 8 + lh * 4 + (r & 3);
-                    if (key >= a.S) accS[kb][r] = -INFINITY;
+                    if (key >= Sk) accS[kb][r] = -INFINITY;
                 }
         }
         float mx = accS[0][0];
@@ -320,7 +355,7 @@ __global__ void __launch_bounds__(256, 2) sdpa_kernel(const SdpaArgs a) {
     // barrier.  (Issuing the next tile's score MFMAs ahead of this tile's softmax inside one wave was measured
     // slower, 69 vs 64 us: in-order issue stalls the VALU behind the dependent MFMA chain, and the second wave
     // on the SIMD already fills those gaps.)
-    const int ntiles = (a.S + 63) / 64;
+    const int ntiles = (Sk + 63) / 64;
     f32x16_t accS[2];
     fetch(0);
     stash(0);
@@ -338,7 +373,9 @@ __global__ void __launch_bounds__(256, 2) sdpa_kernel(const SdpaArgs a) {
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.f / l_tot;
     const int q = q0 + l31;
-    if (q < a.L) {
+    if (VARLEN && q >= Lq) {
+        if (q < a.L) store_zero_row(q);
+    } else if (q < a.L) {
         const size_t orow = (size_t)(seq * (size_t)a.L + q) * a.ldo + h * D;
 #pragma unroll
         for (int d = 0; d < NDB; ++d)
@@ -351,11 +388,11 @@ __global__ void __launch_bounds__(256, 2) sdpa_kernel(const SdpaArgs a) {
     }
 }
 
-template <bool BF16, bool OUT_BF16, int D>
+template <bool BF16, bool OUT_BF16, int D, bool VARLEN>
 int launch_sdpa(const SdpaArgs& a, hipStream_t s) {
     constexpr int ES = BF16 ? 2 : 4;
     constexpr int smem = 2 * (64 * D * ES + D * 64 * ES);
-    auto kern = sdpa_kernel<BF16, OUT_BF16, D>;
+    auto kern = sdpa_kernel<BF16, OUT_BF16, D, VARLEN>;
     static GimPerDevice attr;
     if (attr.needed()) {
         if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
@@ -399,9 +436,21 @@ extern "C" int GIM_FN(gim_lg_transpose)(const void* src, void* dst, int nb, int 
     GIM_REQUIRE(src && dst && nb > 0 && S > 0 && Sp >= S && Sp % 64 == 0 && C > 0 && ld >= C, "lg_transpose: bad args");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(Sp / 64, (C + 63) / 64, nb);
-    if (dtype == GIM_H16) hipLaunchKernelGGL(lg_transpose_kernel<true>, grid, dim3(256), 0, s, src, dst, S, Sp, C, ld);
-    else hipLaunchKernelGGL(lg_transpose_kernel<false>, grid, dim3(256), 0, s, src, dst, S, Sp, C, ld);
+    if (dtype == GIM_H16) hipLaunchKernelGGL(lg_transpose_kernel<true>, grid, dim3(256), 0, s, src, dst, (const int32_t*)nullptr, S, Sp, C, ld);
+    else hipLaunchKernelGGL(lg_transpose_kernel<false>, grid, dim3(256), 0, s, src, dst, (const int32_t*)nullptr, S, Sp, C, ld);
     return gim_check_launch("lg_transpose");
+}
+
+GIM_TWIN(gim_lg_transpose_varlen)
+extern "C" int GIM_FN(gim_lg_transpose_varlen)(const void* src, void* dst, const int32_t* len, int nb, int S, int Sp, int C, int ld,
+                                               int dtype, gim_stream_t stream) {
+    GIM_ROUTE_ANY(dtype, gim_lg_transpose_varlen, src, dst, len, nb, S, Sp, C, ld, dtype, stream);
+    GIM_REQUIRE(src && dst && len && nb > 0 && S > 0 && Sp >= S && Sp % 64 == 0 && C > 0 && ld >= C, "lg_transpose_varlen: bad args");
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(Sp / 64, (C + 63) / 64, nb);
+    if (dtype == GIM_H16) hipLaunchKernelGGL(lg_transpose_kernel<true>, grid, dim3(256), 0, s, src, dst, len, S, Sp, C, ld);
+    else hipLaunchKernelGGL(lg_transpose_kernel<false>, grid, dim3(256), 0, s, src, dst, len, S, Sp, C, ld);
+    return gim_check_launch("lg_transpose_varlen");
 }
 
 GIM_TWIN(gim_cast_rows)
@@ -433,11 +482,12 @@ extern "C" int GIM_FN(gim_layernorm_act)(const float* x, const float* gamma, con
     return gim_check_launch("layernorm_act");
 }
 
-GIM_TWIN(gim_sdpa)
-extern "C" int GIM_FN(gim_sdpa)(const void* q, const void* k, const void* vt, void* out, int nb, int H, int L, int S, int Sp,
-                        int D, int ldq, int ldk, int ldo, int kv_shift, int dtype, int out_dtype, gim_stream_t stream) {
-    GIM_ROUTE_ANY2(dtype, out_dtype, gim_sdpa, q, k, vt, out, nb, H, L, S, Sp, D, ldq, ldk, ldo, kv_shift, dtype, out_dtype, stream);
+namespace {
+template <bool VARLEN>
+int sdpa_dispatch(const void* q, const void* k, const void* vt, void* out, const int32_t* len_q, const int32_t* len_k, int nb, int H, int L,
+                  int S, int Sp, int D, int ldq, int ldk, int ldo, int kv_shift, int dtype, int out_dtype, gim_stream_t stream) {
     GIM_REQUIRE(q && k && vt && out && nb > 0 && H > 0 && L > 0 && S > 0, "sdpa: bad args");
+    GIM_REQUIRE(!VARLEN || (len_q && len_k), "sdpa_varlen: NULL length table");
     GIM_REQUIRE(D == 64 || D == 128, "sdpa: head dim %d unsupported (64, 128)", D);
     GIM_REQUIRE(Sp >= S && Sp % 64 == 0, "sdpa: Sp=%d must be S rounded up to a multiple of 64", Sp);
     const int g = dtype == GIM_H16 ? 8 : 4;
@@ -447,16 +497,34 @@ extern "C" int GIM_FN(gim_sdpa)(const void* q, const void* k, const void* vt, vo
     a.q = q; a.k = k; a.vt = vt; a.out = out;
     a.nb = nb; a.H = H; a.L = L; a.S = S; a.Sp = Sp; a.ldq = ldq; a.ldk = ldk; a.ldo = ldo; a.kv_shift = kv_shift;
     a.scale_log2e = (1.0f / sqrtf((float)D)) * 1.44269504088896340736f;
+    a.len_q = len_q; a.len_k = len_k;
     hipStream_t s = (hipStream_t)stream;
     const bool bf = dtype == GIM_H16, obf = out_dtype == GIM_H16;
     if (D == 64) {
-        if (bf && obf) return launch_sdpa<true, true, 64>(a, s);
-        if (bf) return launch_sdpa<true, false, 64>(a, s);
-        if (obf) return launch_sdpa<false, true, 64>(a, s);
-        return launch_sdpa<false, false, 64>(a, s);
+        if (bf && obf) return launch_sdpa<true, true, 64, VARLEN>(a, s);
+        if (bf) return launch_sdpa<true, false, 64, VARLEN>(a, s);
+        if (obf) return launch_sdpa<false, true, 64, VARLEN>(a, s);
+        return launch_sdpa<false, false, 64, VARLEN>(a, s);
     }
-    if (bf && obf) return launch_sdpa<true, true, 128>(a, s);
-    if (bf) return launch_sdpa<true, false, 128>(a, s);
-    if (obf) return launch_sdpa<false, true, 128>(a, s);
-    return launch_sdpa<false, false, 128>(a, s);
+    if (bf && obf) return launch_sdpa<true, true, 128, VARLEN>(a, s);
+    if (bf) return launch_sdpa<true, false, 128, VARLEN>(a, s);
+    if (obf) return launch_sdpa<false, true, 128, VARLEN>(a, s);
+    return launch_sdpa<false, false, 128, VARLEN>(a, s);
+}
+}  // namespace
+
+GIM_TWIN(gim_sdpa)
+extern "C" int GIM_FN(gim_sdpa)(const void* q, const void* k, const void* vt, void* out, int nb, int H, int L, int S, int Sp,
+                        int D, int ldq, int ldk, int ldo, int kv_shift, int dtype, int out_dtype, gim_stream_t stream) {
+    GIM_ROUTE_ANY2(dtype, out_dtype, gim_sdpa, q, k, vt, out, nb, H, L, S, Sp, D, ldq, ldk, ldo, kv_shift, dtype, out_dtype, stream);
+    return sdpa_dispatch<false>(q, k, vt, out, nullptr, nullptr, nb, H, L, S, Sp, D, ldq, ldk, ldo, kv_shift, dtype, out_dtype, stream);
+}
+
+GIM_TWIN(gim_sdpa_varlen)
+extern "C" int GIM_FN(gim_sdpa_varlen)(const void* q, const void* k, const void* vt, void* out, const int32_t* len_q, const int32_t* len_k,
+                                       int nb, int H, int L, int S, int Sp, int D, int ldq, int ldk, int ldo, int kv_shift, int dtype,
+                                       int out_dtype, gim_stream_t stream) {
+    GIM_ROUTE_ANY2(dtype, out_dtype, gim_sdpa_varlen, q, k, vt, out, len_q, len_k, nb, H, L, S, Sp, D, ldq, ldk, ldo, kv_shift, dtype,
+                   out_dtype, stream);
+    return sdpa_dispatch<true>(q, k, vt, out, len_q, len_k, nb, H, L, S, Sp, D, ldq, ldk, ldo, kv_shift, dtype, out_dtype, stream);
 }

@@ -14,11 +14,14 @@ Two ways in:
                 (gim_amd.lightglue.match_pair_list) and written to `matches` in hloc's layout.  `features`: name -> group with
                 `keypoints`, `descriptors`, `image_size` datasets (an open h5py.File of extract_features.py, or a dict of dicts of
                 arrays); `matches`: anything with h5py's group protocol.  `pairs` is matched as given: apply hloc's
-                find_unique_new_pairs first if (j, i) is to be dropped where (i, j) is listed.
+                find_unique_new_pairs first if (j, i) is to be dropped where (i, j) is listed.  The images may hold different numbers
+                of keypoints (a detection threshold, force_num_keypoints=False, small images, another 256-d extractor): a slot of
+                the bank holds the largest count named, or `max_keypoints` if that is set -- an image above it is refused before
+                anything is launched -- and every pair's datasets have the length of image 0's keypoints, as hloc's have.
 
 conf: `weights` (file under weights/, the reference's 'gim_lightglue_100h.ckpt': the `model.` half is loaded, reconstruction.py:116-123;
 None keeps the module's init), `filter_threshold`, `precision`, `batch_pairs`, `storage` ('fp16' = the feature file's own precision, or
-'fp32').  No CPU fallback.
+'fp32'), `max_keypoints` (None, or the capacity of a bank slot).  No CPU fallback.
 """
 import os
 from os.path import join
@@ -26,6 +29,7 @@ from os.path import join
 import numpy as np
 import torch
 
+from .._lib import GimHipError
 from ..lightglue import KeypointBank, LightGlue, match_pair_list
 from .base import BaseModel
 
@@ -44,6 +48,7 @@ class GimLightGlueHip(BaseModel):
         "precision": None,
         "batch_pairs": 8,
         "storage": "fp16",
+        "max_keypoints": None,
     }
     required_inputs = ["keypoints0", "keypoints1", "descriptors0", "descriptors1", "image_size0", "image_size1"]
 
@@ -71,12 +76,18 @@ class GimLightGlueHip(BaseModel):
         if not names:
             return []
         dev = torch.device(device) if device is not None else next(self.net.parameters()).device
-        first = np.asarray(features[names[0]]["keypoints"])
-        bank = KeypointBank(len(names), first.shape[0], storage=self.conf["storage"], device=dev)
+        counts = {n: int(np.shape(features[n]["keypoints"])[0]) for n in names}
+        cap = self.conf.get("max_keypoints")
+        cap = max(max(counts.values()), 1) if cap is None else int(cap)
+        over = [n for n in names if counts[n] > cap]
+        if over:
+            raise GimHipError(f"image {over[0]!r} has {counts[over[0]]} keypoints, max_keypoints is {cap}"
+                              + (f"; {len(over) - 1} more" if len(over) > 1 else ""))
+        bank = KeypointBank(len(names), cap, storage=self.conf["storage"], device=dev)
         bank.bind(self.net)
         for n in names:
             g = features[n]
-            kp = torch.from_numpy(np.asarray(g["keypoints"])).float()
-            de = _rows256(torch.from_numpy(np.asarray(g["descriptors"])).float())
+            kp = torch.from_numpy(np.asarray(g["keypoints"])).float().reshape(-1, 2)
+            de = _rows256(torch.from_numpy(np.asarray(g["descriptors"])).float()).reshape(-1, 256)
             bank.put(n, kp.to(dev), de.to(dev), torch.from_numpy(np.asarray(g["image_size"])).float())
         return match_pair_list(self.net, bank, pairs, batch_pairs=int(self.conf["batch_pairs"]), writer=matches)

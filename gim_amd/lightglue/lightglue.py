@@ -9,6 +9,11 @@ Drop-in contract:
     (flipped with `[:, [1, 0]]` exactly like lightglue.py:414-415) and returns the reference's dict: matches0/1
     (int64, -1 = unmatched), matching_scores0/1, matches / scores (per-pair lists), ref_descriptors0/1, stop,
     prune0/1 and `log_assignment` (materialised on demand, see `LazyLogAssignment`);
+  * a RAGGED batch -- pairs whose images have different keypoint counts -- keeps the padded row layout: optional
+    `num_keypoints0/1` (int tensors [B]) say how many of the M | N stacked rows of a pair exist.  Pair b then gets what
+    forward() gives for that pair alone with its own (n0_b, n1_b) keypoints (the reference's forward at batch 1 takes any
+    (m, n)): matches0/1 are -1 and the scores 0 behind a pair's lengths, `matches` / `scores` are as before, and
+    `ref_descriptors*` / `prune*` rows behind a length are unspecified.  `log_assignment` is not built for ragged batches;
   * gim runs LightGlue with depth_confidence = width_confidence = -1 (no early stop / pruning,
     `demo.py:345-349`): only that configuration is built.
 
@@ -212,7 +217,29 @@ class LightGlue(nn.Module):
         X32[R0:].copy_(d1.reshape(R1, 256))
         if not alias:
             ops.cast_rows(X32, CAT[:, :256])
-        return self._match_rows(layers, head, dt, B, M, N, CAT, X32, enc, kp0, kp1, data.get("_adapter"))[0]
+        lens = None
+        if "num_keypoints0" in data or "num_keypoints1" in data:
+            lens = self._lengths(data.get("num_keypoints0"), data.get("num_keypoints1"), B, M, N, dev)
+        pred = self._match_rows(layers, head, dt, B, M, N, CAT, X32, enc, kp0, kp1, data.get("_adapter"), lens)[0]
+        if lens is not None:
+            pred["num_keypoints0"], pred["num_keypoints1"] = lens[0], lens[1]
+        return pred
+
+    @staticmethod
+    def _lengths(n0, n1, B, M, N, dev):
+        """(len0, len1) int32 [B] device tables of a ragged batch from what the caller gave (a missing side is full)"""
+        out = []
+        for n, cap, side in ((n0, M, 0), (n1, N, 1)):
+            if n is None:
+                n = torch.full((B,), cap, dtype=torch.int32, device=dev)
+            n = torch.as_tensor(n)
+            if n.numel() != B or n.dtype.is_floating_point:
+                raise GimHipError(f"num_keypoints{side} must be an integer tensor of {B} lengths, got {tuple(n.shape)} {n.dtype}")
+            if not n.is_cuda:   # host lengths are checked here; device ones are clamped to [0, capacity] by the kernels
+                if int(n.min()) < 0 or int(n.max()) > cap:
+                    raise GimHipError(f"num_keypoints{side} must lie in [0, {cap}], got {n.tolist()}")
+            out.append(n.reshape(B).to(device=dev, dtype=torch.int32).contiguous())
+        return tuple(out)
 
     def _packed_for(self, dev):
         """(layers, head, Wr, dtype tag) packed for `dev` in the module's precision (packed on first use and after a repack)"""
@@ -221,9 +248,13 @@ class LightGlue(nn.Module):
             self._prepack(dev)
         return self._packed[:4]
 
-    def _match_rows(self, layers, head, dt, B, M, N, CAT, X32, enc, kp0, kp1, kscale):
+    def _match_rows(self, layers, head, dt, B, M, N, CAT, X32, enc, kp0, kp1, kscale, lens=None):
         """Everything behind the first block, shared by forward() and match_pairs(): the stacked rows CAT[:, :256] / X32 (image-0 rows
-        first) and their encoding table `enc` -> (the reference's result dict, the lg_assign result).  kscale: see below."""
+        first) and their encoding table `enc` -> (the reference's result dict, the lg_assign result).  kscale: see below.
+        lens = (len0, len1), int32 [B] device: a ragged batch -- pair b has len0[b] of its M and len1[b] of its N rows.  The kernels
+        that look across keypoints (V transpose, SDPA, assignment) take the tables; the row-wise ones run over all rows as ever (SDPA
+        writes zeros into the rows that do not exist, so they stay finite and independent of every other pair)."""
+        l0, l1 = lens if lens is not None else (None, None)
         dev, tdt = CAT.device, torch_dtype(dt)
         R0, R1 = B * M, B * N
         R = R0 + R1
@@ -243,18 +274,18 @@ class LightGlue(nn.Module):
             # ---- SelfBlock (lightglue.py:142-156) ----
             ops.linear(x_t, p["s_qkv"], QKV)
             ops.lg_rotary(QKV, enc, 512)
-            ops.lg_transpose(QKV[:R0, 512:], VT0, B, M, Mp, 256)
-            ops.lg_transpose(QKV[R0:, 512:], VT1, B, N, Np, 256)
-            ops.sdpa(QKV[:R0, :256], QKV[:R0, 256:512], VT0, CTX[:R0], B, 4, M, M, Mp)
-            ops.sdpa(QKV[R0:, :256], QKV[R0:, 256:512], VT1, CTX[R0:], B, 4, N, N, Np)
+            ops.lg_transpose(QKV[:R0, 512:], VT0, B, M, Mp, 256, l0)
+            ops.lg_transpose(QKV[R0:, 512:], VT1, B, N, Np, 256, l1)
+            ops.sdpa(QKV[:R0, :256], QKV[:R0, 256:512], VT0, CTX[:R0], B, 4, M, M, Mp, len_q=l0, len_k=l0)
+            ops.sdpa(QKV[R0:, :256], QKV[R0:, 256:512], VT1, CTX[R0:], B, 4, N, N, Np, len_q=l1, len_k=l1)
             ops.linear(CTX, p["s_out"], CAT[:, 256:])
             self._ffn(p, "s", CAT, X32, HID, HID2, alias)
             # ---- CrossBlock (lightglue.py:183-211): q and k share to_qk; both directions ----
             ops.linear(x_t, p["c_qkv"], QKV[:, :512])
-            ops.lg_transpose(QKV[:R0, 256:512], VT0, B, M, Mp, 256)
-            ops.lg_transpose(QKV[R0:, 256:512], VT1, B, N, Np, 256)
-            ops.sdpa(QKV[:R0, :256], QKV[R0:, :256], VT1, CTX[:R0], B, 4, M, N, Np)
-            ops.sdpa(QKV[R0:, :256], QKV[:R0, :256], VT0, CTX[R0:], B, 4, N, M, Mp)
+            ops.lg_transpose(QKV[:R0, 256:512], VT0, B, M, Mp, 256, l0)
+            ops.lg_transpose(QKV[R0:, 256:512], VT1, B, N, Np, 256, l1)
+            ops.sdpa(QKV[:R0, :256], QKV[R0:, :256], VT1, CTX[:R0], B, 4, M, N, Np, len_q=l0, len_k=l1)
+            ops.sdpa(QKV[R0:, :256], QKV[:R0, :256], VT0, CTX[R0:], B, 4, N, M, Mp, len_q=l1, len_k=l0)
             ops.linear(CTX, p["c_out"], CAT[:, 256:])
             self._ffn(p, "c", CAT, X32, HID, HID2, alias)
         # ---- MatchAssignment + filter_matches (lightglue.py:248-300) ----
@@ -262,7 +293,7 @@ class LightGlue(nn.Module):
         MD = torch.empty(R, 256, dtype=torch.float32, device=dev)
         ops.linear(x_t, head["final"], MD)
         r = ops.lg_assign(desc[:R0].view(B, M, 256), desc[R0:].view(B, N, 256), MD[:R0].view(B, M, 256),
-                          MD[R0:].view(B, N, 256), head["mw"], head["mb"], float(self.conf["filter_threshold"]))
+                          MD[R0:].view(B, N, 256), head["mw"], head["mb"], float(self.conf["filter_threshold"]), l0, l1)
         counts = r.count.tolist()  # the one read-back: sizes of the per-pair match lists (torch.where, lightglue.py:500)
         total = sum(counts)
         # kscale: data["_adapter"], set by gim_lightglue_inference: (scale0, scale1) -> fused caller-side adapter
@@ -288,15 +319,32 @@ class LightGlue(nn.Module):
         return pred, r
 
     @torch.no_grad()
-    def match_pairs(self, bank, idx0, idx1, hloc=False):
+    def match_pairs(self, bank, idx0, idx1, hloc=False, ragged=None):
         """forward() for B pairs of images resident in a `KeypointBank`: pair b matches the image in slot idx0[b] against the one in slot
         idx1[b] (int32 device tensors, or sequences of ints as `bank.slots(keys)` returns them).  One gim_lg_gather_pairs launch builds
         what forward()'s first block builds per call; the rest is the same code.  Returns forward()'s dict; hloc=True adds `matches0_i16`
-        [B,K] int16 and `matching_scores0_f16` [B,K] fp16, hloc's match-file datasets for the batch."""
+        [B,K] int16 and `matching_scores0_f16` [B,K] fp16, hloc's match-file datasets for the batch.
+
+        K = bank.num_keypoints is the capacity of a slot.  When every named image fills its slot, this is the uniform path.  Otherwise
+        the batch is RAGGED: pair b gets what forward() gives for that pair alone with its own (n0, n1) keypoints; the [B, K] tensors
+        are padded with -1 (matches) / 0 (scores) behind a pair's lengths, `num_keypoints0` / `num_keypoints1` (int32 [B]) hold the
+        lengths, `matches` / `scores` are as before; `ref_descriptors*` and `prune*` rows behind a length are unspecified.
+        ragged: None decides by the bank's host counts (slot indices given as a device tensor cannot be looked up without a read-back:
+        they take the ragged path unless the whole bank is full); True / False force the path (False with a short image is refused)."""
         dev = bank.device
         layers, head, wr, dt = self._packed_for(dev)
-        bank.ensure_encodings(self, wr)
+        host_idx = None if torch.is_tensor(idx0) or torch.is_tensor(idx1) else (list(idx0), list(idx1))
         idx0, idx1 = bank.slot_tensor(idx0), bank.slot_tensor(idx1)
+        K = bank.num_keypoints
+        if host_idx is not None:
+            full = all(c == K for c in bank.slot_counts(host_idx[0] + host_idx[1]))
+        else:
+            full = all(bank.counts[bank.table.slot_of(k)] == K for k in bank.table.keys())
+        if ragged is None:
+            ragged = not full
+        elif not ragged and not full:
+            raise GimHipError("match_pairs(ragged=False) on images with fewer keypoints than the bank's capacity")
+        bank.ensure_encodings(self, wr)
         B, K = idx0.numel(), bank.num_keypoints
         if B == 0 or idx1.numel() != B:
             raise GimHipError(f"match_pairs needs as many slots on both sides and at least one pair, got {B} and {idx1.numel()}")
@@ -305,8 +353,14 @@ class LightGlue(nn.Module):
         CAT = torch.empty(R, 512, dtype=torch_dtype(dt), device=dev)
         X32 = CAT[:, :256] if alias else torch.empty(R, 256, dtype=torch.float32, device=dev)
         enc = torch.empty(R, 64, dtype=torch.float32, device=dev)
-        ops.lg_gather_pairs(bank.desc, bank.enc, idx0, idx1, X32, None if alias else CAT, enc)
-        pred, r = self._match_rows(layers, head, dt, B, K, K, CAT, X32, enc, None, None, None)
+        lens = None
+        if ragged:
+            lens = ops.lg_gather_pairs_ragged(bank.desc, bank.enc, bank.n, idx0, idx1, X32, None if alias else CAT, enc)
+        else:
+            ops.lg_gather_pairs(bank.desc, bank.enc, idx0, idx1, X32, None if alias else CAT, enc)
+        pred, r = self._match_rows(layers, head, dt, B, K, K, CAT, X32, enc, None, None, None, lens)
+        if ragged:
+            pred["num_keypoints0"], pred["num_keypoints1"] = lens
         if hloc:
             pred["matches0_i16"], pred["matching_scores0_f16"] = ops.lg_emit_hloc(r)
         return pred

@@ -971,18 +971,30 @@ def lg_rotary(x, enc, ncols):
     check(lib.gim_lg_rotary(_p(x), _p(enc), x.shape[0], ncols, x.stride(0), gim_dtype(x), _stream()), "gim_lg_rotary")
 
 
-def lg_transpose(src, dst, nb, S, Sp, C):
-    """src row view [nb*S, >=C] -> dst [nb, C, Sp] (same dtype)"""
-    _req_cuda(src, dst)
+def lg_transpose(src, dst, nb, S, Sp, C, lens=None):
+    """src row view [nb*S, >=C] -> dst [nb, C, Sp] (same dtype); lens: int32 [nb] device, keys per sequence (columns behind them zero)"""
+    _req_cuda(src, dst, lens)
+    if lens is not None:
+        assert lens.dtype == torch.int32 and lens.numel() == nb and lens.is_contiguous()
+        check(lib.gim_lg_transpose_varlen(_p(src), _p(dst), _p(lens), nb, S, Sp, C, src.stride(0), gim_dtype(src), _stream()),
+              "gim_lg_transpose_varlen")
+        return
     check(lib.gim_lg_transpose(_p(src), _p(dst), nb, S, Sp, C, src.stride(0), gim_dtype(src), _stream()), "gim_lg_transpose")
 
 
-def sdpa(q, k, vt, out, nb, H, L, S, Sp, kv_shift=0, D=64):
-    """q row view [nb*L, ..], k row view [nb*S, ..], vt [nb, H*D, Sp], out row view [nb*L, ..]; head dim D in {64, 128}"""
-    _req_cuda(q, k, vt, out)
+def sdpa(q, k, vt, out, nb, H, L, S, Sp, kv_shift=0, D=64, len_q=None, len_k=None):
+    """q row view [nb*L, ..], k row view [nb*S, ..], vt [nb, H*D, Sp], out row view [nb*L, ..]; head dim D in {64, 128}.
+    len_q / len_k: int32 [nb] device (both or neither) -- sequence s has len_q[s] of its L queries and attends to len_k[kvseq] keys"""
+    _req_cuda(q, k, vt, out, len_q, len_k)
     assert q.dtype == k.dtype == vt.dtype
+    assert (len_q is None) == (len_k is None)
     # one 16-bit kind per call (the library routes by it): out is fp32 or of q's kind -- or anything, next to fp32 operands
     assert torch.float32 in (q.dtype, out.dtype) or out.dtype == q.dtype, f"sdpa: {q.dtype} operands with a {out.dtype} output"
+    if len_q is not None:
+        assert len_q.dtype == len_k.dtype == torch.int32 and len_q.numel() == len_k.numel() == nb
+        check(lib.gim_sdpa_varlen(_p(q), _p(k), _p(vt), _p(out), _p(len_q), _p(len_k), nb, H, L, S, Sp, D, q.stride(0), k.stride(0),
+                                  out.stride(0), kv_shift, gim_dtype(q), gim_dtype(out), _stream()), "gim_sdpa_varlen")
+        return
     check(lib.gim_sdpa(_p(q), _p(k), _p(vt), _p(out), nb, H, L, S, Sp, D, q.stride(0), k.stride(0), out.stride(0),
                        kv_shift, gim_dtype(q), gim_dtype(out), _stream()), "gim_sdpa")
 
@@ -1003,12 +1015,14 @@ def cast_rows(src, dst):
 
 
 class AssignResult:
-    __slots__ = ("args", "ws", "matches0", "matches1", "mscores0", "mscores1", "pos", "count", "keep")
+    __slots__ = ("args", "ws", "matches0", "matches1", "mscores0", "mscores1", "pos", "count", "keep", "ragged")
 
 
-def lg_assign(desc0, desc1, md0, md1, match_w, match_b, threshold):
-    """desc0 [B,M,256] / desc1 [B,N,256] fp32 (row stride 256), md0/md1 = final_proj outputs (contiguous)."""
-    _req_cuda(desc0, desc1, md0, md1, match_w, match_b)
+def lg_assign(desc0, desc1, md0, md1, match_w, match_b, threshold, len0=None, len1=None):
+    """desc0 [B,M,256] / desc1 [B,N,256] fp32 (row stride 256), md0/md1 = final_proj outputs (contiguous).
+    len0 / len1: int32 [B] device (both or neither) -- pair b has len0[b] of its M rows and len1[b] of its N columns."""
+    _req_cuda(desc0, desc1, md0, md1, match_w, match_b, len0, len1)
+    assert (len0 is None) == (len1 is None)
     B, M, C = md0.shape
     N = md1.shape[1]
     dev = md0.device
@@ -1022,7 +1036,8 @@ def lg_assign(desc0, desc1, md0, md1, match_w, match_b, threshold):
     r.mscores1 = torch.empty(B, N, dtype=torch.float32, device=dev)
     r.pos = torch.empty(B, M, dtype=torch.int32, device=dev)
     r.count = torch.empty(B, dtype=torch.int32, device=dev)
-    r.keep = (desc0, desc1, md0, md1, match_w, match_b)
+    r.keep = (desc0, desc1, md0, md1, match_w, match_b, len0, len1)
+    r.ragged = len0 is not None
     a = _lib.LgAssignArgs()
     a.desc0, a.desc1, a.md0, a.md1 = desc0.data_ptr(), desc1.data_ptr(), md0.data_ptr(), md1.data_ptr()
     a.match_w, a.match_b, a.ws = match_w.data_ptr(), match_b.data_ptr(), r.ws.data_ptr()
@@ -1031,13 +1046,19 @@ def lg_assign(desc0, desc1, md0, md1, match_w, match_b, threshold):
     a.pos, a.count = r.pos.data_ptr(), r.count.data_ptr()
     a.B, a.M, a.N, a.C, a.ld_desc, a.threshold = B, M, N, C, desc0.stride(-2), threshold
     r.args = a
-    check(lib.gim_lg_assign(ctypes.byref(a), _stream()), "gim_lg_assign")
+    if r.ragged:
+        assert len0.dtype == len1.dtype == torch.int32 and len0.numel() == len1.numel() == B
+        check(lib.gim_lg_assign_ragged(ctypes.byref(a), _p(len0), _p(len1), _stream()), "gim_lg_assign_ragged")
+    else:
+        check(lib.gim_lg_assign(ctypes.byref(a), _stream()), "gim_lg_assign")
     return r
 
 
 def lg_log_assignment(r):
     """Materialise log_assignment [B, M+1, N+1] from a previous lg_assign call's inputs."""
     a = r.args
+    if getattr(r, "ragged", False):
+        raise _lib.GimHipError("log_assignment is not built for a ragged batch: call forward() on the pair alone")
     out = torch.empty(a.B, a.M + 1, a.N + 1, dtype=torch.float32, device=r.count.device)
     check(lib.gim_lg_log_assignment(ctypes.byref(a), _p(out), _stream()), "gim_lg_log_assignment")
     return out
@@ -1085,6 +1106,23 @@ def lg_gather_pairs(bank_desc, bank_enc, idx0, idx1, X32, CAT, enc):
     check(lib.gim_lg_gather_pairs(_p(bank_desc), _p(bank_enc), _p(idx0), _p(idx1), _p(X32), _p(CAT), _p(enc), B, K, bank_desc.shape[0],
                                   gim_dtype(bank_desc), gim_dtype(CAT) if CAT is not None else GIM_F32, X32.stride(0),
                                   CAT.stride(0) if CAT is not None else 0, _stream()), "gim_lg_gather_pairs")
+
+
+def lg_gather_pairs_ragged(bank_desc, bank_enc, counts, idx0, idx1, X32, CAT, enc):
+    """lg_gather_pairs for a bank whose slot s holds counts[s] (int32 [S], device) keypoints: rows behind an image's count are zero.
+    Returns (len0, len1), int32 [B] device: the counts of the images named by idx0 / idx1."""
+    _req_cuda(bank_desc, bank_enc, counts, idx0, idx1, X32, CAT, enc)
+    B, K = idx0.numel(), bank_desc.shape[1]
+    assert idx0.dtype == torch.int32 and idx1.dtype == torch.int32 and idx1.numel() == B
+    assert counts.dtype == torch.int32 and counts.numel() == bank_desc.shape[0] and counts.is_contiguous()
+    assert X32.dtype == torch.float32 and X32.shape[0] == 2 * B * K and enc.is_contiguous() and enc.shape == (2 * B * K, 64)
+    len0 = torch.empty(B, dtype=torch.int32, device=idx0.device)
+    len1 = torch.empty(B, dtype=torch.int32, device=idx0.device)
+    check(lib.gim_lg_gather_pairs_ragged(_p(bank_desc), _p(bank_enc), _p(idx0), _p(idx1), _p(counts), _p(X32), _p(CAT), _p(enc), _p(len0),
+                                         _p(len1), B, K, bank_desc.shape[0], gim_dtype(bank_desc),
+                                         gim_dtype(CAT) if CAT is not None else GIM_F32, X32.stride(0),
+                                         CAT.stride(0) if CAT is not None else 0, _stream()), "gim_lg_gather_pairs_ragged")
+    return len0, len1
 
 
 def lg_emit_hloc(r):

@@ -716,6 +716,40 @@ int gim_lg_gather_pairs(const void* bank_desc, const float* bank_enc, const int3
                         void* cat, float* enc, int B, int K, int n_slots, int storage, int dtype, int ld_x32, int ld_cat,
                         gim_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Ragged batches (added within ABI revision 115: no existing structure or prototype changed with them).  A batch keeps the padded row
+ * layout -- sequence / pair b owns rows [b*K, (b+1)*K) on each side, K the capacity -- and device int32 length tables say how many of
+ * those rows exist.  Contract: pair b gets what the uniform entry point gives for that pair alone at its own sizes (the reference's
+ * LightGlue.forward at batch 1 takes any (m, n): lightglue.py:405-430); rows that do not exist are never read into a result.
+ * The row-wise kernels (linears, gim_lg_rotary, gim_layernorm_act, gim_cast_rows) need no lengths.
+ * ------------------------------------------------------------------------------------------------------ */
+
+/* gim_lg_transpose with a length table: sequence s has len[s] <= S keys, dst columns >= len[s] are ZERO (a masked key has probability
+ * exactly 0, and 0 x NaN is NaN: nothing of the padding may reach gim_sdpa_varlen's second MFMA).  Serves lightglue.py:112-118. */
+int gim_lg_transpose_varlen(const void* src, void* dst, const int32_t* len, int nb, int S, int Sp, int C, int ld, int dtype,
+                            gim_stream_t stream);
+
+/* gim_sdpa (Attention.forward, lightglue.py:104-118, 196-207) over sequences of their own lengths: L and S stay the row strides of a
+ * sequence, sequence s has len_q[s] <= L queries and attends to keys [0, len_k[kvseq]) of sequence kvseq = (s + kv_shift) % nb.  Valid
+ * rows are gim_sdpa's at L = len_q[s], S = len_k[kvseq] bit for bit (the same tile walk); out rows [len_q[s], L) are written as zeros,
+ * and so is the whole sequence when len_k[kvseq] == 0.  vt from gim_lg_transpose_varlen with the key lengths.  dtype_qkv / dtype_out are
+ * gim_sdpa's dtype / out_dtype tags under the same rule: each GIM_F32 / GIM_BF16 / GIM_F16, one 16-bit kind per call. */
+int gim_sdpa_varlen(const void* q, const void* k, const void* vt, void* out, const int32_t* len_q, const int32_t* len_k, int nb, int H,
+                    int L, int S, int Sp, int D, int ldq, int ldk, int ldo, int kv_shift, int dtype_qkv, int dtype_out, gim_stream_t stream);
+
+/* gim_lg_assign (lightglue.py:226-300) where pair b has len0[b] <= M rows and len1[b] <= N columns: the softmax statistics, the
+ * arg-maxima and the mutual check see those only (tiles wholly outside are skipped); matches0 = -1, score 0 for i >= len0[b], likewise
+ * side 1; pos / count and with them gim_lg_emit_matches keep torch.where order over the rows that exist.  An empty side: all -1, zero
+ * scores, count 0.  gim_lg_log_assignment has no ragged form. */
+int gim_lg_assign_ragged(const gim_lg_assign_args* a, const int32_t* len0, const int32_t* len1, gim_stream_t stream);
+
+/* gim_lg_gather_pairs for a bank whose image in slot s has counts[s] <= K keypoints (counts int32 [n_slots]): rows at or beyond the
+ * image's count are ZERO in x32, cat and enc whatever the slab holds there, and len0[b] = counts[idx0[b]], len1[b] = counts[idx1[b]]
+ * (0 for a slot out of range) are written for the kernels above. */
+int gim_lg_gather_pairs_ragged(const void* bank_desc, const float* bank_enc, const int32_t* idx0, const int32_t* idx1,
+                               const int32_t* counts, float* x32, void* cat, float* enc, int32_t* len0, int32_t* len1, int B, int K,
+                               int n_slots, int storage, int dtype, int ld_x32, int ld_cat, gim_stream_t stream);
+
 /* hloc's sparse match-file datasets (hloc/match_features.py:150-160) of a whole batch from a gim_lg_assign result: matches0 int64
  * [B][K] -> int16 (the low 16 bits, as .short()), mscores0 fp32 [B][K] -> IEEE fp16 (round to nearest even, as .half()).  K > 32767
  * does not fit the int16 format and is refused before the launch.  All buffers 16-byte aligned. */
