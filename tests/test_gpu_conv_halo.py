@@ -12,7 +12,7 @@ CASES = [  # B, H, W, cin, cout, act
     (2, 8, 96, 128, 128, "relu"),     # 128-wide tile variant
     (1, 16, 32, 196, 128, "none"),
     (1, 8, 32, 64, 64, "none"),       # single chunk: the halo of the NEXT tile is prefetched at slab 0
-    (3, 40, 64, 40, 72, "relu"),      # tail only (cin < 64), 3 sub-steps per tap, many tiles per workgroup list
+    (3, 40, 64, 40, 72, "relu"),      # tail only (cin < 64), 3 sub-steps per tap; 30 patches on 256 workgroups: one each (several per workgroup: test_gpu_conv_many_tiles.py)
 ]
 
 

@@ -3,7 +3,8 @@ the CPU oracle or the torch fp32 op it replaces, on the same seeded inputs.
 
 Tolerances: fp32 mode (fp32 MFMA = fmaf chain) 2e-5 relative to the output scale -- summation order is
 the only difference; bf16 mode is compared against the fp32 reference evaluated on bf16-rounded
-operands, 1.5e-2 (output rounding 2^-9 + accumulation order).  Integer outputs: exact."""
+operands, 1.5e-2 (output rounding 2^-9 + accumulation order).  Integer outputs: exact.
+The conv cases here have at most 30 tiles, one per workgroup; launches whose workgroups walk several tiles: test_gpu_conv_many_tiles.py."""
 import pytest
 import torch
 import torch.nn.functional as F
