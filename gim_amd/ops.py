@@ -1638,27 +1638,34 @@ def ransac_mask(models, x0, x1, thr2, offsets=None):
 
 
 # ---- homography RANSAC step and perspective warp (gim_amd/pose.py, gim_amd/demo.py) ---------------------------------------
+def _minimal_step(word, symbol, m, k, x0, x1, idx, thr2, offsets):
+    """The one body of homography_step / fundamental_step / essential_step: samples of m points, k models per sample (None: one, and
+    no model axis), the library's `symbol`, `word` names the step in a refusal.  The outputs are zero-filled: without a launch
+    (B * K == 0, or no points, when every index is outside its pair) nothing is valid."""
+    _req_cuda(x0, x1, idx, offsets)
+    single = offsets is None
+    if idx.dtype != torch.int32 or idx.dim() != (2 if single else 3) or idx.shape[-1] != m or not idx.is_contiguous():
+        raise _lib.GimHipError(f"{word} idx must be contiguous int32 {f'[K,{m}]' if single else f'[B,K,{m}]'}, got {idx.dtype} {tuple(idx.shape)}")
+    B, K = (1, idx.shape[0]) if single else idx.shape[:2]
+    offsets, P = _ransac_points(x0, x1, offsets, B)
+    if idx.device != x0.device:
+        raise _lib.GimHipError(f"{word} idx and points are on different devices")
+    lead = tuple(idx.shape[:-1]) + (() if k is None else (k,))
+    models = torch.zeros(*lead, 3, 3, dtype=torch.float64, device=x0.device)
+    valid = torch.zeros(lead, dtype=torch.uint8, device=x0.device)
+    counts = torch.zeros(lead, dtype=torch.int32, device=x0.device)
+    if B * K and P:
+        check(getattr(lib, symbol)(_p(x0), _p(x1), _p(offsets), B, _p(idx), K, float(thr2), _p(models), _p(valid), _p(counts), _stream()),
+              symbol)
+    return models, valid.view(torch.bool), counts
+
+
 def homography_step(src, dst, idx, thr2, offsets=None):
     """Four-point homographies dst ~ H src of the samples `idx`, solved and scored in one launch (gim_homography_step; fp64, the
     arithmetic and validity rules of pose.homography_4pt / pose.transfer_error).  One pair: src / dst fp64 [P,2], idx int32 [K,4]
     -> (models fp64 [K,3,3] with h33 = 1, valid bool [K], counts int32 [K]).  B pairs: offsets int32 [B+1] over the concatenated
     points, idx [B,K,4] relative to each pair's offset -> [B,K,3,3], [B,K], [B,K].  A rejected sample: zero model, valid 0, count 0."""
-    _req_cuda(src, dst, idx, offsets)
-    single = offsets is None
-    if idx.dtype != torch.int32 or idx.dim() != (2 if single else 3) or idx.shape[-1] != 4 or not idx.is_contiguous():
-        raise _lib.GimHipError(f"homography idx must be contiguous int32 {'[K,4]' if single else '[B,K,4]'}, got {idx.dtype} {tuple(idx.shape)}")
-    B, K = (1, idx.shape[0]) if single else idx.shape[:2]
-    offsets, P = _ransac_points(src, dst, offsets, B)
-    if idx.device != src.device:
-        raise _lib.GimHipError("homography idx and points are on different devices")
-    lead = tuple(idx.shape[:-1])
-    models = torch.zeros(*lead, 3, 3, dtype=torch.float64, device=src.device)
-    valid = torch.zeros(lead, dtype=torch.uint8, device=src.device)
-    counts = torch.zeros(lead, dtype=torch.int32, device=src.device)
-    if B * K and P:               # without points every index is outside its pair: nothing is valid
-        check(lib.gim_homography_step(_p(src), _p(dst), _p(offsets), B, _p(idx), K, float(thr2), _p(models), _p(valid), _p(counts),
-                                      _stream()), "gim_homography_step")
-    return models, valid.view(torch.bool), counts
+    return _minimal_step("homography", "gim_homography_step", 4, None, src, dst, idx, thr2, offsets)
 
 
 def fundamental_step(x0, x1, idx, thr2, offsets=None):
@@ -1667,22 +1674,7 @@ def fundamental_step(x0, x1, idx, thr2, offsets=None):
     [K,7] -> (models fp64 [K,3,3,3] of unit Frobenius norm, valid bool [K,3], counts int32 [K,3]): up to three models per sample, in
     the order of their roots.  B pairs: offsets int32 [B+1] over the concatenated points, idx [B,K,7] relative to each pair's offset
     -> [B,K,3,3,3], [B,K,3], [B,K,3].  A rejected sample or an unused slot: zero model, valid 0, count 0."""
-    _req_cuda(x0, x1, idx, offsets)
-    single = offsets is None
-    if idx.dtype != torch.int32 or idx.dim() != (2 if single else 3) or idx.shape[-1] != 7 or not idx.is_contiguous():
-        raise _lib.GimHipError(f"fundamental idx must be contiguous int32 {'[K,7]' if single else '[B,K,7]'}, got {idx.dtype} {tuple(idx.shape)}")
-    B, K = (1, idx.shape[0]) if single else idx.shape[:2]
-    offsets, P = _ransac_points(x0, x1, offsets, B)
-    if idx.device != x0.device:
-        raise _lib.GimHipError("fundamental idx and points are on different devices")
-    lead = tuple(idx.shape[:-1])
-    models = torch.zeros(*lead, 3, 3, 3, dtype=torch.float64, device=x0.device)
-    valid = torch.zeros(*lead, 3, dtype=torch.uint8, device=x0.device)
-    counts = torch.zeros(*lead, 3, dtype=torch.int32, device=x0.device)
-    if B * K and P:               # without points every index is outside its pair: nothing is valid
-        check(lib.gim_fundamental_step(_p(x0), _p(x1), _p(offsets), B, _p(idx), K, float(thr2), _p(models), _p(valid), _p(counts),
-                                       _stream()), "gim_fundamental_step")
-    return models, valid.view(torch.bool), counts
+    return _minimal_step("fundamental", "gim_fundamental_step", 7, 3, x0, x1, idx, thr2, offsets)
 
 
 def essential_step(x0, x1, idx, thr2, offsets=None):
@@ -1692,22 +1684,7 @@ def essential_step(x0, x1, idx, thr2, offsets=None):
     up to ten models per sample, in the order of their roots.  B pairs: offsets int32 [B+1] over the concatenated points, idx
     [B,K,5] relative to each pair's offset -> [B,K,10,3,3], [B,K,10], [B,K,10].  A rejected sample or an unused slot: zero model,
     valid 0, count 0."""
-    _req_cuda(x0, x1, idx, offsets)
-    single = offsets is None
-    if idx.dtype != torch.int32 or idx.dim() != (2 if single else 3) or idx.shape[-1] != 5 or not idx.is_contiguous():
-        raise _lib.GimHipError(f"essential idx must be contiguous int32 {'[K,5]' if single else '[B,K,5]'}, got {idx.dtype} {tuple(idx.shape)}")
-    B, K = (1, idx.shape[0]) if single else idx.shape[:2]
-    offsets, P = _ransac_points(x0, x1, offsets, B)
-    if idx.device != x0.device:
-        raise _lib.GimHipError("essential idx and points are on different devices")
-    lead = tuple(idx.shape[:-1])
-    models = torch.zeros(*lead, 10, 3, 3, dtype=torch.float64, device=x0.device)
-    valid = torch.zeros(*lead, 10, dtype=torch.uint8, device=x0.device)
-    counts = torch.zeros(*lead, 10, dtype=torch.int32, device=x0.device)
-    if B * K and P:               # without points every index is outside its pair: nothing is valid
-        check(lib.gim_essential_step(_p(x0), _p(x1), _p(offsets), B, _p(idx), K, float(thr2), _p(models), _p(valid), _p(counts),
-                                     _stream()), "gim_essential_step")
-    return models, valid.view(torch.bool), counts
+    return _minimal_step("essential", "gim_essential_step", 5, 10, x0, x1, idx, thr2, offsets)
 
 
 def recover_pose(E, x0, x1, mask=None, offsets=None, distance_thresh=1e9):

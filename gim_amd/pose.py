@@ -697,12 +697,10 @@ def _count_inliers(Ms, valid, x0, x1, thr2, chunk=128, error=None):
     return np.where(valid, out, 0)
 
 
-class DeviceScorer:
-    """The scoring half of a RANSAC step on the GPU (csrc/ransac_score.hip through ops.ransac_score / ops.ransac_mask): the points go
-    to the device once, every step uploads its candidate models and reads the counts back, the final mask is one more call.  Same
-    fp64 arithmetic as `sampson_error`, so a RANSAC run scored here walks the trajectory of the host run with the same seed.
-    One pair: x0, x1 [P, 2].  Several pairs in lockstep (`find_essential_mat_batch`): their points concatenated and `offsets` [B + 1];
-    `counts` then takes models [B, K, 3, 3] / valid [B, K] and `mask` one model per pair [B, 3, 3] -> bool [Ptot]."""
+class _DevicePoints:
+    """The matched points of one pair, or of several pairs concatenated with `offsets` [B + 1], uploaded once as fp64 [P, 2] and kept
+    on `device` for every later call.  A subclass names its mask op (looked up on `ops` at call time) and its refit kind."""
+    _mask, _kind = "ransac_mask", 1          # the Sampson error; gim_model_refit's fundamental matrices in pixels
 
     def __init__(self, x0, x1, thr2, device, offsets=None):
         import torch
@@ -711,25 +709,59 @@ class DeviceScorer:
         self.device = torch.device(device)
         self.thr2 = float(thr2)
         with torch.cuda.device(self.device):
-            self.x0 = torch.from_numpy(np.ascontiguousarray(x0, dtype=np.float64)).to(self.device)
-            self.x1 = torch.from_numpy(np.ascontiguousarray(x1, dtype=np.float64)).to(self.device)
-            self.offsets = None if offsets is None else torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int32)).to(self.device)
+            self.x0, self.x1 = self._up(x0, np.float64), self._up(x1, np.float64)
+            self.offsets = None if offsets is None else self._up(offsets, np.int32)
 
     def _up(self, a, dtype):
         return self._torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(self.device)
+
+    def mask(self, M):
+        """one model [3, 3], or with offsets one per pair [B, 3, 3] -> the inlier mask bool [Ptot]"""
+        with self._torch.cuda.device(self.device):
+            return getattr(self._ops, self._mask)(self._up(M, np.float64), self.x0, self.x1, self.thr2, offsets=self.offsets).cpu().numpy()
+
+    def refit(self, M, rounds=1):
+        """gim_model_refit over the points and offsets held here, from the models' own masks: M [3,3] / [B,3,3] ->
+        `_device_refit`'s arrays (models [B,3,3], mask bool [Ptot], counts [B,2], accepted [B]) after ONE copy"""
+        return _device_refit(self._ops, self._torch, self._kind, self.x0, self.x1, self.offsets, self.thr2, M, rounds)
+
+
+class DeviceScorer(_DevicePoints):
+    """The scoring half of a RANSAC step on the GPU (csrc/ransac_score.hip through ops.ransac_score / ops.ransac_mask): every step
+    uploads its candidate models and reads the counts back, the final mask is one more call.  Same fp64 arithmetic as
+    `sampson_error`, so a RANSAC run scored here walks the trajectory of the host run with the same seed.
+    One pair: models [K, 3, 3] / valid [K].  Several pairs in lockstep (`find_essential_mat_batch`): models [B, K, 3, 3] / valid [B, K]."""
 
     def counts(self, Ms, valid):
         with self._torch.cuda.device(self.device):
             c = self._ops.ransac_score(self._up(Ms, np.float64), self.x0, self.x1, self.thr2, valid=self._up(valid, np.uint8), offsets=self.offsets)
             return c.cpu().numpy().astype(np.int64)
 
-    def mask(self, M):
-        with self._torch.cuda.device(self.device):
-            return self._ops.ransac_mask(self._up(M, np.float64), self.x0, self.x1, self.thr2, offsets=self.offsets).cpu().numpy()
 
-    def refit(self, M, rounds=1):
-        """gim_model_refit (kind 1: fundamental matrices in pixels) over the points held here -> `_device_refit`'s arrays"""
-        return _device_refit(self._ops, self._torch, 1, self.x0, self.x1, self.offsets, self.thr2, M, rounds)
+class _DeviceStep(_DevicePoints):
+    """A whole RANSAC step on the GPU: a step uploads only its sample indices and reads back the models, flags and counts of ONE
+    launch that solves and scores.  A subclass declares m (points per sample), k (models per sample) and the name of its step op.
+    `solve` is the `solve_idx` hook of `_ransac_steps`, `counts` / `mask` the scorer interface of `_ransac` (the counts are those of
+    the launch that made the models).  One pair: idx [K, m].  Several pairs in lockstep: idx [B, K, m] relative to each pair (an
+    index of -1 marks padding: invalid)."""
+    _counts = None
+
+    def solve(self, idx):
+        """idx [..., m] -> (models [..., k, 3, 3], valid [..., k]) on the host"""
+        lead = np.shape(idx)[:-1] + (self.k,)
+        with self._torch.cuda.device(self.device):
+            models, valid, counts = getattr(self._ops, self._step)(self.x0, self.x1, self._up(idx, np.int32), self.thr2, offsets=self.offsets)
+            self._counts = counts.cpu().numpy().astype(np.int64).reshape(lead)
+            return models.cpu().numpy().reshape(lead + (3, 3)), valid.cpu().numpy().reshape(lead)      # homography_step has no k axis
+
+    def counts(self, Ms, valid):
+        return self._counts.reshape(-1) if self.offsets is None else self._counts
+
+    def step_on_device(self, idx):
+        """the step's launch alone, for `_ransac_on_device`: idx int32 [B, K, m] on the device -> (models, counts int32) of
+        B * K * k entries on the device; nothing is read back"""
+        models, _, counts = getattr(self._ops, self._step)(self.x0, self.x1, idx, self.thr2, offsets=self.offsets)
+        return models, counts
 
 
 # ---- counter-based sampling and the per-step reduction (csrc/ransac_sample.h, csrc/ransac_records.hip restated) -----------------
@@ -849,9 +881,9 @@ def _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch=250, solve_i
     models (Ms [nb * k, 3, 3], valid [nb * k]) and is sent their inlier counts [nb * k]; the generator's return value is the best
     model [3, 3] or None.  Who counts (the host, a device, one launch for many pairs in lockstep) is the driver's business.
     solve_idx: a hook that receives the step's sample indices idx [nb, m] and returns (Ms [nb, k, 3, 3], valid [nb, k]) in place of
-    solver(s0[idx], s1[idx]) -- a solver that lives where the points already are (`DeviceHomography`, `DeviceFundamental`).  The
+    solver(s0[idx], s1[idx]) -- a solver that lives where the points already are (`_DeviceStep.solve`).  The
     arrays it returns are read only after the counts have been sent, so a lockstep driver may hand out empty ones and fill them in
-    place from one launch for many pairs (`find_fundamental_mat_batch`).
+    place from one launch for many pairs (`_lockstep_device`).
     draw: None draws from `rng` as ever; otherwise draw(first, nb) -> the samples number first .. first + nb - 1 of the run
     (sampler="philox": `device_samples`) and `rng` is not used."""
     lconf = np.log(max(1.0 - conf, 1e-300))
@@ -940,12 +972,7 @@ def find_essential_mat(x0, x1, threshold, prob=0.999, max_iters=1000, seed=0, de
 def _find_essential(x0, x1, threshold, prob, max_iters, seed, device, solve, sampler, step_kw=None):
     """`find_essential_mat` -> (E | None, mask, the DeviceEssential of a solve="device" run that built one, else None);
     step_kw: further keywords of DeviceEssential (recover=True: the pose comes down with the mask)"""
-    if solve not in ("host", "device", "ge"):
-        raise ValueError(f"solve={solve!r}: host, device or ge")
-    if solve == "device" and device is None:
-        raise ValueError("solve='device' needs a device")
-    if solve == "ge" and device is not None:
-        raise ValueError("solve='ge' runs on the host: device must be None")
+    _check_solve(solve, device)
     _check_sampler(sampler, device, solve)
     x0 = np.ascontiguousarray(x0, dtype=np.float64)
     x1 = np.ascontiguousarray(x1, dtype=np.float64)
@@ -999,14 +1026,14 @@ def find_essential_pose_batch(pairs, threshold, prob=0.999, max_iters=1000, seed
     [(E | None, mask, (n_good, R, t) | None)]; a pair's result is find_essential_pose's.  solve="device": the launch runs on the
     lockstep run's points and mask (one copy for the batch); solve="host": the pairs with a model are uploaded for it."""
     _check_recover("device", device)
-    pairs = [(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 2), np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 2)) for a, b in pairs]
+    pairs, _ = _pairs64(pairs)
     if solve == "device":
         _check_sampler(sampler, device, solve)
         kw = dict(recover=True, distance_thresh=distance_thresh)
         if sampler == "device":
             found, dev = _ransac_on_device(pairs, DeviceEssential, threshold, prob, max_iters, seed, device, step_kw=kw)
         else:
-            found, dev = _lockstep_device(pairs, 5, 10, DeviceEssential, threshold, prob, max_iters, seed, device, sampler, step_kw=kw)
+            found, dev = _lockstep_device(pairs, DeviceEssential, threshold, prob, max_iters, seed, device, sampler, step_kw=kw)
         return [(E, mask, dev.pose_of(b) if E is not None else None) for b, (E, mask) in enumerate(found)]
     found = find_essential_mat_batch(pairs, threshold, prob, max_iters, seed, device, solve=solve, sampler=sampler)
     have = [b for b, (E, _) in enumerate(found) if E is not None]
@@ -1029,124 +1056,55 @@ def find_essential_pose_batch(pairs, threshold, prob=0.999, max_iters=1000, seed
 
 
 def find_essential_mat_batch(pairs, threshold, prob=0.999, max_iters=1000, seed=0, device=None, scorer=None, solve="host", sampler="host"):
-    """`find_essential_mat(x0, x1, threshold, prob, max_iters, seed)` for every (x0, x1) of `pairs`, run in lockstep: a step solves
-    the samples of every unfinished pair on the host and scores all of them in ONE launch (ragged point sets through offsets); every
-    pair has its own default_rng(seed) and its own shrinking iteration bound, so its result is that of the single call.
+    """`find_essential_mat(x0, x1, threshold, prob, max_iters, seed)` for every (x0, x1) of `pairs`, run in lockstep (`_lockstep`): a
+    round solves the samples of every unfinished pair on the host and scores all of them in ONE launch (ragged point sets through
+    offsets), and one mask call for all pairs ends the run (`_batch_results`); a pair's result is that of the single call.
     scorer: an object like DeviceScorer over the concatenated points (counts(models [B,K,3,3], valid [B,K]) -> [B,K],
     mask(models [B,3,3]) -> bool [Ptot]); default DeviceScorer on `device`; neither: the pairs run one by one on the host.
-    solve="device" (needs `device`, takes no `scorer`): the lockstep run of `find_fundamental_mat_batch` over five-point samples --
-    a step uploads the sample indices of every unfinished pair and solves and scores all of them in ONE gim_essential_step launch;
-    a pair's result is that of find_essential_mat(..., device=device, solve="device").
+    solve="device" (needs `device`, takes no `scorer`): `_lockstep_device` with `DeviceEssential`, ONE gim_essential_step launch
+    per round; a pair's result is that of find_essential_mat(..., device=device, solve="device").
     sampler: as in find_essential_mat, every pair's ordinals running from 0 under the shared seed ("device" needs solve="device").
     -> [(E [3,3] | None, mask [P_b] bool)] in the order of `pairs`."""
-    if solve not in ("host", "device"):
-        raise ValueError(f"solve={solve!r}: host or device")
+    _check_solve(solve, device, ("host", "device"))
     _check_sampler(sampler, device, solve)
     if solve == "device":
-        if device is None or scorer is not None:
-            raise ValueError("solve='device' needs a device and takes no scorer")
+        if scorer is not None:
+            raise ValueError("solve='device' takes no scorer")
         if sampler == "device":
             return _ransac_on_device(pairs, DeviceEssential, threshold, prob, max_iters, seed, device)[0]
-        return _lockstep_device(pairs, 5, 10, DeviceEssential, threshold, prob, max_iters, seed, device, sampler)[0]
-    pairs = [(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 2), np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 2)) for a, b in pairs]
+        return _lockstep_device(pairs, DeviceEssential, threshold, prob, max_iters, seed, device, sampler)[0]
+    pairs, offsets = _pairs64(pairs)
     if scorer is None and device is None:
         return [find_essential_mat(a, b, threshold, prob, max_iters, seed, sampler=sampler) for a, b in pairs]
     B = len(pairs)
     if B == 0:
         return []
-    offsets = np.concatenate([[0], np.cumsum([a.shape[0] for a, _ in pairs])]).astype(np.int64)
     if scorer is None:
-        scorer = DeviceScorer(np.concatenate([a for a, _ in pairs]), np.concatenate([b for _, b in pairs]), float(threshold) ** 2, device,
-                              offsets=offsets)
-    best = [None] * B
-    steps, pending = {}, {}
-    for b, (a, c) in enumerate(pairs):
-        if a.shape[0] >= 5:
-            steps[b] = _ransac_steps(a.shape[0], five_point, 5, prob, max_iters, np.random.default_rng(seed), a, c,
-                                     draw=_draw(sampler, seed, a.shape[0], 5))
+        scorer = _over_pairs(DeviceScorer, pairs, offsets, threshold, device)
+    steps = {b: _ransac_steps(a.shape[0], five_point, 5, prob, max_iters, np.random.default_rng(seed), a, c, draw=_draw(sampler, seed, a.shape[0], 5))
+             for b, (a, c) in enumerate(pairs) if a.shape[0] >= 5}
 
-    def advance(b, counts):
-        try:
-            pending[b] = next(steps[b]) if counts is None else steps[b].send(counts)
-        except StopIteration as stop:
-            best[b] = stop.value
-            pending.pop(b, None)
-
-    for b in steps:
-        advance(b, None)
-    while pending:
+    def launch(pending):
         K = max(Ms.shape[0] for Ms, _ in pending.values())
         models, valid = np.zeros((B, K, 3, 3)), np.zeros((B, K), dtype=bool)   # finished pairs and padding: valid = 0
         for b, (Ms, v) in pending.items():
             models[b, :Ms.shape[0]], valid[b, :Ms.shape[0]] = Ms, v
         counts = scorer.counts(models, valid)
-        for b in list(pending):
-            advance(b, counts[b, :pending[b][0].shape[0]])
-    found = [b for b in range(B) if best[b] is not None]
-    masks = np.zeros(offsets[-1], dtype=bool)
-    if found:
-        models = np.zeros((B, 3, 3))
-        for b in found:
-            models[b] = best[b]
-        masks = scorer.mask(models)
-    return [(best[b], masks[offsets[b]:offsets[b + 1]] if best[b] is not None else np.zeros(offsets[b + 1] - offsets[b], dtype=bool))
-            for b in range(B)]
+        return {b: counts[b, :Ms.shape[0]] for b, (Ms, _) in pending.items()}
+
+    return _batch_results(_lockstep(B, steps, launch), offsets, scorer)
 
 
-class DeviceFundamental:
-    """A whole fundamental-matrix RANSAC step on the GPU (csrc/fundamental.hip through ops.fundamental_step; the mask through
-    ops.ransac_mask, the same Sampson error): the points go to the device once; a step uploads only its sample indices and reads back
-    the up to three models per sample, their flags and counts of ONE launch.  `solve` is the `solve_idx` hook of `_ransac_steps`,
-    `counts` / `mask` the scorer interface of `_ransac` (the counts are those of the launch that made the models).
-    One pair: x0, x1 [P, 2], idx [K, 7].  Several pairs in lockstep: their points concatenated and `offsets` [B + 1]; `solve` then
-    takes idx [B, K, 7] relative to each pair (an index of -1 marks padding) and `mask` one model per pair [B, 3, 3] -> bool [Ptot]."""
-
+class DeviceFundamental(_DeviceStep):
+    """The fundamental-matrix step (csrc/fundamental.hip through ops.fundamental_step; the mask through ops.ransac_mask, the same
+    Sampson error): points in pixels, up to three models per sample."""
     _step = "fundamental_step"
-    m, k = 7, 3              # points per sample, models per sample
-
-    def __init__(self, x0, x1, thr2, device, offsets=None):
-        import torch
-        from . import ops
-        self._torch, self._ops = torch, ops
-        self.device = torch.device(device)
-        self.thr2 = float(thr2)
-        self._counts = None
-        with torch.cuda.device(self.device):
-            self.x0 = torch.from_numpy(np.ascontiguousarray(x0, dtype=np.float64)).to(self.device)
-            self.x1 = torch.from_numpy(np.ascontiguousarray(x1, dtype=np.float64)).to(self.device)
-            self.offsets = None if offsets is None else torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int32)).to(self.device)
-
-    def solve(self, idx):
-        with self._torch.cuda.device(self.device):
-            d_idx = self._torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(self.device)
-            models, valid, counts = getattr(self._ops, self._step)(self.x0, self.x1, d_idx, self.thr2, offsets=self.offsets)
-            self._counts = counts.cpu().numpy().astype(np.int64)
-            return models.cpu().numpy(), valid.cpu().numpy()
-
-    def counts(self, Ms, valid):
-        return self._counts.reshape(-1) if self.offsets is None else self._counts
-
-    def step_on_device(self, idx):
-        """the step's launch alone, for `_ransac_on_device`: idx int32 [B, K, m] on the device -> (models [B, K, k, 3, 3], counts
-        int32 [B, K, k]) on the device; nothing is read back"""
-        models, _, counts = getattr(self._ops, self._step)(self.x0, self.x1, idx, self.thr2, offsets=self.offsets)
-        return models, counts
-
-    def mask(self, M):
-        with self._torch.cuda.device(self.device):
-            d_M = self._torch.from_numpy(np.ascontiguousarray(M, dtype=np.float64)).to(self.device)
-            return self._ops.ransac_mask(d_M, self.x0, self.x1, self.thr2, offsets=self.offsets).cpu().numpy()
-
-    def refit(self, M, rounds=1):
-        """gim_model_refit (kind 1) over the points and offsets held here, from the models' own masks: M [3,3] / [B,3,3] ->
-        `_device_refit`'s arrays (models [B,3,3], mask bool [Ptot], counts [B,2], accepted [B]) after ONE copy"""
-        return _device_refit(self._ops, self._torch, 1, self.x0, self.x1, self.offsets, self.thr2, M, rounds)
+    m, k = 7, 3
 
 
-class DeviceEssential(DeviceFundamental):
-    """A whole essential-matrix RANSAC step on the GPU, the twin of `DeviceFundamental` (csrc/essential.hip through
-    ops.essential_step; the mask through ops.ransac_mask): points in normalised camera coordinates, idx [K, 5] or [B, K, 5], up to
-    ten models per sample; `counts` are those of the launch that made the models.
+class DeviceEssential(_DeviceStep):
+    """The essential-matrix step (csrc/essential.hip through ops.essential_step; the mask through ops.ransac_mask): points in
+    normalised camera coordinates, up to ten models per sample.
     recover=True: `mask` also runs recoverPose on the points held here (`recover`: gim_recover_pose takes gim_ransac_mask's output
     where it lies) and brings the RANSAC mask, R, t, the four counts and the winner back in ONE copy; the poses are left in
     `self.poses` = (n_good [B, 4], best [B], R [B, 3, 3], t [B, 3]) as numpy arrays (B = 1 for a single pair)."""
@@ -1170,7 +1128,7 @@ class DeviceEssential(DeviceFundamental):
             return super().mask(M)
         torch = self._torch
         with torch.cuda.device(self.device):
-            d_M = torch.from_numpy(np.ascontiguousarray(M, dtype=np.float64)).to(self.device)
+            d_M = self._up(M, np.float64)
             d_mask = self._ops.ransac_mask(d_M, self.x0, self.x1, self.thr2, offsets=self.offsets)
             n_good, best, R, t, _ = self.recover(d_M, d_mask)
             B = 1 if self.offsets is None else d_M.shape[0]
@@ -1204,12 +1162,7 @@ def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, 
     runs up to R rounds of local optimisation on it, the step USAC ends with: the normalised eight-point fit on the current inliers,
     a fresh mask, kept while the inlier count does not fall (`refit_ge`).  With a device it is ONE gim_model_refit launch on the
     points already there (with sampler="device" it also replaces the gim_ransac_mask call), with device=None `refit_ge` itself."""
-    if solve not in ("host", "device", "ge"):
-        raise ValueError(f"solve={solve!r}: host, device or ge")
-    if solve == "device" and device is None:
-        raise ValueError("solve='device' needs a device")
-    if solve == "ge" and device is not None:
-        raise ValueError("solve='ge' runs on the host: device must be None")
+    _check_solve(solve, device)
     _check_sampler(sampler, device, solve)
     refine = _check_refine(refine)
     p0 = np.ascontiguousarray(p0, dtype=np.float64)
@@ -1258,11 +1211,66 @@ def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, 
                            draw=draw), scorer)
 
 
-class _DeferredSolve:
-    """The `solve_idx` hook of one pair of a lockstep run: it keeps the step's indices and hands out empty arrays (k models per
-    sample), which the driver fills in place from the launch that serves every pair before it sends the counts."""
+def _pairs64(pairs):
+    """[(x0, x1)] -> (the pairs as contiguous fp64 [P_b, 2] arrays, offsets int64 [B + 1] of their concatenation)"""
+    pairs = [(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 2), np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 2)) for a, b in pairs]
+    return pairs, np.concatenate([[0], np.cumsum([a.shape[0] for a, _ in pairs])]).astype(np.int64)
 
-    def __init__(self, k=3):
+
+def _over_pairs(cls, pairs, offsets, threshold, device, **kw):
+    """a `_DevicePoints` class (or a stand-in with its constructor) over the concatenated points of `_pairs64`'s pairs"""
+    return cls(np.concatenate([a for a, _ in pairs]), np.concatenate([b for _, b in pairs]), float(threshold) ** 2, device, offsets=offsets, **kw)
+
+
+def _lockstep(B, steps, launch):
+    """Runs the `_ransac_steps` generators steps {b: generator} of a batch of B pairs in lockstep: every pair has its own generator
+    (its own draws and its own shrinking iteration bound, so its result is that of the single call), and every round serves all
+    unfinished pairs with ONE launch: launch({b: what pair b's step yielded}) -> {b: the counts to send it}.  A step shorter than
+    the longest is padded by the launch, a finished pair no longer takes part.  -> [best model | None] * B"""
+    best, pending = [None] * B, {}
+
+    def advance(b, counts):
+        try:
+            pending[b] = next(steps[b]) if counts is None else steps[b].send(counts)
+        except StopIteration as stop:
+            best[b] = stop.value
+            pending.pop(b, None)
+
+    for b in steps:
+        advance(b, None)
+    while pending:
+        counts = launch(pending)
+        for b in sorted(pending):
+            advance(b, counts[b])
+    return best
+
+
+def _batch_results(best, offsets, dev, finish=None):
+    """The tail of every batched run: best [model | None] * B, `dev` the object that holds the concatenated points -> [(model | None,
+    mask [P_b] bool)].  The models go up as one [B, 3, 3] array (zeros where a pair has none) for ONE dev.mask call, whose result is
+    cut by `offsets`; a pair without a model gets an all-False mask, and a batch without any model calls nothing.
+    finish: None, or finish(dev, models [B,3,3]) -> (models [B,3,3], masks [Ptot]) in place of that call (`_refit_finish`)."""
+    B = len(best)
+    found = [b for b in range(B) if best[b] is not None]
+    masks = np.zeros(offsets[-1], dtype=bool)
+    if found:
+        models = np.zeros((B, 3, 3))
+        for b in found:
+            models[b] = best[b]
+        if finish is None:
+            masks = np.asarray(dev.mask(models), dtype=bool)
+        else:
+            models, masks = finish(dev, models)
+            best = [models[b] if b in found else None for b in range(B)]
+    return [(best[b], masks[offsets[b]:offsets[b + 1]] if best[b] is not None else np.zeros(offsets[b + 1] - offsets[b], dtype=bool))
+            for b in range(B)]
+
+
+class _DeferredSolve:
+    """The `solve_idx` hook of one pair of a device-solve lockstep run: it keeps the step's indices and hands out empty arrays (k
+    models per sample), which the launch that serves every pair fills in place before the counts are sent."""
+
+    def __init__(self, k):
         self.k = k
 
     def __call__(self, idx):
@@ -1271,65 +1279,39 @@ class _DeferredSolve:
         return self.models, self.valid
 
 
-def _lockstep_device(pairs, m, k, step_cls, threshold, prob, max_iters, seed, device, sampler="host", step_kw=None, finish=None):
-    """The lockstep driver of find_fundamental_mat_batch and find_essential_mat_batch(solve="device"): samples of m points, k models
-    per sample, `step_cls` (DeviceFundamental, DeviceEssential) over the concatenated points.  A step draws the samples of every
-    unfinished pair on the host and solves and scores all of them in ONE launch (ragged point sets through offsets; a finished pair
-    and the padding of a shorter step are index -1: invalid); one gim_ransac_mask call for all pairs ends the run.  step_kw: further keywords of `step_cls`.
-    finish: None, or finish(dev, models [B,3,3]) -> (models [B,3,3], masks [Ptot]) in place of that last call (`_refit_finish`).
-    -> ([(model | None, mask)], the step object or None)"""
-    pairs = [(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 2), np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 2)) for a, b in pairs]
+def _lockstep_device(pairs, step_cls, threshold, prob, max_iters, seed, device, sampler="host", step_kw=None, finish=None):
+    """`_lockstep` with the solve on the device: a round uploads the sample indices of every unfinished pair and solves and scores
+    all of them in ONE launch of `step_cls` (DeviceFundamental, DeviceEssential) over the concatenated points (ragged point sets
+    through offsets; a finished pair and the padding of a shorter step are index -1: invalid).  The step object is made when the
+    first round needs it: a batch in which no pair has `step_cls.m` points uploads nothing.  step_kw: further keywords of `step_cls`;
+    finish: that of `_batch_results`.  -> ([(model | None, mask)], the step object or None)"""
+    m, k = step_cls.m, step_cls.k
+    pairs, offsets = _pairs64(pairs)
     B = len(pairs)
-    if B == 0:
-        return [], None
-    offsets = np.concatenate([[0], np.cumsum([a.shape[0] for a, _ in pairs])]).astype(np.int64)
-    best = [None] * B
-    steps, hooks, pending = {}, {}, set()
-    for b, (a, c) in enumerate(pairs):
-        if a.shape[0] >= m:
-            hooks[b] = _DeferredSolve(k)
-            steps[b] = _ransac_steps(a.shape[0], None, m, prob, max_iters, np.random.default_rng(seed), a, c, solve_idx=hooks[b],
-                                     draw=_draw(sampler, seed, a.shape[0], m))
-
-    def advance(b, counts):
-        try:
-            next(steps[b]) if counts is None else steps[b].send(counts)
-            pending.add(b)
-        except StopIteration as stop:
-            best[b] = stop.value
-            pending.discard(b)
-
-    for b in steps:
-        advance(b, None)
+    hooks = {b: _DeferredSolve(k) for b, (a, _) in enumerate(pairs) if a.shape[0] >= m}
+    steps = {b: _ransac_steps(pairs[b][0].shape[0], None, m, prob, max_iters, np.random.default_rng(seed), *pairs[b], solve_idx=hook,
+                              draw=_draw(sampler, seed, pairs[b][0].shape[0], m)) for b, hook in hooks.items()}
     dev = None
-    if pending:
-        dev = step_cls(np.concatenate([a for a, _ in pairs]), np.concatenate([b for _, b in pairs]), float(threshold) ** 2, device,
-                       offsets=offsets, **(step_kw or {}))
-    while pending:
+
+    def launch(pending):
+        nonlocal dev
+        if dev is None:
+            dev = _over_pairs(step_cls, pairs, offsets, threshold, device, **(step_kw or {}))
         K = max(hooks[b].idx.shape[0] for b in pending)
         idx = np.full((B, K, m), -1, dtype=np.int32)
         for b in pending:
             idx[b, :hooks[b].idx.shape[0]] = hooks[b].idx
         models, valid = dev.solve(idx)
         counts = dev.counts(models, valid)
-        for b in sorted(pending):
+        out = {}
+        for b in pending:
             nb = hooks[b].idx.shape[0]
             hooks[b].models[...], hooks[b].valid[...] = models[b, :nb], valid[b, :nb]
-            advance(b, counts[b, :nb].reshape(-1))
-    found = [b for b in range(B) if best[b] is not None]
-    masks = np.zeros(offsets[-1], dtype=bool)
-    if found:
-        models = np.zeros((B, 3, 3))
-        for b in found:
-            models[b] = best[b]
-        if finish is None:
-            masks = dev.mask(models)
-        else:
-            models, masks = finish(dev, models)
-            for b in found:
-                best[b] = models[b]
-    return [(best[b], masks[offsets[b]:offsets[b + 1]] if best[b] is not None else np.zeros(offsets[b + 1] - offsets[b], dtype=bool))
-            for b in range(B)], dev
+            out[b] = counts[b, :nb].reshape(-1)
+        return out
+
+    best = _lockstep(B, steps, launch)
+    return _batch_results(best, offsets, dev, finish), dev
 
 
 def _ransac_on_device(pairs, step_cls, threshold, prob, max_iters, seed, device, batch=250, step_kw=None, finish=None):
@@ -1340,23 +1322,19 @@ def _ransac_on_device(pairs, step_cls, threshold, prob, max_iters, seed, device,
     host replays the records (`_RecordWalk`: the rule and the bound of `_ransac_steps`) and reads the 72 bytes of a pair's model
     only in a step that accepted a record of that pair; models, flags and counts are never read back in bulk.  A pair's ordinals run
     from 0 under the shared seed: its result is that of the single call, and that of sampler="philox" on the same device.
-    Pairs with fewer than m points get (None, all-False) and, when no pair has more, nothing is launched.
-    finish: None, or finish(dev, models [B,3,3]) -> (models [B,3,3], masks [Ptot]) in place of the run's last mask call.
+    When no pair has m points, nothing is uploaded or launched.  The run ends with `_batch_results`; finish: its hook.
     -> ([(model [3,3] | None, mask [P_b] bool)], the step object or None -- `find_homography` takes its re-fit mask from it)"""
     m, k = step_cls.m, step_cls.k
     seed = _check_seed64(seed)
-    pairs = [(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 2), np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 2)) for a, b in pairs]
+    pairs, offsets = _pairs64(pairs)
     B = len(pairs)
-    offsets = np.concatenate([[0], np.cumsum([a.shape[0] for a, _ in pairs])]).astype(np.int64)
     walks = {b: _RecordWalk(a.shape[0], m, prob, max_iters, batch) for b, (a, _) in enumerate(pairs) if a.shape[0] >= m}
     best = [None] * B
-    none = [(None, np.zeros(offsets[b + 1] - offsets[b], dtype=bool)) for b in range(B)]
     if not walks:
-        return none, None
+        return _batch_results(best, offsets, None), None
     import torch
     from . import ops
-    dev = step_cls(np.concatenate([a for a, _ in pairs]), np.concatenate([b for _, b in pairs]), float(threshold) ** 2, device, offsets=offsets,
-                   **(step_kw or {}))
+    dev = _over_pairs(step_cls, pairs, offsets, threshold, device, **(step_kw or {}))
     ctl = np.zeros(4 * B, dtype=np.int32)                       # [first as int64 | count | floor]: one upload per step
     first, count, floor = ctl[:2 * B].view(np.int64), ctl[2 * B:3 * B], ctl[3 * B:]
     head = 1 + 3 * RECORDS_FIRST_COPY
@@ -1383,19 +1361,17 @@ def _ransac_on_device(pairs, step_cls, threshold, prob, max_iters, seed, device,
                     hit = w.replay(h[b, 1:1 + 3 * h[b, 0]].reshape(-1, 3))
                     if hit is not None:
                         best[b] = models[b, hit[0], hit[1]].cpu().numpy()
-        found = [b for b in range(B) if best[b] is not None]
-        if not found:
-            return none, dev
-        M = np.zeros((B, 3, 3))
-        for b in found:
-            M[b] = best[b]
-        if finish is None:
-            masks = np.asarray(dev.mask(M), dtype=bool)
-        else:
-            M, masks = finish(dev, M)
-            for b in found:
-                best[b] = M[b]
-    return [(best[b], masks[offsets[b]:offsets[b + 1]]) if best[b] is not None else none[b] for b in range(B)], dev
+    return _batch_results(best, offsets, dev, finish), dev
+
+
+def _check_solve(solve, device, allowed=("host", "device", "ge")):
+    """the `solve=` rules shared by the entry points, `allowed` the names this one takes; raises before anything is uploaded"""
+    if solve not in allowed:
+        raise ValueError(f"solve={solve!r}: {' or '.join(allowed)}")
+    if solve == "device" and device is None:
+        raise ValueError("solve='device' needs a device")
+    if solve == "ge" and device is not None:
+        raise ValueError("solve='ge' runs on the host: device must be None")
 
 
 def _check_sampler(sampler, device, solve="device"):
@@ -1408,24 +1384,21 @@ def _check_sampler(sampler, device, solve="device"):
 
 def find_fundamental_mat_batch(pairs, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, solve="device", sampler="host",
                                refine=0):
-    """`find_fundamental_mat(p0, p1, threshold, prob, max_iters, seed, device, solve="device")` for every (p0, p1) of `pairs`, run in
-    lockstep as find_essential_mat_batch runs its pairs: a step draws the samples of every unfinished pair on the host and solves and
-    scores all of them in ONE gim_fundamental_step launch (ragged point sets through offsets; a finished pair and the padding of a
-    shorter step are index -1: invalid); one gim_ransac_mask call for all pairs ends the run.  Every pair has its own
-    default_rng(seed) and its own shrinking iteration bound, so its result is that of the single call.
+    """`find_fundamental_mat(p0, p1, threshold, prob, max_iters, seed, device, solve="device")` for every (p0, p1) of `pairs`:
+    `_lockstep_device` with `DeviceFundamental`, ONE gim_fundamental_step launch per round and one gim_ransac_mask call for all
+    pairs at the end; a pair's result is that of the single call.
     sampler: "philox" draws every pair's samples with `device_samples` on the host, "device" on the GPU, where each step is then
     reduced to its record samples (`_ransac_on_device`); a pair's result is again that of the single call with that sampler.
     refine: that of find_fundamental_mat; R > 0 replaces the run's gim_ransac_mask call with ONE gim_model_refit launch over all
     pairs (a pair without a model is skipped there, and a batch without any model launches nothing).
     -> [(F [3,3] | None, mask [P_b] bool)] in the order of `pairs`."""
-    if solve != "device" or device is None:
-        raise ValueError("find_fundamental_mat_batch runs solve='device' on a device")
+    _check_solve(solve, device, ("device",))
     _check_sampler(sampler, device, solve)
     refine = _check_refine(refine)
     finish = _refit_finish(refine) if refine else None
     if sampler == "device":
         return _ransac_on_device(pairs, DeviceFundamental, threshold, prob, max_iters, seed, device, finish=finish)[0]
-    return _lockstep_device(pairs, 7, 3, DeviceFundamental, threshold, prob, max_iters, seed, device, sampler, finish=finish)[0]
+    return _lockstep_device(pairs, DeviceFundamental, threshold, prob, max_iters, seed, device, sampler, finish=finish)[0]
 
 
 def verify_pairs(pairs_of_points, threshold=1.0, device=None, prob=0.999999, max_iters=10000, seed=0, batch=32, sampler="host", refine=0):
@@ -1577,49 +1550,14 @@ def homography_dlt(src, dst):
     return H if np.isfinite(H).all() else None
 
 
-class DeviceHomography:
-    """A whole homography RANSAC step on the GPU (csrc/homography.hip through ops.homography_step / ops.homography_mask): the points
-    go to the device once; a step uploads only its sample indices and reads back models, flags and counts of ONE launch.  `solve`
-    is the `solve_idx` hook of `_ransac_steps`, `counts` / `mask` the scorer interface of `_ransac` (the counts are those of the
-    launch that made the models).  offsets [B + 1] (several pairs, their points concatenated) serves `_ransac_on_device` alone:
-    `step_on_device` and `mask` (one model per pair [B, 3, 3]) honour it, `solve` is the single pair's."""
+class DeviceHomography(_DeviceStep):
+    """The homography step (csrc/homography.hip through ops.homography_step / ops.homography_mask, the forward transfer error):
+    dst ~ H src in pixels, one model per sample; the points are held as `x0` (src) and `x1` (dst)."""
+    _step, _mask, _kind = "homography_step", "homography_mask", 0
     m, k = 4, 1
 
     def __init__(self, src, dst, thr2, device, offsets=None):
-        import torch
-        from . import ops
-        self._torch, self._ops = torch, ops
-        self.device = torch.device(device)
-        self.thr2 = float(thr2)
-        self._counts = None
-        with torch.cuda.device(self.device):
-            self.src = torch.from_numpy(np.ascontiguousarray(src, dtype=np.float64)).to(self.device)
-            self.dst = torch.from_numpy(np.ascontiguousarray(dst, dtype=np.float64)).to(self.device)
-            self.offsets = None if offsets is None else torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int32)).to(self.device)
-
-    def step_on_device(self, idx):
-        models, _, counts = self._ops.homography_step(self.src, self.dst, idx, self.thr2, offsets=self.offsets)
-        return models, counts
-
-    def solve(self, idx):
-        with self._torch.cuda.device(self.device):
-            d_idx = self._torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(self.device)
-            models, valid, counts = self._ops.homography_step(self.src, self.dst, d_idx, self.thr2)
-            self._counts = counts.cpu().numpy().astype(np.int64)
-            return models.cpu().numpy()[:, None], valid.cpu().numpy()[:, None]
-
-    def counts(self, Ms, valid):
-        return self._counts
-
-    def mask(self, M):
-        with self._torch.cuda.device(self.device):
-            d_M = self._torch.from_numpy(np.ascontiguousarray(M, dtype=np.float64)).to(self.device)
-            return self._ops.homography_mask(d_M, self.src, self.dst, self.thr2, offsets=self.offsets).cpu().numpy()
-
-    def refit(self, M, rounds=1):
-        """gim_model_refit (kind 0) over the points and offsets held here, from the models' own masks: M [3,3] / [B,3,3] ->
-        `_device_refit`'s arrays (models [B,3,3], mask bool [Ptot], counts [B,2], accepted [B]) after ONE copy"""
-        return _device_refit(self._ops, self._torch, 0, self.src, self.dst, self.offsets, self.thr2, M, rounds)
+        super().__init__(src, dst, thr2, device, offsets)
 
 
 def find_homography(src, dst, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, sampler="host", refit="host"):
@@ -2046,7 +1984,7 @@ def _device_refit(ops, torch, kind, a, b, offsets, thr2, M, rounds):
 
 
 def _refit_finish(rounds):
-    """the `finish` hook of `_lockstep_device` / `_ransac_on_device`: the refit's models and masks in place of the RANSAC's"""
+    """a `finish` hook of `_batch_results`: the refit's models and masks in place of the RANSAC's"""
     def finish(dev, M):
         models, masks, _, _ = dev.refit(M, rounds)
         return models, masks
