@@ -245,6 +245,9 @@ PROTOTYPES = {
     "gim_frame_prep_tile": (c_int, [c_int] * 4 + [c_void_p] * 2),
     "gim_frame_prep": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] + [c_int] * 2 + [c_void_p] * 3 + [c_int] + [c_void_p] * 2 + [c_int]
                        + [c_void_p] * 9),
+    # MAGSAC++ scoring of RANSAC hypotheses and the step reduction keyed on its int64 quality (added within ABI revision 115)
+    "gim_magsac_score": (c_int, [c_int] + [c_void_p] * 5 + [c_int, c_int, ctypes.c_double, ctypes.c_double] + [c_void_p] * 3),
+    "gim_ransac_records64": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 2),
 }
 
 

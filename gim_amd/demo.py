@@ -146,7 +146,7 @@ def build(model_name, weights=None, precision=None, device="cuda", dinov2_weight
 
 @torch.no_grad()
 def match_pair(model_name, model, detector, path0, path1, device="cuda", resize_max=None, num=5000, ransac_solve="host",
-               ransac_sampler="host", ransac_refine=0):
+               ransac_sampler="host", ransac_refine=0, ransac_score="count"):
     """demo.py:405-511 -> dict(mkpts0_f, mkpts1_f, mconf, m_bids, hw0_i, hw1_i); coordinates in pixels of the pre-processed images
     for the dense matchers and gim_loftr (as the reference leaves them), of the original images for gim_lightglue (:499-500).
     ransac_solve="device": the seven-point solve of the geometry filter runs on the matches' device too, fused with the scoring
@@ -155,11 +155,15 @@ def match_pair(model_name, model, detector, path0, path1, device="cuda", resize_
     "philox" (the counter-based draw, made on the host) or "device" (drawn and reduced on the GPU; needs ransac_solve="device").
     OpenCV draws its own samples.
     ransac_refine: the `refine` of pose.find_fundamental_mat on the numpy and device backends -- 0 (the default) or up to 8 rounds
-    of eight-point refit on the inliers, the step OpenCV's USAC ends with."""
+    of eight-point refit on the inliers, the step OpenCV's USAC ends with.
+    ransac_score: the `score` of pose.find_fundamental_mat on the numpy and device backends -- "count" (the default) or "magsac"
+    (the MAGSAC++ loss that the reference's USAC_MAGSAC names; needs ransac_sampler "philox" or "device")."""
     if ransac_solve not in ("host", "device"):
         raise ValueError(f"ransac_solve={ransac_solve!r}: host or device")
     if ransac_sampler not in ("host", "philox", "device") or (ransac_sampler == "device" and ransac_solve != "device"):
         raise ValueError(f"ransac_sampler={ransac_sampler!r}: host, philox or device, the last with ransac_solve='device'")
+    if ransac_score not in ("count", "magsac") or (ransac_score == "magsac" and ransac_sampler == "host"):
+        raise ValueError(f"ransac_score={ransac_score!r}: count or magsac, the last with ransac_sampler='philox' or 'device'")
     image0, scale0 = preprocess(read_image(path0), resize_max=resize_max)
     image1, scale1 = preprocess(read_image(path1), resize_max=resize_max)
     image0, image1 = image0.to(device)[None], image1.to(device)[None]
@@ -190,8 +194,9 @@ def match_pair(model_name, model, detector, path0, path1, device="cuda", resize_
     out = {"mkpts0_f": kpts0, "mkpts1_f": kpts1, "m_bids": b_ids, "mconf": mconf,
            "hw0_i": image0.shape[2:], "hw1_i": image1.shape[2:], "scale0": scale0, "scale1": scale1,
            "color0": image0, "color1": image1}
-    # robust fitting on the host (demo.py:514-517): OpenCV's USAC_MAGSAC when cv2 imports, else plain seven-point RANSAC with the
-    # same threshold / confidence / iteration bound (gim_amd/pose.py; `backend` says which one produced the mask)
+    # robust fitting on the host (demo.py:514-517): OpenCV's USAC_MAGSAC when cv2 imports, else seven-point RANSAC with the same
+    # threshold / confidence / iteration bound (gim_amd/pose.py: plain counting, or its own MAGSAC++ scoring under
+    # ransac_score="magsac"; `backend` says which one produced the mask)
     if len(kpts0) >= 8:
         from . import pose
         p0, p1 = kpts0.float().cpu().numpy(), kpts1.float().cpu().numpy()
@@ -200,7 +205,7 @@ def match_pair(model_name, model, detector, path0, path1, device="cuda", resize_
             # solved and scored on the matches' device, one launch per RANSAC step (pose.DeviceFundamental)
             out["F"], out["inliers"] = pose.find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000,
                                                                  device=kpts0.device if kpts0.is_cuda else None, solve="device",
-                                                                 sampler=ransac_sampler, refine=ransac_refine)
+                                                                 sampler=ransac_sampler, refine=ransac_refine, score=ransac_score)
         elif out["ransac_backend"] == "cv2":
             import cv2
             out["F"], mask = cv2.findFundamentalMat(p0, p1, cv2.USAC_MAGSAC, ransacReprojThreshold=1.0, confidence=0.999999, maxIters=10000)
@@ -209,12 +214,13 @@ def match_pair(model_name, model, detector, path0, path1, device="cuda", resize_
             # the seven-point candidates are scored on the model's device (pose.DeviceScorer), the solver stays on the host
             out["F"], mask = pose.find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000,
                                                        device=kpts0.device if kpts0.is_cuda else None, sampler=ransac_sampler,
-                                                       refine=ransac_refine)
+                                                       refine=ransac_refine, score=ransac_score)
             out["inliers"] = mask
     return out
 
 
-def compute_geom(out, device=None, ransac_solve="host", ransac_sampler="host", ransac_refine=0, homography_refit="host"):
+def compute_geom(out, device=None, ransac_solve="host", ransac_sampler="host", ransac_refine=0, homography_refit="host",
+                 ransac_score="count"):
     """demo.py:180-227 on the dict of `match_pair` -> {"Fundamental": F [3,3] | None, "Homography": H [3,3] | None}, or {} for
     fewer than 8 matches (the reference's 2 x DEFAULT_MIN_NUM_MATCHES).  "Fundamental" is the model the robust-fitting step of
     `match_pair` found (`out["F"]`: pose.find_fundamental_mat's on the numpy backend, cv2's when cv2 filtered; computed here with
@@ -225,16 +231,18 @@ def compute_geom(out, device=None, ransac_solve="host", ransac_sampler="host", r
     needs `device`, and ransac_solve="device" when the fundamental matrix is computed here).  ransac_refine: the `refine` of
     pose.find_fundamental_mat when the fundamental matrix is computed here.  homography_refit: the `refit` of pose.find_homography
     -- "host" (the default: `homography_dlt`) or "device" (one gim_model_refit launch; needs `device`), which `main` asks for
-    whenever the RANSAC already runs on the device, i.e. on a GPU with --ransac-sampler device."""
+    whenever the RANSAC already runs on the device, i.e. on a GPU with --ransac-sampler device.  ransac_score: the `score` of both
+    calls ("magsac" needs ransac_sampler "philox" or "device")."""
     from . import pose
     p0 = np.asarray(out["mkpts0_f"].detach().float().cpu().numpy() if torch.is_tensor(out["mkpts0_f"]) else out["mkpts0_f"], dtype=np.float64)
     p1 = np.asarray(out["mkpts1_f"].detach().float().cpu().numpy() if torch.is_tensor(out["mkpts1_f"]) else out["mkpts1_f"], dtype=np.float64)
     if len(p0) < 8:
         return {}
     F = out["F"] if "F" in out else pose.find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, device=device,
-                                                                   solve=ransac_solve, sampler=ransac_sampler, refine=ransac_refine)[0]
+                                                                   solve=ransac_solve, sampler=ransac_sampler, refine=ransac_refine,
+                                                                   score=ransac_score)[0]
     H, _ = pose.find_homography(p1, p0, 1.0, 0.999999, 10000, device=device, sampler=ransac_sampler,
-                                refit=homography_refit)
+                                refit=homography_refit, score=ransac_score)
     return {"Fundamental": None if F is None else np.asarray(F, dtype=np.float64), "Homography": H}
 
 
@@ -283,9 +291,14 @@ def main(argv=None):
                          "draw on the GPU with every step reduced there (device: needs --ransac-solve device)")
     ap.add_argument("--ransac-refine", type=int, choices=range(0, 9), default=0, metavar="R",
                     help="rounds of eight-point refit on the inliers after the fundamental-matrix RANSAC, 0 to 8 (default 0: none)")
+    ap.add_argument("--ransac-score", choices=["count", "magsac"], default="count",
+                    help="how the RANSAC ranks its hypotheses: the inlier count (default) or the MAGSAC++ loss the reference's USAC_MAGSAC "
+                         "names (magsac: needs --ransac-sampler philox or device)")
     args = ap.parse_args(argv)
     if args.ransac_sampler == "device" and args.ransac_solve != "device":
         ap.error("--ransac-sampler device needs --ransac-solve device")
+    if args.ransac_score == "magsac" and args.ransac_sampler == "host":
+        ap.error("--ransac-score magsac needs --ransac-sampler philox or device")
     weights = args.weights
     if weights is None and args.model in CKPT and os.path.exists(join("weights", CKPT[args.model])):
         weights = join("weights", CKPT[args.model])
@@ -293,7 +306,7 @@ def main(argv=None):
         print(f"gim_amd.demo: no checkpoint ({join('weights', CKPT[args.model])} not found): running on the modules' seeded init")
     model, detector = build(args.model, weights, args.precision, dinov2_weights=args.dinov2_weights)
     out = match_pair(args.model, model, detector, args.image0, args.image1, resize_max=args.resize_max, ransac_solve=args.ransac_solve,
-                     ransac_sampler=args.ransac_sampler, ransac_refine=args.ransac_refine)
+                     ransac_sampler=args.ransac_sampler, ransac_refine=args.ransac_refine, ransac_score=args.ransac_score)
     n = len(out["mconf"])
     print(f"{args.model}: {n} matches" + (f", {int(out['inliers'].sum())} inliers ({out['ransac_backend']} RANSAC)" if "inliers" in out else " (fewer than 8: no RANSAC)"))
     for k in range(min(n, 5)):
@@ -303,7 +316,8 @@ def main(argv=None):
         kp = out["mkpts0_f"]
         out["geom"] = compute_geom(out, device=kp.device if kp.is_cuda else None, ransac_solve=args.ransac_solve,
                                    ransac_sampler=args.ransac_sampler, ransac_refine=args.ransac_refine,
-                                   homography_refit="device" if kp.is_cuda and args.ransac_sampler == "device" else "host")
+                                   homography_refit="device" if kp.is_cuda and args.ransac_sampler == "device" else "host",
+                                   ransac_score=args.ransac_score)
         if out["geom"].get("Homography") is None:
             print("  no homography (fewer than 8 matches, or no sample with 4 inliers): no _warp.png")
         else:

@@ -1825,6 +1825,66 @@ def ransac_records(counts, nb, floor):
     return rec
 
 
+def magsac_score(kind, models, a, b, thr2, max_thr2=None, valid=None, offsets=None):
+    """MAGSAC++ quality and inlier count of candidate models over matched points in one launch (gim_magsac_score; fp64, the
+    arithmetic of pose.magsac_quality).  kind 1: fundamental matrices under the Sampson error (ransac_score's); kind 0: homographies
+    b ~ M a under the forward transfer error (homography_mask's).  max_thr2: the squared k sigma bound the gain is marginalised up
+    to (None: thr2).  Shapes as in ransac_score: models fp64 [K,3,3] (one pair) or [B,K,3,3] with offsets int32 [B+1], valid bool /
+    uint8 [K] / [B,K] or None -> (quality int64, counts int32) of the models' leading shape.  An invalid model or one with an entry
+    that is not finite: 0 and 0."""
+    kind = int(kind)
+    max_thr2 = float(thr2 if max_thr2 is None else max_thr2)
+    if kind not in (0, 1):
+        raise _lib.GimHipError(f"magsac_score kind={kind}: 0 (homography) or 1 (fundamental matrix)")
+    if not (np.isfinite(max_thr2) and max_thr2 > 0.0):
+        raise _lib.GimHipError(f"magsac_score max_thr2={max_thr2}: finite and positive")
+    _req_cuda(models, a, b, valid, offsets)
+    single = offsets is None
+    want = 3 if single else 4
+    if models.dtype != torch.float64 or models.dim() != want or models.shape[-2:] != (3, 3) or not models.is_contiguous():
+        raise _lib.GimHipError(f"magsac models must be contiguous fp64 {'[K,3,3]' if single else '[B,K,3,3]'}, got {models.dtype} {tuple(models.shape)}")
+    B, K = (1, models.shape[0]) if single else models.shape[:2]
+    offsets, P = _ransac_points(a, b, offsets, B)
+    if models.device != a.device:
+        raise _lib.GimHipError("magsac models and points are on different devices")
+    if valid is not None:
+        if valid.dtype == torch.bool:
+            valid = valid.view(torch.uint8)
+        if valid.dtype != torch.uint8 or valid.shape != models.shape[:-2] or not valid.is_contiguous() or valid.device != a.device:
+            raise _lib.GimHipError(f"magsac valid must be contiguous bool / uint8 {tuple(models.shape[:-2])} on the models' device")
+    if P == 0 or B * K == 0:      # nothing to read: every quality and count is 0
+        return (torch.zeros(models.shape[:-2], dtype=torch.int64, device=a.device), torch.zeros(models.shape[:-2], dtype=torch.int32, device=a.device))
+    quality = torch.empty(models.shape[:-2], dtype=torch.int64, device=a.device)
+    counts = torch.empty(models.shape[:-2], dtype=torch.int32, device=a.device)
+    with torch.cuda.device(a.device):
+        check(lib.gim_magsac_score(kind, _p(models), _p(valid), _p(a), _p(b), _p(offsets), B, K, float(thr2), max_thr2, _p(quality), _p(counts),
+                                   _stream()), "gim_magsac_score")
+    return quality, counts
+
+
+def ransac_records64(quality, counts, nb, floor_q, min_count):
+    """ransac_records keyed on an int64 quality (gim_ransac_records64; the rule of pose.step_records64).  quality int64 [B,K,k] and
+    counts int32 [B,K,k], k in (1, 3, 10): magsac_score's outputs over a step's models; nb int32 [B]; floor_q int64 [B]: the quality
+    to beat (tensors on the device, or ints / sequences, which are uploaded); min_count: a slot with fewer inliers has key 0.
+    -> rec int64 [B, 1 + 4 K]: rec[b, 0] = n_rec, then (s, j_s, c_s, Q_s) in ascending s; the words beyond are unspecified."""
+    _req_cuda(quality, counts)
+    if quality.dtype != torch.int64 or quality.dim() != 3 or quality.shape[2] not in (1, 3, 10) or not quality.is_contiguous():
+        raise _lib.GimHipError(f"ransac_records64 quality must be contiguous int64 [B,K,k], k in (1, 3, 10), got {quality.dtype} {tuple(quality.shape)}")
+    if counts.dtype != torch.int32 or counts.shape != quality.shape or not counts.is_contiguous() or counts.device != quality.device:
+        raise _lib.GimHipError(f"ransac_records64 counts must be contiguous int32 {tuple(quality.shape)} on the quality's device")
+    B, K, k = quality.shape
+    nb, floor_q = _on(quality.device, nb, np.int32), _on(quality.device, floor_q, np.int64)
+    for t, dt, name in ((nb, torch.int32, "nb"), (floor_q, torch.int64, "floor_q")):
+        if t.dtype != dt or t.shape != (B,) or not t.is_contiguous() or t.device != quality.device:
+            raise _lib.GimHipError(f"ransac_records64 {name} must be contiguous {dt} [{B}] on the quality's device, got {t.dtype} {tuple(t.shape)}")
+    rec = torch.empty(B, 1 + 4 * K, dtype=torch.int64, device=quality.device)
+    if B:
+        with torch.cuda.device(quality.device):
+            check(lib.gim_ransac_records64(_p(quality), _p(counts), _p(nb), _p(floor_q), int(min_count), B, K, k, _p(rec), _stream()),
+                  "gim_ransac_records64")
+    return rec
+
+
 def homography_mask(model, src, dst, thr2, offsets=None):
     """Inlier mask of one homography per pair (gim_homography_mask): model fp64 [3,3] (one pair) or [B,3,3] with offsets int32 [B+1]
     -> bool [Ptot], transfer_error(model of the point's pair) <= thr2."""

@@ -18,8 +18,11 @@ What is restated (OpenCV 4.x, modules/calib3d/src/five-point.cpp and ptsetreg.cp
     log(1 - conf) / log(1 - w^5) (at most 1000 iterations, cv2.findEssentialMat's default maxIters), NO final re-fit;
   * `recoverPose`: SVD decomposition into (R1 | R2, +-t), DLT triangulation of the masked points, the candidate with the most
     points in front of both cameras (depth < distanceThresh) wins; its count is returned.
-  * seven-point fundamental matrix inside the same RANSAC loop for the demo (plain RANSAC with the Sampson distance in pixels --
-    OpenCV's USAC_MAGSAC scoring is NOT restated; the inlier mask is RANSAC's, which is what the demo prints and draws).
+  * seven-point fundamental matrix inside the same RANSAC loop for the demo (plain RANSAC with the Sampson distance in pixels by
+    default; the inlier mask is RANSAC's, which is what the demo prints and draws).
+  * `score="magsac"`: the MAGSAC++ loss (Barath et al., CVPR 2020) that the reference's cv2.USAC_MAGSAC calls name, as a scoring
+    mode of the F and H loops -- the closed form for 4 degrees of freedom and k = 3.64 (`magsac_gain`), quantised per point and
+    summed in int64 (`magsac_quality`; csrc/magsac.hip on the device).  Not cv2's bytes, no sigma-consensus polish, not for E.
   * four-point homography inside the same loop for the demo's warp (demo.py:180-227 cv2.findHomography; fundam.cpp): forward transfer
     error, re-fit on the inliers by normalised DLT, no Levenberg-Marquardt polish.  This solver also runs on the device, fused with
     the scoring (`find_homography(device=)`, csrc/homography.hip): a step uploads sample indices only.
@@ -701,6 +704,7 @@ class _DevicePoints:
     """The matched points of one pair, or of several pairs concatenated with `offsets` [B + 1], uploaded once as fp64 [P, 2] and kept
     on `device` for every later call.  A subclass names its mask op (looked up on `ops` at call time) and its refit kind."""
     _mask, _kind = "ransac_mask", 1          # the Sampson error; gim_model_refit's fundamental matrices in pixels
+    max_thr2 = None                          # score="magsac": the squared band of gim_magsac_score, set by the entry point
 
     def __init__(self, x0, x1, thr2, device, offsets=None):
         import torch
@@ -737,6 +741,13 @@ class DeviceScorer(_DevicePoints):
             c = self._ops.ransac_score(self._up(Ms, np.float64), self.x0, self.x1, self.thr2, valid=self._up(valid, np.uint8), offsets=self.offsets)
             return c.cpu().numpy().astype(np.int64)
 
+    def quality(self, Ms, valid):
+        """score="magsac": (qualities, counts) of uploaded models through ops.magsac_score, shaped like `counts`"""
+        with self._torch.cuda.device(self.device):
+            q, c = self._ops.magsac_score(self._kind, self._up(Ms, np.float64), self.x0, self.x1, self.thr2, self.max_thr2,
+                                          valid=self._up(valid, np.uint8), offsets=self.offsets)
+            return q.cpu().numpy(), c.cpu().numpy().astype(np.int64)
+
 
 class _DeviceStep(_DevicePoints):
     """A whole RANSAC step on the GPU: a step uploads only its sample indices and reads back the models, flags and counts of ONE
@@ -751,17 +762,33 @@ class _DeviceStep(_DevicePoints):
         lead = np.shape(idx)[:-1] + (self.k,)
         with self._torch.cuda.device(self.device):
             models, valid, counts = getattr(self._ops, self._step)(self.x0, self.x1, self._up(idx, np.int32), self.thr2, offsets=self.offsets)
+            self._resident = (models, valid)                                  # for `quality`: the step's models stay where they are
             self._counts = counts.cpu().numpy().astype(np.int64).reshape(lead)
             return models.cpu().numpy().reshape(lead + (3, 3)), valid.cpu().numpy().reshape(lead)      # homography_step has no k axis
 
     def counts(self, Ms, valid):
         return self._counts.reshape(-1) if self.offsets is None else self._counts
 
-    def step_on_device(self, idx):
+    def quality_on_device(self, models, valid):
+        """gim_magsac_score over models and flags the device holds (any leading shape; with offsets the first axis is the pair)
+        -> (quality int64, counts int32) of B * K * k entries on the device"""
+        lead = (-1,) if self.offsets is None else (models.shape[0], -1)
+        return self._ops.magsac_score(self._kind, models.reshape(*lead, 3, 3), self.x0, self.x1, self.thr2, self.max_thr2,
+                                      valid=valid.reshape(*lead), offsets=self.offsets)
+
+    def quality(self, Ms, valid):
+        """score="magsac": the scorer interface of `_ransac` -- (qualities, counts) of the models the last `solve` left on the
+        device, shaped like `counts`; the step's own counts are not used"""
+        with self._torch.cuda.device(self.device):
+            q, c = self.quality_on_device(*self._resident)
+            q, c = q.cpu().numpy().reshape(self._counts.shape), c.cpu().numpy().astype(np.int64).reshape(self._counts.shape)
+        return (q.reshape(-1), c.reshape(-1)) if self.offsets is None else (q, c)
+
+    def step_on_device(self, idx, flags=False):
         """the step's launch alone, for `_ransac_on_device`: idx int32 [B, K, m] on the device -> (models, counts int32) of
-        B * K * k entries on the device; nothing is read back"""
-        models, _, counts = getattr(self._ops, self._step)(self.x0, self.x1, idx, self.thr2, offsets=self.offsets)
-        return models, counts
+        B * K * k entries on the device -- flags=True: (models, valid) instead; nothing is read back"""
+        models, valid, counts = getattr(self._ops, self._step)(self.x0, self.x1, idx, self.thr2, offsets=self.offsets)
+        return (models, valid) if flags else (models, counts)
 
 
 # ---- counter-based sampling and the per-step reduction (csrc/ransac_sample.h, csrc/ransac_records.hip restated) -----------------
@@ -843,30 +870,144 @@ def step_records(counts, nb, floor):
     return out
 
 
+# ---- MAGSAC++ scoring (csrc/magsac_loss.h, csrc/magsac.hip restated) -----------------------------------------------------------------
+SCORES = ("count", "magsac")
+MAGSAC_K = 3.64                                  # the 0.99 quantile of chi(4): OpenCV's two-view USAC constant
+MAGSAC_UK = 3.64 * 3.64 / 2.0                    # u = r^2 / (2 sigma^2) at r = k sigma
+MAGSAC_GK = 0.0036572608340910747                # Gamma(3/2, u_k), upper incomplete gamma
+MAGSAC_LK = 1.3012265540498873                   # gamma(5/2, u_k), lower incomplete gamma
+MAGSAC_UNITS = 4294967296.0                      # 2^32 quantisation units per point
+_MAGSAC_C_ERF, _MAGSAC_C_ERFC = 1.3293403881791370, 0.88622692545275801      # 3 sqrt(pi) / 4, sqrt(pi) / 2
+
+
+def _erf_erfc(t):
+    try:
+        from scipy.special import erf, erfc
+        return erf(t), erfc(t)
+    except ImportError:                          # the C library's, one value at a time
+        import math
+        return np.frompyfunc(math.erf, 1, 1)(t).astype(np.float64), np.frompyfunc(math.erfc, 1, 1)(t).astype(np.float64)
+
+
+def magsac_n(u):
+    """N(u) = gamma(5/2, u) + u (Gamma(3/2, u) - G_k) in closed form: (3 sqrt(pi)/4) erf(t) - 1.5 t exp(-u) + (sqrt(pi)/2) u erfc(t)
+    - u G_k with t = sqrt(u); u >= 0, any shape"""
+    u = np.asarray(u, dtype=np.float64)
+    t = np.sqrt(u)
+    ef, efc = _erf_erfc(t)
+    return _MAGSAC_C_ERF * ef - 1.5 * t * np.exp(-u) + _MAGSAC_C_ERFC * u * efc - u * MAGSAC_GK
+
+
+def magsac_gain(u):
+    """The MAGSAC++ gain of a point with u = r^2 / (2 sigma^2), sigma = max_threshold / 3.64 (include/gim_hip.h, gim_magsac_score;
+    gim_ms_gain of csrc/magsac_loss.h in numpy): 1 - N(u) / g_k clamped to [0, 1] for 0 <= u < u_k, 0 otherwise (beyond k sigma,
+    negative, NaN, infinite).  1 at 0, 0 at u_k, continuous and non-increasing."""
+    u = np.asarray(u, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        inside = (u >= 0.0) & (u < MAGSAC_UK)
+        g = 1.0 - magsac_n(np.where(inside, u, 0.0)) / MAGSAC_LK
+        return np.where(inside, np.clip(g, 0.0, 1.0), 0.0)
+
+
+def magsac_units(r2, max_thr2):
+    """q = llrint(gain * 2^32) of squared residuals r2 under the band max_thr2 = max_threshold^2 -> int64 of [0, 2^32]"""
+    with np.errstate(all="ignore"):
+        u = np.asarray(r2, dtype=np.float64) / (float(max_thr2) / MAGSAC_UK)
+    return np.rint(magsac_gain(u) * MAGSAC_UNITS).astype(np.int64)
+
+
+def magsac_quality(kind, Ms, valid, a, b, thr2, max_thr2, chunk=128):
+    """What gim_magsac_score writes for one pair, in numpy: models Ms [K, 3, 3], valid [K] or None, points a, b [P, 2]; kind 1 the
+    Sampson error (`sampson_error`), kind 0 the forward transfer error b ~ M a (`transfer_error`) -> (quality int64 [K]: the sum of
+    `magsac_units` over the points, counts int64 [K]: the points with error <= thr2).  A model with valid == 0 or with an entry that
+    is not finite: 0 and 0; a point with a NaN coordinate adds nothing to either."""
+    if kind not in (0, 1):
+        raise ValueError(f"kind={kind!r}: 0 (homography) or 1 (fundamental matrix)")
+    max_thr2 = float(max_thr2)
+    if not (np.isfinite(max_thr2) and max_thr2 > 0.0):
+        raise ValueError(f"max_thr2={max_thr2}: finite and positive")
+    Ms = np.asarray(Ms, dtype=np.float64).reshape(-1, 3, 3)
+    a = np.asarray(a, dtype=np.float64).reshape(-1, 2)
+    b = np.asarray(b, dtype=np.float64).reshape(-1, 2)
+    K = Ms.shape[0]
+    ok = np.isfinite(Ms).all((1, 2)) & (np.ones(K, dtype=bool) if valid is None else np.asarray(valid).reshape(-1) != 0)
+    error = transfer_error if kind == 0 else sampson_error
+    q, c = np.zeros(K, dtype=np.int64), np.zeros(K, dtype=np.int64)
+    for c0 in range(0, K, chunk):
+        with np.errstate(all="ignore"):
+            r2 = error(np.where(ok[c0:c0 + chunk, None, None], Ms[c0:c0 + chunk], 0.0), a, b)
+            c[c0:c0 + chunk] = (r2 <= thr2).sum(1)
+            q[c0:c0 + chunk] = magsac_units(r2, max_thr2).sum(1)
+    return np.where(ok, q, 0), np.where(ok, c, 0)
+
+
+def step_records64(quality, counts, nb, floor_q, min_count):
+    """What gim_ransac_records64 writes (csrc/ransac_records.hip), in numpy.  quality int64 [B, K, k], counts int [B, K, k], nb [B],
+    floor_q int64 [B], min_count: a slot is eligible iff its count is at least min_count, an ineligible slot has key 0 -> int64
+    [B, 1 + 4 K]: n_rec, then (s, j_s, c_s, Q_s) in ascending s with Q_s the largest key of the sample, j_s the lowest slot that
+    holds it, c_s that slot's count, and Q_s > max(floor_q[b], Q_0 .. Q_{s-1}); zeros beyond the last record (the device leaves
+    those words unwritten)."""
+    quality, counts = np.asarray(quality, dtype=np.int64), np.asarray(counts)
+    B, K, _ = quality.shape
+    out = np.zeros((B, 1 + 4 * K), dtype=np.int64)
+    for b in range(B):
+        n = min(max(int(nb[b]), 0), K)
+        key = np.where(counts[b, :n] >= min_count, quality[b, :n], 0)
+        Q, j = key.max(1), key.argmax(1)
+        before = np.maximum.accumulate(np.concatenate([[int(floor_q[b])], Q]))[:n]
+        s = np.flatnonzero(Q > before)
+        out[b, 0] = len(s)
+        out[b, 1:1 + 4 * len(s)] = np.stack([s, j[s], counts[b, s, j[s]], Q[s]], 1).reshape(-1)
+    return out
+
+
+def _check_score(score, sampler, threshold, max_threshold):
+    """the `score=` / `max_threshold=` rules shared by the entry points; raises before anything is launched
+    -> None for score="count", else max_threshold^2 (max_threshold defaults to threshold)"""
+    if score not in SCORES:
+        raise ValueError(f"score={score!r}: count or magsac")
+    if score == "count":
+        if max_threshold is not None:
+            raise ValueError("max_threshold belongs to score='magsac'")
+        return None
+    if sampler == "host":
+        raise ValueError("score='magsac' takes sampler='philox' or sampler='device' (the default_rng path has no quality walk)")
+    mt = float(threshold if max_threshold is None else max_threshold)
+    if not (np.isfinite(mt) and mt > 0.0):
+        raise ValueError(f"max_threshold={mt}: finite and positive")
+    return mt * mt
+
+
 class _RecordWalk:
     """The bookkeeping of `_ransac_steps` for one pair, driven by a step's records instead of its counts: the same best count, the
     same shrinking bound `niters` by the same formula, the same number of samples consumed.  `plan` says how many samples the next
     step takes (0: the run is over) and what count a sample has to beat; `replay` takes the step's records [n_rec, 3] and returns
     the (s, j) of the last one it accepted, or None.  A record is a sample above every earlier count of its step, so up to the
     break point the records are exactly the samples the counts walk accepts; records beyond it (s > niters - done - 1) are ignored
-    as that walk never reaches them."""
+    as that walk never reaches them.
+    quality=True: the walk of score="magsac".  `plan` hands out the best quality so far (0 at the start) as the floor, the records
+    are `step_records64`'s quadruples (s, j, c, Q) -- eligibility, count >= m, was applied where they were made -- and an accepted
+    record updates the bound with its count c by the same formula."""
 
-    def __init__(self, P, m, conf, max_iters, batch=250):
+    def __init__(self, P, m, conf, max_iters, batch=250, quality=False):
         self.P, self.m, self.batch = int(P), int(m), int(batch)
         self.lconf = np.log(max(1.0 - conf, 1e-300))
         self.best_n, self.niters, self.done, self.nb = 0, int(max_iters), 0, 0
+        self.quality, self.best_q = bool(quality), 0
 
     def plan(self):
         self.nb = max(0, min(self.batch, self.niters - self.done))
-        return self.nb, max(self.best_n, self.m - 1)
+        return self.nb, (self.best_q if self.quality else max(self.best_n, self.m - 1))
 
     def replay(self, records):
         last = None
-        for s, j, c in records:
-            s, c = int(s), int(c)
+        for rec in records:
+            s, j, c = (int(v) for v in rec[:3])
             if s >= self.nb or self.done + s >= self.niters:       # the walk broke at an earlier sample
                 break
             self.best_n, last = c, (s, int(j))
+            if self.quality:
+                self.best_q = int(rec[3])
             den = 1.0 - (c / self.P) ** self.m
             if den < 1e-12:
                 self.niters = min(self.niters, self.done + s + 1)
@@ -876,7 +1017,7 @@ class _RecordWalk:
         return last
 
 
-def _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch=250, solve_idx=None, draw=None):
+def _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch=250, solve_idx=None, draw=None, quality=False):
     """The sampling / solving / bookkeeping half of RANSACPointSetRegistrator::run as a generator: every step yields its candidate
     models (Ms [nb * k, 3, 3], valid [nb * k]) and is sent their inlier counts [nb * k]; the generator's return value is the best
     model [3, 3] or None.  Who counts (the host, a device, one launch for many pairs in lockstep) is the driver's business.
@@ -885,9 +1026,13 @@ def _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch=250, solve_i
     arrays it returns are read only after the counts have been sent, so a lockstep driver may hand out empty ones and fill them in
     place from one launch for many pairs (`_lockstep_device`).
     draw: None draws from `rng` as ever; otherwise draw(first, nb) -> the samples number first .. first + nb - 1 of the run
-    (sampler="philox": `device_samples`) and `rng` is not used."""
+    (sampler="philox": `device_samples`) and `rng` is not used.
+    quality=True (score="magsac"): a step is sent (qualities [nb * k], counts [nb * k]) instead; a slot is eligible iff its count
+    is at least m, a sample's quality is the largest of its eligible slots' (the lowest such slot), it is accepted iff that is
+    strictly above the best so far (0 at the start), and the bound is updated with the accepted slot's count."""
     lconf = np.log(max(1.0 - conf, 1e-300))
     best_n, best_M = 0, None
+    best_q = 0
     niters, done = int(max_iters), 0
     while done < niters:
         nb = min(batch, niters - done)
@@ -900,12 +1045,22 @@ def _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch=250, solve_i
         Ms, valid = solver(s0[idx], s1[idx]) if solve_idx is None else solve_idx(idx)
         k = Ms.shape[1]
         Ms = Ms.reshape(-1, 3, 3)
-        per = (yield Ms, valid.reshape(-1)).reshape(nb, k)
+        sent = yield Ms, valid.reshape(-1)
+        if quality:
+            per = np.asarray(sent[1]).reshape(nb, k)
+            key = np.where(per >= m, np.asarray(sent[0], dtype=np.int64).reshape(nb, k), 0)
+        else:
+            per = sent.reshape(nb, k)
         # walk the batch in sample order so that the shrinking iteration bound behaves like the sequential loop
         for s in range(nb):
-            j = int(per[s].argmax())
+            j = int(key[s].argmax()) if quality else int(per[s].argmax())
             c = int(per[s, j])
-            if c > max(best_n, m - 1):
+            if quality:
+                accept = int(key[s, j]) > best_q
+                best_q = int(key[s, j]) if accept else best_q
+            else:
+                accept = c > max(best_n, m - 1)
+            if accept:
                 best_n, best_M = c, Ms[s * k + j]
                 den = 1.0 - (c / P) ** m
                 if den < 1e-12:
@@ -927,13 +1082,16 @@ def _draw(sampler, seed, P, m):
 
 
 def _ransac(x0, x1, solver, m, thr, conf, max_iters, rng, s0=None, s1=None, batch=250, scorer=None, solve_idx=None, error=None,
-            draw=None):
+            draw=None, max_thr2=None, kind=1):
     """RANSACPointSetRegistrator::run with `solver` on samples of m points; the error is evaluated on (x0, x1), the solver sees
     (s0, s1) when given (normalised copies of the same points).  `scorer`: None counts inliers and takes the final mask on the host
     (`_count_inliers`, `sampson_error`); otherwise an object with counts(Ms [K,3,3], valid [K]) -> int64 [K] and
     mask(M [3,3]) -> bool [P] over the same points and threshold (`DeviceScorer`).  solve_idx: the hook of `_ransac_steps`.
     error: the host error in place of `sampson_error`, error(Ms [..., 3, 3], x0, x1) -> [..., P] (`transfer_error`).
     draw: the sampling hook of `_ransac_steps` (`_draw`).
+    max_thr2: None ranks the models by their inlier counts; a number runs the quality walk of `_ransac_steps` over
+    `magsac_quality` under that band (score="magsac"), or over scorer.quality(Ms, valid) -> (int64 [K], int64 [K]).
+    kind: `magsac_quality`'s, for the host scoring of that walk -- 1 with `sampson_error`, 0 with `transfer_error`.
     -> (model [3,3] or None, mask [P] bool)"""
     P = x0.shape[0]
     if P < m:
@@ -941,13 +1099,16 @@ def _ransac(x0, x1, solver, m, thr, conf, max_iters, rng, s0=None, s1=None, batc
     s0 = x0 if s0 is None else s0
     s1 = x1 if s1 is None else s1
     thr2 = float(thr) ** 2
-    steps = _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch, solve_idx, draw)
+    steps = _ransac_steps(P, solver, m, conf, max_iters, rng, s0, s1, batch, solve_idx, draw, quality=max_thr2 is not None)
     error = sampson_error if error is None else error
     try:
         Ms, valid = next(steps)
         while True:
-            counts = _count_inliers(Ms, valid, x0, x1, thr2, error=error) if scorer is None else scorer.counts(Ms, valid)
-            Ms, valid = steps.send(counts)
+            if max_thr2 is not None:       # (qualities, counts)
+                scores = magsac_quality(kind, Ms, valid, x0, x1, thr2, max_thr2) if scorer is None else scorer.quality(Ms, valid)
+            else:                          # counts
+                scores = _count_inliers(Ms, valid, x0, x1, thr2, error=error) if scorer is None else scorer.counts(Ms, valid)
+            Ms, valid = steps.send(scores)
     except StopIteration as stop:
         best_M = stop.value
     if best_M is None:
@@ -1148,9 +1309,10 @@ class DeviceEssential(_DeviceStep):
 
 
 def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, solve="host", sampler="host",
-                         refine=0):
-    """Plain RANSAC over seven-point samples with the Sampson distance in pixels (the demo's geometry filter, demo.py:514-517;
-    the reference's USAC_MAGSAC scoring is not restated).  -> (F [3,3] | None, mask [P])
+                         refine=0, score="count", max_threshold=None):
+    """RANSAC over seven-point samples with the Sampson distance in pixels (the demo's geometry filter, demo.py:514-517): plain
+    inlier counting by default; score="magsac" ranks the hypotheses by the MAGSAC++ loss the reference's USAC_MAGSAC names (the
+    published closed form, not cv2's bytes; below).  -> (F [3,3] | None, mask [P])
     solve="host": `seven_point` (SVD null space, eigenvalues) on points Hartley-normalised once per call, the candidates mapped back
     to pixel units for scoring (on `device` when given, as in find_essential_mat: same trajectory as the host run).
     solve="device" (needs `device`): the same indices are drawn on the host and uploaded; models, flags and counts come from one
@@ -1161,15 +1323,21 @@ def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, 
     refine: 0 returns the RANSAC's best seven-point model and its mask (the default; every seeded result so far).  R in 1 .. 8 then
     runs up to R rounds of local optimisation on it, the step USAC ends with: the normalised eight-point fit on the current inliers,
     a fresh mask, kept while the inlier count does not fall (`refit_ge`).  With a device it is ONE gim_model_refit launch on the
-    points already there (with sampler="device" it also replaces the gim_ransac_mask call), with device=None `refit_ge` itself."""
+    points already there (with sampler="device" it also replaces the gim_ransac_mask call), with device=None `refit_ge` itself.
+    score: "count" (the default; every seeded result so far) accepts the sample with the most inliers.  "magsac" (needs
+    sampler="philox" or "device") accepts a sample iff it has at least 7 inliers and its quality -- the int64 sum over the points
+    of the quantised MAGSAC++ gain (`magsac_quality`, gim_magsac_score) -- is strictly above the best so far; the iteration bound
+    is updated with the accepted model's inlier count, the mask is the same mask call, and `refine` composes unchanged.
+    max_threshold (score="magsac"): the k sigma bound the gain is marginalised up to, in pixels; None: `threshold`."""
     _check_solve(solve, device)
     _check_sampler(sampler, device, solve)
+    max_thr2 = _check_score(score, sampler, threshold, max_threshold)
     refine = _check_refine(refine)
     p0 = np.ascontiguousarray(p0, dtype=np.float64)
     p1 = np.ascontiguousarray(p1, dtype=np.float64)
     if sampler == "device":
         return _ransac_on_device([(p0, p1)], DeviceFundamental, threshold, prob, max_iters, seed, device,
-                                 finish=_refit_finish(refine) if refine else None)[0][0]
+                                 finish=_refit_finish(refine) if refine else None, max_thr2=max_thr2)[0][0]
     draw = _draw(sampler, seed, p0.shape[0], 7)
     if p0.shape[0] < 7:
         return None, np.zeros(p0.shape[0], dtype=bool)
@@ -1185,11 +1353,13 @@ def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, 
         return models[0], mask
 
     if solve == "ge":
-        return refined(_ransac(p0, p1, seven_point_ge, 7, threshold, prob, max_iters, np.random.default_rng(seed), draw=draw), None)
+        return refined(_ransac(p0, p1, seven_point_ge, 7, threshold, prob, max_iters, np.random.default_rng(seed), draw=draw,
+                               max_thr2=max_thr2), None)
     if solve == "device":
         dev = DeviceFundamental(p0, p1, float(threshold) ** 2, device)
+        dev.max_thr2 = max_thr2
         return refined(_ransac(p0, p1, None, 7, threshold, prob, max_iters, np.random.default_rng(seed), scorer=dev, solve_idx=dev.solve,
-                               draw=draw), dev)
+                               draw=draw, max_thr2=max_thr2), dev)
 
     def norm_T(p):
         c = p.mean(0)
@@ -1207,8 +1377,10 @@ def find_fundamental_mat(p0, p1, threshold=1.0, prob=0.999999, max_iters=10000, 
         return Fp / np.where(nrm > 0, nrm, 1.0)[..., None, None], v
 
     scorer = DeviceScorer(p0, p1, float(threshold) ** 2, device) if device is not None else None
+    if scorer is not None:
+        scorer.max_thr2 = max_thr2
     return refined(_ransac(p0, p1, solver, 7, threshold, prob, max_iters, np.random.default_rng(seed), s0=q0, s1=q1, scorer=scorer,
-                           draw=draw), scorer)
+                           draw=draw, max_thr2=max_thr2), scorer)
 
 
 def _pairs64(pairs):
@@ -1279,42 +1451,47 @@ class _DeferredSolve:
         return self.models, self.valid
 
 
-def _lockstep_device(pairs, step_cls, threshold, prob, max_iters, seed, device, sampler="host", step_kw=None, finish=None):
+def _lockstep_device(pairs, step_cls, threshold, prob, max_iters, seed, device, sampler="host", step_kw=None, finish=None, max_thr2=None):
     """`_lockstep` with the solve on the device: a round uploads the sample indices of every unfinished pair and solves and scores
     all of them in ONE launch of `step_cls` (DeviceFundamental, DeviceEssential) over the concatenated points (ragged point sets
     through offsets; a finished pair and the padding of a shorter step are index -1: invalid).  The step object is made when the
     first round needs it: a batch in which no pair has `step_cls.m` points uploads nothing.  step_kw: further keywords of `step_cls`;
-    finish: that of `_batch_results`.  -> ([(model | None, mask)], the step object or None)"""
+    finish: that of `_batch_results`.  max_thr2: a number runs the quality walk (score="magsac"): a round then also scores the
+    resident models with ONE gim_magsac_score launch.  -> ([(model | None, mask)], the step object or None)"""
     m, k = step_cls.m, step_cls.k
     pairs, offsets = _pairs64(pairs)
     B = len(pairs)
     hooks = {b: _DeferredSolve(k) for b, (a, _) in enumerate(pairs) if a.shape[0] >= m}
     steps = {b: _ransac_steps(pairs[b][0].shape[0], None, m, prob, max_iters, np.random.default_rng(seed), *pairs[b], solve_idx=hook,
-                              draw=_draw(sampler, seed, pairs[b][0].shape[0], m)) for b, hook in hooks.items()}
+                              draw=_draw(sampler, seed, pairs[b][0].shape[0], m), quality=max_thr2 is not None) for b, hook in hooks.items()}
     dev = None
 
     def launch(pending):
         nonlocal dev
         if dev is None:
             dev = _over_pairs(step_cls, pairs, offsets, threshold, device, **(step_kw or {}))
+            dev.max_thr2 = max_thr2
         K = max(hooks[b].idx.shape[0] for b in pending)
         idx = np.full((B, K, m), -1, dtype=np.int32)
         for b in pending:
             idx[b, :hooks[b].idx.shape[0]] = hooks[b].idx
         models, valid = dev.solve(idx)
-        counts = dev.counts(models, valid)
+        if max_thr2 is not None:
+            qual, counts = dev.quality(models, valid)
+        else:
+            counts = dev.counts(models, valid)
         out = {}
         for b in pending:
             nb = hooks[b].idx.shape[0]
             hooks[b].models[...], hooks[b].valid[...] = models[b, :nb], valid[b, :nb]
-            out[b] = counts[b, :nb].reshape(-1)
+            out[b] = counts[b, :nb].reshape(-1) if max_thr2 is None else (qual[b, :nb].reshape(-1), counts[b, :nb].reshape(-1))
         return out
 
     best = _lockstep(B, steps, launch)
     return _batch_results(best, offsets, dev, finish), dev
 
 
-def _ransac_on_device(pairs, step_cls, threshold, prob, max_iters, seed, device, batch=250, step_kw=None, finish=None):
+def _ransac_on_device(pairs, step_cls, threshold, prob, max_iters, seed, device, batch=250, step_kw=None, finish=None, max_thr2=None):
     """sampler="device": the RANSAC runs of `pairs` in lockstep with sampling, solving, scoring and the reduction of every step on
     the GPU.  A step is three launches of this library -- gim_ransac_sample, the step kernel of `step_cls` (DeviceHomography,
     DeviceFundamental, DeviceEssential), gim_ransac_records -- fed by ONE upload of 4 B words (first as int64, count, floor) and
@@ -1323,21 +1500,31 @@ def _ransac_on_device(pairs, step_cls, threshold, prob, max_iters, seed, device,
     only in a step that accepted a record of that pair; models, flags and counts are never read back in bulk.  A pair's ordinals run
     from 0 under the shared seed: its result is that of the single call, and that of sampler="philox" on the same device.
     When no pair has m points, nothing is uploaded or launched.  The run ends with `_batch_results`; finish: its hook.
+    max_thr2: a number runs the quality walk (score="magsac"): a step is then four launches -- the sampler, the untouched step
+    kernel (its counts are unused), gim_magsac_score on the step's resident models, gim_ransac_records64 with min_count = m -- fed
+    by 5 B words (the floor is an int64 quality) and read by n_rec and the first RECORDS_FIRST_COPY quadruples of every pair.
     -> ([(model [3,3] | None, mask [P_b] bool)], the step object or None -- `find_homography` takes its re-fit mask from it)"""
     m, k = step_cls.m, step_cls.k
     seed = _check_seed64(seed)
     pairs, offsets = _pairs64(pairs)
     B = len(pairs)
-    walks = {b: _RecordWalk(a.shape[0], m, prob, max_iters, batch) for b, (a, _) in enumerate(pairs) if a.shape[0] >= m}
+    magsac = max_thr2 is not None
+    walks = {b: _RecordWalk(a.shape[0], m, prob, max_iters, batch, quality=magsac) for b, (a, _) in enumerate(pairs) if a.shape[0] >= m}
     best = [None] * B
     if not walks:
         return _batch_results(best, offsets, None), None
     import torch
     from . import ops
     dev = _over_pairs(step_cls, pairs, offsets, threshold, device, **(step_kw or {}))
-    ctl = np.zeros(4 * B, dtype=np.int32)                       # [first as int64 | count | floor]: one upload per step
-    first, count, floor = ctl[:2 * B].view(np.int64), ctl[2 * B:3 * B], ctl[3 * B:]
-    head = 1 + 3 * RECORDS_FIRST_COPY
+    dev.max_thr2 = max_thr2
+    if magsac:
+        ctl = np.zeros(5 * B, dtype=np.int32)                   # [first as int64 | floor as int64 | count]: one upload per step
+        first, floor, count = ctl[:2 * B].view(np.int64), ctl[2 * B:4 * B].view(np.int64), ctl[4 * B:]
+    else:
+        ctl = np.zeros(4 * B, dtype=np.int32)                   # [first as int64 | count | floor]: one upload per step
+        first, count, floor = ctl[:2 * B].view(np.int64), ctl[2 * B:3 * B], ctl[3 * B:]
+    w_rec = 4 if magsac else 3
+    head = 1 + w_rec * RECORDS_FIRST_COPY
     with torch.cuda.device(dev.device):
         while True:
             count[:] = 0
@@ -1348,17 +1535,25 @@ def _ransac_on_device(pairs, step_cls, threshold, prob, max_iters, seed, device,
             if K == 0:
                 break
             d_ctl = torch.from_numpy(ctl).to(dev.device)
-            d_count, d_floor = d_ctl[2 * B:3 * B], d_ctl[3 * B:]
+            if magsac:
+                d_count, d_floor = d_ctl[4 * B:], d_ctl[2 * B:4 * B].view(torch.int64)
+            else:
+                d_count, d_floor = d_ctl[2 * B:3 * B], d_ctl[3 * B:]
             idx = ops.ransac_sample(dev.offsets, d_ctl[:2 * B].view(torch.int64), d_count, K, m, seed)
-            models, counts = dev.step_on_device(idx)
-            rec = ops.ransac_records(counts.view(B, K, k), d_count, d_floor)
+            if magsac:
+                models, flags = dev.step_on_device(idx, flags=True)
+                qual, counts = dev.quality_on_device(models, flags)
+                rec = ops.ransac_records64(qual.view(B, K, k), counts.view(B, K, k), d_count, d_floor, m)
+            else:
+                models, counts = dev.step_on_device(idx)
+                rec = ops.ransac_records(counts.view(B, K, k), d_count, d_floor)
             h = rec[:, :head].cpu().numpy()
             if (h[:, 0] > RECORDS_FIRST_COPY).any():
                 h = np.concatenate([h, rec[:, head:].cpu().numpy()], 1)
             models = models.view(B, K, k, 3, 3)
             for b, w in walks.items():
                 if count[b]:
-                    hit = w.replay(h[b, 1:1 + 3 * h[b, 0]].reshape(-1, 3))
+                    hit = w.replay(h[b, 1:1 + w_rec * h[b, 0]].reshape(-1, w_rec))
                     if hit is not None:
                         best[b] = models[b, hit[0], hit[1]].cpu().numpy()
     return _batch_results(best, offsets, dev, finish), dev
@@ -1383,7 +1578,7 @@ def _check_sampler(sampler, device, solve="device"):
 
 
 def find_fundamental_mat_batch(pairs, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, solve="device", sampler="host",
-                               refine=0):
+                               refine=0, score="count", max_threshold=None):
     """`find_fundamental_mat(p0, p1, threshold, prob, max_iters, seed, device, solve="device")` for every (p0, p1) of `pairs`:
     `_lockstep_device` with `DeviceFundamental`, ONE gim_fundamental_step launch per round and one gim_ransac_mask call for all
     pairs at the end; a pair's result is that of the single call.
@@ -1391,27 +1586,31 @@ def find_fundamental_mat_batch(pairs, threshold=1.0, prob=0.999999, max_iters=10
     reduced to its record samples (`_ransac_on_device`); a pair's result is again that of the single call with that sampler.
     refine: that of find_fundamental_mat; R > 0 replaces the run's gim_ransac_mask call with ONE gim_model_refit launch over all
     pairs (a pair without a model is skipped there, and a batch without any model launches nothing).
+    score, max_threshold: those of find_fundamental_mat; "magsac" adds ONE gim_magsac_score launch over all pairs to every round.
     -> [(F [3,3] | None, mask [P_b] bool)] in the order of `pairs`."""
     _check_solve(solve, device, ("device",))
     _check_sampler(sampler, device, solve)
+    max_thr2 = _check_score(score, sampler, threshold, max_threshold)
     refine = _check_refine(refine)
     finish = _refit_finish(refine) if refine else None
     if sampler == "device":
-        return _ransac_on_device(pairs, DeviceFundamental, threshold, prob, max_iters, seed, device, finish=finish)[0]
-    return _lockstep_device(pairs, DeviceFundamental, threshold, prob, max_iters, seed, device, sampler, finish=finish)[0]
+        return _ransac_on_device(pairs, DeviceFundamental, threshold, prob, max_iters, seed, device, finish=finish, max_thr2=max_thr2)[0]
+    return _lockstep_device(pairs, DeviceFundamental, threshold, prob, max_iters, seed, device, sampler, finish=finish, max_thr2=max_thr2)[0]
 
 
-def verify_pairs(pairs_of_points, threshold=1.0, device=None, prob=0.999999, max_iters=10000, seed=0, batch=32, sampler="host", refine=0):
+def verify_pairs(pairs_of_points, threshold=1.0, device=None, prob=0.999999, max_iters=10000, seed=0, batch=32, sampler="host", refine=0,
+                 score="count", max_threshold=None):
     """Two-view verification of a pair list (the matches of a LightGlue / root_sift / dense pair list, in pixels) without OpenCV:
     `find_fundamental_mat_batch` over `batch` pairs per launch sequence -> [(F [3,3] | None, mask [P_b] bool)] in the list's order.
-    sampler, refine: those of find_fundamental_mat_batch."""
+    sampler, refine, score, max_threshold: those of find_fundamental_mat_batch."""
     _check_sampler(sampler, device)
+    _check_score(score, sampler, threshold, max_threshold)
     refine = _check_refine(refine)
     pairs_of_points = list(pairs_of_points)
     out = []
     for i in range(0, len(pairs_of_points), int(batch)):
         out += find_fundamental_mat_batch(pairs_of_points[i:i + int(batch)], threshold, prob, max_iters, seed, device, sampler=sampler,
-                                          refine=refine)
+                                          refine=refine, score=score, max_threshold=max_threshold)
     return out
 
 
@@ -1560,7 +1759,8 @@ class DeviceHomography(_DeviceStep):
         super().__init__(src, dst, thr2, device, offsets)
 
 
-def find_homography(src, dst, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, sampler="host", refit="host"):
+def find_homography(src, dst, threshold=1.0, prob=0.999999, max_iters=10000, seed=0, device=None, sampler="host", refit="host",
+                    score="count", max_threshold=None):
     """cv2.findHomography(src, dst, RANSAC, threshold, maxIters=max_iters, confidence=prob) restated: dst ~ H src
     -> (H [3, 3] with h33 = 1 | None, mask [P] bool).  Plain RANSAC over four-point samples with the forward transfer error in
     pixels; sampling and the shrinking iteration bound are `_ransac_steps`'.  Host path: `homography_4pt` and `transfer_error`.
@@ -1568,16 +1768,19 @@ def find_homography(src, dst, threshold=1.0, prob=0.999999, max_iters=10000, see
     step (`DeviceHomography`; the device rounds differently, so its trajectory need not be the host's).  Then, as
     RANSACPointSetRegistrator::run + findHomography do, the model is re-fitted on the inliers of the best sample (`homography_dlt`)
     and the mask taken once more with the re-fitted model; the re-fit is kept only if it does not lose inliers.  OpenCV's final
-    Levenberg-Marquardt polish of the re-fit (HomographyRefineCallback) is NOT built, and neither is USAC_MAGSAC's scoring (the
-    reference's demo asks for it; the mask here is RANSAC's).
+    Levenberg-Marquardt polish of the re-fit (HomographyRefineCallback) is NOT built.  score="magsac" ranks the hypotheses by the
+    MAGSAC++ loss the reference's demo asks for with USAC_MAGSAC (the published closed form, not cv2's bytes; below).
     sampler: "host", "philox" or "device", as in find_essential_mat ("device" needs `device`; the solve is the device's whenever
     a device is given).
     refit: "host" re-fits with `homography_dlt` (LAPACK's SVD of the 2n x 9 system) and takes the second mask where the first was
     taken (the default; every seeded result so far).  "device" (needs `device`) replaces both with ONE gim_model_refit launch of one
     round on the points the step object holds, and one copy of H, the mask and the counts; with sampler="device" that launch also
     replaces the gim_homography_mask call that ends the RANSAC.  "ge" (device=None) is the same on the host through `refit_ge`,
-    the CPU oracle of "device"."""
+    the CPU oracle of "device".
+    score, max_threshold: as in find_fundamental_mat, over the forward transfer error and with 4 inliers to be eligible; "magsac"
+    needs sampler="philox" or "device"; the re-fit that follows starts from the returned model, unchanged."""
     _check_sampler(sampler, device)
+    max_thr2 = _check_score(score, sampler, threshold, max_threshold)
     if refit not in REFITS:
         raise ValueError(f"refit={refit!r}: host, device or ge")
     if refit == "device" and device is None:
@@ -1593,14 +1796,16 @@ def find_homography(src, dst, threshold=1.0, prob=0.999999, max_iters=10000, see
     thr2 = float(threshold) ** 2
     if sampler == "device":
         found, dev = _ransac_on_device([(src, dst)], DeviceHomography, threshold, prob, max_iters, seed, device,
-                                       finish=_refit_finish(1) if refit == "device" else None)
+                                       finish=_refit_finish(1) if refit == "device" else None, max_thr2=max_thr2)
         H, mask = found[0]
         if refit == "device":
             return H, np.asarray(mask, dtype=bool)
     else:
         dev = DeviceHomography(src, dst, thr2, device) if device is not None else None
+        if dev is not None:
+            dev.max_thr2 = max_thr2
         H, mask = _ransac(src, dst, homography_4pt, 4, threshold, prob, max_iters, np.random.default_rng(seed), scorer=dev,
-                          solve_idx=None if dev is None else dev.solve, error=transfer_error, draw=draw)
+                          solve_idx=None if dev is None else dev.solve, error=transfer_error, draw=draw, max_thr2=max_thr2, kind=0)
     if H is None:
         return None, mask
     mask = np.asarray(mask, dtype=bool)

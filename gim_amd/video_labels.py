@@ -248,12 +248,15 @@ def _keypoints(matcher_out):
 
 
 def label_pair(matcher_out, *, device, affine=None, vratio=1.0, threshold=0.5, confidence=0.999999, max_iters=100000, seed=0,
-               refine=0):
+               refine=0, score="count"):
     """The tail of a labelling step (video_preprocessor.py:513-555) for one frame pair -> label fp32 [n,4] on the device.
     matcher_out: a matcher's result dict (`mkpts0_f` / `mkpts1_f`, matched keypoints [n,2] in pixels) or a (k0, k1) pair.
       1. ops.label_pack with moved_thr = 1 drops static matches (watermarks, line 516);
-      2. pose.find_fundamental_mat(solve="device", sampler="device") on the survivors: PLAIN RANSAC with the Sampson distance where
-         the reference calls cv2.findFundamentalMat(USAC_MAGSAC, 0.5, 0.999999, 100000) -- MAGSAC's scoring is not restated;
+      2. pose.find_fundamental_mat(solve="device", sampler="device") on the survivors, where the reference calls
+         cv2.findFundamentalMat(USAC_MAGSAC, 0.5, 0.999999, 100000): score="count" (the default) is plain RANSAC with the Sampson
+         distance; score="magsac" ranks the hypotheses by the MAGSAC++ loss on the device (gim_magsac_score: the published closed
+         form, not cv2's bytes) -- at 0.5 px an inlier count picks among near-ties arbitrarily, the marginalised score prefers the
+         model whose inliers are tight;
          refine = R in 1 .. 8 adds the step USAC ends with, up to R rounds of eight-point refit on the inliers in the launch that
          takes the mask (pose.find_fundamental_mat's `refine`; 0, the default, keeps the minimal-sample model's mask);
       3. ops.label_pack with the inlier mask and the rescale: `affine` (sx0, sy0, ox0, oy0, sx1, sy1, ox1, oy1) and `vratio` of
@@ -274,7 +277,7 @@ def label_pair(matcher_out, *, device, affine=None, vratio=1.0, threshold=0.5, c
         moved = moved[:n]
         pts = moved.cpu().numpy().astype(np.float64)
         F, mask = pose.find_fundamental_mat(pts[:, :2], pts[:, 2:], threshold=threshold, prob=confidence, max_iters=max_iters, seed=seed,
-                                            device=device, solve="device", sampler="device", refine=refine)
+                                            device=device, solve="device", sampler="device", refine=refine, score=score)
         if F is None or not mask.any():
             return empty
         m0, m1 = moved[:, :2].contiguous(), moved[:, 2:].contiguous()
@@ -427,9 +430,11 @@ def prepare_pair(bank, idx0, idx1, method, exclude, resize=None):
     return method_inputs(method, sides[0], sides[1], lambda a: a), affine, r.kept
 
 
-def label_pair_host(matcher_out, *, affine=None, vratio=1.0, threshold=0.5, confidence=0.999999, max_iters=100000, seed=0, refine=0):
+def label_pair_host(matcher_out, *, affine=None, vratio=1.0, threshold=0.5, confidence=0.999999, max_iters=100000, seed=0, refine=0,
+                    score="count"):
     """`label_pair` on the host, the CPU oracle of its control flow: label_pack_np for both packs, pose.find_fundamental_mat with the
-    host solver and sampler -> label fp32 [n,4] as a numpy array"""
+    host solver and sampler -> label fp32 [n,4] as a numpy array.  score="magsac" has no default_rng walk: it runs
+    solve="ge", sampler="philox", the all-CPU restatement of label_pair's device run."""
     from . import pose
     k0, k1 = (np.asarray(t.detach().cpu() if hasattr(t, "detach") else t, dtype=np.float32).reshape(-1, 2) for t in _keypoints(matcher_out))
     moved = label_pack_np(k0, k1, moved_thr=1.0)
@@ -437,14 +442,16 @@ def label_pair_host(matcher_out, *, affine=None, vratio=1.0, threshold=0.5, conf
     if len(moved) < 7:
         return empty
     pts = moved.astype(np.float64)
-    F, mask = pose.find_fundamental_mat(pts[:, :2], pts[:, 2:], threshold=threshold, prob=confidence, max_iters=max_iters, seed=seed, refine=refine)
+    how = dict(solve="ge", sampler="philox", score=score) if score != "count" else {}
+    F, mask = pose.find_fundamental_mat(pts[:, :2], pts[:, 2:], threshold=threshold, prob=confidence, max_iters=max_iters, seed=seed, refine=refine,
+                                        **how)
     if F is None or not mask.any():
         return empty
     return label_pack_np(moved[:, :2], moved[:, 2:], keep=mask, affine=affine, vratio=vratio)
 
 
 def label_pair_list(match, bank, ids, method, out_dir, *, vratio, exclude, resize_cache=None, resize_hw=(900, 1600), refine=0, seed=0,
-                    **ransac):
+                    score="count", **ransac):
     """The labelling loop of video_preprocessor.py:255-566 without decoding: for every (idx0, idx1) of `ids`, in order,
         prepare_pair -> match(inputs) -> label_pair -> out_dir/str(np.array([idx0, idx1])) + '.npy', nums.npy, idxs.npy
     in the reference's layout (`LabelStore.from_dirs` reads it back).  match(inputs) returns a matcher's result dict (mkpts0_f /
@@ -453,7 +460,7 @@ def label_pair_list(match, bank, ids, method, out_dir, *, vratio, exclude, resiz
     label in that directory and resized into the resize_hw = (h, w) box.  Skipped, as the reference skips them: a pair whose file
     exists, a second-pass pair without a cached label (:287), kept == 0 on either side (:367), a match of None, no inliers (:522).
     Host reads per pair: `kept` (8 bytes) and what label_pair reads.  With a host bank (FrameBank(device=None)) everything runs in
-    numpy (`label_pair_host`).  ransac: threshold / confidence / max_iters of label_pair.
+    numpy (`label_pair_host`).  score: that of label_pair.  ransac: threshold / confidence / max_iters of label_pair.
     -> {"written": [(idx0, idx1)], "skipped": {(idx0, idx1): reason}}"""
     os.makedirs(out_dir, exist_ok=True)
     nums_path, idxs_path = os.path.join(out_dir, "nums.npy"), os.path.join(out_dir, "idxs.npy")
@@ -485,9 +492,9 @@ def label_pair_list(match, bank, ids, method, out_dir, *, vratio, exclude, resiz
             skipped[(idx0, idx1)] = "no match"
             continue
         if bank.device is None:
-            pts = label_pair_host(out, affine=affine, vratio=vratio, seed=seed, refine=refine, **ransac)
+            pts = label_pair_host(out, affine=affine, vratio=vratio, seed=seed, refine=refine, score=score, **ransac)
         else:
-            pts = label_pair(out, device=bank.device, affine=affine, vratio=vratio, seed=seed, refine=refine, **ransac).cpu().numpy()
+            pts = label_pair(out, device=bank.device, affine=affine, vratio=vratio, seed=seed, refine=refine, score=score, **ransac).cpu().numpy()
         if len(pts) == 0:
             skipped[(idx0, idx1)] = "no inliers"
             continue

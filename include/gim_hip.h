@@ -1329,6 +1329,49 @@ int gim_frame_prep(const uint8_t* frames, int S, int H, int W, const uint8_t* se
                    const int64_t* out_elems, uint8_t* out_u8, uint8_t* out_mask, uint8_t* out_mask8, float* out_rgb,
                    float* out_gray, float* out_norm, int32_t* kept, gim_stream_t stream);
 
+/* ======================================================================================================
+ * MAGSAC++ scoring of RANSAC hypotheses (added within ABI revision 115: no existing structure or prototype changed with it).
+ * The reference filters matches with cv2.USAC_MAGSAC (demo.py:197-217 and :514-517, video_preprocessor.py:578,
+ * datasets/walk/walk.py:295); this is the published loss (Barath et al., CVPR 2020), pinned by the contract below, a numpy oracle
+ * (pose.magsac_gain / pose.magsac_quality) and an independent special-function library -- no claim of byte-equality with cv2.
+ * ====================================================================================================== */
+
+/* Quality and inlier count of K candidate 3x3 models per pair over that pair's points, B pairs in ONE launch.  All pointers are
+ * DEVICE memory; models, valid, a, b, offsets as in gim_ransac_score (a = x0 / src, b = x1 / dst).  kind 1: the Sampson error with
+ * the expressions and operation order of gim_ransac_score; kind 0: the forward transfer error b ~ M a with those of
+ * gim_homography_mask (w == 0 or an error that is not finite: no inlier, no gain).  For a point with squared residual r2:
+ *   sigma = max_threshold / 3.64,  u = r2 / (2 sigma^2) = r2 / (max_thr2 / u_k),  t = sqrt(u),  u_k = 3.64^2 / 2
+ *   G_k  = Gamma(3/2, u_k) = 0.0036572608340910747  (upper incomplete gamma)
+ *   g_k  = gamma(5/2, u_k) = 1.3012265540498873     (lower incomplete gamma)
+ *   N(u) = (3 sqrt(pi)/4) erf(t) - 1.5 t exp(-u) + (sqrt(pi)/2) u erfc(t) - u G_k  = gamma(5/2, u) + u (Gamma(3/2, u) - G_k)
+ *   gain(u) = 1 - N(u) / g_k clamped to [0, 1] for 0 <= u < u_k and r2 finite, 0 otherwise
+ * (the paper's rho(r) for n = 4 degrees of freedom and k = 3.64 up to the factor that cancels in the ratio; gain is 1 at 0, 0 at
+ * u_k, continuous and non-increasing; erf, erfc, exp and sqrt in fp64, csrc/magsac_loss.h is the code for device and host).  A
+ * point contributes q = llrint(gain * 2^32), an integer of [0, 2^32]; quality int64 [B][K] is the sum of q over the pair's points;
+ * counts int32 [B][K] is the number of points with err <= thr2, gim_ransac_score's (kind 1) or gim_homography_mask's (kind 0).
+ * Both are FULLY written by the call: 0 and 0 for a model with valid == 0 or with an entry that is not finite, and for a pair
+ * without points.  A VALID ALL-ZERO model under kind 1 has err = 0 / 1e-300 = 0 at every point whose coordinates are finite, as in
+ * gim_ransac_score: it counts every such point and gets the largest quality there is, 2^32 per point (under kind 0 it has w == 0:
+ * 0 and 0).  Nothing here keeps it out of a RANSAC walk; the valid flags of the step entry points do (a rejected sample or an
+ * unused slot is a zero model with valid == 0).  Only integer sums cross lanes and workgroups: the result does not depend on the launch shape, the point split,
+ * the batch or the pair's place in it.  B == 0 or K == 0 returns without touching anything.  Refused before a launch: kind outside
+ * {0, 1}, max_thr2 not finite or not positive, B > 65535, a NULL pointer, a or b not 16-byte aligned, models or quality not 8-byte
+ * aligned, offsets or counts not 4-byte aligned. */
+int gim_magsac_score(int kind, const double* models, const uint8_t* valid, const double* a, const double* b, const int32_t* offsets,
+                     int B, int K, double thr2, double max_thr2, int64_t* quality, int32_t* counts, gim_stream_t stream);
+
+/* gim_ransac_records keyed on an int64 quality.  quality int64 [B][K][k] and counts int32 [B][K][k], k in {1, 3, 10}: the outputs
+ * of gim_magsac_score over the models of a step; nb int32 [B] as in gim_ransac_records; floor_q int64 [B]: the quality to beat.
+ * A slot is eligible iff its count is at least min_count; an ineligible slot has key 0.  For s < nb[b]: Q_s = the largest key of
+ * the sample's k slots, j_s the lowest slot that holds it; s is a record iff Q_s > max(floor_q[b], Q_0 .. Q_{s-1}).
+ * rec int64 [B][1 + 4 K]: rec[b][0] = n_rec, then (s, j_s, c_s, Q_s) per record in ascending s, c_s the count of slot j_s; the
+ * words beyond the last record are NOT written.  The same walk as gim_ransac_records, no atomics.  (pose.step_records64 is the
+ * numpy restatement.)  B == 0 returns without touching anything; K == 0 writes n_rec = 0.  Refused before a launch: k outside
+ * {1, 3, 10}, a NULL pointer, quality, floor_q or rec not 8-byte or counts or nb not 4-byte aligned, B > 65535, B * K * k or
+ * B * (1 + 4 K) > INT32_MAX. */
+int gim_ransac_records64(const int64_t* quality, const int32_t* counts, const int32_t* nb, const int64_t* floor_q, int min_count,
+                         int B, int K, int k, int64_t* rec, gim_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
