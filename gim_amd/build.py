@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libgimhip.so")
 SOURCES = ["runtime.hip", "conv_igemm.hip", "elementwise.hip", "linear_attention.hip", "coarse_match.hip",
-           "fine_match.hip", "fine_fused.hip", "token_mlp.hip", "bneck_fused.hip", "bneck_tail.hip", "stem7x7.hip", "emit.hip", "superpoint.hip", "lightglue.hip", "lg_assign.hip", "dkm.hip", "gp_solve.hip", "sample.hip", "semseg.hip", "feature_bank.hip", "nn_match.hip", "ransac_score.hip", "lg_bank.hip", "dense_agg.hip", "dense_bank.hip", "sample_pairs.hip", "homography.hip", "warp.hip", "fundamental.hip", "essential.hip", "ransac_sample.hip", "ransac_records.hip", "recover_pose.hip", "label_link.hip", "model_refit.hip", "frame_prep.hip", "magsac.hip"]
+           "fine_match.hip", "fine_fused.hip", "token_mlp.hip", "bneck_fused.hip", "bneck_tail.hip", "stem7x7.hip", "emit.hip", "superpoint.hip", "lightglue.hip", "lg_assign.hip", "dkm.hip", "gp_solve.hip", "sample.hip", "semseg.hip", "feature_bank.hip", "nn_match.hip", "ransac_score.hip", "lg_bank.hip", "dense_agg.hip", "dense_bank.hip", "sample_pairs.hip", "homography.hip", "warp.hip", "fundamental.hip", "essential.hip", "ransac_sample.hip", "ransac_records.hip", "recover_pose.hip", "label_link.hip", "model_refit.hip", "frame_prep.hip"]
 # the gim_loftr path exists in two 16-bit operand flavours (bf16 / IEEE fp16, csrc/gim_common.h): these files are compiled a
 # second time with -DGIM_HALF_KIND=1 into *_f16.o, whose entry points carry the suffix `_f16`
 F16_SOURCES = ["conv_igemm.hip", "elementwise.hip", "linear_attention.hip", "coarse_match.hip", "fine_match.hip", "fine_fused.hip",

@@ -185,15 +185,3 @@ GIM_F7_FN void gim_f7_solve(const double p0[14], const double p1[14], double* A 
         ok[j] = true;
     }
 }
-
-// Sampson error (x1^T F x0)^2 / max(|F x0|_xy^2 + |F^T x1|_xy^2, 1e-300) <= thr2, the operation order of csrc/ransac_score.hip
-GIM_F7_FN bool gim_f7_inlier(const double* m, double ax, double ay, double bx, double by, double thr2) {
-    const double r0 = m[0] * ax + m[1] * ay + m[2];          // F x0
-    const double r1 = m[3] * ax + m[4] * ay + m[5];
-    const double r2 = m[6] * ax + m[7] * ay + m[8];
-    const double c0 = m[0] * bx + m[3] * by + m[6];          // F^T x1, first two rows
-    const double c1 = m[1] * bx + m[4] * by + m[7];
-    const double e = r0 * bx + r1 * by + r2;                 // x1^T F x0
-    const double den = r0 * r0 + r1 * r1 + c0 * c0 + c1 * c1;
-    return (e * e) / (den < 1e-300 ? 1e-300 : den) <= thr2;
-}

@@ -109,14 +109,3 @@ GIM_H4_FN bool gim_h4_solve(const double* src, const double* dst, double* A /* [
     H[8] = 1.0;
     return ok;
 }
-
-// forward transfer error |dst - proj(H src)|^2 <= thr2 (HomographyEstimatorCallback::computeError, in fp64 and with an IEEE division);
-// w == 0 or a projection that is not finite: an outlier
-GIM_H4_FN bool gim_h4_inlier(const double* H, double sx, double sy, double dx, double dy, double thr2) {
-    const double w = H[6] * sx + H[7] * sy + H[8];
-    if (w == 0.0) return false;
-    const double ex = dx - (H[0] * sx + H[1] * sy + H[2]) / w;
-    const double ey = dy - (H[3] * sx + H[4] * sy + H[5]) / w;
-    const double e = ex * ex + ey * ey;
-    return isfinite(e) && e <= thr2;
-}

@@ -1,4 +1,4 @@
-// The MAGSAC++ gain of one point and its quantisation (magsac.hip), written once for the device and the host.  Plain C++:
+// The MAGSAC++ gain of one point and its quantisation (ransac_score.hip), written once for the device and the host.  Plain C++:
 // tools/magsac_host_check.cpp compiles it on the CPU and pose.magsac_gain restates it in numpy.  fp64 throughout, no fast-math.
 //
 // Barath, Noskova, Ivashechkin, Matas: "MAGSAC++, a fast, reliable and accurate robust estimator" (CVPR 2020), the loss rho(r)

@@ -105,7 +105,7 @@ __global__ void __launch_bounds__(MR_THREADS) model_refit_kernel(const f64x2_t* 
             in = mask_in[i] != 0 ? 1 : 0;
         } else {
             const f64x2_t a = pa[i], d = pb[i];
-            in = gim_mr_inlier(KIND, M, a.x, a.y, d.x, d.y, thr2) ? 1 : 0;
+            in = gim_tv_inlier(KIND, M, a.x, a.y, d.x, d.y, thr2) ? 1 : 0;
         }
         mask_out[i] = (uint8_t)in;
         n += in;
@@ -177,7 +177,7 @@ __global__ void __launch_bounds__(MR_THREADS) model_refit_kernel(const f64x2_t* 
         for (int p = tid; p < n_pts; p += MR_THREADS) {
             const int64_t i = (int64_t)base + p;
             const f64x2_t a = pa[i], d = pb[i];
-            const int in = gim_mr_inlier(KIND, C, a.x, a.y, d.x, d.y, thr2) ? 1 : 0;
+            const int in = gim_tv_inlier(KIND, C, a.x, a.y, d.x, d.y, thr2) ? 1 : 0;
             const int was = mask_out[i];
             mask_out[i] = (uint8_t)(was | (in << 1));
             nc += in, ndiff += in != was ? 1 : 0;

@@ -16,7 +16,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "homography_solve.h"      // gim_h4_inlier: the error and the comparison of gim_homography_mask
+#include "two_view_residual.h"     // gim_tv_inlier: the error and the comparison of the step, score and mask kernels
 #include "recover_pose_solve.h"    // gim_rp_jacobi3, gim_rp_order: the 3 x 3 eigen-decomposition of the rank-2 step
 
 #if defined(__HIPCC__)
@@ -45,22 +45,6 @@ GIM_MR_FN bool gim_mr_model_ok(const double* M) {
     bool finite = true, any = false;
     for (int i = 0; i < 9; ++i) finite = finite && gim_mr_finite(M[i]), any = any || M[i] != 0.0;
     return finite && any;
-}
-
-// sampson_inlier of csrc/ransac_score.hip (pose.sampson_error <= thr2): the same expression, operation for operation
-GIM_MR_FN bool gim_mr_sampson_inlier(const double* m, double ax, double ay, double bx, double by, double thr2) {
-    const double r0 = m[0] * ax + m[1] * ay + m[2];
-    const double r1 = m[3] * ax + m[4] * ay + m[5];
-    const double r2 = m[6] * ax + m[7] * ay + m[8];
-    const double c0 = m[0] * bx + m[3] * by + m[6];
-    const double c1 = m[1] * bx + m[4] * by + m[7];
-    const double e = r0 * bx + r1 * by + r2;
-    const double den = r0 * r0 + r1 * r1 + c0 * c0 + c1 * c1;
-    return (e * e) / (den < 1e-300 ? 1e-300 : den) <= thr2;
-}
-
-GIM_MR_FN bool gim_mr_inlier(int kind, const double* M, double ax, double ay, double bx, double by, double thr2) {
-    return kind == 0 ? gim_h4_inlier(M, ax, ay, bx, by, thr2) : gim_mr_sampson_inlier(M, ax, ay, bx, by, thr2);
 }
 
 // Hartley's normalisation of one pair: centres and scales of both sides, q = (p - c) * s
@@ -279,7 +263,7 @@ inline int gim_mr_refit_kind(const double* pa, const double* pb, int P, const do
     for (int i = 0; i < 9; ++i) cur[i] = model_in[i];
     int n = 0;
     for (int p = 0; p < P; ++p) {
-        mask_out[p] = mask_in ? (mask_in[p] != 0) : gim_mr_inlier(KIND, cur, pa[2 * p], pa[2 * p + 1], pb[2 * p], pb[2 * p + 1], thr2);
+        mask_out[p] = mask_in ? (mask_in[p] != 0) : gim_tv_inlier(KIND, cur, pa[2 * p], pa[2 * p + 1], pb[2 * p], pb[2 * p + 1], thr2);
         n += mask_out[p];
     }
     counts[0] = n;
@@ -294,7 +278,7 @@ inline int gim_mr_refit_kind(const double* pa, const double* pb, int P, const do
         if (!gim_mr_fit<KIND>(pa, pb, P, mask_out, n, cand)) break;
         int nc = 0, ndiff = 0;
         for (int p = 0; p < P; ++p) {
-            const int in = gim_mr_inlier(KIND, cand, pa[2 * p], pa[2 * p + 1], pb[2 * p], pb[2 * p + 1], thr2) ? 1 : 0;
+            const int in = gim_tv_inlier(KIND, cand, pa[2 * p], pa[2 * p + 1], pb[2 * p], pb[2 * p + 1], thr2) ? 1 : 0;
             nc += in, ndiff += in != mask_out[p];
             mask_out[p] |= (uint8_t)(in << 1);
         }

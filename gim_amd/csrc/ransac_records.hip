@@ -1,7 +1,7 @@
 // The reduction of one RANSAC step on the device (gfx950): of the step's inlier counts, only the samples that set a new strict
 // maximum -- the only ones the host's bookkeeping acts on (gim_amd/pose.py, _ransac_steps) -- in sample order.  Integer arithmetic
 // only; pose.step_records is the numpy restatement.  gim_ransac_records64 is the same walk keyed on an int64 quality
-// (csrc/magsac.hip) with the counts beside it; pose.step_records64 restates it.
+// (csrc/ransac_score.hip) with the counts beside it; pose.step_records64 restates it.
 //
 // Replaces the bulk read-back of a step (every model, flag and count: 250 x 10 x 9 doubles for the five-point solver) and the
 // Python walk over its counts; the reference keeps this loop inside OpenCV's RANSACPointSetRegistrator::run, on the host.  The

@@ -1593,25 +1593,32 @@ def _ransac_points(x0, x1, offsets, B):
     return offsets, P
 
 
+def _score_args(word, models, x0, x1, valid, offsets):
+    """The checks of ransac_score / magsac_score on the models, the points and `valid`; `word` names the scorer in a refusal.
+    -> (valid as uint8 or None, offsets int32 [B + 1] on the device, B, K, Ptot)"""
+    _req_cuda(models, x0, x1, valid, offsets)
+    single = offsets is None
+    want = 3 if single else 4
+    if models.dtype != torch.float64 or models.dim() != want or models.shape[-2:] != (3, 3) or not models.is_contiguous():
+        raise _lib.GimHipError(f"{word} models must be contiguous fp64 {'[K,3,3]' if single else '[B,K,3,3]'}, got {models.dtype} {tuple(models.shape)}")
+    B, K = (1, models.shape[0]) if single else models.shape[:2]
+    offsets, P = _ransac_points(x0, x1, offsets, B)
+    if models.device != x0.device:
+        raise _lib.GimHipError(f"{word} models and points are on different devices")
+    if valid is not None:
+        if valid.dtype == torch.bool:
+            valid = valid.view(torch.uint8)
+        if valid.dtype != torch.uint8 or valid.shape != models.shape[:-2] or not valid.is_contiguous() or valid.device != x0.device:
+            raise _lib.GimHipError(f"{word} valid must be contiguous bool / uint8 {tuple(models.shape[:-2])} on the models' device")
+    return valid, offsets, B, K, P
+
+
 def ransac_score(models, x0, x1, thr2, valid=None, offsets=None):
     """Inlier counts of candidate models over matched points (gim_ransac_score; fp64, the arithmetic of pose.sampson_error).
     One pair: models fp64 [K,3,3], x0 / x1 fp64 [P,2], valid bool / uint8 [K] or None -> int32 [K].
     B pairs: offsets int32 [B+1] (pair b owns the points offsets[b] .. offsets[b+1] of the concatenated x0 / x1), models [B,K,3,3],
     valid [B,K] -> int32 [B,K].  An invalid or NaN model counts 0."""
-    _req_cuda(models, x0, x1, valid, offsets)
-    single = offsets is None
-    want = 3 if single else 4
-    if models.dtype != torch.float64 or models.dim() != want or models.shape[-2:] != (3, 3) or not models.is_contiguous():
-        raise _lib.GimHipError(f"ransac models must be contiguous fp64 {'[K,3,3]' if single else '[B,K,3,3]'}, got {models.dtype} {tuple(models.shape)}")
-    B, K = (1, models.shape[0]) if single else models.shape[:2]
-    offsets, P = _ransac_points(x0, x1, offsets, B)
-    if models.device != x0.device:
-        raise _lib.GimHipError("ransac models and points are on different devices")
-    if valid is not None:
-        if valid.dtype == torch.bool:
-            valid = valid.view(torch.uint8)
-        if valid.dtype != torch.uint8 or valid.shape != models.shape[:-2] or not valid.is_contiguous() or valid.device != x0.device:
-            raise _lib.GimHipError(f"ransac valid must be contiguous bool / uint8 {tuple(models.shape[:-2])} on the models' device")
+    valid, offsets, B, K, P = _score_args("ransac", models, x0, x1, valid, offsets)
     if P == 0 or B * K == 0:      # nothing to read: every count is 0
         return torch.zeros(models.shape[:-2], dtype=torch.int32, device=x0.device)
     counts = torch.empty(models.shape[:-2], dtype=torch.int32, device=x0.device)
@@ -1620,21 +1627,27 @@ def ransac_score(models, x0, x1, thr2, valid=None, offsets=None):
     return counts
 
 
-def ransac_mask(models, x0, x1, thr2, offsets=None):
-    """Inlier mask of one model per pair (gim_ransac_mask): model fp64 [3,3] (one pair) or [B,3,3] with offsets int32 [B+1]
-    -> bool [Ptot], sampson_error(model of the point's pair) <= thr2."""
+def _model_mask(word, word_dev, symbol, models, x0, x1, thr2, offsets):
+    """The one body of ransac_mask / homography_mask: the library's `symbol`; `word` names the models and `word_dev` the caller in
+    a refusal."""
     _req_cuda(models, x0, x1, offsets)
     single = offsets is None
     if models.dtype != torch.float64 or models.shape != ((3, 3) if single else (models.shape[0], 3, 3)) or not models.is_contiguous():
-        raise _lib.GimHipError(f"ransac_mask models must be contiguous fp64 {'[3,3]' if single else '[B,3,3]'}, got {models.dtype} {tuple(models.shape)}")
+        raise _lib.GimHipError(f"{word} must be contiguous fp64 {'[3,3]' if single else '[B,3,3]'}, got {models.dtype} {tuple(models.shape)}")
     B = 1 if single else models.shape[0]
     offsets, P = _ransac_points(x0, x1, offsets, B)
     if models.device != x0.device:
-        raise _lib.GimHipError("ransac models and points are on different devices")
+        raise _lib.GimHipError(f"{word_dev} and points are on different devices")
     mask = torch.empty(P, dtype=torch.uint8, device=x0.device)
     if P and B:
-        check(lib.gim_ransac_mask(_p(models), _p(x0), _p(x1), _p(offsets), B, float(thr2), _p(mask), _stream()), "gim_ransac_mask")
+        check(getattr(lib, symbol)(_p(models), _p(x0), _p(x1), _p(offsets), B, float(thr2), _p(mask), _stream()), symbol)
     return mask.view(torch.bool)
+
+
+def ransac_mask(models, x0, x1, thr2, offsets=None):
+    """Inlier mask of one model per pair (gim_ransac_mask): model fp64 [3,3] (one pair) or [B,3,3] with offsets int32 [B+1]
+    -> bool [Ptot], sampson_error(model of the point's pair) <= thr2."""
+    return _model_mask("ransac_mask models", "ransac models", "gim_ransac_mask", models, x0, x1, thr2, offsets)
 
 
 # ---- homography RANSAC step and perspective warp (gim_amd/pose.py, gim_amd/demo.py) ---------------------------------------
@@ -1838,20 +1851,7 @@ def magsac_score(kind, models, a, b, thr2, max_thr2=None, valid=None, offsets=No
         raise _lib.GimHipError(f"magsac_score kind={kind}: 0 (homography) or 1 (fundamental matrix)")
     if not (np.isfinite(max_thr2) and max_thr2 > 0.0):
         raise _lib.GimHipError(f"magsac_score max_thr2={max_thr2}: finite and positive")
-    _req_cuda(models, a, b, valid, offsets)
-    single = offsets is None
-    want = 3 if single else 4
-    if models.dtype != torch.float64 or models.dim() != want or models.shape[-2:] != (3, 3) or not models.is_contiguous():
-        raise _lib.GimHipError(f"magsac models must be contiguous fp64 {'[K,3,3]' if single else '[B,K,3,3]'}, got {models.dtype} {tuple(models.shape)}")
-    B, K = (1, models.shape[0]) if single else models.shape[:2]
-    offsets, P = _ransac_points(a, b, offsets, B)
-    if models.device != a.device:
-        raise _lib.GimHipError("magsac models and points are on different devices")
-    if valid is not None:
-        if valid.dtype == torch.bool:
-            valid = valid.view(torch.uint8)
-        if valid.dtype != torch.uint8 or valid.shape != models.shape[:-2] or not valid.is_contiguous() or valid.device != a.device:
-            raise _lib.GimHipError(f"magsac valid must be contiguous bool / uint8 {tuple(models.shape[:-2])} on the models' device")
+    valid, offsets, B, K, P = _score_args("magsac", models, a, b, valid, offsets)
     if P == 0 or B * K == 0:      # nothing to read: every quality and count is 0
         return (torch.zeros(models.shape[:-2], dtype=torch.int64, device=a.device), torch.zeros(models.shape[:-2], dtype=torch.int32, device=a.device))
     quality = torch.empty(models.shape[:-2], dtype=torch.int64, device=a.device)
@@ -1888,18 +1888,7 @@ def ransac_records64(quality, counts, nb, floor_q, min_count):
 def homography_mask(model, src, dst, thr2, offsets=None):
     """Inlier mask of one homography per pair (gim_homography_mask): model fp64 [3,3] (one pair) or [B,3,3] with offsets int32 [B+1]
     -> bool [Ptot], transfer_error(model of the point's pair) <= thr2."""
-    _req_cuda(model, src, dst, offsets)
-    single = offsets is None
-    if model.dtype != torch.float64 or model.shape != ((3, 3) if single else (model.shape[0], 3, 3)) or not model.is_contiguous():
-        raise _lib.GimHipError(f"homography_mask model must be contiguous fp64 {'[3,3]' if single else '[B,3,3]'}, got {model.dtype} {tuple(model.shape)}")
-    B = 1 if single else model.shape[0]
-    offsets, P = _ransac_points(src, dst, offsets, B)
-    if model.device != src.device:
-        raise _lib.GimHipError("homography model and points are on different devices")
-    mask = torch.empty(P, dtype=torch.uint8, device=src.device)
-    if P and B:
-        check(lib.gim_homography_mask(_p(model), _p(src), _p(dst), _p(offsets), B, float(thr2), _p(mask), _stream()), "gim_homography_mask")
-    return mask.view(torch.bool)
+    return _model_mask("homography_mask model", "homography model", "gim_homography_mask", model, src, dst, thr2, offsets)
 
 
 def warp_perspective(image, H, out_hw):

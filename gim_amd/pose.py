@@ -22,7 +22,7 @@ What is restated (OpenCV 4.x, modules/calib3d/src/five-point.cpp and ptsetreg.cp
     default; the inlier mask is RANSAC's, which is what the demo prints and draws).
   * `score="magsac"`: the MAGSAC++ loss (Barath et al., CVPR 2020) that the reference's cv2.USAC_MAGSAC calls name, as a scoring
     mode of the F and H loops -- the closed form for 4 degrees of freedom and k = 3.64 (`magsac_gain`), quantised per point and
-    summed in int64 (`magsac_quality`; csrc/magsac.hip on the device).  Not cv2's bytes, no sigma-consensus polish, not for E.
+    summed in int64 (`magsac_quality`; csrc/ransac_score.hip on the device).  Not cv2's bytes, no sigma-consensus polish, not for E.
   * four-point homography inside the same loop for the demo's warp (demo.py:180-227 cv2.findHomography; fundam.cpp): forward transfer
     error, re-fit on the inliers by normalised DLT, no Levenberg-Marquardt polish.  This solver also runs on the device, fused with
     the scoring (`find_homography(device=)`, csrc/homography.hip): a step uploads sample indices only.
@@ -870,7 +870,7 @@ def step_records(counts, nb, floor):
     return out
 
 
-# ---- MAGSAC++ scoring (csrc/magsac_loss.h, csrc/magsac.hip restated) -----------------------------------------------------------------
+# ---- MAGSAC++ scoring (csrc/magsac_loss.h, csrc/ransac_score.hip restated) -----------------------------------------------------------------
 SCORES = ("count", "magsac")
 MAGSAC_K = 3.64                                  # the 0.99 quantile of chi(4): OpenCV's two-view USAC constant
 MAGSAC_UK = 3.64 * 3.64 / 2.0                    # u = r^2 / (2 sigma^2) at r = k sigma

@@ -1,4 +1,4 @@
-"""GPU tests of MAGSAC++ scoring (gim_amd/csrc/magsac.hip, gim_amd/csrc/ransac_records.hip: ops.magsac_score, ops.ransac_records64,
+"""GPU tests of MAGSAC++ scoring (gim_amd/csrc/ransac_score.hip, gim_amd/csrc/ransac_records.hip: ops.magsac_score, ops.ransac_records64,
 `score="magsac"` through pose, the video labeller and the demo) against the host: counts and records EXACTLY, qualities within one
 quantisation unit per point of pose.magsac_quality (the device's erf / erfc / exp and its fused multiply-adds against numpy's;
 2^-33 of gain is 1.2e-10, the two differ by about 1e-15), batches against single calls bit for bit, and end to end

@@ -1,0 +1,142 @@
+"""The two residuals of csrc/two_view_residual.h without a GPU: tools/residual_host_check.cpp, built with the host compiler at
+-O1 -ffp-contract=off, against the same two expressions restated in Python floats in the same operation order (IEEE double, no
+contraction: equal bits), and its verdicts against pose.sampson_error / pose.transfer_error."""
+import math
+import os
+import re
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+from gim_amd import pose
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAN = float("nan")
+
+
+def _f(bits):
+    return struct.unpack("<d", struct.pack("<Q", int(bits, 16)))[0]
+
+
+def _bits(x):
+    return struct.unpack("<Q", struct.pack("<d", x))[0]
+
+
+def _div(a, b):
+    """IEEE division of two Python floats (Python raises where C returns an infinity or a NaN)"""
+    with np.errstate(all="ignore"):
+        return float(np.float64(a) / np.float64(b))
+
+
+def _sq(a):
+    """a * a with IEEE overflow (a Python float's own * overflows to inf as C does; ** would raise)"""
+    return a * a
+
+
+def sampson(m, ax, ay, bx, by):
+    r0 = m[0] * ax + m[1] * ay + m[2]
+    r1 = m[3] * ax + m[4] * ay + m[5]
+    r2 = m[6] * ax + m[7] * ay + m[8]
+    c0 = m[0] * bx + m[3] * by + m[6]
+    c1 = m[1] * bx + m[4] * by + m[7]
+    e = r0 * bx + r1 * by + r2
+    den = r0 * r0 + r1 * r1 + c0 * c0 + c1 * c1
+    return _div(e * e, 1e-300 if den < 1e-300 else den)
+
+
+def transfer(h, sx, sy, dx, dy):
+    w = h[6] * sx + h[7] * sy + h[8]
+    if w == 0.0:
+        return NAN
+    ex = dx - _div(h[0] * sx + h[1] * sy + h[2], w)
+    ey = dy - _div(h[3] * sx + h[4] * sy + h[5], w)
+    return _sq(ex) + _sq(ey)
+
+
+def within(kind, err, thr2):
+    return (math.isfinite(err) and err <= thr2) if kind == 0 else err <= thr2
+
+
+@pytest.fixture(scope="module")
+def cases(tmp_path_factory):
+    from gim_amd.build import _hipcc
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or _hipcc()
+    exe = str(tmp_path_factory.mktemp("residual") / "residual_host_check")
+    r = subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O1", "-ffp-contract=off", "-I", os.path.join(ROOT, "gim_amd", "csrc"),
+                        os.path.join(ROOT, "tools", "residual_host_check.cpp"), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
+    rows = re.findall(r"^case (\w+)((?: [0-9a-f]{16}){14}) -> ([0-9a-f]{16}) ([0-9a-f]{16}) ([01]) ([01])$", r.stdout, re.M)
+    out = []
+    for label, ins, s, t, in1, in0 in rows:
+        v = [_f(b) for b in ins.split()]
+        out.append(dict(label=label, m=v[:9], p=v[9:13], thr2=v[13], s=int(s, 16), t=int(t, 16), in1=int(in1), in0=int(in0)))
+    return out
+
+
+def test_the_case_list(cases):
+    n = {}
+    for c in cases:
+        n[c["label"]] = n.get(c["label"], 0) + 1
+    assert n == {"1": 200, "0": 200, "zero": 1, "nan": 9, "den": 1, "w0": 1, "overflow": 1, "at": 1}, n
+    # the seeded cases decide both ways
+    for kind, key in ((1, "in1"), (0, "in0")):
+        ins = sum(c[key] for c in cases if c["label"] == str(kind))
+        print(f"kind {kind}: {ins} of 200 seeded cases are inliers")
+        assert 40 <= ins <= 160, (kind, ins)
+
+
+def test_equal_bits_with_the_python_restatement(cases):
+    """-ffp-contract=off removes the only licensed difference (an FMA where Python rounds twice): the tolerance is zero"""
+    for c in cases:
+        s, t = sampson(c["m"], *c["p"]), transfer(c["m"], *c["p"])
+        for name, got, want in (("sampson", c["s"], s), ("transfer", c["t"], t)):
+            if math.isnan(want):
+                assert math.isnan(_f(f"{got:016x}")), (c["label"], name)
+            else:
+                assert got == _bits(want), (c["label"], name, _f(f"{got:016x}"), want)
+        assert c["in1"] == int(within(1, s, c["thr2"])) and c["in0"] == int(within(0, t, c["thr2"])), c["label"]
+
+
+def test_edge_cases(cases):
+    by = {}
+    for c in cases:
+        by.setdefault(c["label"], []).append(c)
+    z = by["zero"][0]
+    assert z["s"] == _bits(0.0) and z["thr2"] == 0.0 and z["in1"] == 1          # Sampson 0: an inlier at any thr2 >= 0
+    assert math.isnan(_f(f"{z['t']:016x}")) and z["in0"] == 0
+    for c in by["nan"]:                                                          # thr2 = inf, and still no inlier
+        assert sum(math.isnan(x) for x in c["m"]) == 1 and math.isinf(c["thr2"]) and c["in1"] == 0 and c["in0"] == 0
+    assert {tuple(math.isnan(x) for x in c["m"]).index(True) for c in by["nan"]} == set(range(9))
+    d = by["den"][0]
+    m, (ax, ay, bx, by_) = d["m"], d["p"]
+    r0, r1 = m[0] * ax + m[1] * ay + m[2], m[3] * ax + m[4] * ay + m[5]
+    c0, c1 = m[0] * bx + m[3] * by_ + m[6], m[1] * bx + m[4] * by_ + m[7]
+    assert 0.0 < r0 * r0 + r1 * r1 + c0 * c0 + c1 * c1 < 1e-300                  # the clamp is what divides
+    w0 = by["w0"][0]
+    assert math.isnan(_f(f"{w0['t']:016x}")) and math.isinf(w0["thr2"]) and w0["in0"] == 0
+    o = by["overflow"][0]
+    assert o["m"][8] != 0.0 and math.isinf(_f(f"{o['t']:016x}")) and math.isinf(o["thr2"]) and o["in0"] == 0
+    a = by["at"][0]
+    assert _f(f"{a['t']:016x}") == a["thr2"] == 25.0 and a["in0"] == 1
+
+
+def test_verdicts_are_numpys(cases):
+    """pose.sampson_error / pose.transfer_error <= thr2 on the seeded cases.  numpy sums in another order, so a point whose error
+    lies within a relative 1e-9 of the threshold could be decided either way: the seed is chosen so that there is none."""
+    near = 0
+    for kind, error, key in ((1, pose.sampson_error, "in1"), (0, pose.transfer_error, "in0")):
+        for c in cases:
+            if c["label"] != str(kind):
+                continue
+            M = np.array(c["m"]).reshape(3, 3)
+            e = float(error(M, np.array([c["p"][:2]]), np.array([c["p"][2:]]))[0])
+            if abs(e - c["thr2"]) <= 1e-9 * c["thr2"]:
+                near += 1
+                continue
+            assert c[key] == int(e <= c["thr2"]), (kind, e, c["thr2"])
+    assert near == 0, near

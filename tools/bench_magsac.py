@@ -1,5 +1,5 @@
 """RANSAC ranked by the inlier count (`score="count"`, the default) against the MAGSAC++ quality (`score="magsac"`,
-csrc/magsac.hip + gim_ransac_records64), both with sampler="device" on the same inputs: 2 000 matches of a two-view scene in
+csrc/ransac_score.hip + gim_ransac_records64), both with sampler="device" on the same inputs: 2 000 matches of a two-view scene in
 pixels, 50 % gross outliers, 0.3 px noise.
 
     python tools/bench_magsac.py [--matches 2000] [--steps 3] [--repeats 5] [--out profiles/magsac.txt]

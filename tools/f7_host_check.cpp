@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "fundamental_solve.h"
+#include "two_view_residual.h"
 
 namespace {
 
@@ -50,7 +51,7 @@ int run(const double* p0, const double* p1, Tally* t) {
         if (fabs(n2 - 1.0) > 1e-12) printf("FAIL: |F| = %.17g\n", sqrt(n2)), t->rejected = -1000000;
         for (int i = 0; i < 7; ++i) {
             // a point exactly on its epipolar line has Sampson error 0: thr2 = 1e-12 px^2 accepts rounding only
-            if (!gim_f7_inlier(F + 9 * j, p0[2 * i], p0[2 * i + 1], p1[2 * i], p1[2 * i + 1], 1e-12)) t->worst = 1.0;
+            if (!gim_tv_inlier(GIM_TV_EPIPOLAR, F + 9 * j, p0[2 * i], p0[2 * i + 1], p1[2 * i], p1[2 * i + 1], 1e-12)) t->worst = 1.0;
         }
         for (int i = 0; i < 9; ++i) t->sum += fabs(F[9 * j + i]) * (double)(1 + i + 9 * j);
     }
