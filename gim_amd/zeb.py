@@ -135,7 +135,7 @@ def _check_recover(recover, device):
     """the `recover=` rules of estimate_pose and the two hooks: "device" needs a device and the numpy backend; raises before any
     launch"""
     from . import pose
-    pose._check_recover(recover, device)
+    pose.check_recover(recover, device)
     if recover == "device" and pose.backend() != "numpy":
         raise ValueError("recover='device' belongs to the numpy backend (GIM_POSE_BACKEND=numpy): OpenCV recovers the pose itself")
 
@@ -153,7 +153,7 @@ def estimate_pose(kpts0, kpts1, K0, K1, thresh=0.5, conf=0.99999, device=None, s
     (pose.find_essential_pose): with solve="device" on the points and the mask the RANSAC left on the GPU, one copy bringing the
     mask, R and t back.  The returned inliers are the RANSAC mask either way."""
     from . import pose
-    pose._check_sampler(sampler, device, solve)
+    pose.check_sampler(sampler, device, solve)
     _check_recover(recover, device)
     if len(kpts0) < 5:
         return None
@@ -199,7 +199,7 @@ def device_estimator(device, thresh=0.5, conf=0.99999, solve="host", sampler="ho
     """`estimate=` hook of evaluate_batch / run_scene: estimate_pose with the RANSAC candidates scored on `device`
     (solve="device": solved there too; sampler, recover: estimate_pose's)"""
     from . import pose
-    pose._check_sampler(sampler, device, solve)
+    pose.check_sampler(sampler, device, solve)
     _check_recover(recover, device)
     return lambda a, b, k0, k1: estimate_pose(a, b, k0, k1, thresh, conf, device=device, solve=solve, sampler=sampler, recover=recover)
 
@@ -215,7 +215,7 @@ def device_batch_estimator(device, thresh=0.5, conf=0.99999, solve="host", sampl
     recover="device": the poses of a group come from ONE gim_recover_pose launch (pose.find_essential_pose_batch); the results
     equal estimate_pose(..., recover="device") on each pair."""
     from . import pose
-    pose._check_sampler(sampler, device, solve)
+    pose.check_sampler(sampler, device, solve)
     _check_recover(recover, device)
 
     def estimate_batch(pairs):

@@ -6,7 +6,7 @@ import functools
 
 import numpy as np
 
-from gim_amd import pose
+from gim_amd import pose, pose_math
 
 THR2 = 1.0                       # (1 px)^2, the demo's threshold
 W, H_IMG = 640.0, 480.0
@@ -54,7 +54,7 @@ def sin_dist(A, B):
 def residuals(F, x0s, x1s):
     """F [N, 3, 3, 3] (unit norm), samples x0s, x1s [N, 7, 2] -> (largest |row . f| over the seven unit-norm epipolar rows [N, 3],
     |det F| [N, 3])"""
-    rows = pose._epipolar_rows(x0s, x1s)
+    rows = pose_math._epipolar_rows(x0s, x1s)
     rows = rows / np.linalg.norm(rows, axis=-1, keepdims=True)
     r = np.abs(np.einsum("nik,nmk->nmi", rows, F.reshape(F.shape[0], 3, 9))).max(-1)
     return r, np.abs(np.linalg.det(F))

@@ -77,6 +77,49 @@ def run_cases():
     return out
 
 
+@functools.lru_cache(maxsize=None)
+def quality_run_cases():
+    """whole runs for the quality walk (score="magsac"), k = 3: {name: (P, m, conf, max_iters, counts [N, 3], quality int64 [N, 3], the
+    best (sample, slot) and final bound that the plant implies)}.  The background is ineligible (counts below m) with large random
+    qualities, so only the planted samples can be accepted."""
+    rng = np.random.default_rng(51)
+    out = {}
+
+    def background(N, m):
+        return rng.integers(0, m, (N, 3)), rng.integers(1, 1 << 60, (N, 3)).astype(np.int64)
+
+    # two samples of equal quality: the earlier one is kept (strictly above)
+    c, q = background(300, 7)
+    c[20, 1], q[20, 1] = 100, 1 << 40
+    c[60, 2], q[60, 2] = 120, 1 << 40
+    out["two samples of equal quality"] = (2000, 7, 0.999999, 300, c, q, (20, 1), 300)
+    # the highest quality sits in a slot with count < m; another slot of that sample is eligible
+    c, q = background(300, 7)
+    c[30], q[30] = (3, 0, 50), (1 << 61, 5, 1 << 30)
+    out["the highest quality is ineligible"] = (2000, 7, 0.999999, 300, c, q, (30, 2), 300)
+    # the accepted slot is not the slot with the most inliers: the bound comes from 1 200 inliers (487), not from 1 900 (a dozen)
+    c, q = background(600, 7)
+    c[40], q[40] = (1200, 1900, 0), (1 << 35, 1 << 30, 7)
+    out["the accepted slot has fewer inliers than another"] = (2000, 7, 0.999999, 600, c, q, (40, 0), 487)
+    # the bound shrinks inside the first step to before a better later sample
+    c, q = background(500, 5)
+    c[30, 1], q[30, 1] = 1900, 1 << 40
+    c[100, 2], q[100, 2] = 1950, 1 << 45
+    out["the bound shrinks inside the first step"] = (2000, 5, 0.999, 500, c, q, (30, 1), 31)
+    # c == P: den < 1e-12, the run ends at that sample
+    c, q = background(500, 4)
+    c[260, 0], q[260, 0] = 300, 1 << 40
+    out["all points are inliers in the second step"] = (300, 4, 0.999999, 500, c, q, (260, 0), 261)
+    # max_iters is no multiple of 250, increasing records across the step edges
+    c, q = background(610, 7)
+    for i, s in enumerate((5, 249, 250, 499, 500, 609)):
+        c[s, i % 3], q[s, i % 3] = 20 + i, (1 << 40) + i
+    out["max_iters = 610 is no multiple of 250"] = (2000, 7, 0.999999, 610, c, q, (609, 2), 610)
+    for case in out.values():
+        case[4].setflags(write=False), case[5].setflags(write=False)
+    return out
+
+
 # ---- scenes of the end-to-end tests ------------------------------------------------------------------------------------------------
 def _outliers(rng, b, share, lo, hi):
     out = rng.random(len(b)) < share

@@ -7,8 +7,6 @@ import ctypes
 import math
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -16,6 +14,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import frame_prep_cases as C  # noqa: E402
+import host_check  # noqa: E402
 
 from gim_amd import frame_prep as fp  # noqa: E402
 from gim_amd import video_labels as VL  # noqa: E402
@@ -407,14 +406,8 @@ def _lcg_bytes(seed, n):
 def test_host_check_agrees_with_the_numpy_oracle(tmp_path):
     """tools/frame_prep_host_check.cpp is plain C++ over the kernel's header; built with the host compiler (no sanitizer here: that
     run is a development step, recorded in the README), every byte it prints is frame_prep_np's"""
-    from gim_amd.build import _hipcc
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or _hipcc()   # hipcc compiles plain C++ too
-    exe = str(tmp_path / "frame_prep_host_check")
-    r = subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O1", "-ffp-contract=off", "-I", os.path.join(ROOT, "gim_amd", "csrc"),
-                        os.path.join(ROOT, "tools", "frame_prep_host_check.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout[-2000:]
+    r = host_check.run("frame_prep_host_check", tmp_path, "-ffp-contract=off")
+    assert r.stdout.strip().endswith("OK"), r.stdout[-2000:]
     lines = r.stdout.strip().split("\n")
     assert (len(lines) - 1) % 7 == 0 and len(lines) >= 50
     for i in range(0, len(lines) - 1, 7):

@@ -1,5 +1,5 @@
 """GPU tests of the RANSAC hypothesis scorer (gim_amd/csrc/ransac_score.hip, ops.ransac_score / ops.ransac_mask, pose.DeviceScorer and
-the `device=` paths of gim_amd/pose.py and gim_amd/zeb.py) against the host: pose.sampson_error / pose._count_inliers in fp64.
+the `device=` paths of gim_amd/pose.py and gim_amd/zeb.py) against the host: pose.sampson_error / pose_math._count_inliers in fp64.
 
 Parity bar: counts and masks are EXACTLY the host's.  The device may contract a * b + c into an FMA where numpy rounds twice, so an
 error could land on the other side of thr2 only when it is within rounding of it: the module checks on the host that NO
@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from gim_amd import ops, pose, zeb
+from gim_amd import ops, pose, pose_math, zeb
 from gim_amd._lib import GimHipError
 
 pytestmark = pytest.mark.gpu
@@ -87,7 +87,7 @@ def test_counts_equal_the_host(case, K, P):
     want = case.oracle(K, P)
     assert np.array_equal(got.cpu().numpy(), want), (K, P, int((got.cpu().numpy() != want).sum()))
     if K == 2500 and P == 2000:
-        assert np.array_equal(want, pose._count_inliers(case.models, case.valid, case.x0, case.x1, THR2))
+        assert np.array_equal(want, pose_math._count_inliers(case.models, case.valid, case.x0, case.x1, THR2))
         # without `valid` the rejected candidates (zero matrices) count every point
         allv = ops.ransac_score(case.d_models, case.d_x0, case.d_x1, THR2).cpu().numpy()
         assert np.array_equal(allv, (case.err <= THR2).sum(1)) and (allv[~case.valid] == 2000).all()
@@ -102,7 +102,7 @@ def test_invalid_nan_and_zero_models(case):
     models[2] = 0.0
     models[62] = 0.0
     got = ops.ransac_score(torch.from_numpy(models).to(DEV), case.d_x0[:P], case.d_x1[:P], THR2, valid=torch.from_numpy(valid).to(DEV)).cpu().numpy()
-    want = pose._count_inliers(models, valid, case.x0[:P], case.x1[:P], THR2)
+    want = pose_math._count_inliers(models, valid, case.x0[:P], case.x1[:P], THR2)
     assert np.array_equal(got, want)
     assert (got[[0, 5, 64]] == 0).all() and (got[[1, 63]] == 0).all() and (got[[2, 62]] == P).all()
     # counts is fully written: a second call into the same allocation pattern with everything invalid gives zeros
@@ -122,7 +122,7 @@ def test_ragged_batch(case):
     got = ops.ransac_score(d(models), d(x0), d(x1), THR2, valid=d(valid), offsets=d(off))
     assert got.shape == (3, K) and got.dtype == torch.int32
     for b, (s, n) in enumerate(zip(starts, sizes)):
-        want = pose._count_inliers(models[b], valid[b], case.x0[s:s + n], case.x1[s:s + n], THR2)
+        want = pose_math._count_inliers(models[b], valid[b], case.x0[s:s + n], case.x1[s:s + n], THR2)
         assert np.array_equal(got[b].cpu().numpy(), want), b
         one = ops.ransac_score(d(models[b]), d(case.x0[s:s + n]), d(case.x1[s:s + n]), THR2, valid=d(valid[b]))
         assert np.array_equal(one.cpu().numpy(), want), b

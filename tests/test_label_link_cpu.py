@@ -6,13 +6,13 @@ the CPU) against numpy.  Every comparison is exact: indices are integers and coo
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import host_check
 import label_link_cases as C
 import label_link_oracle as O
 from gim_amd import video_labels as V
@@ -281,14 +281,7 @@ def test_host_check_agrees_with_numpy(tmp_path):
     """tools/label_key_host_check.cpp is plain C++ over csrc/label_key.h; built with the host compiler, every key, slot, watermark
     test and rescaled coordinate it prints equals the numpy restatement bit for bit (a NaN as a NaN).  The sanitizer run of the same
     program is a development step, recorded in profiles/label_link.txt."""
-    from gim_amd.build import _hipcc
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or _hipcc()
-    exe = str(tmp_path / "label_key_host_check")
-    r = subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O1", "-ffp-contract=off", "-I", os.path.join(ROOT, "gim_amd", "csrc"),
-                        os.path.join(ROOT, "tools", "label_key_host_check.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    r = host_check.run("label_key_host_check", tmp_path, "-ffp-contract=off")
     rows = [ln.split() for ln in r.stdout.splitlines()]
     seen = {"K": 0, "M": 0, "R": 0}
     same = lambda a, b: (np.isnan(a) and np.isnan(b)) or a.tobytes() == b.tobytes()   # noqa: E731

@@ -6,14 +6,13 @@ over csrc/magsac_loss.h (tools/magsac_host_check.cpp).  Inputs: tests/magsac_cas
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import fundamental_cases as FC
 import homography_cases as HC
+import host_check
 import label_link_cases as LC
 import magsac_cases as MC
 import ransac_sampler_cases as C
@@ -208,7 +207,7 @@ def test_quality_walk_equals_a_sequential_loop_and_the_scenes_are_decidable(kind
 
 
 def test_record_walk_with_qualities_equals_the_steps_walk():
-    """`_RecordWalk(quality=True)` fed with step_records64 accepts what the quality walk of `_ransac_steps` accepts"""
+    """`_Walk(quality=True)` fed with step_records64 accepts what the quality walk of `_ransac_steps` accepts"""
     rng = np.random.default_rng(9)
     P, m, k, N = 2000, 7, 3, 1500
     c = rng.integers(0, 40, (N, k))
@@ -235,7 +234,7 @@ def test_record_walk_with_qualities_equals_the_steps_walk():
     except StopIteration as stop:
         best = stop.value
     want = (int(best[0, 0]), int(best[0, 1]))
-    w = pose._RecordWalk(P, m, 0.999999, N, quality=True)
+    w = pose._Walk(P, m, 0.999999, N, quality=True)
     got, steps2 = None, []
     while True:
         nb, floor = w.plan()
@@ -248,6 +247,69 @@ def test_record_walk_with_qualities_equals_the_steps_walk():
             got = (first + hit[0], hit[1])
         steps2.append(nb)
     assert got == want == (300, 2) and steps2 == nbs and w.done == sum(nbs) and w.niters < N
+
+
+def _sequential_quality(P, m, conf, max_iters, c, q):
+    """the quality rule one sample at a time, written here: the test's own statement -> (best (sample, slot) | None, niters)"""
+    lconf = np.log(max(1.0 - conf, 1e-300))
+    best_q, best, niters, n = 0, None, int(max_iters), 0
+    while n < niters:
+        key = np.where(c[n] >= m, q[n], 0)
+        j = int(key.argmax())
+        if int(key[j]) > best_q:
+            best_q, best = int(key[j]), (n, j)
+            den = 1.0 - (int(c[n, j]) / P) ** m
+            niters = min(niters, n + 1) if den < 1e-12 else min(niters, max(n + 1, int(np.ceil(lconf / np.log(den)))))
+        n += 1
+    return best, niters
+
+
+@pytest.mark.parametrize("name", sorted(C.quality_run_cases()))
+def test_quality_run_cases_three_drivers_agree(name):
+    """tests/ransac_sampler_cases.quality_run_cases: the records driver (`_Walk` fed by step_records64), the generator driver
+    (`_ransac_steps(quality=True)`) and the sequential loop above agree on the best (sample, slot), the step sizes and the final
+    bound; the plant of each case is really there (the best and the bound it implies)."""
+    P, m, conf, N, c, q, plant_best, plant_niters = C.quality_run_cases()[name]
+    k = c.shape[1]
+    seq_best, seq_niters = _sequential_quality(P, m, conf, N, c, q)
+    assert (seq_best, seq_niters) == (plant_best, plant_niters), name
+    if name == "the highest quality is ineligible":
+        assert q[30].argmax() == 0 and c[30, 0] < m <= c[30, 2]
+    if name == "the accepted slot has fewer inliers than another":
+        assert c[40].argmax() == 1 != plant_best[1]
+    if name == "two samples of equal quality":
+        assert q[20, 1] == q[60, 2] and c[60, 2] >= m
+
+    def hook(idx):
+        Ms = np.zeros((len(idx), k, 3, 3))
+        Ms[:, :, 0, 0], Ms[:, :, 0, 1] = idx[:, None], np.arange(k)[None]
+        hook.idx = idx
+        return Ms, np.ones((len(idx), k), dtype=bool)
+
+    steps = pose._ransac_steps(P, None, m, conf, N, None, None, None, solve_idx=hook, draw=lambda first, nb: np.arange(first, first + nb), quality=True)
+    gen_nbs = []
+    try:
+        next(steps)
+        while True:
+            gen_nbs.append(len(hook.idx))
+            steps.send((q[hook.idx].reshape(-1), c[hook.idx].reshape(-1)))
+    except StopIteration as stop:
+        gen_best = None if stop.value is None else (int(stop.value[0, 0]), int(stop.value[0, 1]))
+    w = pose._Walk(P, m, conf, N, quality=True)
+    rec_best, rec_nbs = None, []
+    while True:
+        nb, floor = w.plan()
+        if nb == 0:
+            break
+        first = w.done
+        rec = pose.step_records64(q[None, first:first + nb], c[None, first:first + nb], [nb], [floor], m)[0]
+        hit = w.replay(rec[1:1 + 4 * rec[0]].reshape(-1, 4))
+        if hit is not None:
+            rec_best = (first + hit[0], hit[1])
+        rec_nbs.append(nb)
+    print(f"{name}: best {seq_best}, bound {seq_niters}, steps {rec_nbs}")
+    assert gen_best == rec_best == seq_best and gen_nbs == rec_nbs
+    assert w.niters == seq_niters and w.done == sum(rec_nbs) and w.done - rec_nbs[-1] < seq_niters <= w.done
 
 
 # ---- score="magsac" on the scenes -------------------------------------------------------------------------------------------------------
@@ -423,14 +485,8 @@ def test_host_check_agrees_with_numpy(tmp_path):
     """tools/magsac_host_check.cpp is plain C++ over csrc/magsac_loss.h: built with the host compiler (no sanitizer here; that run
     is a development step recorded in profiles/magsac.txt) it passes its own checks, and its gains and units are numpy's: the
     gain within 1e-14 (two C libraries' erf, erfc and exp), the units within one"""
-    from gim_amd.build import _hipcc
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or _hipcc()
-    exe = str(tmp_path / "magsac_host_check")
-    r = subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "gim_amd", "csrc"),
-                        os.path.join(ROOT, "tools", "magsac_host_check.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
+    r = host_check.run("magsac_host_check", tmp_path)
+    assert r.stdout.strip().endswith("OK"), r.stdout + r.stderr
     rows = re.findall(r"u (\S+) gain ([0-9a-f]{16}) (\S+) units (-?\d+)", r.stdout)
     assert len(rows) == 30
     for u, bits, _, units in rows:

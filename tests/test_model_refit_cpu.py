@@ -6,14 +6,13 @@ import ctypes
 import inspect
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_check
 import model_refit_cases as C
-from gim_amd import demo, pose, video_labels
+from gim_amd import demo, pose, pose_math, video_labels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "gim_hip.h")
@@ -35,7 +34,7 @@ def _system(kind, a, b):
     Ta, Tb = _norm_T(a), _norm_T(b)
     p, q = a * Ta[0, 0] + Ta[:2, 2], b * Tb[0, 0] + Tb[:2, 2]
     if kind == 1:
-        return pose._epipolar_rows(p, q), Ta, Tb
+        return pose_math._epipolar_rows(p, q), Ta, Tb
     x, y, u, v = p[:, 0], p[:, 1], q[:, 0], q[:, 1]
     o, z = np.ones_like(x), np.zeros_like(x)
     return np.concatenate([np.stack([x, y, o, z, z, z, -u * x, -u * y, -u], 1), np.stack([z, z, z, x, y, o, -v * x, -v * y, -v], 1)]), Ta, Tb
@@ -335,14 +334,8 @@ def test_host_check_agrees_with_the_numpy_oracle(tmp_path):
     """tools/refit_host_check.cpp is plain C++ over the kernel's header; built with the host compiler (no sanitizer here: that run is
     a development step, recorded in the README), its self-check passes and the models it prints equal the restatement's to 1e-12 on
     the scenes it prints"""
-    from gim_amd.build import _hipcc
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or _hipcc()   # hipcc compiles plain C++ too
-    exe = str(tmp_path / "refit_host_check")
-    r = subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "gim_amd", "csrc"),
-                        os.path.join(ROOT, "tools", "refit_host_check.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout[-2000:]
+    r = host_check.run("refit_host_check", tmp_path)
+    assert r.stdout.strip().endswith("OK"), r.stdout[-2000:]
     lines = r.stdout.strip().split("\n")
     i, scenes = 0, 0
     while lines[i].startswith("scene"):

@@ -6,14 +6,13 @@ host program over the header (tools/rs_host_check.cpp)."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import essential_cases as EC
 import fundamental_cases as FC
+import host_check
 import ransac_sampler_cases as C
 from gim_amd import demo, pose, zeb
 
@@ -150,7 +149,7 @@ def test_records_walk_equals_the_counts_walk():
         want_best, want_nbs = _counts_walk(P, m, conf, max_iters, counts)
         seq_best, seq_niters = _sequential(P, m, conf, max_iters, counts)
         assert want_best == seq_best, name
-        w = pose._RecordWalk(P, m, conf, max_iters)
+        w = pose._Walk(P, m, conf, max_iters)
         best, nbs, most = None, [], 0
         while True:
             nb, floor = w.plan()
@@ -355,14 +354,8 @@ def test_host_check_agrees_with_numpy(tmp_path):
     """tools/rs_host_check.cpp is plain C++ over the sampler's header: built with the host compiler (no sanitizer here; that run is a
     development step recorded in profiles/ransac_sampler.txt) it passes its own checks, and its checksums -- 4 000 samples from
     ordinal 2^32 - 1001 on for every m at the edge point counts -- are those of pose.device_samples"""
-    from gim_amd.build import _hipcc
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or _hipcc()   # hipcc compiles plain C++ too
-    exe = str(tmp_path / "rs_host_check")
-    r = subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "gim_amd", "csrc"),
-                        os.path.join(ROOT, "tools", "rs_host_check.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
+    r = host_check.run("rs_host_check", tmp_path)
+    assert r.stdout.strip().endswith("OK"), r.stdout + r.stderr
     got = dict(((int(a), int(b)), c) for a, b, c in re.findall(r"m (\d+) P (\d+) checksum ([0-9a-f]{16})", r.stdout))
     assert len(got) == 24
     w = np.arange(1, 8, dtype=np.uint64)

@@ -5,12 +5,12 @@ header on the CPU) against recover_pose_ge.  tests/recover_pose_cases.py builds 
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import host_check
 import recover_pose_cases as C
 from gim_amd import pose, zeb
 
@@ -242,14 +242,8 @@ def test_host_check_agrees_with_the_numpy_oracle(tmp_path):
     results on problems written here equal recover_pose_ge's: counts, winner and mask exactly on these scenes, R and t within
     C.RT_BAR (the two differ at most by how the compiler rounds a*b+c).  The sanitizer run is a development step, recorded in
     profiles/recover_pose.txt."""
-    from gim_amd.build import _hipcc
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or _hipcc()   # hipcc compiles plain C++ too
-    exe = str(tmp_path / "rp_host_check")
-    r = subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "gim_amd", "csrc"),
-                        os.path.join(ROOT, "tools", "rp_host_check.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout
+    r = host_check.run("rp_host_check", tmp_path)
+    assert r.stdout.strip().endswith("OK"), r.stdout
     E, x0, x1, _, _ = C.scene(101, 2000)
     Es, s0, s1, _, _ = C.scene(125, 5)
     Eb, b0, b1 = C.behind_scene()
@@ -258,7 +252,7 @@ def test_host_check_agrees_with_the_numpy_oracle(tmp_path):
                 (Eb, b0, b1, 1e9, None)]
     path = tmp_path / "problems.txt"
     path.write_text("".join(_problem_text(*p) for p in problems))
-    r = subprocess.run([exe, str(path)], capture_output=True, text=True)
+    r = subprocess.run([str(tmp_path / "rp_host_check"), str(path)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     out = r.stdout.strip().split("\n")
     assert len(out) == 3 * len(problems)

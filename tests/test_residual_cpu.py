@@ -4,13 +4,12 @@ contraction: equal bits), and its verdicts against pose.sampson_error / pose.tra
 import math
 import os
 import re
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_check
 from gim_amd import pose
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -62,14 +61,8 @@ def within(kind, err, thr2):
 
 @pytest.fixture(scope="module")
 def cases(tmp_path_factory):
-    from gim_amd.build import _hipcc
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or _hipcc()
-    exe = str(tmp_path_factory.mktemp("residual") / "residual_host_check")
-    r = subprocess.run([cxx, "-x", "c++", "-std=c++17", "-O1", "-ffp-contract=off", "-I", os.path.join(ROOT, "gim_amd", "csrc"),
-                        os.path.join(ROOT, "tools", "residual_host_check.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
+    r = host_check.run("residual_host_check", tmp_path_factory.mktemp("residual"), "-ffp-contract=off")
+    assert r.stdout.strip().endswith("OK"), r.stdout + r.stderr
     rows = re.findall(r"^case (\w+)((?: [0-9a-f]{16}){14}) -> ([0-9a-f]{16}) ([0-9a-f]{16}) ([01]) ([01])$", r.stdout, re.M)
     out = []
     for label, ins, s, t, in1, in0 in rows:

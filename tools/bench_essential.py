@@ -34,7 +34,7 @@ def main(argv=None):
     os.environ["GIM_POSE_BACKEND"] = "numpy"
     import numpy as np
     import torch
-    from gim_amd import pose, zeb
+    from gim_amd import pose, pose_math, zeb
     assert torch.cuda.is_available(), "bench_essential.py needs a HIP device (the device paths have no CPU mode)"
     dev = torch.device("cuda", 0)
 
@@ -97,7 +97,7 @@ def main(argv=None):
         E, v = pose.five_point(x0[idx], x1[idx])
         return E.reshape(-1, 3, 3), v.reshape(-1)
 
-    compare({"one step (a) host solve + host score (250 samples)": lambda: pose._count_inliers(*host_solve(), x0, x1, thr2),
+    compare({"one step (a) host solve + host score (250 samples)": lambda: pose_math._count_inliers(*host_solve(), x0, x1, thr2),
              "one step (b) host solve + device score: upload 2500 models + gim_ransac_score + read-back": lambda: scorer.counts(*host_solve()),
              "one step (c) device: upload idx + gim_essential_step + read-back": lambda: fused.solve(idx),
              "one step, the host solve alone (pose.five_point, 250 samples)": host_solve}, {"P": P, "K": 250})

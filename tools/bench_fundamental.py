@@ -31,7 +31,7 @@ def main(argv=None):
     sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")))
     import numpy as np
     import torch
-    from gim_amd import pose
+    from gim_amd import pose, pose_math
     assert torch.cuda.is_available(), "bench_fundamental.py needs a HIP device (the device paths have no CPU mode)"
     dev = torch.device("cuda", 0)
 
@@ -87,7 +87,7 @@ def main(argv=None):
         F, v = pose.seven_point(p0[idx], p1[idx])
         return F.reshape(-1, 3, 3), v.reshape(-1)
 
-    compare({"one step (a) host solve + host score (250 samples)": lambda: pose._count_inliers(*host_solve(), p0, p1, 1.0),
+    compare({"one step (a) host solve + host score (250 samples)": lambda: pose_math._count_inliers(*host_solve(), p0, p1, 1.0),
              "one step (b) host solve + device score: upload 750 models + gim_ransac_score + read-back": lambda: scorer.counts(*host_solve()),
              "one step (c) device: upload idx + gim_fundamental_step + read-back": lambda: fused.solve(idx),
              "one step, the host solve alone (pose.seven_point, 250 samples)": host_solve}, {"P": P, "K": 250})

@@ -29,7 +29,7 @@ def main(argv=None):
     sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")))
     import numpy as np
     import torch
-    from gim_amd import ops, pose
+    from gim_amd import ops, pose, pose_math
     assert torch.cuda.is_available(), "bench_homography.py needs a HIP device (the device paths have no CPU mode)"
     dev = torch.device("cuda", 0)
 
@@ -81,7 +81,7 @@ def main(argv=None):
     idx = np.argsort(rng.random((250, P)), axis=1)[:, :4]
     dh = pose.DeviceHomography(src, dst, 1.0, dev)
     compare({"one step, host: homography_4pt + transfer_error counts (250 samples)":
-             lambda: pose._count_inliers(*[x.reshape(-1, *x.shape[2:]) for x in pose.homography_4pt(src[idx], dst[idx])], src, dst, 1.0, error=pose.transfer_error),
+             lambda: pose_math._count_inliers(*[x.reshape(-1, *x.shape[2:]) for x in pose.homography_4pt(src[idx], dst[idx])], src, dst, 1.0, error=pose.transfer_error),
              "one step, device: upload idx + gim_homography_step + read-back (250 samples)": lambda: dh.solve(idx)}, {"P": P, "K": 250})
 
     # ---- (c) the warp ---------------------------------------------------------------------------------------------------------------

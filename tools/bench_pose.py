@@ -4,7 +4,7 @@ the host path of gim_amd/pose.py (numpy), on synthetic two-view matches: 2 000 m
     python tools/bench_pose.py [--matches 2000] [--models 2500] [--pairs 8] [--steps 3] [--repeats 5] [--out profiles/<name>_pose_score.txt]
 
 Two comparisons, both sides in one process, alternating, on the same inputs:
-  (a) one scoring step: K = 2 500 five-point candidates x P = 2 000 points.  Host: pose._count_inliers.  Device: DeviceScorer.counts,
+  (a) one scoring step: K = 2 500 five-point candidates x P = 2 000 points.  Host: pose_math._count_inliers.  Device: DeviceScorer.counts,
       i.e. the upload of the step's models, the launch and the read-back of the counts; the kernel alone (device events around
       gim_ransac_score, models already resident) is reported next to it.
   (b) zeb.estimate_pose per pair, host against `device=`, and `--pairs` such pairs through zeb.device_batch_estimator (lockstep RANSAC,
@@ -33,7 +33,7 @@ def main(argv=None):
     os.environ["GIM_POSE_BACKEND"] = "numpy"
     import numpy as np
     import torch
-    from gim_amd import ops, pose, zeb
+    from gim_amd import ops, pose, pose_math, zeb
     assert torch.cuda.is_available(), "bench_pose.py needs a HIP device (the device scorer has no CPU mode)"
     dev = torch.device("cuda", 0)
 
@@ -96,10 +96,10 @@ def main(argv=None):
     E, valid = pose.five_point(x0[idx], x1[idx])
     Ms, valid = np.ascontiguousarray(E.reshape(-1, 3, 3)[:K]), np.ascontiguousarray(valid.reshape(-1)[:K])
     scorer = pose.DeviceScorer(x0, x1, thr2, dev)
-    want, got = pose._count_inliers(Ms, valid, x0, x1, thr2), scorer.counts(Ms, valid)
+    want, got = pose_math._count_inliers(Ms, valid, x0, x1, thr2), scorer.counts(Ms, valid)
     emit({"what": "agreement (a)", "K": K, "P": P, "models_whose_count_differs": int((want != got).sum()), "best_count": int(want.max())})
     assert (want == got).all()
-    compare("(a) scoring step", {"pose._count_inliers (host)": lambda: pose._count_inliers(Ms, valid, x0, x1, thr2),
+    compare("(a) scoring step", {"pose_math._count_inliers (host)": lambda: pose_math._count_inliers(Ms, valid, x0, x1, thr2),
                                  "DeviceScorer.counts (upload + kernel + read-back)": lambda: scorer.counts(Ms, valid)}, {"K": K, "P": P})
     d_m, d_v = torch.from_numpy(Ms).to(dev), torch.from_numpy(valid).to(dev).view(torch.uint8)
     d_off = torch.tensor([0, P], dtype=torch.int32, device=dev)
